@@ -7,11 +7,14 @@ scratch sets on their own streams: mark_docs, pretok_split, piece_resolve, bpe_m
 chunk), ending with every document's token ids and offsets in HBM.
 
 N = 1 (default): BASELINE.json configs[2] -- cl100k_base, 1M mixed UTF-8 docs (emoji + CJK, ~4 KB each, ~4.1 GB), the largest
-single-GPU configuration -- is the headline; the same JSON line carries sub-records for configs[1] (100k English docs),
-configs[4] (r50k_base + p50k_base back to back on the 1M-doc corpus), one shard of configs[3] (1.25M English docs), an
-end-to-end figure (host buffers in, token ids on the host) and a vocabulary-stress corpus.
+single-GPU configuration -- is the headline.  With --full the same JSON line carries sub-records for configs[1] (100k English
+docs), configs[4] (r50k_base + p50k_base back to back on the 1M-doc corpus), configs[3] whole on one GPU, end-to-end figures
+(host buffers in, token ids on the host), the maxTokens early exit, the per-call shapes and a vocabulary-stress corpus.
 N > 1: configs[3] -- 10M English docs (~10 GB) in contiguous document shards, one per rank (strong scaling: the corpus is
 fixed, 10M / N docs per GPU), one RCCL all-gather of the per-shard token totals per step for the offset stitch.
+A plain run sets up, warms up, times --steps steps and prints the line (headline, per-kernel times of the timed steps,
+roofline).  --full adds what the figure does not need: the after-the-clock checks of a document sample against the CPU
+oracle, the sub-records and the CPU baseline.  --dump-outputs DIR writes a seeded sample of the last step's result as .npy.
 Launch: `python bench.py` or `python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N`.
 """
 import argparse
@@ -256,6 +259,38 @@ def verify_host_sample(enc_name, res, text, doc_off, n_sample, ordinary, seed=3)
     return len(sample)
 
 
+def dump_outputs(torch, dev, batch, out_dir, prefix="", n_sample=4096, max_tokens=8 << 20, seed=0):
+    """--dump-outputs: what the timed path handed its caller after the last step (every document's token ids, token offsets
+    and status, in HBM), for a seeded sample of documents (the whole result is gigabytes): doc_ids, token_offsets (start and
+    end of each sampled document in the result, so they carry the token counts of all documents before it), status and
+    tokens (the sampled documents' ids, concatenated; the sample stops before max_tokens ids), as float .npy files."""
+    nt, nd, _ = batch.result()
+    tok_ptr, off_ptr, st_ptr = batch.device_result()
+    off = torch.as_tensor(_DevArray(off_ptr, nd + 1, "<i8"), device=dev)
+    status = torch.as_tensor(_DevArray(st_ptr, nd, "<i4"), device=dev)
+    docs = np.sort(np.random.default_rng(seed).choice(nd, min(nd, n_sample), replace=False))
+    d_docs = torch.from_numpy(docs).to(dev)
+    start, end = off[d_docs].cpu().numpy(), off[d_docs + 1].cpu().numpy()
+    keep = np.cumsum(end - start) <= max_tokens
+    docs, start, end = docs[keep], start[keep], end[keep]
+    lens = end - start
+    assert (lens >= 0).all() and (len(docs) == 0 or int(end[-1]) <= nt), "token offsets out of range"
+    s_off = np.zeros(len(docs) + 1, dtype=np.int64)
+    np.cumsum(lens, out=s_off[1:])
+    tokens = np.zeros(0, dtype=np.int32)
+    if s_off[-1] > 0:
+        idx = np.arange(int(s_off[-1]), dtype=np.int64)
+        idx += np.repeat(start - s_off[:-1], lens)
+        toks = torch.as_tensor(_DevArray(tok_ptr, nt, "<i4"), device=dev)
+        tokens = toks[torch.from_numpy(idx).to(dev)].cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"doc_ids": docs.astype(np.float64), "token_offsets": np.stack([start, end], axis=1).astype(np.float64),
+              "status": status[d_docs[torch.from_numpy(keep).to(dev)]].cpu().numpy().astype(np.float32),
+              "tokens": tokens.astype(np.float32)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, prefix + name + ".npy"), a)
+
+
 def traffic_for(workload_key, kernel):
     """HBM bytes per launch of `kernel` from the committed PMC passes of this workload (profiles/pmc_traffic.json), collected
     and corrected as MI355X_MICROARCH.md prescribes (separate FETCH_SIZE / WRITE_SIZE passes, FETCH_SIZE x 2 on gfx950)."""
@@ -276,18 +311,27 @@ def main():
                     help="headline workload (default: cfg3 at N = 1, cfg4 at N > 1)")
     ap.add_argument("--docs", type=int, default=None, help="documents in the headline corpus (default: the config's stated size)")
     ap.add_argument("--encoding", default="cl100k_base")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the after-the-clock checks against the oracle, the "
+                         "sub-records and the CPU baseline (a plain run sets up, warms up, times the steps and prints the line)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (a seeded document sample of it) as DIR/<name>.npy "
+                         "(bench_outputs/ in the repository is ignored by git)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) skip the CPU baseline")
     ap.add_argument("--cpu-threads", type=int, default=16)
     ap.add_argument("--ordinary", action="store_true",
                     help="time encodeOrdinary() instead of encode() (skips the special-token check of GptBytePairEncoding.java:52-56)")
-    ap.add_argument("--no-verify", action="store_true", help="skip the after-the-clock check of a document sample against the oracle")
-    ap.add_argument("--no-subrecords", action="store_true", help="headline only")
+    ap.add_argument("--no-verify", action="store_true",
+                    help="(with --full) skip the after-the-clock check of a document sample against the oracle")
+    ap.add_argument("--no-subrecords", action="store_true", help="(with --full) headline only")
     ap.add_argument("--no-cfg4", action="store_true", help="skip the cfg4_full sub-record (10M documents on one GPU: about two minutes)")
     ap.add_argument("--chunk-mb", type=int, default=None, help="JTK_OPT_CHUNK_BYTES in MiB (library default: 1024)")
     ap.add_argument("--in-flight", type=int, default=None, help="JTK_OPT_CHUNKS_IN_FLIGHT (library default: 2)")
     ap.add_argument("--serial", action="store_true", help="one chunk at a time (clean per-kernel times, no overlap)")
     ap.add_argument("--gen-workers", type=int, default=None)
     args = ap.parse_args()
+    if not args.full:
+        args.no_verify = args.no_subrecords = args.no_cpu_baseline = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -418,8 +462,12 @@ def main():
     t_max = float(allst[:, 0].max())
     total_bytes = float(allst[:, 1].sum())
 
+    if args.dump_outputs:
+        dump_outputs(torch, dev, batch, args.dump_outputs, "" if world == 1 else "rank%d_" % rank)
+        log("outputs written to %s" % args.dump_outputs)
+
     # after the clock: the stitch's result (every rank sees every total; bases are their exclusive prefix)
-    if comm is not None:
+    if comm is not None and args.full:
         totals, base = comm.fetch(batch.stream())
         assert int(totals[rank]) == nt and int(base) == int(totals[:rank].sum())
         g = d_global_off.cpu().numpy()

@@ -1109,7 +1109,7 @@ def test_bench_two_rank_rehearsal():
     env = dict(os.environ, JTK_BENCH_REHEARSAL="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", "29517", os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--docs", "200000",
-           "--no-cpu-baseline"]
+           "--full", "--no-cpu-baseline"]
     p = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600, cwd=ROOT)
     assert p.returncode == 0, (p.returncode, p.stdout[-500:], p.stderr[-1500:])
     line = [l for l in p.stdout.splitlines() if l.startswith("{")][-1]

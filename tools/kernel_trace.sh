@@ -7,5 +7,5 @@ root=$(pwd)
 out=$root/gpurun_out/kt_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --stats --output-format csv -d $out -o kt -- python3 $root/bench.py --no-cpu-baseline "$@" > $out/bench.json 2> $out/rocprof.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $out -o kt -- python3 $root/bench.py --full --no-cpu-baseline "$@" > $out/bench.json 2> $out/rocprof.log
 cat $out/bench.json

@@ -11,7 +11,7 @@ mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 pass() {
   name=$1; shift
-  rocprofv3 --pmc "$@" -d $out/$name -o c -- python3 $root/bench.py --steps 2 --warmup 1 --no-cpu-baseline $BENCH_ARGS > $out/$name.log 2>&1
+  rocprofv3 --pmc "$@" -d $out/$name -o c -- python3 $root/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline $BENCH_ARGS > $out/$name.log 2>&1
   echo "pass $name done"
 }
 BENCH_ARGS="$*"

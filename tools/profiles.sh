@@ -1,8 +1,8 @@
 #!/bin/bash
 # Profiles of the headline run, committed under profiles/ (run through gpurun from the repo root):
 #   bash tools/profiles.sh <tag>
-# 1. rocprofv3 --kernel-trace --stats of `python bench.py --no-subrecords --no-cpu-baseline` (the headline alone: the
-#    default command adds the sub-records' workloads to the same process)
+# 1. rocprofv3 --kernel-trace --stats of `python bench.py --full --no-subrecords --no-cpu-baseline` (the headline alone,
+#    checked against the oracle after the clock: --full alone adds the sub-records' workloads to the same process)
 # 2. PMC passes (one counter group per run, never combined with trace domains) of a one-chunk slice of the headline corpus
 #    (250k docs = 1 GiB = one launch of every kernel, as in the headline's chunks) and of configs[1]
 set +e
@@ -12,7 +12,7 @@ out=$root/gpurun_out/prof_$tag
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 if [ ! -s $out/bench_under_rocprof.json ]; then
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt -o kt -- python3 $root/bench.py --no-subrecords --no-cpu-baseline > $out/bench_under_rocprof.json 2> $out/kt.log
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/kt -o kt -- python3 $root/bench.py --full --no-subrecords --no-cpu-baseline > $out/bench_under_rocprof.json 2> $out/kt.log
 fi
 cd $root
 cp $(find $out/kt -name "*kernel_stats.csv" | head -1) $out/kernel_stats.csv

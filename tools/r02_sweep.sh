@@ -9,4 +9,4 @@ d=json.loads(sys.stdin.read())
 print('$wl | $opt |', d['value'], 'MB/s', d['ms_per_step'], 'ms', {k:round(v,2) for k,v in d['kernel_ms'].items() if v>0.05})
 "
 done; done
-python bench.py --workload cfg2 --steps 10 --warmup 2 --no-subrecords --no-cpu-baseline 2>/dev/null | cut -c1-900
+python bench.py --workload cfg2 --steps 10 --warmup 2 --full --no-subrecords --no-cpu-baseline 2>/dev/null | cut -c1-900
