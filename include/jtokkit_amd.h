@@ -214,6 +214,26 @@ int jtk_batch_device_truncated(jtk_batch* b, const int64_t** d_kept, const uint8
 int jtk_batch_encode_max_tokens(jtk_batch* b, const uint8_t* utf8, const int64_t* doc_off, int64_t n_docs, uint32_t flags,
                                 int64_t max_tokens, int32_t* tokens, int64_t* kept, uint8_t* truncated, int32_t* status);
 
+/* Encoding.encode(String, maxTokens) / encodeOrdinary(String, maxTokens) (GptBytePairEncoding.java:43-45, 66-69, 79-100) for
+ * every document of a device-resident batch, with the early exit of jtk_batch_encode_max_tokens, on the device.
+ * d_tokens[n_docs * max_tokens]: row d holds document d's first kept[d] ids, then pad_id up to max_tokens.
+ *   Results: tokens[:kept], kept, truncated and status equal what jtk_batch_encode_max_tokens returns on the same bytes
+ *            (its conservative JTK_ERR_UNENCODABLE rule included).  Rows that get no tokens (special-token and error
+ *            documents among them) are all pad_id.  status[d]: JTK_OK, JTK_ERR_UNSUPPORTED_SPECIAL, JTK_ERR_UNENCODABLE ...
+ *   flags:   JTK_ENCODE_ORDINARY or 0 (anything else: JTK_ERR_INVALID_ARGUMENT).
+ *   Input:   d_utf8 needs no alignment (the library encodes its own aligned copy of the documents' leading bytes); only the
+ *            16-byte blocks that hold [0, n_bytes) are read.  d_doc_off[n_docs + 1] is checked on the device: offsets that are
+ *            decreasing or outside [0, n_bytes] make the call return JTK_ERR_INVALID_ARGUMENT, and no row is written.
+ *   Order:   the work is ordered on stream_or_null (a hipStream_t), or on the batch's stream when it is NULL, like
+ *            jtk_batch_encode_device.  The call waits for the device once per round, to read a 16-byte word (open
+ *            documents, gathered bytes), plus the chunk plan's wait when the leading bytes span more than one chunk
+ *            (JTK_OPT_CHUNK_BYTES).  It returns when all rows are written.
+ *   Batch:   afterwards the batch holds no encode result: jtk_batch_fetch / jtk_batch_truncate fail until the next encode. */
+int jtk_batch_encode_device_max_tokens(jtk_batch* b, const uint8_t* d_utf8, const int64_t* d_doc_off, int64_t n_docs,
+                                       int64_t n_bytes, uint32_t flags, int64_t max_tokens, int32_t pad_id,
+                                       int32_t* d_tokens, int64_t* d_kept, uint8_t* d_truncated, int32_t* d_status,
+                                       void* stream_or_null);
+
 /* ---- batch decode on the device ---------------------------------------------------------------------
  * Replaces a loop of Encoding.decodeBytes(List<Integer>) (GptBytePairEncoding.java:137-151, 302-314; special-token
  * ids decode to their literals, :308-311) over n_seqs token lists: all ids back to back in `ids`, list q occupying

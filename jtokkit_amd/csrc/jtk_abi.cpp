@@ -15,6 +15,7 @@
 
 #include "../../include/jtokkit_amd.h"
 #include "jtk_kernels.h"
+#include "jtk_maxtok_rules.h"
 #include "jtk_tables.h"
 
 namespace {
@@ -128,6 +129,8 @@ struct jtk_batch {
     // batch decode (jtk_batch_decode*)
     DevBuf dec_in_ids, dec_in_off, dec_zero, dec_tile, dec_pre, dec_out, dec_byte_off;
     DevBuf trunc_kept, trunc_flag;   // jtk_batch_truncate
+    DevBuf mt_scratch, mt_gather;    // jtk_batch_encode_device_max_tokens: per-document state of the rounds | the gathered prefixes
+    int64_t* h_mt = nullptr; size_t h_mt_cap = 0;   // pinned: the round's (open documents, gathered bytes)
     bool have_trunc = false;
     JtkDecodeWork dwork{};
     bool have_decode = false;
@@ -383,7 +386,8 @@ void jtk_batch_destroy(jtk_batch* b) {
         if (cs.stream) (void)hipStreamDestroy(cs.stream);
     }
     DevBuf* bufs[] = {&b->in_text, &b->in_off, &b->in_pieces, &b->out, &b->plan, &b->dec_in_ids, &b->dec_in_off,
-                      &b->dec_zero, &b->dec_tile, &b->dec_pre, &b->dec_out, &b->dec_byte_off, &b->trunc_kept, &b->trunc_flag};
+                      &b->dec_zero, &b->dec_tile, &b->dec_pre, &b->dec_out, &b->dec_byte_off, &b->trunc_kept, &b->trunc_flag,
+                      &b->mt_scratch, &b->mt_gather};
     for (DevBuf* d : bufs) d->release();
     for (hipEvent_t ev : b->prof_ev) (void)hipEventDestroy(ev);
     if (b->ev_fork) (void)hipEventDestroy(b->ev_fork);
@@ -394,6 +398,7 @@ void jtk_batch_destroy(jtk_batch* b) {
     if (b->h_small) (void)hipHostFree(b->h_small);
     if (b->h_in) (void)hipHostFree(b->h_in);
     if (b->h_gather) (void)hipHostFree(b->h_gather);
+    if (b->h_mt) (void)hipHostFree(b->h_mt);
     if (b->host_plan) (void)hipHostFree(b->host_plan);
     if (b->h_tokens) (void)hipHostFree(b->h_tokens);
     if (b->h_tok_off) (void)hipHostFree(b->h_tok_off);
@@ -531,8 +536,10 @@ struct PieceArgs {               // caller-supplied pieces instead of pretok_spl
     int64_t n;
 };
 
+// mt != NULL: the maxTokens decision (jtk_batch_encode_device_max_tokens) runs as every chunk's epilogue, on the chunk's stream
+// behind doc_offsets, while the chunk's piece mask is still in its scratch set.
 int run_job(jtk_batch* b, const uint8_t* d_text, const uint8_t* h_text, const int64_t* d_doc_off, int64_t n_docs, int64_t n_bytes,
-            uint32_t flags, hipStream_t s, bool to_host, const PieceArgs* pieces = nullptr) {
+            uint32_t flags, hipStream_t s, bool to_host, const PieceArgs* pieces = nullptr, const JtkMaxTokWork* mt = nullptr) {
     const jtk_encoding* enc = b->enc;
     const int n_chunks = (int)b->chunk_doc.size() - 1;
     // (ids streamed to the host chunk by chunk: the host waits for a chunk's scan before it can issue that chunk's copy, one
@@ -695,6 +702,7 @@ int run_job(jtk_batch* b, const uint8_t* d_text, const uint8_t* h_text, const in
         jtk_launch_doc_offsets(w, cst);
         if (enc->dt.pseudo_base) jtk_launch_flag_unencodable(w, enc->dt.pseudo_base, cst);
         end();
+        if (mt) jtk_launch_maxtok_decide(w, *mt, d0, cst);
         HIP_TRY(hipGetLastError());
         if (small_to_host && !zero_copy_out) {
             // the whole answer in one copy: header, status, offsets and the worst-case token range (one token per byte)
@@ -742,24 +750,9 @@ int run_job(jtk_batch* b, const uint8_t* d_text, const uint8_t* h_text, const in
     return JTK_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int jtk_batch_encode_device(jtk_batch* b, const uint8_t* d_utf8, const int64_t* d_doc_off, int64_t n_docs,
-                            int64_t n_bytes, uint32_t flags, void* stream_or_null, int64_t* n_tokens) {
-    if (!b || n_docs < 0 || n_bytes < 0 || (n_bytes > 0 && !d_utf8) || !d_doc_off)
-        return fail(JTK_ERR_INVALID_ARGUMENT, "bad arguments");
-    if (((uintptr_t)d_utf8 & 15u) != 0) return fail(JTK_ERR_INVALID_ARGUMENT, "device text must be 16-byte aligned");
-    if (n_bytes >= (int64_t)1 << 37) return fail(JTK_ERR_INVALID_ARGUMENT, "batch too large (128 GiB of text per call at most)");
-    if (flags & JTK_ENCODE_TO_HOST) return fail(JTK_ERR_INVALID_ARGUMENT, "JTK_ENCODE_TO_HOST is for jtk_batch_encode (host buffers)");
-    HIP_TRY(hipSetDevice(b->enc->device));
-    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
-    // chunk plan: a batch of up to one chunk needs none; a larger one reads the chunk boundaries from the offsets (the one
-    // place where this call waits for the work queued on `s` before it)
-    const bool same_plan = b->reuse_plan && b->plan_doc_off == d_doc_off && b->plan_docs == n_docs && b->plan_bytes == n_bytes && b->plan_chunk_bytes == b->chunk_bytes &&
-                           b->chunk_doc.size() >= 2 && b->chunk_doc.back() == n_docs && b->chunk_off.back() == n_bytes;
-    if (!same_plan) {
+// Chunk plan of a batch whose offsets are in device memory: a batch of up to one chunk needs none; a larger one reads the chunk
+// boundaries from the offsets (the one place where this waits for the work queued on `s` before it).
+int plan_device_chunks(jtk_batch* b, const int64_t* d_doc_off, int64_t n_docs, int64_t n_bytes, hipStream_t s) {
     b->chunk_doc.assign(1, 0);
     b->chunk_off.assign(1, 0);
     if (n_bytes > b->chunk_bytes + b->chunk_bytes / 4 && n_docs > 1) {
@@ -784,7 +777,30 @@ int jtk_batch_encode_device(jtk_batch* b, const uint8_t* d_utf8, const int64_t* 
     }
     b->chunk_doc.push_back(n_docs);
     b->chunk_off.push_back(n_bytes);
-    b->plan_doc_off = d_doc_off; b->plan_docs = n_docs; b->plan_bytes = n_bytes; b->plan_chunk_bytes = b->chunk_bytes;
+    return JTK_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int jtk_batch_encode_device(jtk_batch* b, const uint8_t* d_utf8, const int64_t* d_doc_off, int64_t n_docs,
+                            int64_t n_bytes, uint32_t flags, void* stream_or_null, int64_t* n_tokens) {
+    if (!b || n_docs < 0 || n_bytes < 0 || (n_bytes > 0 && !d_utf8) || !d_doc_off)
+        return fail(JTK_ERR_INVALID_ARGUMENT, "bad arguments");
+    if (((uintptr_t)d_utf8 & 15u) != 0) return fail(JTK_ERR_INVALID_ARGUMENT, "device text must be 16-byte aligned");
+    if (n_bytes >= (int64_t)1 << 37) return fail(JTK_ERR_INVALID_ARGUMENT, "batch too large (128 GiB of text per call at most)");
+    if (flags & JTK_ENCODE_TO_HOST) return fail(JTK_ERR_INVALID_ARGUMENT, "JTK_ENCODE_TO_HOST is for jtk_batch_encode (host buffers)");
+    HIP_TRY(hipSetDevice(b->enc->device));
+    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    // chunk plan: a batch of up to one chunk needs none; a larger one reads the chunk boundaries from the offsets (the one
+    // place where this call waits for the work queued on `s` before it)
+    const bool same_plan = b->reuse_plan && b->plan_doc_off == d_doc_off && b->plan_docs == n_docs && b->plan_bytes == n_bytes && b->plan_chunk_bytes == b->chunk_bytes &&
+                           b->chunk_doc.size() >= 2 && b->chunk_doc.back() == n_docs && b->chunk_off.back() == n_bytes;
+    if (!same_plan) {
+        const int rc = plan_device_chunks(b, d_doc_off, n_docs, n_bytes, s);
+        if (rc != JTK_OK) return rc;
+        b->plan_doc_off = d_doc_off; b->plan_docs = n_docs; b->plan_bytes = n_bytes; b->plan_chunk_bytes = b->chunk_bytes;
     }
     int rc = run_job(b, d_utf8, nullptr, d_doc_off, n_docs, n_bytes, flags, s, false);
     if (rc != JTK_OK) b->plan_doc_off = nullptr;
@@ -1128,40 +1144,14 @@ int jtk_decode(const jtk_encoding* enc, const int32_t* ids, int64_t n, uint8_t* 
 // tokens.  Returns the count kept; *truncated = EncodingResult.isTruncated().
 int64_t jtk_max_tokens_backoff(const jtk_encoding* enc, const uint8_t* utf8, int64_t len, const int32_t* head, int64_t nt,
                                int64_t max_tokens, int* truncated) {
-    int64_t keep = nt < max_tokens ? nt : max_tokens;
-    static thread_local std::vector<int64_t> cum;
-    cum.assign((size_t)keep + 1, 0);
-    for (int64_t k = 0; k < keep; k++) cum[(size_t)k + 1] = cum[(size_t)k] + enc->tok_len[(size_t)head[(size_t)k]];
-    if (truncated) *truncated = 0;
-    // does text[from:] hold more than `k` UTF-16 units?  (looks at the first few bytes only: the document may be long)
-    auto more_units_than = [&](int64_t from, int64_t k) {
-        int64_t u = 0;
-        for (int64_t i = from; i < len; i++)
-            if ((utf8[i] & 0xC0) != 0x80) { u += (utf8[i] >= 0xF0) ? 2 : 1; if (u > k) return true; }
-        return false;
-    };
-    for (;; keep--) {
-        // decode(tokens) is the byte prefix [0, nb) of the text.  text.startsWith(decoded) holds when
-        // nb is a code-point boundary, or when the cut character decodes to one U+FFFD and the text
-        // has U+FFFD there.  truncated = text.length() > decoded.length(), both in UTF-16 units: the units before the
-        // cut are common to both, so only the text from the cut on is counted.
-        const int64_t nb = cum[(size_t)keep];
-        const bool boundary = (nb == len) || ((utf8[nb] & 0xC0) != 0x80);
-        bool starts, longer;
-        if (boundary) { starts = true; longer = more_units_than(nb, 0); }
-        else {
-            int64_t c = nb;
-            while (c > 0 && (utf8[c] & 0xC0) == 0x80) c--;
-            starts = (c + 2 < len) && utf8[c] == 0xEF && utf8[c + 1] == 0xBF && utf8[c + 2] == 0xBD;
-            longer = more_units_than(c, 1);                       // the decoded text ends in one U+FFFD for the cut character
-        }
-        if (starts) {
-            if (truncated) *truncated = longer;
-            break;
-        }
-        if (keep == 0) break;
-    }
-    return keep;
+    const int64_t keep = nt < max_tokens ? nt : max_tokens;
+    int64_t nb = 0;
+    for (int64_t k = 0; k < keep; k++) nb += enc->tok_len[(size_t)head[(size_t)k]];
+    // truncated = text.length() > decoded.length(), both in UTF-16 units: the units before the cut are common to both, so only
+    // the text from the cut on is counted
+    const JtkBackoff r = jtk_maxtok_backoff(utf8, len, keep, nb, [&](int64_t k) { return (int64_t)enc->tok_len[(size_t)head[(size_t)k]]; });
+    if (truncated) *truncated = r.ok && jtk_more_units_than(utf8, r.from, len, r.units);
+    return r.keep;
 }
 
 extern "C" {
@@ -1207,10 +1197,6 @@ int jtk_encode(jtk_batch* b, const uint8_t* utf8, int64_t len, uint32_t flags, i
     return JTK_OK;
 }
 
-// A byte that may begin a white-space character: the ASCII ones, and the lead bytes of U+0085/U+00A0 (C2), U+1680 (E1),
-// U+2000..U+205F (E2) and U+3000 (E3).  Conservative on purpose: it only ever makes the early exit below look further.
-static inline bool maybe_space(uint8_t c) { return (c >= 0x09 && c <= 0x0D) || c == 0x20 || c == 0xC2 || c == 0xE1 || c == 0xE2 || c == 0xE3; }
-
 // Encoding.encode(text, maxTokens) for every document, without encoding the documents whole.  The reference stops matching
 // once maxTokens tokens exist (GptBytePairEncoding.java:83-88); here each document's leading P bytes are encoded (P = 8 bytes
 // per wanted token + 64 to begin with), and the result is taken when it is certain to be the head of the document's full token
@@ -1247,9 +1233,8 @@ int jtk_batch_encode_max_tokens(jtk_batch* b, const uint8_t* utf8, const int64_t
         }
         active.push_back(d);
     }
-    const int64_t margin = 16;
     const int64_t cb = b->host_chunk_bytes < b->chunk_bytes ? b->host_chunk_bytes : b->chunk_bytes;   // a group stays one chunk
-    int64_t P = max_tokens > ((int64_t)1 << 40) ? (int64_t)1 << 44 : 8 * max_tokens + 64;
+    int64_t P = jtk_maxtok_first_prefix(max_tokens);
     uint8_t* gtext = nullptr;                                        // (pinned: the prefixes go down by DMA while the kernels start)
     std::vector<int64_t> goff, next_active;
     std::vector<uint64_t> mask;
@@ -1267,8 +1252,7 @@ int jtk_batch_encode_max_tokens(jtk_batch* b, const uint8_t* utf8, const int64_t
             goff.assign(1, 0);
             while (a1 < active.size()) {
                 const int64_t d = active[a1], len = doc_off[d + 1] - doc_off[d];
-                int64_t p = len < P ? len : P;
-                if (p > cb) p = len;                                 // past one host chunk the document goes whole, and alone
+                const int64_t p = jtk_maxtok_prefix_bytes(len, P, cb);     // past one host chunk the document goes whole, and alone
                 if (a1 > a0 && gbytes + p > cb) break;
                 gbytes += p;
                 goff.push_back(gbytes);
@@ -1322,30 +1306,12 @@ int jtk_batch_encode_max_tokens(jtk_batch* b, const uint8_t* utf8, const int64_t
                     int64_t k = -1;
                     if (p == len) k = n;
                     else {
-                        // the last safe piece start at or before p - margin
-                        const uint8_t* t = gtext + goff[i];
-                        int64_t q = 0;
-                        for (int64_t pos = goff[i] + p - margin; pos > goff[i]; ) {
-                            uint64_t w = mask[(size_t)(pos >> 6)];
-                            const int sh = (int)(pos & 63);
-                            w = sh == 63 ? w : (w & ((2ull << sh) - 1));                 // bits 0..sh
-                            const int64_t wbase = pos & ~(int64_t)63;
-                            bool found = false;
-                            while (w) {
-                                const int bit = 63 - __builtin_clzll(w);
-                                const int64_t cand = wbase + bit;
-                                if (cand <= goff[i]) { w = 0; break; }
-                                const uint8_t c0 = t[cand - goff[i]], c1 = t[cand - goff[i] + 1];
-                                if (!maybe_space(c0) || (c0 < 0x80 && !maybe_space(c1))) { q = cand - goff[i]; found = true; break; }
-                                w &= ~(1ull << bit);
-                            }
-                            if (found) break;
-                            pos = wbase - 1;
-                        }
-                        if (q > 0) {
-                            int64_t cum = 0, kk = 0;
-                            while (kk < n && kk < max_tokens && cum < q) cum += enc->tok_len[(size_t)toks[t0 + kk]], kk++;
-                            if (cum <= q && kk >= max_tokens) k = kk;                   // maxTokens tokens, all before q
+                        // the last safe piece start at or before p - JTK_MAXTOK_MARGIN
+                        const int64_t q = jtk_maxtok_last_safe_start(mask.data(), goff[i], gtext + goff[i], p);
+                        if (q > 0 && n >= max_tokens) {
+                            int64_t cum = 0;
+                            for (int64_t kk = 0; kk < max_tokens && cum <= q; kk++) cum += enc->tok_len[(size_t)toks[t0 + kk]];
+                            if (jtk_maxtok_decided(n, max_tokens, cum, q)) k = max_tokens;          // maxTokens tokens, all before q
                         }
                     }
                     if (k < 0) { again[slice].push_back(d); continue; }
@@ -1365,8 +1331,108 @@ int jtk_batch_encode_max_tokens(jtk_batch* b, const uint8_t* utf8, const int64_t
         if (trace) fprintf(stderr, "[max_tokens] P=%lld docs=%zu -> %zu again; gather %.2f encode %.2f mask %.2f decide(incl. mask) %.2f ms; %.2f ms since the rounds began\n",
                            (long long)P, active.size(), next_active.size(), t_gather, t_enc, t_mask, t_dec, now() - t_begin);
         active.swap(next_active);
-        P = P > ((int64_t)1 << 40) ? P : P * 4;
+        P = jtk_maxtok_next_prefix(P);
     }
+    return JTK_OK;
+}
+
+// jtk_batch_encode_max_tokens with device input and device rows: the same rounds, as kernels (jtk_maxtok.hip).  Per round the
+// host reads one 16-byte word (open documents, gathered bytes) to size the gather and the encode; everything else stays on the
+// device.  The decisions run as run_job's per-chunk epilogue.
+int jtk_batch_encode_device_max_tokens(jtk_batch* b, const uint8_t* d_utf8, const int64_t* d_doc_off, int64_t n_docs,
+                                       int64_t n_bytes, uint32_t flags, int64_t max_tokens, int32_t pad_id,
+                                       int32_t* d_tokens, int64_t* d_kept, uint8_t* d_truncated, int32_t* d_status,
+                                       void* stream_or_null) {
+    if (!b || n_docs < 0 || n_bytes < 0 || (n_bytes > 0 && !d_utf8) || !d_doc_off || max_tokens < 0 ||
+        (max_tokens > 0 && n_docs > 0 && !d_tokens) || (n_docs > 0 && (!d_kept || !d_truncated || !d_status)))
+        return fail(JTK_ERR_INVALID_ARGUMENT, "bad arguments");
+    if (flags & ~(uint32_t)JTK_ENCODE_ORDINARY) return fail(JTK_ERR_INVALID_ARGUMENT, "flags: JTK_ENCODE_ORDINARY or 0");
+    if (n_bytes >= (int64_t)1 << 37) return fail(JTK_ERR_INVALID_ARGUMENT, "batch too large (128 GiB of text per call at most)");
+    const jtk_encoding* enc = b->enc;
+    HIP_TRY(hipSetDevice(enc->device));
+    // the batch's last encode result is given up (its chunk plan and scratch are reused below)
+    b->have_result = false;
+    b->have_trunc = false;
+    b->plan_doc_off = nullptr;
+    if (n_docs == 0) return JTK_OK;
+    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    const size_t nd = (size_t)n_docs;
+    const int64_t n_blk = (n_docs + 1023) / 1024;
+    // scratch: hdr (4 x i64: open documents, gathered bytes, bad flag) | act[2][nd] | goff[nd + 1] | blk_base[2 * n_blk] |
+    //          blk_bytes[n_blk] | blk_cnt[n_blk] | special[nd] | again[2][nd]
+    const size_t o_act = 32, o_goff = o_act + 2 * nd * 8, o_base = o_goff + (nd + 1) * 8, o_bb = o_base + (size_t)n_blk * 16,
+                 o_bc = o_bb + (size_t)n_blk * 8, o_sp = align_up(o_bc + (size_t)n_blk * 4, 16), o_ag = o_sp + align_up(nd, 16),
+                 total = o_ag + 2 * align_up(nd, 16);
+    int rc;
+    if ((rc = b->mt_scratch.ensure(total)) || (rc = ensure_pinned((void**)&b->h_mt, &b->h_mt_cap, 16, 0))) return rc;
+    uint8_t* z = (uint8_t*)b->mt_scratch.p;
+    JtkMaxTokWork m{};
+    m.text = d_utf8; m.doc_off = d_doc_off; m.n_docs = n_docs; m.n_bytes = n_bytes;
+    m.max_tokens = max_tokens; m.pad_id = pad_id;
+    m.out_tokens = d_tokens; m.out_kept = d_kept; m.out_truncated = d_truncated; m.out_status = d_status;
+    m.hdr = (int64_t*)z; m.bad = (uint32_t*)(z + 16);
+    m.goff = (int64_t*)(z + o_goff);
+    m.blk_base = (int64_t*)(z + o_base); m.blk_bytes = (int64_t*)(z + o_bb); m.blk_cnt = (uint32_t*)(z + o_bc);
+    m.special = z + o_sp;
+    m.tab_off = (const uint32_t*)enc->dec_off.p; m.n_ids_table = enc->n_ids_table;
+    int64_t* act[2] = {(int64_t*)(z + o_act), (int64_t*)(z + o_act) + nd};
+    uint8_t* again[2] = {z + o_ag, z + o_ag + align_up(nd, 16)};
+    // round 1: offsets, encode()'s special-token check over the whole text, the rows that need no encode
+    HIP_TRY(hipMemsetAsync(z, 0, 32, s));
+    HIP_TRY(hipMemsetAsync(m.special, 0, nd, s));
+    jtk_launch_maxtok_check(m, s);
+    if (!(flags & JTK_ENCODE_ORDINARY)) jtk_launch_maxtok_special(m, enc->dt, s);
+    jtk_launch_maxtok_finish_closed(m, s);
+    HIP_TRY(hipGetLastError());
+    // as on the host (jtk_batch_encode_max_tokens): the same prefix sizes, so that the same bytes are encoded
+    const int64_t cb = b->host_chunk_bytes < b->chunk_bytes ? b->host_chunk_bytes : b->chunk_bytes;
+    const bool trace = getenv("JTK_MAXTOK_TRACE") != nullptr;
+    int64_t n_in = n_docs;
+    for (int round = 1;; round++) {
+        const int cur = (round - 1) & 1;
+        m.round = round;
+        m.P = round == 1 ? jtk_maxtok_first_prefix(max_tokens) : jtk_maxtok_next_prefix(m.P);
+        m.cb = cb;
+        m.n_in = n_in;
+        m.n_blk = (n_in + 1023) / 1024;
+        m.act_in = act[cur ^ 1]; m.again_in = again[cur ^ 1];
+        m.act = act[cur]; m.again = again[cur];
+        hipEvent_t ev[5] = {};
+        if (trace) for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
+        if (trace) HIP_TRY(hipEventRecord(ev[0], s));
+        jtk_launch_maxtok_plan(m, s);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(b->h_mt, m.hdr, 16, hipMemcpyDeviceToHost, s));
+        if (trace) HIP_TRY(hipEventRecord(ev[1], s));
+        HIP_TRY(hipStreamSynchronize(s));
+        const int64_t n_act = b->h_mt[0], gbytes = b->h_mt[1];
+        if (n_act < 0) return fail(JTK_ERR_INVALID_ARGUMENT, "document offsets are not non-decreasing within [0, n_bytes]");
+        if (n_act == 0) { if (trace) for (auto& e : ev) (void)hipEventDestroy(e); break; }
+        if ((rc = b->mt_gather.ensure((size_t)gbytes + 64))) return rc;
+        m.gather = (uint8_t*)b->mt_gather.p;
+        m.gbytes = gbytes;
+        jtk_launch_maxtok_gather(m, n_act, s);
+        HIP_TRY(hipGetLastError());
+        if (trace) HIP_TRY(hipEventRecord(ev[2], s));
+        if ((rc = plan_device_chunks(b, m.goff, n_act, gbytes, s))) return rc;
+        if (trace) HIP_TRY(hipEventRecord(ev[3], s));
+        rc = run_job(b, m.gather, nullptr, m.goff, n_act, gbytes, JTK_ENCODE_ORDINARY, s, false, nullptr, &m);
+        if (rc != JTK_OK) return rc;
+        if (trace) {
+            HIP_TRY(hipEventRecord(ev[4], s));
+            HIP_TRY(hipStreamSynchronize(s));
+            float t_plan = 0, t_gather = 0, t_encode = 0;
+            (void)hipEventElapsedTime(&t_plan, ev[0], ev[1]);
+            (void)hipEventElapsedTime(&t_gather, ev[1], ev[2]);
+            (void)hipEventElapsedTime(&t_encode, ev[3], ev[4]);
+            fprintf(stderr, "[device max_tokens] round %d P=%lld docs=%lld bytes=%lld chunks=%zu: plan %.3f gather %.3f encode+decide %.3f ms\n",
+                    round, (long long)m.P, (long long)n_act, (long long)gbytes, b->chunk_doc.size() - 1, t_plan, t_gather, t_encode);
+            for (auto& e : ev) (void)hipEventDestroy(e);
+        }
+        n_in = n_act;
+    }
+    b->have_result = false;
+    b->plan_doc_off = nullptr;
     return JTK_OK;
 }
 

@@ -10,6 +10,7 @@
 //   dec_offsets  byte_off[q] per sequence
 // Integer / byte gather work; bound by the random reads of the token byte strings (L2-resident blob).
 #include "jtk_kernels.h"
+#include "jtk_maxtok_rules.h"
 
 namespace {
 
@@ -169,16 +170,12 @@ __global__ void __launch_bounds__(256) k_truncate(JtkTruncWork w) {
         const int64_t len = w.doc_off[d + 1] - w.doc_off[d];
         int64_t nb = 0;
         for (int64_t k = 0; k < keep; k++) { const int32_t id = w.tokens[t0 + k]; nb += w.tab_off[id + 1] - w.tab_off[id]; }
-        for (;; keep--) {
-            const bool boundary = (nb == len) || ((tx[nb] & 0xC0) != 0x80);
-            if (boundary) { trunc = nb < len; break; }
-            int64_t c = nb;
-            while (c > 0 && (tx[c] & 0xC0) == 0x80) c--;
-            if (c + 2 < len && tx[c] == 0xEF && tx[c + 1] == 0xBF && tx[c + 2] == 0xBD) { trunc = c + 3 < len; break; }
-            if (keep == 0) break;
-            const int32_t id = w.tokens[t0 + keep - 1];
-            nb -= w.tab_off[id + 1] - w.tab_off[id];
-        }
+        const JtkBackoff r = jtk_maxtok_backoff(tx, len, keep, nb, [&](int64_t k) {
+            const int32_t id = w.tokens[t0 + k];
+            return (int64_t)(w.tab_off[id + 1] - w.tab_off[id]);
+        });
+        keep = r.keep;
+        trunc = r.ok && (r.units == 0 ? r.from < len : r.from + 3 < len);
     }
     w.kept[d] = keep;
     w.truncated[d] = trunc;

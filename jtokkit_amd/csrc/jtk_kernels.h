@@ -196,6 +196,47 @@ struct JtkTruncWork {
     uint8_t* truncated;         // [n_docs] EncodingResult.isTruncated()
 };
 void jtk_launch_truncate(const JtkTruncWork& w, hipStream_t s);
+// Device-side state of jtk_batch_encode_device_max_tokens (jtk_maxtok.hip): the caller's batch and output rows, and the
+// rounds of the early exit.  A round takes the documents that are still open (round 1: all), gathers their leading bytes
+// back to back into `gather` (slot i = the round's i-th open document, bytes [goff[i], goff[i + 1])), encodes them with
+// run_job and decides per chunk which documents are done.
+struct JtkMaxTokWork {
+    const uint8_t* text;        // caller text (any alignment; only the 16-byte blocks that hold [0, n_bytes) are read)
+    const int64_t* doc_off;     // [n_docs + 1] caller offsets into text
+    int64_t n_docs, n_bytes;
+    int64_t max_tokens;
+    int32_t pad_id;
+    int32_t round;              // 1, 2, ...
+    int32_t* out_tokens;        // [n_docs * max_tokens] rows
+    int64_t* out_kept;          // [n_docs]
+    uint8_t* out_truncated;     // [n_docs]
+    int32_t* out_status;        // [n_docs]
+    uint8_t* special;           // [n_docs] encode(): the document holds a special-token literal (round 1)
+    uint32_t* bad;              // the offsets are not non-decreasing within [0, n_bytes]
+    int64_t* hdr;               // [2] after the plan: open documents of this round (-1: bad offsets), gathered bytes
+    int64_t P, cb;              // prefix size of this round; documents whose prefix exceeds cb go whole
+    const int64_t* act_in;      // round > 1: the documents of the previous round [n_in] ...
+    const uint8_t* again_in;    //            ... and whether each is still open
+    int64_t n_in;               // items the plan looks at (round 1: n_docs)
+    int64_t* act;               // [n_docs] this round's documents, in document order
+    int64_t* goff;              // [n_docs + 1] their prefixes in the gather buffer
+    uint8_t* again;             // [n_docs] per slot of this round: still open after the decision
+    uint32_t* blk_cnt;          // [n_blk] plan: open documents per block of 1024 items
+    int64_t* blk_bytes;         // [n_blk] ... and their prefix bytes
+    int64_t* blk_base;          // [2 * n_blk] exclusive scans of both
+    int64_t n_blk;
+    uint8_t* gather;            // the prefixes (16-byte aligned, 64 bytes of tail)
+    int64_t gbytes;             // gathered bytes of this round
+    const uint32_t* tab_off;    // decode table offsets (token byte lengths)
+    uint32_t n_ids_table;
+};
+void jtk_launch_maxtok_check(const JtkMaxTokWork& m, hipStream_t s);                              // offsets valid?
+void jtk_launch_maxtok_special(const JtkMaxTokWork& m, const JtkDeviceTables& t, hipStream_t s);  // text.contains(literal)
+void jtk_launch_maxtok_finish_closed(const JtkMaxTokWork& m, hipStream_t s);                      // round 1: rows needing no encode
+void jtk_launch_maxtok_plan(const JtkMaxTokWork& m, hipStream_t s);                               // count, scan, place
+void jtk_launch_maxtok_gather(const JtkMaxTokWork& m, int64_t n_act, hipStream_t s);
+// per-chunk epilogue of run_job: chunk documents are slots [slot0, slot0 + w.n_docs) of the round
+void jtk_launch_maxtok_decide(const JtkWork& w, const JtkMaxTokWork& m, int64_t slot0, hipStream_t s);
 void jtk_launch_decode_count(const JtkDecodeWork& w, hipStream_t s);     // mark, count, scan
 void jtk_launch_decode_scatter(const JtkDecodeWork& w, hipStream_t s);   // scatter, offsets
 

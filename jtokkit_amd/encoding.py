@@ -213,6 +213,14 @@ class Batch:
                                                    kept.ctypes.data, flag.ctypes.data, status.ctypes.data))
         return toks, kept, flag, status
 
+    def encode_device_max_tokens(self, d_text_ptr, d_doc_off_ptr, n_docs, n_bytes, max_tokens, d_tokens_ptr, d_kept_ptr,
+                                 d_trunc_ptr, d_status_ptr, ordinary=False, pad_id=-1, stream=None):
+        """jtk_batch_encode_device_max_tokens: device text and offsets in, rows [n_docs, max_tokens] (int32, pad_id after the
+        kept ids), kept (int64), truncated (uint8) and status (int32) out, all device pointers; ordered on `stream`."""
+        _check(N.lib().jtk_batch_encode_device_max_tokens(self._h, d_text_ptr, d_doc_off_ptr, int(n_docs), int(n_bytes),
+                                                          N.JTK_ENCODE_ORDINARY if ordinary else 0, int(max_tokens), int(pad_id),
+                                                          d_tokens_ptr, d_kept_ptr, d_trunc_ptr, d_status_ptr, stream))
+
     def truncate(self, max_tokens):
         """Encoding.encode(text, maxTokens) for every document of the last encode -> (kept int64[n], truncated bool[n])."""
         _check(N.lib().jtk_batch_truncate(self._h, int(max_tokens)))
@@ -457,6 +465,43 @@ class HipEncoding:
         if len(status) and status.min() < 0:
             _check(int(status.min()))
         return [EncodingResult(toks[d, :kept[d]].tolist(), bool(flag[d])) for d in range(len(bs))]
+
+    def encode_batch_max_tokens_device(self, text, doc_off, max_tokens, ordinary=False, pad_id=-1, out=None):
+        """Encoding.encode(text, maxTokens) / encodeOrdinary for every document of a device-resident batch, in a model's layout.
+        text: CUDA torch.uint8 tensor, doc_off: CUDA torch.int64 tensor [n_docs + 1], on this encoding's device.  Returns CUDA
+        tensors (tokens int32 [n_docs, max_tokens] -- `out` if given --, kept int64, truncated bool, status int32), written on
+        torch.cuda.current_stream().  Per-document statuses come back in `status`; they do not raise."""
+        import torch
+        if self._host_pattern is not None:
+            raise ValueError("encode_batch_max_tokens_device: the device cannot run this encoding's custom split pattern")
+        dev = N.lib().jtk_encoding_device(self._h)
+        for name, t, dt in (("text", text, torch.uint8), ("doc_off", doc_off, torch.int64)):
+            if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != dt or t.dim() != 1:
+                raise ValueError("%s must be a 1-d CUDA tensor of %s" % (name, dt))
+            if t.device.index != dev:
+                raise ValueError("%s is on cuda:%s, the encoding on cuda:%d" % (name, t.device.index, dev))
+            if not t.is_contiguous():
+                raise ValueError("%s must be contiguous" % name)
+        mt = int(max_tokens)
+        if mt < 0:
+            raise ValueError("max_tokens must be >= 0")
+        nd = doc_off.numel() - 1
+        if nd < 0:
+            raise ValueError("doc_off needs n_docs + 1 entries")
+        device = text.device
+        if out is None:
+            out = torch.empty((nd, mt), dtype=torch.int32, device=device)
+        elif (not isinstance(out, torch.Tensor) or out.shape != (nd, mt) or out.dtype != torch.int32 or out.device != device
+              or not out.is_contiguous()):
+            raise ValueError("out must be a contiguous int32 tensor of shape (%d, %d) on %s" % (nd, mt, device))
+        kept = torch.empty(nd, dtype=torch.int64, device=device)
+        truncated = torch.empty(nd, dtype=torch.bool, device=device)
+        status = torch.empty(nd, dtype=torch.int32, device=device)
+        if nd > 0:
+            stream = torch.cuda.current_stream(device).cuda_stream
+            self._b().encode_device_max_tokens(text.data_ptr(), doc_off.data_ptr(), nd, text.numel(), mt, out.data_ptr(),
+                                               kept.data_ptr(), truncated.data_ptr(), status.data_ptr(), ordinary, pad_id, stream)
+        return out, kept, truncated, status
 
     def count_tokens_batch(self, texts, ordinary=False):
         """Encoding.countTokens / countTokensOrdinary for every text, one device call, no token ids written."""
