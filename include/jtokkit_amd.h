@@ -234,6 +234,42 @@ int jtk_batch_encode_device_max_tokens(jtk_batch* b, const uint8_t* d_utf8, cons
                                        int32_t* d_tokens, int64_t* d_kept, uint8_t* d_truncated, int32_t* d_status,
                                        void* stream_or_null);
 
+/* ---- chunks of a token budget, on the device -------------------------------------------------------------------------
+ * Every document of the LAST batch encode on `b` cut into consecutive chunks of at most chunk_tokens (N) of its tokens, each a
+ * whole number of characters where the tokens allow it, with the byte span of each: what RAG, embedding and long-context data
+ * pipelines do with a limit.  The rule (jtokkit_amd/csrc/jtk_chunk_rules.h): a chunk that starts at token s ends at the last
+ * token boundary e in (s, s + N] that is also a character boundary -- the back-off of GptBytePairEncoding.java:90-100, except that
+ * a cut inside a U+FFFD of the text is not taken --, or at s + N if there is none (then split = 1: the chunk starts or ends
+ * inside a character); the next chunk starts at e, or with overlap > 0 at the first character boundary in
+ * [max(e - overlap, s + 1), e].  The last chunk ends at the document's end.  Chunks are exact slices of encode(doc), NOT what
+ * repeated encode(rest, N) calls on the remaining text would give; with overlap 0 they concatenate to encode(doc).  Chunk 0
+ * equals encode(doc, N).getTokens() whenever that is non-empty and ends on a byte boundary.  Documents that are empty or have a
+ * negative status get no chunks.
+ *   Input:  the last encode (host- or device-input; not after a JTK_ENCODE_COUNT_ONLY encode, not after
+ *           jtk_batch_encode_device_max_tokens: JTK_ERR_INVALID_ARGUMENT); 1 <= chunk_tokens < 2^31, 0 <= overlap < chunk_tokens.
+ *   Order:  queued after that encode on stream_or_null (a hipStream_t), or on the batch's stream when it is NULL; the call
+ *           waits once, to read *n_chunks (the records are then still being written on that stream).  Does not read the text.
+ *   Spans:  byte_begin / byte_end are positions in the batch text: doc_off[d] + the decoded bytes of the document's tokens
+ *           before the chunk's first / after its last token.  After jtk_batch_encode_pieces, bytes that no piece covers are
+ *           not encoded: spans are then positions in the decoded stream of the document, counted from doc_off[d]. */
+int jtk_batch_chunk(jtk_batch* b, int64_t chunk_tokens, int64_t overlap, void* stream_or_null, int64_t* n_chunks);
+/* The last jtk_batch_chunk to host buffers (synchronises): chunk_off[n_docs + 1] (document d has chunks
+ * [chunk_off[d], chunk_off[d + 1])), and per chunk [n_chunks]: its document, tok_begin (index into the batch's token array),
+ * n_tok, byte_begin, byte_end, split.  Any may be NULL. */
+int jtk_batch_chunk_fetch(jtk_batch* b, int64_t* chunk_off, int64_t* chunk_doc, int64_t* tok_begin, int32_t* n_tok,
+                          int64_t* byte_begin, int64_t* byte_end, uint8_t* split);
+/* Device pointers of the same arrays (valid until the next encode or chunk call on this batch). */
+int jtk_batch_chunk_device_result(jtk_batch* b, const int64_t** d_chunk_off, const int64_t** d_chunk_doc,
+                                  const int64_t** d_tok_begin, const int32_t** d_n_tok, const int64_t** d_byte_begin,
+                                  const int64_t** d_byte_end, const uint8_t** d_split);
+/* d_rows[n_chunks * chunk_tokens] (device, 4-byte aligned): row c holds chunk c's ids, then pad_id.  Ordered after the chunk
+ * call on stream_or_null (or the batch's stream); does not wait. */
+int jtk_batch_chunk_rows(jtk_batch* b, int32_t pad_id, int32_t* d_rows, void* stream_or_null);
+/* d_byte_pos[n_tokens] (device): for every token of the last encode, its position in the batch text (doc_off[d] + the decoded
+ * bytes of the document's tokens before it) -- a tokenizer's offset mapping.  Reuses the byte scan of a jtk_batch_chunk on the
+ * same encode; without one it synchronises once for the token count.  Not after a count-only encode. */
+int jtk_batch_token_offsets(jtk_batch* b, int64_t* d_byte_pos, void* stream_or_null);
+
 /* ---- batch decode on the device ---------------------------------------------------------------------
  * Replaces a loop of Encoding.decodeBytes(List<Integer>) (GptBytePairEncoding.java:137-151, 302-314; special-token
  * ids decode to their literals, :308-311) over n_seqs token lists: all ids back to back in `ids`, list q occupying

@@ -68,6 +68,11 @@ SIGNATURES = {
     "jtk_batch_encode_device_max_tokens": (C.c_int, [_p, _p, _p, _i64, _i64, C.c_uint32, _i64, C.c_int32, _p, _p, _p, _p, _p]),
     "jtk_batch_fetch_truncated": (C.c_int, [_p, _p, _p]),
     "jtk_batch_device_truncated": (C.c_int, [_p, C.POINTER(_p), C.POINTER(_p)]),
+    "jtk_batch_chunk": (C.c_int, [_p, _i64, _i64, _p, C.POINTER(_i64)]),
+    "jtk_batch_chunk_fetch": (C.c_int, [_p, _p, _p, _p, _p, _p, _p, _p]),
+    "jtk_batch_chunk_device_result": (C.c_int, [_p] + [C.POINTER(_p)] * 7),
+    "jtk_batch_chunk_rows": (C.c_int, [_p, C.c_int32, _p, _p]),
+    "jtk_batch_token_offsets": (C.c_int, [_p, _p, _p]),
     "jtk_batch_decode": (C.c_int, [_p, _p, _p, _i64, C.POINTER(_i64)]),
     "jtk_batch_decode_device": (C.c_int, [_p, _p, _p, _i64, _i64, _p, C.POINTER(_i64)]),
     "jtk_batch_decode_fetch": (C.c_int, [_p, _p, _i64, _p, _p]),

@@ -14,6 +14,7 @@
 #include <chrono>
 
 #include "../../include/jtokkit_amd.h"
+#include "jtk_chunk_rules.h"
 #include "jtk_kernels.h"
 #include "jtk_maxtok_rules.h"
 #include "jtk_tables.h"
@@ -61,6 +62,8 @@ struct jtk_encoding {
     JtkHostTables host;
     int device = 0;
     DevBuf uc1, uc2, brank, pairs, tok8, tok16, bprank, bpbits, bpcum, bpranks, pairin, dec_off, dec_blob, longtok, longblob, specials;
+    DevBuf bnd;                      // jtk_batch_chunk: one bit per id of the decode table, set when its byte string does not start
+                                     // with a UTF-8 continuation byte (lengths come from dec_off)
     uint32_t n_ids_table = 0;        // ids 0 .. n_ids_table-1 have an entry in the decode table (incl. special tokens)
     JtkDeviceTables dt;
     std::vector<uint32_t> tok_len;   // byte length per id (0 = absent), for the maxTokens back-off
@@ -132,6 +135,13 @@ struct jtk_batch {
     DevBuf mt_scratch, mt_gather;    // jtk_batch_encode_device_max_tokens: per-document state of the rounds | the gathered prefixes
     int64_t* h_mt = nullptr; size_t h_mt_cap = 0;   // pinned: the round's (open documents, gathered bytes)
     bool have_trunc = false;
+    // jtk_batch_chunk: hdr | per-document scan, long list, bases | tiles of the byte scan | records
+    DevBuf ck_scratch, ck_tiles, ck_rec;
+    int64_t* h_ck = nullptr; size_t h_ck_cap = 0;   // pinned: (chunks, tokens) read once per call
+    JtkChunkWork ck{};
+    bool have_chunk = false, have_tiles = false;
+    hipStream_t ck_stream = nullptr;     // stream of the last chunk plan
+    hipEvent_t ev_ck = nullptr;          // orders a chunk call's stream after the encode / the plan
     JtkDecodeWork dwork{};
     bool have_decode = false;
     int64_t dec_total = 0;
@@ -242,7 +252,7 @@ int jtk_encoding_create(const char* name, int pattern_kind, const uint8_t* tikto
     }
     if (device < 0 || device >= ndev) { delete enc; return fail(JTK_ERR_INVALID_ARGUMENT, "device index out of range"); }
     enc->device = device;
-    auto cleanup = [&]() { enc->uc1.release(); enc->uc2.release(); enc->brank.release(); enc->pairs.release(); enc->tok8.release(); enc->tok16.release(); enc->bprank.release(); enc->bpbits.release(); enc->bpcum.release(); enc->bpranks.release(); enc->pairin.release(); enc->dec_off.release(); enc->dec_blob.release(); enc->longtok.release(); enc->longblob.release(); enc->specials.release(); delete enc; };
+    auto cleanup = [&]() { enc->uc1.release(); enc->uc2.release(); enc->brank.release(); enc->pairs.release(); enc->tok8.release(); enc->tok16.release(); enc->bprank.release(); enc->bpbits.release(); enc->bpcum.release(); enc->bpranks.release(); enc->pairin.release(); enc->dec_off.release(); enc->dec_blob.release(); enc->longtok.release(); enc->longblob.release(); enc->specials.release(); enc->bnd.release(); delete enc; };
 #define ENC_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { cleanup(); return fail(JTK_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } } while (0)
     ENC_TRY(hipSetDevice(device));
     const size_t tok8_bytes = (enc->host.tok8.size() * sizeof(JtkTok8Slot) + 31) & ~(size_t)31;
@@ -279,6 +289,11 @@ int jtk_encoding_create(const char* name, int pattern_kind, const uint8_t* tikto
         ENC_TRY(hipMemcpy(enc->dec_off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice));
         ENC_TRY(hipMemcpy(enc->dec_blob.p, blob.data(), blob.size(), hipMemcpyHostToDevice));
         enc->n_ids_table = n_ids;
+        std::vector<uint32_t> bits((n_ids + 31) / 32 + 1, 0);
+        for (uint32_t i = 0; i < n_ids; i++)
+            if (!str[i] || str[i]->empty() || ((uint8_t)(*str[i])[0] & 0xC0) != 0x80) bits[i >> 5] |= 1u << (i & 31);
+        if (enc->bnd.ensure(bits.size() * 4)) { cleanup(); return JTK_ERR_OUT_OF_MEMORY; }
+        ENC_TRY(hipMemcpy(enc->bnd.p, bits.data(), bits.size() * 4, hipMemcpyHostToDevice));
     }
     if (!enc->host.long_tok.empty()) {
         if (enc->longtok.ensure(enc->host.long_tok.size() * sizeof(JtkLongTokSlot)) || enc->longblob.ensure(enc->host.long_blob.size())) { cleanup(); return JTK_ERR_OUT_OF_MEMORY; }
@@ -342,6 +357,7 @@ void jtk_encoding_destroy(jtk_encoding* enc) {
     enc->uc1.release(); enc->uc2.release(); enc->brank.release(); enc->pairs.release();
     enc->tok8.release(); enc->tok16.release(); enc->bprank.release(); enc->bpbits.release(); enc->bpcum.release(); enc->bpranks.release(); enc->pairin.release();
     enc->dec_off.release(); enc->dec_blob.release(); enc->longtok.release(); enc->longblob.release(); enc->specials.release();
+    enc->bnd.release();
     delete enc;
 }
 const char* jtk_encoding_name(const jtk_encoding* enc) { return enc ? enc->host.name.c_str() : ""; }
@@ -387,7 +403,7 @@ void jtk_batch_destroy(jtk_batch* b) {
     }
     DevBuf* bufs[] = {&b->in_text, &b->in_off, &b->in_pieces, &b->out, &b->plan, &b->dec_in_ids, &b->dec_in_off,
                       &b->dec_zero, &b->dec_tile, &b->dec_pre, &b->dec_out, &b->dec_byte_off, &b->trunc_kept, &b->trunc_flag,
-                      &b->mt_scratch, &b->mt_gather};
+                      &b->mt_scratch, &b->mt_gather, &b->ck_scratch, &b->ck_tiles, &b->ck_rec};
     for (DevBuf* d : bufs) d->release();
     for (hipEvent_t ev : b->prof_ev) (void)hipEventDestroy(ev);
     if (b->ev_fork) (void)hipEventDestroy(b->ev_fork);
@@ -399,6 +415,8 @@ void jtk_batch_destroy(jtk_batch* b) {
     if (b->h_in) (void)hipHostFree(b->h_in);
     if (b->h_gather) (void)hipHostFree(b->h_gather);
     if (b->h_mt) (void)hipHostFree(b->h_mt);
+    if (b->h_ck) (void)hipHostFree(b->h_ck);
+    if (b->ev_ck) (void)hipEventDestroy(b->ev_ck);
     if (b->host_plan) (void)hipHostFree(b->host_plan);
     if (b->h_tokens) (void)hipHostFree(b->h_tokens);
     if (b->h_tok_off) (void)hipHostFree(b->h_tok_off);
@@ -744,6 +762,8 @@ int run_job(jtk_batch* b, const uint8_t* d_text, const uint8_t* h_text, const in
     b->have_result = true;
     b->have_host_result = to_host;
     b->have_trunc = false;
+    b->have_chunk = false;
+    b->have_tiles = false;
     b->synced = false;
     b->last_stream = s;
     b->prof_chunks = prof ? n_chunks : 0;
@@ -1353,6 +1373,8 @@ int jtk_batch_encode_device_max_tokens(jtk_batch* b, const uint8_t* d_utf8, cons
     // the batch's last encode result is given up (its chunk plan and scratch are reused below)
     b->have_result = false;
     b->have_trunc = false;
+    b->have_chunk = false;
+    b->have_tiles = false;
     b->plan_doc_off = nullptr;
     if (n_docs == 0) return JTK_OK;
     hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
@@ -1433,6 +1455,157 @@ int jtk_batch_encode_device_max_tokens(jtk_batch* b, const uint8_t* d_utf8, cons
     }
     b->have_result = false;
     b->plan_doc_off = nullptr;
+    return JTK_OK;
+}
+
+
+// ---- chunks of the last encode (jtk_chunk.hip) --------------------------------------------------------------------------
+// `to` waits for the work queued on `from` so far (nothing when they are the same stream).
+static int ck_order(jtk_batch* b, hipStream_t from, hipStream_t to) {
+    if (from == to) return JTK_OK;
+    if (!b->ev_ck) HIP_TRY(hipEventCreateWithFlags(&b->ev_ck, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(b->ev_ck, from));
+    HIP_TRY(hipStreamWaitEvent(to, b->ev_ck, 0));
+    return JTK_OK;
+}
+
+// the inputs of the chunk kernels (the last encode) and the per-document scratch: hdr[4] | chunk_off[nd + 1] | long[nd] | dbase[nd]
+static int ck_setup(jtk_batch* b) {
+    const size_t nd = (size_t)b->job_docs;
+    int rc;
+    if ((rc = b->ck_scratch.ensure(32 + (3 * nd + 1) * 8))) return rc;
+    JtkChunkWork& w = b->ck;
+    w = JtkChunkWork{};
+    w.tokens = (const int32_t*)b->tokens.p; w.tok_off = (const int64_t*)b->tok_off.p; w.status = (const int32_t*)b->status.p;
+    w.doc_off = b->job_doc_off; w.n_docs = b->job_docs;
+    w.bnd = (const uint32_t*)b->enc->bnd.p; w.tab_off = (const uint32_t*)b->enc->dec_off.p; w.n_ids_table = b->enc->n_ids_table;
+    w.hdr = (int64_t*)b->ck_scratch.p;
+    w.chunk_off = w.hdr + 4;
+    w.long_docs = w.chunk_off + nd + 1;
+    w.dbase = w.long_docs + nd;
+    return JTK_OK;
+}
+
+// the byte scan over the tokens (tiles, sub16) and the document bases
+static int ck_tiles(jtk_batch* b, int64_t n_tok, hipStream_t s) {
+    JtkChunkWork& w = b->ck;
+    w.n_tok = n_tok;
+    w.n_tiles = (n_tok + JTK_DEC_TILE - 1) / JTK_DEC_TILE;
+    const size_t o_off = align_up((size_t)w.n_tiles * 4 + 4, 16), o_sub = o_off + ((size_t)w.n_tiles + 1) * 8;
+    int rc;
+    if ((rc = b->ck_tiles.ensure(o_sub + ((size_t)n_tok / 16 + 1) * 4))) return rc;
+    w.tile_bytes = (uint32_t*)b->ck_tiles.p;
+    w.tile_off = (int64_t*)((uint8_t*)b->ck_tiles.p + o_off);
+    w.sub16 = (uint32_t*)((uint8_t*)b->ck_tiles.p + o_sub);
+    jtk_launch_chunk_tiles(w, s);
+    HIP_TRY(hipGetLastError());
+    b->have_tiles = true;
+    return JTK_OK;
+}
+
+int jtk_batch_chunk(jtk_batch* b, int64_t chunk_tokens, int64_t overlap, void* stream_or_null, int64_t* n_chunks) {
+    if (!b || !n_chunks) return fail(JTK_ERR_INVALID_ARGUMENT, "bad arguments");
+    *n_chunks = 0;
+    if (!b->have_result) return fail(JTK_ERR_INVALID_ARGUMENT, "no batch encode result on this batch (jtk_batch_encode_device_max_tokens leaves none)");
+    if (b->job_flags & JTK_ENCODE_COUNT_ONLY) return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode was count-only: there are no token ids");
+    if (chunk_tokens < 1 || chunk_tokens > INT32_MAX) return fail(JTK_ERR_INVALID_ARGUMENT, "chunk_tokens must be in [1, 2^31 - 1]");
+    if (overlap < 0 || overlap >= chunk_tokens) return fail(JTK_ERR_INVALID_ARGUMENT, "overlap must be in [0, chunk_tokens)");
+    HIP_TRY(hipSetDevice(b->enc->device));
+    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    int rc;
+    b->have_chunk = false;
+    b->have_tiles = false;
+    if ((rc = ck_order(b, b->last_stream, s)) || (rc = ck_setup(b)) || (rc = ensure_pinned((void**)&b->h_ck, &b->h_ck_cap, 32, 0))) return rc;
+    JtkChunkWork& w = b->ck;
+    w.N = chunk_tokens; w.overlap = overlap;
+    // count per document, scan; the one wait: (chunks, tokens)
+    HIP_TRY(hipMemsetAsync(w.hdr, 0, 32, s));
+    jtk_launch_chunk_count(w, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(b->h_ck, w.hdr, 16, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const int64_t nc = b->h_ck[0], nt = b->h_ck[1];
+    if ((rc = ck_tiles(b, nt, s))) return rc;
+    // records: chunk_doc | tok_begin | byte_begin | byte_end (i64) | n_tok (i32) | split (u8)
+    const size_t n = (size_t)(nc > 0 ? nc : 1), o_i32 = 4 * n * 8, o_u8 = align_up(o_i32 + n * 4, 16);
+    if ((rc = b->ck_rec.ensure(o_u8 + n))) return rc;
+    int64_t* r64 = (int64_t*)b->ck_rec.p;
+    w.chunk_doc = r64; w.tok_begin = r64 + n; w.byte_begin = r64 + 2 * n; w.byte_end = r64 + 3 * n;
+    w.n_tok_out = (int32_t*)((uint8_t*)b->ck_rec.p + o_i32);
+    w.split = (uint8_t*)b->ck_rec.p + o_u8;
+    w.n_chunks = nc;
+    jtk_launch_chunk_write(w, s);
+    HIP_TRY(hipGetLastError());
+    b->have_chunk = true;
+    b->ck_stream = s;
+    *n_chunks = nc;
+    return JTK_OK;
+}
+
+int jtk_batch_chunk_fetch(jtk_batch* b, int64_t* chunk_off, int64_t* chunk_doc, int64_t* tok_begin, int32_t* n_tok,
+                          int64_t* byte_begin, int64_t* byte_end, uint8_t* split) {
+    if (!b || !b->have_chunk) return fail(JTK_ERR_INVALID_ARGUMENT, "jtk_batch_chunk has not run on the last encode of this batch");
+    HIP_TRY(hipSetDevice(b->enc->device));
+    HIP_TRY(hipStreamSynchronize(b->ck_stream));
+    const JtkChunkWork& w = b->ck;
+    const size_t nc = (size_t)w.n_chunks;
+    if (chunk_off) HIP_TRY(hipMemcpy(chunk_off, w.chunk_off, ((size_t)w.n_docs + 1) * 8, hipMemcpyDeviceToHost));
+    if (nc) {
+        if (chunk_doc) HIP_TRY(hipMemcpy(chunk_doc, w.chunk_doc, nc * 8, hipMemcpyDeviceToHost));
+        if (tok_begin) HIP_TRY(hipMemcpy(tok_begin, w.tok_begin, nc * 8, hipMemcpyDeviceToHost));
+        if (n_tok) HIP_TRY(hipMemcpy(n_tok, w.n_tok_out, nc * 4, hipMemcpyDeviceToHost));
+        if (byte_begin) HIP_TRY(hipMemcpy(byte_begin, w.byte_begin, nc * 8, hipMemcpyDeviceToHost));
+        if (byte_end) HIP_TRY(hipMemcpy(byte_end, w.byte_end, nc * 8, hipMemcpyDeviceToHost));
+        if (split) HIP_TRY(hipMemcpy(split, w.split, nc, hipMemcpyDeviceToHost));
+    }
+    return JTK_OK;
+}
+
+int jtk_batch_chunk_device_result(jtk_batch* b, const int64_t** d_chunk_off, const int64_t** d_chunk_doc,
+                                  const int64_t** d_tok_begin, const int32_t** d_n_tok, const int64_t** d_byte_begin,
+                                  const int64_t** d_byte_end, const uint8_t** d_split) {
+    if (!b || !b->have_chunk) return fail(JTK_ERR_INVALID_ARGUMENT, "jtk_batch_chunk has not run on the last encode of this batch");
+    const JtkChunkWork& w = b->ck;
+    if (d_chunk_off) *d_chunk_off = w.chunk_off;
+    if (d_chunk_doc) *d_chunk_doc = w.chunk_doc;
+    if (d_tok_begin) *d_tok_begin = w.tok_begin;
+    if (d_n_tok) *d_n_tok = w.n_tok_out;
+    if (d_byte_begin) *d_byte_begin = w.byte_begin;
+    if (d_byte_end) *d_byte_end = w.byte_end;
+    if (d_split) *d_split = w.split;
+    return JTK_OK;
+}
+
+int jtk_batch_chunk_rows(jtk_batch* b, int32_t pad_id, int32_t* d_rows, void* stream_or_null) {
+    if (!b || !b->have_chunk) return fail(JTK_ERR_INVALID_ARGUMENT, "jtk_batch_chunk has not run on the last encode of this batch");
+    if (b->ck.n_chunks > 0 && !d_rows) return fail(JTK_ERR_INVALID_ARGUMENT, "d_rows is NULL");
+    if (((uintptr_t)d_rows & 3u) != 0) return fail(JTK_ERR_INVALID_ARGUMENT, "d_rows must be 4-byte aligned");
+    HIP_TRY(hipSetDevice(b->enc->device));
+    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    int rc;
+    if ((rc = ck_order(b, b->ck_stream, s))) return rc;
+    jtk_launch_chunk_rows(b->ck, pad_id, d_rows, s);
+    HIP_TRY(hipGetLastError());
+    return JTK_OK;
+}
+
+int jtk_batch_token_offsets(jtk_batch* b, int64_t* d_byte_pos, void* stream_or_null) {
+    if (!b || !b->have_result) return fail(JTK_ERR_INVALID_ARGUMENT, "no batch encode result on this batch");
+    if (b->job_flags & JTK_ENCODE_COUNT_ONLY) return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode was count-only: there are no token ids");
+    HIP_TRY(hipSetDevice(b->enc->device));
+    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    int rc;
+    if (!b->have_tiles) {                   // no chunk plan on this encode: the byte scan first
+        int64_t nt = 0;
+        if ((rc = jtk_batch_result(b, &nt, nullptr, nullptr)) || (rc = ck_order(b, b->last_stream, s)) || (rc = ck_setup(b))) return rc;
+        if ((rc = ck_tiles(b, nt, s))) return rc;
+        b->ck_stream = s;
+    } else if ((rc = ck_order(b, b->ck_stream, s))) {
+        return rc;
+    }
+    if (b->ck.n_tok > 0 && !d_byte_pos) return fail(JTK_ERR_INVALID_ARGUMENT, "d_byte_pos is NULL");
+    jtk_launch_token_offsets(b->ck, d_byte_pos, s);
+    HIP_TRY(hipGetLastError());
     return JTK_OK;
 }
 

@@ -237,6 +237,41 @@ void jtk_launch_maxtok_plan(const JtkMaxTokWork& m, hipStream_t s);             
 void jtk_launch_maxtok_gather(const JtkMaxTokWork& m, int64_t n_act, hipStream_t s);
 // per-chunk epilogue of run_job: chunk documents are slots [slot0, slot0 + w.n_docs) of the round
 void jtk_launch_maxtok_decide(const JtkWork& w, const JtkMaxTokWork& m, int64_t slot0, hipStream_t s);
+// Device-side state of jtk_batch_chunk (jtk_chunk.hip): chunks of at most chunk_tokens tokens of every document of the last
+// batch encode, by the rule of jtk_chunk_rules.h.  G(t) = bytes of the batch's tokens before token t (all documents): per tile
+// of JTK_DEC_TILE tokens its start tile_off[], and per group of 16 tokens the bytes of its tile before it, sub16[].
+struct JtkChunkWork {
+    const int32_t* tokens;      // result of the last batch encode
+    const int64_t* tok_off;     // [n_docs + 1]
+    const int32_t* status;      // [n_docs]
+    const int64_t* doc_off;     // [n_docs + 1] the encode's offsets into its text
+    int64_t n_docs, n_tok;
+    int64_t N, overlap;
+    const uint32_t* bnd;        // boundary bit per id: the id's byte string does not start with a continuation byte
+    const uint32_t* tab_off;    // decode table offsets (token byte lengths)
+    uint32_t n_ids_table;
+    int64_t* hdr;               // [0] chunks, [1] tokens (tok_off[n_docs]), [2] long documents
+    int64_t* chunk_off;         // [n_docs + 1] chunks per document, then their exclusive scan
+    int64_t* long_docs;         // [n_docs] documents with many chunks (a workgroup each)
+    int64_t* dbase;             // [n_docs] doc_off[d] - G(tok_off[d])
+    uint32_t* tile_bytes;       // [n_tiles]
+    int64_t* tile_off;          // [n_tiles + 1]
+    uint32_t* sub16;            // [n_tok / 16 + 1]
+    int64_t n_tiles;
+    // records [n_chunks]
+    int64_t* chunk_doc;
+    int64_t* tok_begin;
+    int32_t* n_tok_out;
+    int64_t* byte_begin;
+    int64_t* byte_end;
+    uint8_t* split;
+    int64_t n_chunks;
+};
+void jtk_launch_chunk_count(const JtkChunkWork& w, hipStream_t s);      // count per document, scan -> hdr
+void jtk_launch_chunk_tiles(const JtkChunkWork& w, hipStream_t s);      // tile sums, sub16, tile scan, dbase (needs n_tok)
+void jtk_launch_chunk_write(const JtkChunkWork& w, hipStream_t s);      // records (needs n_chunks and the tiles)
+void jtk_launch_chunk_rows(const JtkChunkWork& w, int32_t pad_id, int32_t* rows, hipStream_t s);
+void jtk_launch_token_offsets(const JtkChunkWork& w, int64_t* byte_pos, hipStream_t s);   // (needs the tiles)
 void jtk_launch_decode_count(const JtkDecodeWork& w, hipStream_t s);     // mark, count, scan
 void jtk_launch_decode_scatter(const JtkDecodeWork& w, hipStream_t s);   // scatter, offsets
 

@@ -39,6 +39,22 @@ def _check(rc):
     raise EncodingError(rc, msg)
 
 
+_hip_memcpy_async = None
+
+
+def _copy_d2d(dst, src, n_bytes, stream):
+    """hipMemcpyAsync(dst, src, n, DeviceToDevice, stream) of the HIP runtime the library is bound to."""
+    global _hip_memcpy_async
+    if _hip_memcpy_async is None:
+        f = N.lib().hipMemcpyAsync                                  # (found through the library's own dependencies)
+        f.restype = C.c_int
+        f.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
+        _hip_memcpy_async = f
+    rc = _hip_memcpy_async(dst, src, n_bytes, 3, stream)
+    if rc != 0:
+        raise EncodingError(N.JTK_ERR_HIP, "hipMemcpyAsync failed (%d)" % rc)
+
+
 class EncodingResult:
     """api/EncodingResult.java"""
 
@@ -229,6 +245,41 @@ class Batch:
         flag = np.zeros(max(nd, 1), dtype=np.uint8)
         _check(N.lib().jtk_batch_fetch_truncated(self._h, kept.ctypes.data, flag.ctypes.data))
         return kept[:nd], flag[:nd].astype(bool)
+
+    # ---- chunks of a token budget (device) ---------------------------------------------------------------
+    def chunk(self, chunk_tokens, overlap=0, stream=None):
+        """jtk_batch_chunk on the last encode: chunks of at most chunk_tokens tokens (jtk_chunk_rules.h).  Returns n_chunks."""
+        n = C.c_int64(0)
+        _check(N.lib().jtk_batch_chunk(self._h, int(chunk_tokens), int(overlap), stream, C.byref(n)))
+        self._n_chunks = n.value
+        return n.value
+
+    def chunk_fetch(self):
+        """The last chunk call's arrays on the host: dict of chunk_off [n_docs + 1], doc, tok_begin, n_tok, byte_begin,
+        byte_end, split [n_chunks]."""
+        _, nd, _ = self.result()
+        nc = self._n_chunks
+        f = dict(chunk_off=np.zeros(nd + 1, dtype=np.int64), doc=np.zeros(max(nc, 1), dtype=np.int64),
+                 tok_begin=np.zeros(max(nc, 1), dtype=np.int64), n_tok=np.zeros(max(nc, 1), dtype=np.int32),
+                 byte_begin=np.zeros(max(nc, 1), dtype=np.int64), byte_end=np.zeros(max(nc, 1), dtype=np.int64),
+                 split=np.zeros(max(nc, 1), dtype=np.uint8))
+        _check(N.lib().jtk_batch_chunk_fetch(self._h, *(f[k].ctypes.data for k in ("chunk_off", "doc", "tok_begin", "n_tok",
+                                                                                   "byte_begin", "byte_end", "split"))))
+        return {k: (v if k == "chunk_off" else v[:nc]) for k, v in f.items()}
+
+    def chunk_device_result(self):
+        """Device pointers (chunk_off, doc, tok_begin, n_tok, byte_begin, byte_end, split) of the last chunk call."""
+        ps = [C.c_void_p() for _ in range(7)]
+        _check(N.lib().jtk_batch_chunk_device_result(self._h, *(C.byref(p) for p in ps)))
+        return tuple(p.value for p in ps)
+
+    def chunk_rows(self, pad_id, d_rows_ptr, stream=None):
+        """jtk_batch_chunk_rows: [n_chunks, chunk_tokens] int32 at d_rows_ptr, the chunk's ids then pad_id."""
+        _check(N.lib().jtk_batch_chunk_rows(self._h, int(pad_id), d_rows_ptr, stream))
+
+    def token_offsets(self, d_byte_pos_ptr, stream=None):
+        """jtk_batch_token_offsets: int64 [n_tokens] at d_byte_pos_ptr, each token's byte position in the batch text."""
+        _check(N.lib().jtk_batch_token_offsets(self._h, d_byte_pos_ptr, stream))
 
     # ---- batch decode (device) -------------------------------------------------------------------------
     def decode_host(self, ids, seq_off):
@@ -472,16 +523,7 @@ class HipEncoding:
         tensors (tokens int32 [n_docs, max_tokens] -- `out` if given --, kept int64, truncated bool, status int32), written on
         torch.cuda.current_stream().  Per-document statuses come back in `status`; they do not raise."""
         import torch
-        if self._host_pattern is not None:
-            raise ValueError("encode_batch_max_tokens_device: the device cannot run this encoding's custom split pattern")
-        dev = N.lib().jtk_encoding_device(self._h)
-        for name, t, dt in (("text", text, torch.uint8), ("doc_off", doc_off, torch.int64)):
-            if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != dt or t.dim() != 1:
-                raise ValueError("%s must be a 1-d CUDA tensor of %s" % (name, dt))
-            if t.device.index != dev:
-                raise ValueError("%s is on cuda:%s, the encoding on cuda:%d" % (name, t.device.index, dev))
-            if not t.is_contiguous():
-                raise ValueError("%s must be contiguous" % name)
+        self._check_device_inputs("encode_batch_max_tokens_device", text, doc_off)
         mt = int(max_tokens)
         if mt < 0:
             raise ValueError("max_tokens must be >= 0")
@@ -502,6 +544,93 @@ class HipEncoding:
             self._b().encode_device_max_tokens(text.data_ptr(), doc_off.data_ptr(), nd, text.numel(), mt, out.data_ptr(),
                                                kept.data_ptr(), truncated.data_ptr(), status.data_ptr(), ordinary, pad_id, stream)
         return out, kept, truncated, status
+
+    def _check_device_inputs(self, what, text, doc_off):
+        import torch
+        if self._host_pattern is not None:
+            raise ValueError("%s: the device cannot run this encoding's custom split pattern" % what)
+        dev = N.lib().jtk_encoding_device(self._h)
+        for name, t, dt in (("text", text, torch.uint8), ("doc_off", doc_off, torch.int64)):
+            if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != dt or t.dim() != 1:
+                raise ValueError("%s must be a 1-d CUDA tensor of %s" % (name, dt))
+            if t.device.index != dev:
+                raise ValueError("%s is on cuda:%s, the encoding on cuda:%d" % (name, t.device.index, dev))
+            if not t.is_contiguous():
+                raise ValueError("%s must be contiguous" % name)
+
+    def chunk_batch(self, texts, chunk_tokens, overlap=0, ordinary=False):
+        """Every text cut into consecutive chunks of at most chunk_tokens tokens (overlapping by up to `overlap` tokens), each a
+        whole number of characters unless the tokens do not allow it: per document a list of (tokens, start, end, split), with
+        start / end byte positions in that document (jtk_batch_chunk; the rule is in jtk_chunk_rules.h).  The chunks are
+        slices of encode(text); with overlap 0 they concatenate to it.  A document that cannot be encoded raises."""
+        bs = [t if isinstance(t, (bytes, bytearray)) else t.encode("utf-8") for t in texts]
+        doc_off = np.zeros(len(bs) + 1, dtype=np.int64)
+        if bs:
+            np.cumsum([len(x) for x in bs], out=doc_off[1:])
+        text = np.frombuffer(b"".join(bs), dtype=np.uint8) if doc_off[-1] else np.zeros(0, dtype=np.uint8)
+        res = self.encode_batch_packed(text, doc_off, ordinary)
+        if len(res.status) and res.status.min() < 0:
+            _check(int(res.status.min()))
+        b = self._b()
+        b.chunk(chunk_tokens, overlap)
+        f = b.chunk_fetch()
+        out = [[] for _ in bs]
+        for c in range(len(f["doc"])):
+            d, tb, n = int(f["doc"][c]), int(f["tok_begin"][c]), int(f["n_tok"][c])
+            out[d].append((res.tokens[tb:tb + n].tolist(), int(f["byte_begin"][c] - doc_off[d]), int(f["byte_end"][c] - doc_off[d]),
+                           bool(f["split"][c])))
+        return out
+
+    def chunk_batch_device(self, text, doc_off, chunk_tokens, overlap=0, ordinary=False, pad_id=-1):
+        """chunk_batch for a device-resident batch, in a model's layout.  text: CUDA torch.uint8 tensor, doc_off: CUDA torch.int64
+        tensor [n_docs + 1], on this encoding's device.  Returns a dict of CUDA tensors written on torch.cuda.current_stream():
+        rows int32 [n_chunks, chunk_tokens] (the chunk's ids, then pad_id), n_tok int32, doc int64, byte_begin / byte_end int64
+        (positions in `text`), split bool [n_chunks], chunk_off int64 [n_docs + 1] and the per-document status int32 (documents
+        with a negative status have no chunks; they do not raise).  The call waits once, for the chunk count."""
+        import torch
+        self._check_device_inputs("chunk_batch_device", text, doc_off)
+        N_, ov = int(chunk_tokens), int(overlap)
+        if N_ < 1 or not 0 <= ov < N_:
+            raise ValueError("need chunk_tokens >= 1 and 0 <= overlap < chunk_tokens")
+        nd = doc_off.numel() - 1
+        if nd < 0:
+            raise ValueError("doc_off needs n_docs + 1 entries")
+        device = text.device
+        n = text.numel()
+        st = text.untyped_storage()
+        if text.data_ptr() % 16 or st.data_ptr() + st.nbytes() < text.data_ptr() + (n + 15) // 16 * 16:
+            # (the encode reads whole aligned 16-byte blocks)
+            buf = torch.zeros((n + 15) // 16 * 16 + 16, dtype=torch.uint8, device=device)
+            buf[:n].copy_(text)
+            text = buf
+        b = self._b()
+        cur = torch.cuda.current_stream(device)
+        side = None
+        if cur.cuda_stream == 0:
+            # (the legacy default stream: a NULL handle means "the batch's own stream" to the library, a non-blocking stream
+            # that does not order against it -- so the work goes there explicitly, forked from and joined into `cur`)
+            side = torch.cuda.ExternalStream(b.stream(), device=device)
+            side.wait_stream(cur)
+        stream = (side or cur).cuda_stream
+        b.encode_device(text.data_ptr(), doc_off.data_ptr(), nd, n, ordinary, stream=stream, sync=False)
+        nc = b.chunk(N_, ov, stream)
+        out = dict(rows=torch.empty((nc, N_), dtype=torch.int32, device=device),
+                   n_tok=torch.empty(nc, dtype=torch.int32, device=device), doc=torch.empty(nc, dtype=torch.int64, device=device),
+                   byte_begin=torch.empty(nc, dtype=torch.int64, device=device),
+                   byte_end=torch.empty(nc, dtype=torch.int64, device=device), split=torch.empty(nc, dtype=torch.bool, device=device),
+                   chunk_off=torch.empty(nd + 1, dtype=torch.int64, device=device),
+                   status=torch.empty(nd, dtype=torch.int32, device=device))
+        b.chunk_rows(pad_id, out["rows"].data_ptr(), stream)
+        p_off, p_doc, _, p_ntok, p_bb, p_be, p_split = b.chunk_device_result()
+        p_status = b.device_result()[2]
+        for key, src in (("chunk_off", p_off), ("doc", p_doc), ("n_tok", p_ntok), ("byte_begin", p_bb), ("byte_end", p_be),
+                         ("split", p_split), ("status", p_status)):
+            t = out[key]
+            if t.numel():
+                _copy_d2d(t.data_ptr(), src, t.numel() * t.element_size(), stream)
+        if side is not None:
+            cur.wait_stream(side)
+        return out
 
     def count_tokens_batch(self, texts, ordinary=False):
         """Encoding.countTokens / countTokensOrdinary for every text, one device call, no token ids written."""
