@@ -59,8 +59,11 @@ enum {
     JTK_ENCODE_COUNT_ONLY = 4u,   /* Encoding.countTokens() / countTokensOrdinary() (GptBytePairEncoding.java:122-129) for
                                      the whole batch: token offsets (tok_off[d + 1] - tok_off[d] = the count) and
                                      status, but no token ids -- fetch with tokens == NULL */
-    JTK_ENCODE_TO_HOST = 8u       /* jtk_batch_encode only: stream the result to pinned host memory while later chunks
+    JTK_ENCODE_TO_HOST = 8u,      /* jtk_batch_encode only: stream the result to pinned host memory while later chunks
                                      are still being encoded; read it in place with jtk_batch_host_result() */
+    JTK_ENCODE_ALLOW_SPECIAL = 16u/* jtk_batch_encode / jtk_batch_encode_device only: the batch's allowed special-token
+                                     literals are encoded as their ids (jtk_batch_set_allowed_special has the rule);
+                                     every other entry point that takes flags returns JTK_ERR_INVALID_ARGUMENT for it */
 };
 
 /* Options of jtk_batch_set_option.  A batch larger than one chunk is cut into runs of whole documents ("chunks") that flow
@@ -162,6 +165,36 @@ int jtk_batch_host_result(jtk_batch* b, const int32_t** tokens, const int64_t** 
  * device: offsets that are out of range or decreasing make JTK_ERR_INVALID_ARGUMENT the batch's worst status. */
 int jtk_batch_encode_device(jtk_batch* b, const uint8_t* d_utf8, const int64_t* d_doc_off, int64_t n_docs,
                             int64_t n_bytes, uint32_t flags, void* stream_or_null, int64_t* n_tokens);
+
+/* ---- special tokens as ids (JTK_ENCODE_ALLOW_SPECIAL) -----------------------------------------------------------------
+ * A batch has an allowed set of special ids; a new batch allows all of the encoding's specials.  n < 0: all, n == 0: none;
+ * an id that is no special id of the encoding is JTK_ERR_INVALID_ARGUMENT (the set is then unchanged).  An id that several
+ * literals map to allows all of them.  Waits for the batch's last encode if it may still be running.
+ *
+ * With the flag, each document is encoded as tiktoken's encode(doc, allowed_special=A, disallowed_special=D) does:
+ *   Matching:    from the document's start, the next match is the leftmost position where some allowed literal occurs
+ *                entirely inside the document, and of the literals matching there the longest; scanning resumes after it,
+ *                so matches never overlap (jtokkit_amd/csrc/jtk_special_rules.h).  tiktoken breaks ties by the order of its
+ *                regex alternation; no allowed literal of the four shipped encodings is a prefix of another, so the results
+ *                agree there.  For custom sets, leftmost-longest is the rule.
+ *   Segments:    the text before, between and after the matches is encoded as encodeOrdinary(segment) -- a split of its
+ *                own per segment, not a slice of the whole document's split --, and each match gives its id.
+ *   Disallowed:  without JTK_ENCODE_ORDINARY (encode()), a literal outside the allowed set that occurs anywhere in the
+ *                document (text.contains, even overlapping an allowed match) gives it JTK_ERR_UNSUPPORTED_SPECIAL and no
+ *                tokens; with JTK_ENCODE_ORDINARY such literals are ordinary text.
+ *   Empty set:   the results are those of the call without the flag (it is that call).
+ *   Flags:       JTK_ENCODE_COUNT_ONLY, JTK_ENCODE_VALIDATE_UTF8 (it judges the whole document: a document is well-formed
+ *                when its segments and literals are, for literals that are well-formed UTF-8 themselves) and
+ *                JTK_ENCODE_TO_HOST compose with it.  tok_off and status are per document of the call; fetch, device and host
+ *                results, jtk_batch_chunk / _chunk_rows / _token_offsets read them as any other (a special token's byte span
+ *                is its literal, as the decode table holds it); jtk_batch_truncate returns JTK_ERR_INVALID_ARGUMENT after it.
+ *   Waits:       once for the number of literal candidates in the batch, plus the chunk plan's wait of a text larger than
+ *                JTK_OPT_CHUNK_BYTES (JTK_OPT_HOST_CHUNK_BYTES for host input) as without the flag -- at most two before the
+ *                work is queued; a batch without a match then runs exactly the call without the flag.  Host input is
+ *                copied down whole before the candidates are found (no overlap of the copy with the kernels), and with
+ *                JTK_ENCODE_TO_HOST the result goes to the pinned buffers in one copy behind the last chunk (one more wait,
+ *                for its size) instead of chunk by chunk.  JTK_OPT_REUSE_CHUNK_PLAN does not apply to these calls. */
+int jtk_batch_set_allowed_special(jtk_batch* b, const int32_t* special_ids, int n);
 
 /* The batch's own HIP stream (a hipStream_t), e.g. to order a caller's work after a non-synchronising encode. */
 void* jtk_batch_stream(jtk_batch* b);

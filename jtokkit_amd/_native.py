@@ -29,6 +29,7 @@ JTK_ENCODE_ORDINARY = 1
 JTK_ENCODE_VALIDATE_UTF8 = 2
 JTK_ENCODE_COUNT_ONLY = 4
 JTK_ENCODE_TO_HOST = 8
+JTK_ENCODE_ALLOW_SPECIAL = 16
 JTK_OPT_CHUNK_BYTES = 1
 JTK_OPT_CHUNKS_IN_FLIGHT = 2
 JTK_OPT_HOST_CHUNK_BYTES = 3
@@ -57,6 +58,7 @@ SIGNATURES = {
     "jtk_batch_encode": (C.c_int, [_p, _p, _p, _i64, C.c_uint32, C.POINTER(_i64)]),
     "jtk_batch_encode_pieces": (C.c_int, [_p, _p, _p, _i64, _p, _p, _i64, C.c_uint32, C.POINTER(_i64)]),
     "jtk_batch_encode_device": (C.c_int, [_p, _p, _p, _i64, _i64, C.c_uint32, _p, C.POINTER(_i64)]),
+    "jtk_batch_set_allowed_special": (C.c_int, [_p, _p, C.c_int]),
     "jtk_batch_stream": (_p, [_p]),
     "jtk_batch_result": (C.c_int, [_p, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(C.c_int32)]),
     "jtk_batch_fetch": (C.c_int, [_p, _p, _i64, _p, _p]),

@@ -142,6 +142,13 @@ struct jtk_batch {
     bool have_chunk = false, have_tiles = false;
     hipStream_t ck_stream = nullptr;     // stream of the last chunk plan
     hipEvent_t ev_ck = nullptr;          // orders a chunk call's stream after the encode / the plan
+    // JTK_ENCODE_ALLOW_SPECIAL (jtk_special.hip): the allowed set per literal of the encoding (a new batch allows all) and its
+    // device copy; find scratch (hdr | the stitched status | per-block counts), candidates and sub-documents, the stitched result
+    std::vector<uint8_t> sp_allowed;
+    bool sp_dirty = true;
+    DevBuf sp_lits;                  // ids [n] (int32) | allowed [n]
+    DevBuf sp_find, sp_cand, sp_out;
+    int64_t* h_sp = nullptr; size_t h_sp_cap = 0;   // pinned: (candidates, bad offsets) read once per call
     JtkDecodeWork dwork{};
     bool have_decode = false;
     int64_t dec_total = 0;
@@ -372,6 +379,7 @@ int jtk_batch_create(const jtk_encoding* enc, jtk_batch** out) {
     jtk_batch* b = new (std::nothrow) jtk_batch();
     if (!b) return fail(JTK_ERR_OUT_OF_MEMORY, "out of host memory");
     b->enc = enc;
+    b->sp_allowed.assign(enc->host.specials.size(), 1);
     if (const char* e = getenv("JTK_CHUNK_BYTES")) { const long long v = atoll(e); if (v >= (1 << 20)) b->chunk_bytes = v; }
     if (const char* e = getenv("JTK_HOST_CHUNK_BYTES")) { const long long v = atoll(e); if (v >= (1 << 16)) b->host_chunk_bytes = v; }
     if (const char* e = getenv("JTK_CHUNKS_IN_FLIGHT")) { const int v = atoi(e); if (v >= 1 && v <= MAX_SETS) { b->n_sets = v; b->n_sets_chosen = true; } }
@@ -403,8 +411,10 @@ void jtk_batch_destroy(jtk_batch* b) {
     }
     DevBuf* bufs[] = {&b->in_text, &b->in_off, &b->in_pieces, &b->out, &b->plan, &b->dec_in_ids, &b->dec_in_off,
                       &b->dec_zero, &b->dec_tile, &b->dec_pre, &b->dec_out, &b->dec_byte_off, &b->trunc_kept, &b->trunc_flag,
-                      &b->mt_scratch, &b->mt_gather, &b->ck_scratch, &b->ck_tiles, &b->ck_rec};
+                      &b->mt_scratch, &b->mt_gather, &b->ck_scratch, &b->ck_tiles, &b->ck_rec, &b->sp_lits, &b->sp_find,
+                      &b->sp_cand, &b->sp_out};
     for (DevBuf* d : bufs) d->release();
+    if (b->h_sp) (void)hipHostFree(b->h_sp);
     for (hipEvent_t ev : b->prof_ev) (void)hipEventDestroy(ev);
     if (b->ev_fork) (void)hipEventDestroy(b->ev_fork);
     if (b->ev_copy) (void)hipEventDestroy(b->ev_copy);
@@ -453,6 +463,24 @@ int jtk_batch_set_profiling(jtk_batch* b, int enabled) {
     if (!b) return fail(JTK_ERR_INVALID_ARGUMENT, "batch is NULL");
     b->profiling = enabled != 0;
     b->prof_chunks = 0;
+    return JTK_OK;
+}
+
+int jtk_batch_set_allowed_special(jtk_batch* b, const int32_t* special_ids, int n) {
+    if (!b || (n > 0 && !special_ids)) return fail(JTK_ERR_INVALID_ARGUMENT, "bad arguments");
+    const auto& sp = b->enc->host.specials;
+    std::vector<uint8_t> allowed(sp.size(), n < 0 ? 1 : 0);
+    for (int k = 0; k < n; k++) {
+        bool known = false;
+        for (size_t i = 0; i < sp.size(); i++)
+            if (sp[i].second == special_ids[k]) { allowed[i] = 1; known = true; }   // (every literal of the id)
+        if (!known) return fail(JTK_ERR_INVALID_ARGUMENT, "id " + std::to_string(special_ids[k]) + " is not a special token of this encoding");
+    }
+    // (the device copy is rewritten by the next allow-special encode: the last one's kernels must be done reading it)
+    HIP_TRY(hipSetDevice(b->enc->device));
+    if (b->have_result && !b->synced) { HIP_TRY(hipStreamSynchronize(b->last_stream)); b->synced = true; }
+    b->sp_allowed.swap(allowed);
+    b->sp_dirty = true;
     return JTK_OK;
 }
 
@@ -800,6 +828,129 @@ int plan_device_chunks(jtk_batch* b, const int64_t* d_doc_off, int64_t n_docs, i
     return JTK_OK;
 }
 
+bool sp_any_allowed(const jtk_batch* b) {
+    for (uint8_t a : b->sp_allowed) if (a) return true;
+    return false;
+}
+
+// JTK_ENCODE_ALLOW_SPECIAL on a device-resident batch (host input is copied down whole first), jtk_special.hip: find the
+// candidates; with none in any document the pipeline runs on the documents as they are (today's call: its own special-token
+// check then sees only literals outside the allowed set), else on the sub-documents, and the stitch writes the result.  cb: the
+// chunk size of the pipeline run.  Waits once, for the candidate count, plus the chunk plan's wait of a run longer than one
+// chunk (plan_device_chunks), plus, with JTK_ENCODE_TO_HOST after a stitch, once for the token count of the copy.
+int run_allow_special(jtk_batch* b, const uint8_t* d_text, const int64_t* d_doc_off, int64_t n_docs, int64_t n_bytes, uint32_t flags,
+                      hipStream_t s, int64_t cb) {
+    const jtk_encoding* enc = b->enc;
+    const bool to_host = (flags & JTK_ENCODE_TO_HOST) != 0, count_only = (flags & JTK_ENCODE_COUNT_ONLY) != 0;
+    const uint32_t base_flags = flags & ~(uint32_t)(JTK_ENCODE_ALLOW_SPECIAL | JTK_ENCODE_TO_HOST);
+    const int n_lits = (int)enc->host.specials.size();
+    int rc;
+    if (b->sp_dirty) {
+        const size_t n = (size_t)n_lits;
+        std::vector<uint8_t> h(n * 5 + 16, 0);
+        for (size_t i = 0; i < n; i++) {
+            const int32_t id = enc->host.specials[i].second;
+            memcpy(&h[i * 4], &id, 4);
+            h[n * 4 + i] = b->sp_allowed[i];
+        }
+        if ((rc = b->sp_lits.ensure(h.size()))) return rc;
+        HIP_TRY(hipMemcpy(b->sp_lits.p, h.data(), h.size(), hipMemcpyHostToDevice));
+        b->sp_dirty = false;
+    }
+    JtkSpecialWork w{};
+    w.text = d_text; w.doc_off = d_doc_off; w.n_docs = n_docs; w.n_bytes = n_bytes;
+    w.n_lits = n_lits; w.lit_off = enc->dt.special_off; w.lit_blob = enc->dt.special_blob;
+    w.lit_id = (const int32_t*)b->sp_lits.p;
+    w.allowed = (const uint8_t*)b->sp_lits.p + (size_t)n_lits * 4;
+    w.check_dis = (flags & JTK_ENCODE_ORDINARY) ? 0u : 1u;
+    for (int i = 0; i < n_lits; i++) {
+        const std::string& lit = enc->host.specials[(size_t)i].first;
+        if (b->sp_allowed[(size_t)i]) w.maxlen = std::max<int64_t>(w.maxlen, (int64_t)lit.size());
+        else if (!w.check_dis) continue;
+        const uint8_t f = (uint8_t)lit[0];
+        w.first[f >> 5] |= 1u << (f & 31);
+    }
+    // find scratch: hdr [4] | status [n_docs] (the result's) | per-block counts [n_blk + 1]
+    w.n_blk = (n_bytes + JTK_SPECIAL_BLOCK - 1) / JTK_SPECIAL_BLOCK;
+    const size_t status_bytes = align_up((size_t)(n_docs > 0 ? n_docs : 1) * 4, 16);
+    if ((rc = b->sp_find.ensure(32 + status_bytes + ((size_t)w.n_blk + 1) * 8)) ||
+        (rc = ensure_pinned((void**)&b->h_sp, &b->h_sp_cap, 16, 0)))
+        return rc;
+    uint8_t* z = (uint8_t*)b->sp_find.p;
+    w.hdr = (int64_t*)z;
+    w.status = (int32_t*)(z + 32);
+    w.blk = (int64_t*)(z + 32 + status_bytes);
+    HIP_TRY(hipMemsetAsync(z, 0, 32 + status_bytes, s));
+    jtk_launch_special_find(w, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(b->h_sp, w.hdr, 16, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    w.n_cand = b->h_sp[0];
+    const int64_t save_cb = b->chunk_bytes;
+    auto plan = [&](const int64_t* off, int64_t nd) {
+        b->chunk_bytes = cb;
+        const int r = plan_device_chunks(b, off, nd, n_bytes, s);
+        b->chunk_bytes = save_cb;
+        return r;
+    };
+    if (b->h_sp[1] != 0 || w.n_cand == 0) {
+        // no allowed literal in any document (or bad offsets, which today's call reports as it always does)
+        if ((rc = plan(d_doc_off, n_docs)) || (rc = run_job(b, d_text, nullptr, d_doc_off, n_docs, n_bytes, base_flags, s, to_host))) return rc;
+        b->job_flags |= JTK_ENCODE_ALLOW_SPECIAL;
+        return JTK_OK;
+    }
+    // candidates: pos, doc (i64) | len, id (i32) | keep (u8);  sub-documents: off [ns + 1], doc [ns], cnt [ns + 1] (i64),
+    // doc_first [n_docs] (i64) | lit [ns] (i32)
+    w.n_sub = n_docs + 2 * w.n_cand;
+    const size_t nc = (size_t)w.n_cand, ns = (size_t)w.n_sub;
+    const size_t o_cdoc = nc * 8, o_len = o_cdoc + nc * 8, o_id = o_len + nc * 4, o_keep = o_id + nc * 4;
+    const size_t o_soff = align_up(o_keep + nc, 16), o_sdoc = o_soff + (ns + 1) * 8, o_cnt = o_sdoc + ns * 8,
+                 o_first = o_cnt + (ns + 1) * 8, o_lit = o_first + (size_t)n_docs * 8, c_total = o_lit + ns * 4;
+    if ((rc = b->sp_cand.ensure(c_total + 16))) return rc;
+    uint8_t* c = (uint8_t*)b->sp_cand.p;
+    w.cand_pos = (int64_t*)c; w.cand_doc = (int64_t*)(c + o_cdoc); w.cand_len = (int32_t*)(c + o_len);
+    w.cand_id = (int32_t*)(c + o_id); w.cand_keep = c + o_keep;
+    w.sub_off = (int64_t*)(c + o_soff); w.sub_doc = (int64_t*)(c + o_sdoc); w.cnt = (int64_t*)(c + o_cnt);
+    w.doc_first = (int64_t*)(c + o_first); w.sub_lit = (int32_t*)(c + o_lit);
+    jtk_launch_special_write(w, s);
+    HIP_TRY(hipGetLastError());
+    // encodeOrdinary of every sub-document (the literals' tokens are not used: their ids are written instead)
+    const uint32_t sub_flags = JTK_ENCODE_ORDINARY | (flags & (JTK_ENCODE_VALIDATE_UTF8 | JTK_ENCODE_COUNT_ONLY));
+    if ((rc = plan(w.sub_off, w.n_sub)) || (rc = run_job(b, d_text, nullptr, w.sub_off, w.n_sub, n_bytes, sub_flags, s, false))) return rc;
+    // the stitched result: JtkResult | tok_off [n_docs + 1] | tokens (status: in the find scratch)
+    const size_t o_tok_off = 64, o_tokens = align_up(o_tok_off + ((size_t)n_docs + 1) * 8, 256);
+    if ((rc = b->sp_out.ensure(o_tokens + (count_only ? 0 : ((size_t)n_bytes + 64) * 4)))) return rc;
+    uint8_t* out = (uint8_t*)b->sp_out.p;
+    w.sub_tok_off = (const int64_t*)b->tok_off.p; w.sub_status = (const int32_t*)b->status.p; w.sub_tokens = (const int32_t*)b->tokens.p;
+    w.result = (JtkResult*)out; w.tok_off = (int64_t*)(out + o_tok_off); w.tokens = (int32_t*)(out + o_tokens);
+    w.count_only = count_only ? 1u : 0u;
+    HIP_TRY(hipMemsetAsync(out, 0, sizeof(JtkResult), s));
+    jtk_launch_special_stitch(w, s);
+    HIP_TRY(hipGetLastError());
+    b->job.p = out; b->status.p = w.status; b->tok_off.p = w.tok_off; b->tokens.p = w.tokens;
+    b->host_result = b->host_result_own;
+    HIP_TRY(hipMemcpyAsync(b->host_result, w.result, sizeof(JtkResult), hipMemcpyDeviceToHost, s));
+    b->job_doc_off = d_doc_off;
+    b->job_docs = n_docs;
+    b->job_flags = flags & ~(uint32_t)JTK_ENCODE_TO_HOST;
+    b->have_host_result = false;
+    if (to_host) {
+        // (the stitch comes after the last chunk: the ids go to the host in one copy behind it, not chunk by chunk)
+        HIP_TRY(hipStreamSynchronize(s));
+        const int64_t nt = b->host_result->n_tokens;
+        if ((rc = ensure_pinned((void**)&b->h_tok_off, &b->h_tok_off_cap, ((size_t)n_docs + 1) * 8, 0)) ||
+            (rc = ensure_pinned((void**)&b->h_status, &b->h_status_cap, (size_t)(n_docs > 0 ? n_docs : 1) * 4, 0)) ||
+            (rc = ensure_pinned((void**)&b->h_tokens, &b->h_tokens_cap, (size_t)nt * 4 + 4096, 0)))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(b->h_tok_off, w.tok_off, ((size_t)n_docs + 1) * 8, hipMemcpyDeviceToHost, s));
+        if (n_docs > 0) HIP_TRY(hipMemcpyAsync(b->h_status, w.status, (size_t)n_docs * 4, hipMemcpyDeviceToHost, s));
+        if (nt > 0 && !count_only) HIP_TRY(hipMemcpyAsync(b->h_tokens, w.tokens, (size_t)nt * 4, hipMemcpyDeviceToHost, s));
+        b->r_tokens = b->h_tokens; b->r_tok_off = b->h_tok_off; b->r_status = b->h_status;
+        b->have_host_result = true;
+    }
+    return JTK_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -813,6 +964,18 @@ int jtk_batch_encode_device(jtk_batch* b, const uint8_t* d_utf8, const int64_t* 
     if (flags & JTK_ENCODE_TO_HOST) return fail(JTK_ERR_INVALID_ARGUMENT, "JTK_ENCODE_TO_HOST is for jtk_batch_encode (host buffers)");
     HIP_TRY(hipSetDevice(b->enc->device));
     hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    if ((flags & JTK_ENCODE_ALLOW_SPECIAL) && !sp_any_allowed(b)) flags &= ~(uint32_t)JTK_ENCODE_ALLOW_SPECIAL;   // empty set: today's call
+    if (flags & JTK_ENCODE_ALLOW_SPECIAL) {
+        b->plan_doc_off = nullptr;                                  // (no JTK_OPT_REUSE_CHUNK_PLAN here)
+        const int rc = run_allow_special(b, d_utf8, d_doc_off, n_docs, n_bytes, flags, s, b->chunk_bytes);
+        if (rc != JTK_OK) return rc;
+        if (n_tokens) {
+            HIP_TRY(hipStreamSynchronize(s));
+            b->synced = true;
+            *n_tokens = b->host_result->n_tokens;
+        }
+        return JTK_OK;
+    }
     // chunk plan: a batch of up to one chunk needs none; a larger one reads the chunk boundaries from the offsets (the one
     // place where this call waits for the work queued on `s` before it)
     const bool same_plan = b->reuse_plan && b->plan_doc_off == d_doc_off && b->plan_docs == n_docs && b->plan_bytes == n_bytes && b->plan_chunk_bytes == b->chunk_bytes &&
@@ -860,6 +1023,19 @@ int jtk_batch_encode(jtk_batch* b, const uint8_t* utf8, const int64_t* doc_off, 
     b->chunk_off.push_back(n_bytes);
     HIP_TRY(hipSetDevice(b->enc->device));
     int rc;
+    if ((flags & JTK_ENCODE_ALLOW_SPECIAL) && !sp_any_allowed(b)) flags &= ~(uint32_t)JTK_ENCODE_ALLOW_SPECIAL;   // empty set: today's call
+    if (flags & JTK_ENCODE_ALLOW_SPECIAL) {
+        // the text goes down whole (the candidates are found before any chunk is encoded); then as device input
+        if ((rc = b->in_text.ensure((size_t)n_bytes + 64)) || (rc = b->in_off.ensure(((size_t)n_docs + 1) * 8))) return rc;
+        HIP_TRY(hipMemcpyAsync(b->in_off.p, doc_off, ((size_t)n_docs + 1) * 8, hipMemcpyHostToDevice, b->stream));
+        if (n_bytes > 0) HIP_TRY(hipMemcpyAsync(b->in_text.p, utf8, (size_t)n_bytes, hipMemcpyHostToDevice, b->stream));
+        rc = run_allow_special(b, (const uint8_t*)b->in_text.p, (const int64_t*)b->in_off.p, n_docs, n_bytes, flags, b->stream, cb);
+        if (rc != JTK_OK) return rc;
+        HIP_TRY(hipStreamSynchronize(b->stream));
+        b->synced = true;
+        if (n_tokens) *n_tokens = b->host_result->n_tokens;
+        return JTK_OK;
+    }
     if (b->chunk_doc.size() == 2 && n_bytes <= TINY_JOB_BYTES) {
         // a per-call device batch: offsets and text go down in ONE copy (staged side by side in pinned memory; copying a few KB on
         // the host costs less than a second DMA)
@@ -889,6 +1065,7 @@ int jtk_batch_encode_pieces(jtk_batch* b, const uint8_t* utf8, const int64_t* do
                             const int64_t* piece_begin, const int64_t* piece_end, int64_t n_pieces, uint32_t flags, int64_t* n_tokens) {
     if (!b || n_docs < 0 || !doc_off || n_pieces < 0 || (n_pieces > 0 && (!piece_begin || !piece_end)))
         return fail(JTK_ERR_INVALID_ARGUMENT, "bad arguments");
+    if (flags & JTK_ENCODE_ALLOW_SPECIAL) return fail(JTK_ERR_INVALID_ARGUMENT, "JTK_ENCODE_ALLOW_SPECIAL is for jtk_batch_encode / jtk_batch_encode_device");
     if (doc_off[0] != 0) return fail(JTK_ERR_INVALID_ARGUMENT, "doc_off[0] must be 0");
     const int64_t n_bytes = doc_off[n_docs];
     if (n_bytes > 0 && !utf8) return fail(JTK_ERR_INVALID_ARGUMENT, "utf8 is NULL");
@@ -1033,6 +1210,7 @@ int jtk_batch_kernel_times(jtk_batch* b, const char** names, float* ms, int cap,
 // ---- maxTokens on the device ---------------------------------------------------------------------------
 int jtk_batch_truncate(jtk_batch* b, int64_t max_tokens) {
     if (!b || !b->have_result || max_tokens < 0) return fail(JTK_ERR_INVALID_ARGUMENT, "bad arguments (an encode must have run on this batch)");
+    if (b->job_flags & JTK_ENCODE_ALLOW_SPECIAL) return fail(JTK_ERR_INVALID_ARGUMENT, "maxTokens is not defined after a JTK_ENCODE_ALLOW_SPECIAL encode");
     HIP_TRY(hipSetDevice(b->enc->device));
     if (!b->synced) { HIP_TRY(hipStreamSynchronize(b->last_stream)); b->synced = true; }
     const int64_t nd = b->job_docs;
@@ -1179,6 +1357,7 @@ extern "C" {
 int jtk_encode(jtk_batch* b, const uint8_t* utf8, int64_t len, uint32_t flags, int64_t max_tokens,
                int32_t* tokens, int64_t tokens_cap, int64_t* n_tokens, int* truncated) {
     if (!b || len < 0) return fail(JTK_ERR_INVALID_ARGUMENT, "bad arguments");
+    if (flags & JTK_ENCODE_ALLOW_SPECIAL) return fail(JTK_ERR_INVALID_ARGUMENT, "JTK_ENCODE_ALLOW_SPECIAL is for jtk_batch_encode / jtk_batch_encode_device");
     if (truncated) *truncated = 0;
     if (n_tokens) *n_tokens = 0;
     if (!utf8) return JTK_OK;                                    // text == null -> empty result
@@ -1229,6 +1408,7 @@ int jtk_batch_encode_max_tokens(jtk_batch* b, const uint8_t* utf8, const int64_t
                                 int64_t max_tokens, int32_t* tokens, int64_t* kept, uint8_t* truncated, int32_t* status) {
     if (!b || n_docs < 0 || !doc_off || max_tokens < 0 || !kept || (max_tokens > 0 && n_docs > 0 && !tokens))
         return fail(JTK_ERR_INVALID_ARGUMENT, "bad arguments");
+    if (flags & JTK_ENCODE_ALLOW_SPECIAL) return fail(JTK_ERR_INVALID_ARGUMENT, "JTK_ENCODE_ALLOW_SPECIAL is for jtk_batch_encode / jtk_batch_encode_device");
     if (doc_off[0] != 0) return fail(JTK_ERR_INVALID_ARGUMENT, "doc_off[0] must be 0");
     for (int64_t d = 0; d < n_docs; d++)
         if (doc_off[d + 1] < doc_off[d]) return fail(JTK_ERR_INVALID_ARGUMENT, "doc_off must be non-decreasing");

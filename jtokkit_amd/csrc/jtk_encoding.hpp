@@ -73,6 +73,19 @@ public:
         check(jtk_batch_fetch(batch_, tokens.data(), nt, tokOff.data(), status.data()));
     }
 
+    // encodeBatch with the allowed special ids encoded as ids (JTK_ENCODE_ALLOW_SPECIAL; the rule is in jtokkit_amd.h);
+    // allowedIds empty: none allowed, as the call without the flag
+    void encodeBatchWithSpecialTokens(const uint8_t* utf8, const std::vector<int64_t>& docOff, const std::vector<int32_t>& allowedIds,
+                                      bool ordinary, std::vector<int32_t>& tokens, std::vector<int64_t>& tokOff,
+                                      std::vector<int32_t>& status) {
+        int64_t nt = 0;
+        const int64_t n = (int64_t)docOff.size() - 1;
+        check(jtk_batch_set_allowed_special(batch_, allowedIds.data(), (int)allowedIds.size()));
+        check(jtk_batch_encode(batch_, utf8, docOff.data(), n, (ordinary ? JTK_ENCODE_ORDINARY : 0u) | JTK_ENCODE_ALLOW_SPECIAL, &nt));
+        tokens.resize((size_t)nt); tokOff.resize((size_t)n + 1); status.resize((size_t)n);
+        check(jtk_batch_fetch(batch_, tokens.data(), nt, tokOff.data(), status.data()));
+    }
+
     // custom split pattern: the caller's matches (byte ranges in the whole batch) instead of the device's split
     // (api/GptBytePairEncodingParams.java:36-46); text between matches is skipped as matcher.find() does
     void encodeBatchPieces(const uint8_t* utf8, const std::vector<int64_t>& docOff, const std::vector<int64_t>& pieceBegin,

@@ -272,6 +272,52 @@ void jtk_launch_chunk_tiles(const JtkChunkWork& w, hipStream_t s);      // tile 
 void jtk_launch_chunk_write(const JtkChunkWork& w, hipStream_t s);      // records (needs n_chunks and the tiles)
 void jtk_launch_chunk_rows(const JtkChunkWork& w, int32_t pad_id, int32_t* rows, hipStream_t s);
 void jtk_launch_token_offsets(const JtkChunkWork& w, int64_t* byte_pos, hipStream_t s);   // (needs the tiles)
+// Device-side state of an allow-special encode (jtk_special.hip, JTK_ENCODE_ALLOW_SPECIAL; the rule is jtk_special_rules.h).
+// Candidates (per position, the longest allowed literal there) are found in position order, resolved to the kept matches, and
+// the batch is cut into sub-documents that partition the text: per document a segment, then per candidate i two slots
+// d + 2i + 1 (its literal) and d + 2i + 2 (the segment after it).  A candidate that is not kept gets two empty slots at the
+// start of the next kept match (or the document's end).  The encode pipeline runs on the sub-documents (encodeOrdinary), and
+// the stitch writes each document's segment tokens and special ids into the final result.
+struct JtkSpecialWork {
+    const uint8_t* text;        // the batch text (16-byte aligned, readable up to the next multiple of 16 past n_bytes)
+    const int64_t* doc_off;     // [n_docs + 1]
+    int64_t n_docs, n_bytes;
+    int n_lits;                 // the encoding's special literals: special_off / special_blob of JtkDeviceTables
+    const uint32_t* lit_off;
+    const uint8_t* lit_blob;
+    const uint8_t* allowed;     // [n_lits] literal i is in the allowed set
+    const int32_t* lit_id;      // [n_lits] its id
+    int64_t maxlen;             // longest allowed literal
+    uint32_t check_dis;         // encode(): a literal outside the allowed set anywhere in a document -> JTK_ERR_UNSUPPORTED_SPECIAL
+    uint32_t first[8];          // bit b: a literal the find pass looks for starts with byte b
+    int64_t* hdr;               // [0] candidates, [1] offsets are bad (not non-decreasing within [0, n_bytes], doc_off[0] != 0)
+    int64_t* blk;               // [n_blk + 1] candidates per block of JTK_SPECIAL_BLOCK text bytes, then their exclusive scan
+    int64_t n_blk;
+    int64_t n_cand;             // candidates, in position order:
+    int64_t* cand_pos;
+    int32_t* cand_len;
+    int32_t* cand_id;
+    int64_t* cand_doc;
+    uint8_t* cand_keep;         // 1 kept for certain, 2 undecided (a chain), then 3 kept / 0 not kept by the walk
+    int64_t n_sub;              // n_docs + 2 * n_cand
+    int64_t* sub_off;           // [n_sub + 1]
+    int32_t* sub_lit;           // [n_sub] -1 segment, -2 empty slot of a candidate not kept, else the special id of a literal
+    int64_t* sub_doc;           // [n_sub] its document
+    int64_t* doc_first;         // [n_docs] the document's first sub-document
+    const int64_t* sub_tok_off; // the pipeline's result on the sub-documents: [n_sub + 1]
+    const int32_t* sub_status;  // [n_sub]
+    const int32_t* sub_tokens;
+    int64_t* cnt;               // [n_sub + 1] tokens per sub-document in the final result, then their exclusive scan
+    uint32_t count_only;
+    int32_t* status;            // final, [n_docs] (zeroed before the find pass, which records disallowed literals)
+    int64_t* tok_off;           // final, [n_docs + 1]
+    int32_t* tokens;            // final
+    JtkResult* result;          // final (zeroed before the stitch)
+};
+#define JTK_SPECIAL_BLOCK 4096   // text bytes per find workgroup (256 lanes x 16 bytes)
+void jtk_launch_special_find(const JtkSpecialWork& w, hipStream_t s);      // offsets check, candidates per block, scan -> hdr
+void jtk_launch_special_write(const JtkSpecialWork& w, hipStream_t s);     // candidates, resolve, sub-documents (needs n_cand)
+void jtk_launch_special_stitch(const JtkSpecialWork& w, hipStream_t s);    // status, counts, scan, offsets, ids (after the pipeline)
 void jtk_launch_decode_count(const JtkDecodeWork& w, hipStream_t s);     // mark, count, scan
 void jtk_launch_decode_scatter(const JtkDecodeWork& w, hipStream_t s);   // scatter, offsets
 

@@ -136,14 +136,25 @@ class Batch:
         """jtk_batch_set_option: N.JTK_OPT_CHUNK_BYTES, N.JTK_OPT_CHUNKS_IN_FLIGHT."""
         _check(N.lib().jtk_batch_set_option(self._h, int(option), int(value)))
 
-    def encode_host(self, text_u8, doc_off, ordinary=False, validate=False, count_only=False, to_host=False):
+    def set_allowed_special(self, ids):
+        """jtk_batch_set_allowed_special: the special ids that encodes with allow_special=True take as ids.  None or "all":
+        every special of the encoding; an iterable of ids (empty: none)."""
+        if ids is None or (isinstance(ids, str) and ids == "all"):
+            _check(N.lib().jtk_batch_set_allowed_special(self._h, None, -1))
+            return
+        arr = np.ascontiguousarray(list(ids), dtype=np.int32)
+        _check(N.lib().jtk_batch_set_allowed_special(self._h, arr.ctypes.data if len(arr) else None, len(arr)))
+
+    def encode_host(self, text_u8, doc_off, ordinary=False, validate=False, count_only=False, to_host=False, allow_special=False):
         """Host buffers in (numpy arrays, or anything with .ctypes.data such as a pinned HostBuffer view).  to_host: the result
-        is streamed to the batch's pinned host memory while later chunks are encoded (read it with host_result())."""
+        is streamed to the batch's pinned host memory while later chunks are encoded (read it with host_result()).
+        allow_special: the batch's allowed special-token literals become their ids (JTK_ENCODE_ALLOW_SPECIAL)."""
         text_u8 = np.ascontiguousarray(text_u8, dtype=np.uint8)
         doc_off = np.ascontiguousarray(doc_off, dtype=np.int64)
         nt = C.c_int64(0)
         flags = ((N.JTK_ENCODE_ORDINARY if ordinary else 0) | (N.JTK_ENCODE_VALIDATE_UTF8 if validate else 0)
-                 | (N.JTK_ENCODE_COUNT_ONLY if count_only else 0) | (N.JTK_ENCODE_TO_HOST if to_host else 0))
+                 | (N.JTK_ENCODE_COUNT_ONLY if count_only else 0) | (N.JTK_ENCODE_TO_HOST if to_host else 0)
+                 | (N.JTK_ENCODE_ALLOW_SPECIAL if allow_special else 0))
         self._count_only = count_only
         _check(N.lib().jtk_batch_encode(self._h, text_u8.ctypes.data, doc_off.ctypes.data, len(doc_off) - 1,
                                         flags, C.byref(nt)))
@@ -177,10 +188,12 @@ class Batch:
         tokens = view(a.value, nt, C.c_int32, np.int32)
         return BatchResult(tokens, view(b.value, nd + 1, C.c_int64, np.int64), view(c.value, nd, C.c_int32, np.int32))
 
-    def encode_device(self, d_text_ptr, d_doc_off_ptr, n_docs, n_bytes, ordinary=False, stream=None, sync=True):
+    def encode_device(self, d_text_ptr, d_doc_off_ptr, n_docs, n_bytes, ordinary=False, stream=None, sync=True,
+                      allow_special=False, validate=False, count_only=False):
         nt = C.c_int64(0)
-        _check(N.lib().jtk_batch_encode_device(self._h, d_text_ptr, d_doc_off_ptr, n_docs, n_bytes,
-                                               N.JTK_ENCODE_ORDINARY if ordinary else 0, stream,
+        flags = ((N.JTK_ENCODE_ORDINARY if ordinary else 0) | (N.JTK_ENCODE_ALLOW_SPECIAL if allow_special else 0)
+                 | (N.JTK_ENCODE_VALIDATE_UTF8 if validate else 0) | (N.JTK_ENCODE_COUNT_ONLY if count_only else 0))
+        _check(N.lib().jtk_batch_encode_device(self._h, d_text_ptr, d_doc_off_ptr, n_docs, n_bytes, flags, stream,
                                                C.byref(nt) if sync else None))
         return nt.value if sync else None
 
@@ -337,6 +350,7 @@ class HipEncoding:
         pattern's text) for encodings whose split pattern is neither of the two the device evaluates; the batch methods
         then match on the host and encode the matches through jtk_batch_encode_pieces."""
         self._host_pattern = host_pattern
+        self._specials = dict(special_tokens)
         lits = [k.encode("utf-8") for k in special_tokens]
         arr = (C.c_char_p * max(len(lits), 1))(*lits)
         ids = (C.c_int32 * max(len(lits), 1))(*special_tokens.values())
@@ -455,23 +469,63 @@ class HipEncoding:
     getName = get_name
 
     # ---- batch -----------------------------------------------------------------------------------------
-    def encode_batch(self, texts, ordinary=False, validate=False):
-        """List of str/bytes -> BatchResult (one jtk_batch_encode call)."""
+    def encode_batch(self, texts, ordinary=False, validate=False, allowed_special=None):
+        """List of str/bytes -> BatchResult (one jtk_batch_encode call).  allowed_special: None (the literals are refused by
+        encode() and ordinary text to encodeOrdinary()), "all", or an iterable of literals that are encoded as their ids
+        (JTK_ENCODE_ALLOW_SPECIAL; the rule is in include/jtokkit_amd.h)."""
         bs = [t if isinstance(t, (bytes, bytearray)) else t.encode("utf-8") for t in texts]
         doc_off = np.zeros(len(bs) + 1, dtype=np.int64)
         if bs:
             np.cumsum([len(b) for b in bs], out=doc_off[1:])
         text = np.frombuffer(b"".join(bs), dtype=np.uint8) if doc_off[-1] else np.zeros(0, dtype=np.uint8)
-        return self.encode_batch_packed(text, doc_off, ordinary, validate)
+        return self.encode_batch_packed(text, doc_off, ordinary, validate, allowed_special)
 
-    def encode_batch_packed(self, text_u8, doc_off, ordinary=False, validate=False):
+    def encode_batch_packed(self, text_u8, doc_off, ordinary=False, validate=False, allowed_special=None):
         b = self._b()
-        if self._host_pattern is not None:
+        if self._allow(b, allowed_special):
+            b.encode_host(text_u8, doc_off, ordinary, validate, allow_special=True)
+        elif self._host_pattern is not None:
             pb, pe = self._match_on_host(text_u8, doc_off)
             b.encode_pieces(text_u8, doc_off, pb, pe, ordinary)
         else:
             b.encode_host(text_u8, doc_off, ordinary, validate)
         return b.fetch()
+
+    def special_ids(self, allowed_special):
+        """"all" or an iterable of special-token literals -> their ids (ValueError for a literal that is no special token)."""
+        if isinstance(allowed_special, str):
+            if allowed_special != "all":
+                raise ValueError('allowed_special must be "all" or an iterable of special-token literals')
+            return sorted(set(self._specials.values()))
+        ids = []
+        for lit in allowed_special:
+            key = lit.decode("utf-8") if isinstance(lit, (bytes, bytearray)) else lit
+            if key not in self._specials:
+                raise ValueError("%r is not a special token of %s" % (lit, self._name))
+            ids.append(self._specials[key])
+        return ids
+
+    def _allow(self, b, allowed_special):
+        """Sets the batch's allowed set for allowed_special (not None); returns whether the encode takes the flag."""
+        if allowed_special is None:
+            return False
+        if self._host_pattern is not None:
+            raise ValueError("allowed_special: the device cannot run this encoding's custom split pattern")
+        b.set_allowed_special(self.special_ids(allowed_special))
+        return True
+
+    def encode_with_special_tokens(self, text, allowed_special="all", ordinary=False):
+        """tiktoken's encode(text, allowed_special=...) for one document, through a batch of one: the allowed literals become
+        their ids, the text between them is encodeOrdinary() of each segment.  Without `ordinary`, a literal outside the
+        allowed set raises UnsupportedOperationError, as encode() does; with it, such literals are ordinary text."""
+        if text is None:
+            return []
+        b = text if isinstance(text, (bytes, bytearray)) else text.encode("utf-8")
+        res = self.encode_batch_packed(np.frombuffer(bytes(b), dtype=np.uint8), np.array([0, len(b)], dtype=np.int64), ordinary,
+                                       False, allowed_special)
+        if res.status[0] < 0:
+            _check(int(res.status[0]))
+        return res.tokens.tolist()
 
     def _match_on_host(self, text_u8, doc_off):
         """while (matcher.find()) over every document (GptBytePairEncoding.java:77-80) -> byte ranges of the matches."""
@@ -558,17 +612,18 @@ class HipEncoding:
             if not t.is_contiguous():
                 raise ValueError("%s must be contiguous" % name)
 
-    def chunk_batch(self, texts, chunk_tokens, overlap=0, ordinary=False):
+    def chunk_batch(self, texts, chunk_tokens, overlap=0, ordinary=False, allowed_special=None):
         """Every text cut into consecutive chunks of at most chunk_tokens tokens (overlapping by up to `overlap` tokens), each a
         whole number of characters unless the tokens do not allow it: per document a list of (tokens, start, end, split), with
         start / end byte positions in that document (jtk_batch_chunk; the rule is in jtk_chunk_rules.h).  The chunks are
-        slices of encode(text); with overlap 0 they concatenate to it.  A document that cannot be encoded raises."""
+        slices of encode(text); with overlap 0 they concatenate to it.  A document that cannot be encoded raises.
+        allowed_special: as for encode_batch (a special token's byte span is its literal)."""
         bs = [t if isinstance(t, (bytes, bytearray)) else t.encode("utf-8") for t in texts]
         doc_off = np.zeros(len(bs) + 1, dtype=np.int64)
         if bs:
             np.cumsum([len(x) for x in bs], out=doc_off[1:])
         text = np.frombuffer(b"".join(bs), dtype=np.uint8) if doc_off[-1] else np.zeros(0, dtype=np.uint8)
-        res = self.encode_batch_packed(text, doc_off, ordinary)
+        res = self.encode_batch_packed(text, doc_off, ordinary, False, allowed_special)
         if len(res.status) and res.status.min() < 0:
             _check(int(res.status.min()))
         b = self._b()
@@ -581,14 +636,16 @@ class HipEncoding:
                            bool(f["split"][c])))
         return out
 
-    def chunk_batch_device(self, text, doc_off, chunk_tokens, overlap=0, ordinary=False, pad_id=-1):
+    def chunk_batch_device(self, text, doc_off, chunk_tokens, overlap=0, ordinary=False, pad_id=-1, allowed_special=None):
         """chunk_batch for a device-resident batch, in a model's layout.  text: CUDA torch.uint8 tensor, doc_off: CUDA torch.int64
         tensor [n_docs + 1], on this encoding's device.  Returns a dict of CUDA tensors written on torch.cuda.current_stream():
         rows int32 [n_chunks, chunk_tokens] (the chunk's ids, then pad_id), n_tok int32, doc int64, byte_begin / byte_end int64
         (positions in `text`), split bool [n_chunks], chunk_off int64 [n_docs + 1] and the per-document status int32 (documents
-        with a negative status have no chunks; they do not raise).  The call waits once, for the chunk count."""
+        with a negative status have no chunks; they do not raise).  The call waits once, for the chunk count (and, with
+        allowed_special -- as for encode_batch --, once more for the encode's count of literal candidates)."""
         import torch
         self._check_device_inputs("chunk_batch_device", text, doc_off)
+        allow = self._allow(self._b(), allowed_special)
         N_, ov = int(chunk_tokens), int(overlap)
         if N_ < 1 or not 0 <= ov < N_:
             raise ValueError("need chunk_tokens >= 1 and 0 <= overlap < chunk_tokens")
@@ -612,7 +669,7 @@ class HipEncoding:
             side = torch.cuda.ExternalStream(b.stream(), device=device)
             side.wait_stream(cur)
         stream = (side or cur).cuda_stream
-        b.encode_device(text.data_ptr(), doc_off.data_ptr(), nd, n, ordinary, stream=stream, sync=False)
+        b.encode_device(text.data_ptr(), doc_off.data_ptr(), nd, n, ordinary, stream=stream, sync=False, allow_special=allow)
         nc = b.chunk(N_, ov, stream)
         out = dict(rows=torch.empty((nc, N_), dtype=torch.int32, device=device),
                    n_tok=torch.empty(nc, dtype=torch.int32, device=device), doc=torch.empty(nc, dtype=torch.int64, device=device),
@@ -632,15 +689,16 @@ class HipEncoding:
             cur.wait_stream(side)
         return out
 
-    def count_tokens_batch(self, texts, ordinary=False):
-        """Encoding.countTokens / countTokensOrdinary for every text, one device call, no token ids written."""
+    def count_tokens_batch(self, texts, ordinary=False, allowed_special=None):
+        """Encoding.countTokens / countTokensOrdinary for every text, one device call, no token ids written.  allowed_special:
+        as for encode_batch."""
         bs = [t if isinstance(t, (bytes, bytearray)) else t.encode("utf-8") for t in texts]
         doc_off = np.zeros(len(bs) + 1, dtype=np.int64)
         if bs:
             np.cumsum([len(x) for x in bs], out=doc_off[1:])
         text = np.frombuffer(b"".join(bs), dtype=np.uint8) if doc_off[-1] else np.zeros(0, dtype=np.uint8)
         b = self._b()
-        b.encode_host(text, doc_off, ordinary, count_only=True)
+        b.encode_host(text, doc_off, ordinary, count_only=True, allow_special=self._allow(b, allowed_special))
         counts, status = b.fetch_counts()
         if len(status) and status.min() < 0:
             _check(int(status.min()))
