@@ -303,6 +303,41 @@ int jtk_batch_chunk_rows(jtk_batch* b, int32_t pad_id, int32_t* d_rows, void* st
  * same encode; without one it synchronises once for the token count.  Not after a count-only encode. */
 int jtk_batch_token_offsets(jtk_batch* b, int64_t* d_byte_pos, void* stream_or_null);
 
+/* ---- packed training rows, on the device ---------------------------------------------------------------------------
+ * The documents of the LAST batch encode on `b` packed into rows of seq_len (L) tokens, as a pretraining or fine-tuning
+ * loader does, with the document boundaries inside every row for a varlen attention call.  The rule
+ * (jtokkit_amd/csrc/jtk_pack_rules.h): a document with a negative status contributes nothing; otherwise its unit is its ids
+ * followed by sep_id (sep_id >= 0), sep_id followed by its ids (JTK_PACK_SEP_FIRST), or its ids alone (sep_id == -1); a unit
+ * of length 0 is dropped.
+ *   concat (default)      the units one after another, cut every L cells: n_rows = ceil(|S| / L), the last row padded with
+ *                         pad_id -- or floor(|S| / L) with JTK_PACK_DROP_LAST, the partial row omitted.
+ *   JTK_PACK_WHOLE_DOCS   each unit cut into items of L tokens (the last holds the rest), placed in order by next-fit: an item
+ *                         goes into the current row if it fits in the cells left, else it starts a new row; every row padded to
+ *                         L.  No document straddles two rows unless it is longer than a row.  Not with JTK_PACK_DROP_LAST.
+ *   Segments              maximal runs of one unit's cells, or of pad cells, inside one row, in row-major order:
+ *                         cu_seqlens[n_segments + 1] (int32; cu_seqlens[k + 1] - cu_seqlens[k] = the length of segment k, the
+ *                         last entry n_rows * L), seg_doc[n_segments] (its document, -1 for pad), max_seqlen (0 without rows);
+ *                         positions[r][c] = the offset of cell c in its segment (0 at every document boundary and row start).
+ *   Input:   as jtk_batch_chunk (not after a count-only encode or jtk_batch_encode_device_max_tokens); seq_len >= 1;
+ *            sep_id -1 or a rank or special id of the encoding; n_rows * seq_len < 2^31 (cu_seqlens is int32: split the batch
+ *            otherwise).  Any violation: JTK_ERR_INVALID_ARGUMENT.
+ *   Order:   the plan is queued after that encode on stream_or_null (or the batch's stream) and waits once, for the counts; a
+ *            new encode drops it; pack and chunk results do not replace each other. */
+enum {
+    JTK_PACK_WHOLE_DOCS = 1u,     /* next-fit of whole documents (fine-tuning) instead of one concatenated stream */
+    JTK_PACK_SEP_FIRST = 2u,      /* the separator before each document (BOS style) instead of after it (EOS style) */
+    JTK_PACK_DROP_LAST = 4u       /* concat: omit a partial last row instead of padding it */
+};
+int jtk_batch_pack(jtk_batch* b, int64_t seq_len, int32_t sep_id, uint32_t flags, void* stream_or_null,
+                   int64_t* n_rows, int64_t* n_segments, int32_t* max_seqlen);
+/* The packed rows of the last jtk_batch_pack to device memory: d_rows[n_rows * seq_len] int32 (ids, then pad_id),
+ * d_positions[n_rows * seq_len] int32, d_cu_seqlens[n_segments + 1] int32, d_seg_doc[n_segments] int64; all but d_rows may
+ * be NULL.  Ordered after the plan on stream_or_null (or the batch's stream); does not wait. */
+int jtk_batch_pack_write(jtk_batch* b, int32_t pad_id, int32_t* d_rows, int32_t* d_positions, int32_t* d_cu_seqlens,
+                         int64_t* d_seg_doc, void* stream_or_null);
+/* The same to host buffers (synchronises); any may be NULL. */
+int jtk_batch_pack_fetch(jtk_batch* b, int32_t pad_id, int32_t* rows, int32_t* positions, int32_t* cu_seqlens, int64_t* seg_doc);
+
 /* ---- batch decode on the device ---------------------------------------------------------------------
  * Replaces a loop of Encoding.decodeBytes(List<Integer>) (GptBytePairEncoding.java:137-151, 302-314; special-token
  * ids decode to their literals, :308-311) over n_seqs token lists: all ids back to back in `ids`, list q occupying

@@ -30,6 +30,9 @@ JTK_ENCODE_VALIDATE_UTF8 = 2
 JTK_ENCODE_COUNT_ONLY = 4
 JTK_ENCODE_TO_HOST = 8
 JTK_ENCODE_ALLOW_SPECIAL = 16
+JTK_PACK_WHOLE_DOCS = 1
+JTK_PACK_SEP_FIRST = 2
+JTK_PACK_DROP_LAST = 4
 JTK_OPT_CHUNK_BYTES = 1
 JTK_OPT_CHUNKS_IN_FLIGHT = 2
 JTK_OPT_HOST_CHUNK_BYTES = 3
@@ -75,6 +78,9 @@ SIGNATURES = {
     "jtk_batch_chunk_device_result": (C.c_int, [_p] + [C.POINTER(_p)] * 7),
     "jtk_batch_chunk_rows": (C.c_int, [_p, C.c_int32, _p, _p]),
     "jtk_batch_token_offsets": (C.c_int, [_p, _p, _p]),
+    "jtk_batch_pack": (C.c_int, [_p, _i64, C.c_int32, C.c_uint32, _p, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(C.c_int32)]),
+    "jtk_batch_pack_write": (C.c_int, [_p, C.c_int32, _p, _p, _p, _p, _p]),
+    "jtk_batch_pack_fetch": (C.c_int, [_p, C.c_int32, _p, _p, _p, _p]),
     "jtk_batch_decode": (C.c_int, [_p, _p, _p, _i64, C.POINTER(_i64)]),
     "jtk_batch_decode_device": (C.c_int, [_p, _p, _p, _i64, _i64, _p, C.POINTER(_i64)]),
     "jtk_batch_decode_fetch": (C.c_int, [_p, _p, _i64, _p, _p]),

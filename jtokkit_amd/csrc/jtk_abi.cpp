@@ -142,6 +142,12 @@ struct jtk_batch {
     bool have_chunk = false, have_tiles = false;
     hipStream_t ck_stream = nullptr;     // stream of the last chunk plan
     hipEvent_t ev_ck = nullptr;          // orders a chunk call's stream after the encode / the plan
+    // jtk_batch_pack: hdr | P | SEG | RS | flag | lifting table (its own scratch: pack and chunk results outlive each other)
+    DevBuf pk_scratch;
+    int64_t* h_pk = nullptr; size_t h_pk_cap = 0;   // pinned: the plan's hdr, read once per call
+    JtkPackWork pk{};
+    bool have_pack = false;
+    hipStream_t pk_stream = nullptr;     // stream of the last pack plan
     // JTK_ENCODE_ALLOW_SPECIAL (jtk_special.hip): the allowed set per literal of the encoding (a new batch allows all) and its
     // device copy; find scratch (hdr | the stitched status | per-block counts), candidates and sub-documents, the stitched result
     std::vector<uint8_t> sp_allowed;
@@ -411,7 +417,7 @@ void jtk_batch_destroy(jtk_batch* b) {
     }
     DevBuf* bufs[] = {&b->in_text, &b->in_off, &b->in_pieces, &b->out, &b->plan, &b->dec_in_ids, &b->dec_in_off,
                       &b->dec_zero, &b->dec_tile, &b->dec_pre, &b->dec_out, &b->dec_byte_off, &b->trunc_kept, &b->trunc_flag,
-                      &b->mt_scratch, &b->mt_gather, &b->ck_scratch, &b->ck_tiles, &b->ck_rec, &b->sp_lits, &b->sp_find,
+                      &b->mt_scratch, &b->mt_gather, &b->ck_scratch, &b->ck_tiles, &b->ck_rec, &b->pk_scratch, &b->sp_lits, &b->sp_find,
                       &b->sp_cand, &b->sp_out};
     for (DevBuf* d : bufs) d->release();
     if (b->h_sp) (void)hipHostFree(b->h_sp);
@@ -426,6 +432,7 @@ void jtk_batch_destroy(jtk_batch* b) {
     if (b->h_gather) (void)hipHostFree(b->h_gather);
     if (b->h_mt) (void)hipHostFree(b->h_mt);
     if (b->h_ck) (void)hipHostFree(b->h_ck);
+    if (b->h_pk) (void)hipHostFree(b->h_pk);
     if (b->ev_ck) (void)hipEventDestroy(b->ev_ck);
     if (b->host_plan) (void)hipHostFree(b->host_plan);
     if (b->h_tokens) (void)hipHostFree(b->h_tokens);
@@ -792,6 +799,7 @@ int run_job(jtk_batch* b, const uint8_t* d_text, const uint8_t* h_text, const in
     b->have_trunc = false;
     b->have_chunk = false;
     b->have_tiles = false;
+    b->have_pack = false;
     b->synced = false;
     b->last_stream = s;
     b->prof_chunks = prof ? n_chunks : 0;
@@ -1555,6 +1563,7 @@ int jtk_batch_encode_device_max_tokens(jtk_batch* b, const uint8_t* d_utf8, cons
     b->have_trunc = false;
     b->have_chunk = false;
     b->have_tiles = false;
+    b->have_pack = false;
     b->plan_doc_off = nullptr;
     if (n_docs == 0) return JTK_OK;
     hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
@@ -1786,6 +1795,127 @@ int jtk_batch_token_offsets(jtk_batch* b, int64_t* d_byte_pos, void* stream_or_n
     if (b->ck.n_tok > 0 && !d_byte_pos) return fail(JTK_ERR_INVALID_ARGUMENT, "d_byte_pos is NULL");
     jtk_launch_token_offsets(b->ck, d_byte_pos, s);
     HIP_TRY(hipGetLastError());
+    return JTK_OK;
+}
+
+
+// ---- packed rows of the last encode (jtk_pack.hip) ---------------------------------------------------------------------
+static bool pk_known_id(const jtk_encoding* enc, int32_t id) {
+    const JtkHostTables& h = enc->host;
+    if ((uint32_t)id <= h.max_id && (size_t)id < h.id_present.size() && h.id_present[(size_t)id]) return true;
+    for (const auto& sp : h.specials) if (sp.second == id) return true;
+    return false;
+}
+
+int jtk_batch_pack(jtk_batch* b, int64_t seq_len, int32_t sep_id, uint32_t flags, void* stream_or_null,
+                   int64_t* n_rows, int64_t* n_segments, int32_t* max_seqlen) {
+    if (!b || !n_rows || !n_segments || !max_seqlen) return fail(JTK_ERR_INVALID_ARGUMENT, "bad arguments");
+    *n_rows = 0; *n_segments = 0; *max_seqlen = 0;
+    if (!b->have_result) return fail(JTK_ERR_INVALID_ARGUMENT, "no batch encode result on this batch (jtk_batch_encode_device_max_tokens leaves none)");
+    if (b->job_flags & JTK_ENCODE_COUNT_ONLY) return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode was count-only: there are no token ids");
+    if (seq_len < 1) return fail(JTK_ERR_INVALID_ARGUMENT, "seq_len must be at least 1");
+    if (seq_len > INT32_MAX)
+        return fail(JTK_ERR_INVALID_ARGUMENT, "seq_len must be below 2^31: cu_seqlens (int32) indexes the cells of the rows");
+    if (sep_id < -1) return fail(JTK_ERR_INVALID_ARGUMENT, "sep_id must be -1 (no separator) or a token id");
+    if (sep_id >= 0 && !pk_known_id(b->enc, sep_id))
+        return fail(JTK_ERR_INVALID_ARGUMENT, "sep_id " + std::to_string(sep_id) + " is neither a rank id nor a special id of the encoding");
+    if (flags & ~(uint32_t)(JTK_PACK_WHOLE_DOCS | JTK_PACK_SEP_FIRST | JTK_PACK_DROP_LAST))
+        return fail(JTK_ERR_INVALID_ARGUMENT, "flags: JTK_PACK_WHOLE_DOCS, JTK_PACK_SEP_FIRST, JTK_PACK_DROP_LAST");
+    const bool whole = (flags & JTK_PACK_WHOLE_DOCS) != 0, drop = (flags & JTK_PACK_DROP_LAST) != 0;
+    if (whole && drop) return fail(JTK_ERR_INVALID_ARGUMENT, "JTK_PACK_DROP_LAST does not apply with JTK_PACK_WHOLE_DOCS (every row is padded)");
+    const int64_t n = b->job_docs;
+    if (n >= INT32_MAX) return fail(JTK_ERR_INVALID_ARGUMENT, "too many documents to pack in one call (2^31 - 1 at most)");
+    HIP_TRY(hipSetDevice(b->enc->device));
+    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    b->have_pack = false;
+    int K = 1;
+    while (K < 62 && ((int64_t)1 << K) <= n) K++;                      // 2^K > n >= the number of groups
+    // scratch: hdr[4] | P | SEG | RS [n + 1] | flag [n] | up [K][n + 1]
+    const size_t m = (size_t)n + 1, o_flag = 32 + 3 * m * 8, o_up = align_up(o_flag + m, 16);
+    const size_t bytes = whole ? o_up + (size_t)K * m * 4 : o_flag;
+    int rc;
+    if ((rc = b->pk_scratch.ensure(bytes)) || (rc = ensure_pinned((void**)&b->h_pk, &b->h_pk_cap, 32, 0)) ||
+        (rc = ck_order(b, b->last_stream, s)))
+        return rc;
+    JtkPackWork& w = b->pk;
+    w = JtkPackWork{};
+    uint8_t* base = (uint8_t*)b->pk_scratch.p;
+    w.hdr = (int64_t*)base;
+    w.P = (int64_t*)(base + 32);
+    w.SEG = w.P + m;
+    w.RS = w.SEG + m;
+    w.flag = base + o_flag;
+    w.up = whole ? (int32_t*)(base + o_up) : nullptr;
+    w.K = K;
+    w.drop_last = drop;
+    w.status = (const int32_t*)b->status.p;
+    JtkPackView& v = w.v;
+    v.tokens = (const int32_t*)b->tokens.p; v.tok_off = (const int64_t*)b->tok_off.p;
+    v.P = w.P; v.SEG = w.SEG; v.RS = w.RS; v.flag = w.flag; v.nxt = w.up;
+    v.n = n; v.L = seq_len; v.sep_id = sep_id; v.sep_first = (flags & JTK_PACK_SEP_FIRST) != 0 && sep_id >= 0; v.whole = whole;
+    // plan; the one wait: hdr
+    HIP_TRY(hipMemsetAsync(w.hdr, 0, 32, s));
+    jtk_launch_pack_plan(w, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(b->h_pk, w.hdr, 32, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const int64_t S = b->h_pk[0];
+    int64_t rows, segs, longest = b->h_pk[3];
+    if (whole) {
+        rows = b->h_pk[2];
+        segs = b->h_pk[1];
+    } else {
+        rows = jtk_pack_concat_rows(S, seq_len, drop);
+        const int64_t pad = rows > 0 ? rows * seq_len - S : 0;        // (the last row's pad; never with DROP_LAST)
+        segs = b->h_pk[1] + (pad > 0 ? 1 : 0);
+        if (pad > longest) longest = pad;
+    }
+    if (rows > INT32_MAX / seq_len)
+        return fail(JTK_ERR_INVALID_ARGUMENT, "the rows would hold " + std::to_string(rows) + " x " + std::to_string(seq_len) +
+                                                  " cells, more than cu_seqlens (int32) can index (2^31 - 1): split the batch");
+    w.n_rows = rows;
+    w.n_seg = segs;
+    b->have_pack = true;
+    b->pk_stream = s;
+    *n_rows = rows; *n_segments = segs; *max_seqlen = (int32_t)longest;
+    return JTK_OK;
+}
+
+int jtk_batch_pack_write(jtk_batch* b, int32_t pad_id, int32_t* d_rows, int32_t* d_positions, int32_t* d_cu_seqlens,
+                         int64_t* d_seg_doc, void* stream_or_null) {
+    if (!b || !b->have_pack) return fail(JTK_ERR_INVALID_ARGUMENT, "jtk_batch_pack has not run on the last encode of this batch");
+    if (b->pk.n_rows > 0 && !d_rows) return fail(JTK_ERR_INVALID_ARGUMENT, "d_rows is NULL");
+    if (((uintptr_t)d_rows & 3u) || ((uintptr_t)d_positions & 3u) || ((uintptr_t)d_cu_seqlens & 3u) || ((uintptr_t)d_seg_doc & 7u))
+        return fail(JTK_ERR_INVALID_ARGUMENT, "unaligned output (4-byte int32, 8-byte int64 arrays)");
+    HIP_TRY(hipSetDevice(b->enc->device));
+    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    int rc;
+    if ((rc = ck_order(b, b->pk_stream, s))) return rc;
+    jtk_launch_pack_write(b->pk, pad_id, d_rows, d_positions, d_cu_seqlens, d_seg_doc, s);
+    HIP_TRY(hipGetLastError());
+    return JTK_OK;
+}
+
+int jtk_batch_pack_fetch(jtk_batch* b, int32_t pad_id, int32_t* rows, int32_t* positions, int32_t* cu_seqlens, int64_t* seg_doc) {
+    if (!b || !b->have_pack) return fail(JTK_ERR_INVALID_ARGUMENT, "jtk_batch_pack has not run on the last encode of this batch");
+    const size_t cells = (size_t)(b->pk.n_rows * b->pk.v.L), ns = (size_t)b->pk.n_seg;
+    // device staging: rows | positions | cu_seqlens | seg_doc
+    const size_t o_pos = align_up(cells * 4, 16), o_cu = o_pos + align_up(cells * 4, 16), o_sd = align_up(o_cu + (ns + 1) * 4, 16);
+    HIP_TRY(hipSetDevice(b->enc->device));
+    DevBuf tmp;
+    int rc = tmp.ensure(o_sd + ns * 8 + 16);
+    if (rc) return rc;
+    uint8_t* p = (uint8_t*)tmp.p;
+    rc = jtk_batch_pack_write(b, pad_id, (int32_t*)p, positions ? (int32_t*)(p + o_pos) : nullptr, (int32_t*)(p + o_cu),
+                              seg_doc ? (int64_t*)(p + o_sd) : nullptr, b->pk_stream);
+    hipError_t e = rc == JTK_OK ? hipStreamSynchronize(b->pk_stream) : hipSuccess;
+    if (rc == JTK_OK && e == hipSuccess && rows && cells) e = hipMemcpy(rows, p, cells * 4, hipMemcpyDeviceToHost);
+    if (rc == JTK_OK && e == hipSuccess && positions && cells) e = hipMemcpy(positions, p + o_pos, cells * 4, hipMemcpyDeviceToHost);
+    if (rc == JTK_OK && e == hipSuccess && cu_seqlens) e = hipMemcpy(cu_seqlens, p + o_cu, (ns + 1) * 4, hipMemcpyDeviceToHost);
+    if (rc == JTK_OK && e == hipSuccess && seg_doc && ns) e = hipMemcpy(seg_doc, p + o_sd, ns * 8, hipMemcpyDeviceToHost);
+    tmp.release();
+    if (rc != JTK_OK) return rc;
+    HIP_TRY(e);
     return JTK_OK;
 }
 

@@ -315,3 +315,8 @@ void jtk_launch_chunk_rows(const JtkChunkWork& w, int32_t pad_id, int32_t* rows,
 void jtk_launch_token_offsets(const JtkChunkWork& w, int64_t* byte_pos, hipStream_t s) {
     if (w.n_tok > 0) hipLaunchKernelGGL(k_ck_tokpos, dim3((unsigned)w.n_tiles), dim3(256), 0, s, w, byte_pos);
 }
+
+void jtk_launch_scan_i64(int64_t* inout, int64_t n, int64_t* total, hipStream_t s) {
+    hipLaunchKernelGGL(k_ck_scan<int64_t>, dim3(1), dim3(1024), 0, s, (const int64_t*)inout, n, inout, total, (const int64_t*)nullptr,
+                       (int64_t)0, (int64_t*)nullptr);
+}

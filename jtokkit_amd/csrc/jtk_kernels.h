@@ -6,6 +6,7 @@
 #include <stdint.h>
 
 #include "jtk_common.h"
+#include "jtk_pack_rules.h"
 
 #define JTK_SPLIT_TILE 4096      // bytes per pretok_split workgroup
 #define JTK_SPLIT_HALO 64
@@ -272,6 +273,26 @@ void jtk_launch_chunk_tiles(const JtkChunkWork& w, hipStream_t s);      // tile 
 void jtk_launch_chunk_write(const JtkChunkWork& w, hipStream_t s);      // records (needs n_chunks and the tiles)
 void jtk_launch_chunk_rows(const JtkChunkWork& w, int32_t pad_id, int32_t* rows, hipStream_t s);
 void jtk_launch_token_offsets(const JtkChunkWork& w, int64_t* byte_pos, hipStream_t s);   // (needs the tiles)
+// exclusive scan of in[0, n) into out[0, n] in place (k_ck_scan, one workgroup); *total (may be NULL) = the sum
+void jtk_launch_scan_i64(int64_t* inout, int64_t n, int64_t* total, hipStream_t s);
+// Device-side state of jtk_batch_pack (jtk_pack.hip): the units of the last batch encode packed into rows of L tokens by the
+// rule of jtk_pack_rules.h.  The view's P, SEG, RS, flag and nxt point into the scratch below.
+struct JtkPackWork {
+    JtkPackView v;
+    const int32_t* status;      // [n] of the last encode
+    int64_t* hdr;               // [0] |S|, [1] SEG[n], [2] RS[n] (whole: rows), [3] the longest segment
+    int64_t* P;                 // [n + 1] unit offsets in S
+    int64_t* SEG;               // [n + 1]
+    int64_t* RS;                // [n + 1] (whole)
+    uint8_t* flag;              // [n]     (whole)
+    int32_t* up;                // [K][n + 1] (whole): up[k][d] = the head 2^k groups after the group of d; up[0] = nxt
+    int K;                      // ceil(log2(n + 1)) lifting levels
+    bool drop_last;
+    int64_t n_rows, n_seg;
+};
+void jtk_launch_pack_plan(const JtkPackWork& w, hipStream_t s);        // units, scans, groups -> hdr
+void jtk_launch_pack_write(const JtkPackWork& w, int32_t pad_id, int32_t* rows, int32_t* positions, int32_t* cu_seqlens,
+                           int64_t* seg_doc, hipStream_t s);           // (needs n_rows, n_seg)
 // Device-side state of an allow-special encode (jtk_special.hip, JTK_ENCODE_ALLOW_SPECIAL; the rule is jtk_special_rules.h).
 // Candidates (per position, the longest allowed literal there) are found in position order, resolved to the kept matches, and
 // the batch is cut into sub-documents that partition the text: per document a segment, then per candidate i two slots

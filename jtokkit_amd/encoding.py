@@ -294,6 +294,33 @@ class Batch:
         """jtk_batch_token_offsets: int64 [n_tokens] at d_byte_pos_ptr, each token's byte position in the batch text."""
         _check(N.lib().jtk_batch_token_offsets(self._h, d_byte_pos_ptr, stream))
 
+    # ---- packed training rows (device) -------------------------------------------------------------------
+    def pack(self, seq_len, sep_id=-1, whole_docs=False, sep_first=False, drop_last=False, stream=None):
+        """jtk_batch_pack on the last encode (the rule is in jtk_pack_rules.h).  Returns (n_rows, n_segments, max_seqlen)."""
+        flags = ((N.JTK_PACK_WHOLE_DOCS if whole_docs else 0) | (N.JTK_PACK_SEP_FIRST if sep_first else 0)
+                 | (N.JTK_PACK_DROP_LAST if drop_last else 0))
+        nr, ns, mx = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+        _check(N.lib().jtk_batch_pack(self._h, int(seq_len), int(sep_id), flags, stream, C.byref(nr), C.byref(ns), C.byref(mx)))
+        self._pack = (nr.value, int(seq_len), ns.value)
+        return nr.value, ns.value, mx.value
+
+    def pack_write(self, pad_id, d_rows_ptr, d_positions_ptr=None, d_cu_seqlens_ptr=None, d_seg_doc_ptr=None, stream=None):
+        """jtk_batch_pack_write: rows / positions int32 [n_rows, seq_len], cu_seqlens int32 [n_segments + 1], seg_doc int64
+        [n_segments] at the given device pointers (all but the rows may be None); does not wait."""
+        _check(N.lib().jtk_batch_pack_write(self._h, int(pad_id), d_rows_ptr, d_positions_ptr, d_cu_seqlens_ptr, d_seg_doc_ptr,
+                                            stream))
+
+    def pack_fetch(self, pad_id=-1):
+        """The last pack call's result on the host: dict of rows, positions [n_rows, seq_len] int32, cu_seqlens int32,
+        seg_doc int64."""
+        nr, L, ns = self._pack
+        f = dict(rows=np.zeros((nr, L), dtype=np.int32), positions=np.zeros((nr, L), dtype=np.int32),
+                 cu_seqlens=np.zeros(ns + 1, dtype=np.int32), seg_doc=np.zeros(max(ns, 1), dtype=np.int64))
+        _check(N.lib().jtk_batch_pack_fetch(self._h, int(pad_id), *(f[k].ctypes.data for k in ("rows", "positions", "cu_seqlens",
+                                                                                               "seg_doc"))))
+        f["seg_doc"] = f["seg_doc"][:ns]
+        return f
+
     # ---- batch decode (device) -------------------------------------------------------------------------
     def decode_host(self, ids, seq_off):
         """ids int32[n], seq_off int64[n_seqs+1] -> total byte count (result stays on the device)."""
@@ -687,6 +714,90 @@ class HipEncoding:
                 _copy_d2d(t.data_ptr(), src, t.numel() * t.element_size(), stream)
         if side is not None:
             cur.wait_stream(side)
+        return out
+
+    def _sep_id(self, sep):
+        """None -> -1, a special-token literal -> its id, an int -> itself."""
+        if sep is None:
+            return -1
+        if isinstance(sep, (str, bytes, bytearray)):
+            key = sep.decode("utf-8") if isinstance(sep, (bytes, bytearray)) else sep
+            if key not in self._specials:
+                raise ValueError("%r is not a special token of %s" % (sep, self._name))
+            return self._specials[key]
+        return int(sep)
+
+    def pack_batch(self, texts, seq_len, sep=None, sep_first=False, whole_docs=False, drop_last=False, pad_id=-1, ordinary=False,
+                   allowed_special=None):
+        """Every text encoded, then packed into rows of seq_len tokens (jtk_batch_pack; the rule is in jtk_pack_rules.h): a dict
+        of numpy arrays rows, positions int32 [n_rows, seq_len], cu_seqlens int32 [n_segments + 1], seg_doc int64
+        [n_segments], status int32 [n_docs] and max_seqlen (int).  sep: None, a token id or a special-token literal such as
+        "<|endoftext|>", after each document (or before it with sep_first).  whole_docs: next-fit of whole documents instead of
+        one concatenated stream; drop_last (concat only): omit a partial last row.  Documents with a negative status are left
+        out (they do not raise)."""
+        bs = [t if isinstance(t, (bytes, bytearray)) else t.encode("utf-8") for t in texts]
+        doc_off = np.zeros(len(bs) + 1, dtype=np.int64)
+        if bs:
+            np.cumsum([len(x) for x in bs], out=doc_off[1:])
+        text = np.frombuffer(b"".join(bs), dtype=np.uint8) if doc_off[-1] else np.zeros(0, dtype=np.uint8)
+        sep_id = self._sep_id(sep)
+        res = self.encode_batch_packed(text, doc_off, ordinary, False, allowed_special)
+        b = self._b()
+        _, _, mx = b.pack(seq_len, sep_id, whole_docs, sep_first, drop_last)
+        f = b.pack_fetch(pad_id)
+        f["status"] = res.status.copy()
+        f["max_seqlen"] = mx
+        return f
+
+    def pack_batch_device(self, text, doc_off, seq_len, sep=None, sep_first=False, whole_docs=False, drop_last=False, pad_id=-1,
+                          ordinary=False, allowed_special=None):
+        """pack_batch for a device-resident batch.  text: CUDA torch.uint8 tensor, doc_off: CUDA torch.int64 tensor [n_docs + 1],
+        on this encoding's device.  Returns a dict of CUDA tensors written on torch.cuda.current_stream(): rows int32
+        [n_rows, seq_len], positions int32 [n_rows, seq_len], cu_seqlens int32 [n_segments + 1], seg_doc int64 [n_segments],
+        status int32 [n_docs], and max_seqlen as a Python int -- what a varlen attention call takes.  The call waits once, for
+        the counts (and, with allowed_special, once more for the encode's count of literal candidates)."""
+        import torch
+        self._check_device_inputs("pack_batch_device", text, doc_off)
+        L = int(seq_len)
+        if L < 1:
+            raise ValueError("seq_len must be >= 1")
+        if whole_docs and drop_last:
+            raise ValueError("drop_last applies to the concatenated stream only")
+        sep_id = self._sep_id(sep)
+        allow = self._allow(self._b(), allowed_special)
+        nd = doc_off.numel() - 1
+        if nd < 0:
+            raise ValueError("doc_off needs n_docs + 1 entries")
+        device = text.device
+        n = text.numel()
+        st = text.untyped_storage()
+        if text.data_ptr() % 16 or st.data_ptr() + st.nbytes() < text.data_ptr() + (n + 15) // 16 * 16:
+            # (the encode reads whole aligned 16-byte blocks)
+            buf = torch.zeros((n + 15) // 16 * 16 + 16, dtype=torch.uint8, device=device)
+            buf[:n].copy_(text)
+            text = buf
+        b = self._b()
+        cur = torch.cuda.current_stream(device)
+        side = None
+        if cur.cuda_stream == 0:
+            # (the legacy default stream: as in chunk_batch_device, the work goes to the batch's own stream explicitly)
+            side = torch.cuda.ExternalStream(b.stream(), device=device)
+            side.wait_stream(cur)
+        stream = (side or cur).cuda_stream
+        b.encode_device(text.data_ptr(), doc_off.data_ptr(), nd, n, ordinary, stream=stream, sync=False, allow_special=allow)
+        nr, ns, mx = b.pack(L, sep_id, whole_docs, sep_first, drop_last, stream)
+        out = dict(rows=torch.empty((nr, L), dtype=torch.int32, device=device),
+                   positions=torch.empty((nr, L), dtype=torch.int32, device=device),
+                   cu_seqlens=torch.empty(ns + 1, dtype=torch.int32, device=device),
+                   seg_doc=torch.empty(ns, dtype=torch.int64, device=device),
+                   status=torch.empty(nd, dtype=torch.int32, device=device))
+        b.pack_write(pad_id, out["rows"].data_ptr(), out["positions"].data_ptr(), out["cu_seqlens"].data_ptr(),
+                     out["seg_doc"].data_ptr(), stream)
+        if nd:
+            _copy_d2d(out["status"].data_ptr(), b.device_result()[2], nd * 4, stream)
+        if side is not None:
+            cur.wait_stream(side)
+        out["max_seqlen"] = mx
         return out
 
     def count_tokens_batch(self, texts, ordinary=False, allowed_special=None):
