@@ -59,11 +59,16 @@ enum {
     JTK_ENCODE_COUNT_ONLY = 4u,   /* Encoding.countTokens() / countTokensOrdinary() (GptBytePairEncoding.java:122-129) for
                                      the whole batch: token offsets (tok_off[d + 1] - tok_off[d] = the count) and
                                      status, but no token ids -- fetch with tokens == NULL */
-    JTK_ENCODE_TO_HOST = 8u,      /* jtk_batch_encode only: stream the result to pinned host memory while later chunks
-                                     are still being encoded; read it in place with jtk_batch_host_result() */
-    JTK_ENCODE_ALLOW_SPECIAL = 16u/* jtk_batch_encode / jtk_batch_encode_device only: the batch's allowed special-token
+    JTK_ENCODE_TO_HOST = 8u,      /* jtk_batch_encode / jtk_batch_encode_pieces only: stream the result to pinned host
+                                     memory while later chunks are still being encoded; read it in place with
+                                     jtk_batch_host_result() */
+    JTK_ENCODE_ALLOW_SPECIAL = 16u,/* jtk_batch_encode / jtk_batch_encode_device only: the batch's allowed special-token
                                      literals are encoded as their ids (jtk_batch_set_allowed_special has the rule);
                                      every other entry point that takes flags returns JTK_ERR_INVALID_ARGUMENT for it */
+    JTK_ENCODE_COMPACT_IDS = 32u  /* jtk_batch_encode / jtk_batch_encode_pieces, only together with JTK_ENCODE_TO_HOST: the ids
+                                     reach pinned host memory as a 16-bit plane plus a plane of the bits above ("compact
+                                     token ids" below) -- 2 to 2.125 bytes per token over the link instead of 4; read them
+                                     with jtk_batch_host_result_compact().  Anywhere else: JTK_ERR_INVALID_ARGUMENT */
 };
 
 /* Options of jtk_batch_set_option.  A batch larger than one chunk is cut into runs of whole documents ("chunks") that flow
@@ -107,7 +112,8 @@ int jtk_device_count(void);
  * GptBytePairEncoding.java:81-83 is honoured for pieces of any length: for tables in which merging a token's bytes
  * reproduces the token (every table trained by byte-pair merging; the three shipped ones) it is a pure shortcut, for others
  * the unreproducible entries get a lookup of their own and the exact intra-piece cuts are switched off.
- * Special tokens: any number of literals of any length >= 1 (any first byte), ids < 131071 + 2^20. */
+ * Special tokens: any number of literals of any length >= 1 (any first byte), ids < 2^25 (the decode table is dense: 4 bytes
+ * of device memory per id up to the largest). */
 int jtk_encoding_create(const char* name, int pattern_kind, const uint8_t* tiktoken, size_t tiktoken_len,
                         const char* const* special_literals, const int32_t* special_ids, int n_specials,
                         int device, jtk_encoding** out);
@@ -116,6 +122,7 @@ const char* jtk_encoding_name(const jtk_encoding* enc);          /* Encoding.get
 int jtk_encoding_device(const jtk_encoding* enc);
 int64_t jtk_encoding_vocab_size(const jtk_encoding* enc);        /* number of rank-table entries */
 int64_t jtk_encoding_pair_count(const jtk_encoding* enc);        /* (left,right) -> rank entries */
+int jtk_encoding_id_bits(const jtk_encoding* enc);               /* 16 + hb of "compact token ids" below: 16, 17, 18, 20, 24 or 32 */
 
 /* ---- batch encode: the hot path ------------------------------------------------------------------
  * Replaces a loop of Encoding.encode(String) / encodeOrdinary(String) / countTokens(String)
@@ -155,6 +162,40 @@ int jtk_batch_encode_pieces(jtk_batch* b, const uint8_t* utf8, const int64_t* do
 /* After an encode with JTK_ENCODE_TO_HOST: the result in the batch's pinned host buffers (valid until the next encode
  * on this batch): tokens[n_tokens], tok_off[n_docs + 1], status[n_docs]. */
 int jtk_batch_host_result(jtk_batch* b, const int32_t** tokens, const int64_t** tok_off, const int32_t** status);
+
+/* ---- compact token ids: a 16-bit plane plus a plane of the bits above ---------------------------------------------------
+ * The format (jtokkit_amd/csrc/jtk_compact_rules.h).  max_id = the largest id a result of the encoding can hold: its rank
+ * table's largest id, the pseudo ids of single bytes the table lacks (they stay in the result; their document gets
+ * JTK_ERR_UNENCODABLE) and every special id.  hb = the smallest of {0, 1, 2, 4, 8, 16} with max_id < 2^(16 + hb);
+ * jtk_encoding_id_bits() = 16 + hb.  A compact result of n tokens is
+ *   lo  uint16[n]                  lo[i] = id[i] & 0xFFFF
+ *   hi  uint32[ceil(n * hb / 32)]  token i's hb bits (id[i] >> 16) at bit (i * hb) % 32 of word (i * hb) / 32, little-endian
+ *                                  bit order; the unused bits of the last word are zero; absent (NULL) when hb == 0
+ * and tok_off / status as ever (token indices: they address both planes).  r50k_base, p50k_base, p50k_edit: hb = 0, and lo
+ * alone is the uint16 token shard GPT-2-style loaders read; cl100k_base: hb = 1 (2.125 bytes per token).  Widening gives back
+ * exactly the int32 ids of the plain result.
+ *
+ * jtk_batch_host_result_compact: after jtk_batch_encode / _encode_pieces with JTK_ENCODE_TO_HOST | JTK_ENCODE_COMPACT_IDS, the
+ *   planes in the batch's pinned host buffers (valid until the next encode on this batch); lo and hi are NULL after a
+ *   count-only encode.  Each chunk's id range is compacted on the device behind the chunk's kernels and its two plane ranges
+ *   copied up, one chunk behind the kernels like the int32 copy of the plain route; the pinned buffers are sized and grown by
+ *   the compact sizes.  JTK_ENCODE_ALLOW_SPECIAL, JTK_ENCODE_VALIDATE_UTF8 and JTK_ENCODE_COUNT_ONLY compose with the flag.
+ *   The device-side result stays int32: jtk_batch_fetch, jtk_batch_device_result, jtk_batch_chunk, jtk_batch_pack,
+ *   jtk_batch_truncate and jtk_batch_token_offsets work as after the plain encode.  jtk_batch_host_result returns
+ *   JTK_ERR_INVALID_ARGUMENT after such an encode (host memory holds no int32 ids).  jtk_encode and the service do not take
+ *   the flag.
+ * jtk_batch_compact: the planes of the LAST batch encode on `b` (host- or device-input, any flags but JTK_ENCODE_COUNT_ONLY:
+ *   JTK_ERR_INVALID_ARGUMENT then, and with no result) into caller-owned device buffers: d_lo[n_tokens] uint16,
+ *   d_hi[ceil(n_tokens * hb / 32)] uint32 (may be NULL when hb == 0).  Waits once, for the token count (as jtk_batch_result);
+ *   the pass is then queued behind the encode on stream_or_null (a hipStream_t), or on the batch's stream when it is NULL, and
+ *   the call does not wait for it.  It reads the ids only: chunk, pack and truncate results are untouched.  16-byte aligned
+ *   buffers take the fast path.
+ * jtk_widen_ids: out[k] = id of token first + k for k < n, on the host, from planes as above (id_bits = 16 + hb) -- any range,
+ *   so that a caller widens one document at a time: first = tok_off[d], n = tok_off[d + 1] - tok_off[d]. */
+int jtk_batch_host_result_compact(jtk_batch* b, const uint16_t** lo, const uint32_t** hi, int* id_bits, const int64_t** tok_off,
+                                  const int32_t** status);
+int jtk_batch_compact(jtk_batch* b, uint16_t* d_lo, uint32_t* d_hi, void* stream_or_null);
+int jtk_widen_ids(const uint16_t* lo, const uint32_t* hi, int id_bits, int64_t first, int64_t n, int32_t* out_int32);
 
 /* Device buffers already resident in HBM (what bench.py times).  `stream_or_null` = a hipStream_t
  * to order against, or NULL for the batch's own stream: the whole encode is ordered like one operation on that stream

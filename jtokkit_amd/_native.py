@@ -30,6 +30,7 @@ JTK_ENCODE_VALIDATE_UTF8 = 2
 JTK_ENCODE_COUNT_ONLY = 4
 JTK_ENCODE_TO_HOST = 8
 JTK_ENCODE_ALLOW_SPECIAL = 16
+JTK_ENCODE_COMPACT_IDS = 32
 JTK_PACK_WHOLE_DOCS = 1
 JTK_PACK_SEP_FIRST = 2
 JTK_PACK_DROP_LAST = 4
@@ -52,12 +53,16 @@ SIGNATURES = {
     "jtk_encoding_device": (C.c_int, [_p]),
     "jtk_encoding_vocab_size": (_i64, [_p]),
     "jtk_encoding_pair_count": (_i64, [_p]),
+    "jtk_encoding_id_bits": (C.c_int, [_p]),
     "jtk_batch_create": (C.c_int, [_p, C.POINTER(_p)]),
     "jtk_batch_destroy": (None, [_p]),
     "jtk_batch_set_option": (C.c_int, [_p, C.c_int, _i64]),
     "jtk_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(_p)]),
     "jtk_host_free": (None, [_p]),
     "jtk_batch_host_result": (C.c_int, [_p, C.POINTER(_p), C.POINTER(_p), C.POINTER(_p)]),
+    "jtk_batch_host_result_compact": (C.c_int, [_p, C.POINTER(_p), C.POINTER(_p), C.POINTER(C.c_int), C.POINTER(_p), C.POINTER(_p)]),
+    "jtk_batch_compact": (C.c_int, [_p, _p, _p, _p]),
+    "jtk_widen_ids": (C.c_int, [_p, _p, C.c_int, _i64, _i64, _p]),
     "jtk_batch_encode": (C.c_int, [_p, _p, _p, _i64, C.c_uint32, C.POINTER(_i64)]),
     "jtk_batch_encode_pieces": (C.c_int, [_p, _p, _p, _i64, _p, _p, _i64, C.c_uint32, C.POINTER(_i64)]),
     "jtk_batch_encode_device": (C.c_int, [_p, _p, _p, _i64, _i64, C.c_uint32, _p, C.POINTER(_i64)]),

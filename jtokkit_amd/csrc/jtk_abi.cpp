@@ -15,6 +15,7 @@
 
 #include "../../include/jtokkit_amd.h"
 #include "jtk_chunk_rules.h"
+#include "jtk_compact_rules.h"
 #include "jtk_kernels.h"
 #include "jtk_maxtok_rules.h"
 #include "jtk_tables.h"
@@ -65,6 +66,7 @@ struct jtk_encoding {
     DevBuf bnd;                      // jtk_batch_chunk: one bit per id of the decode table, set when its byte string does not start
                                      // with a UTF-8 continuation byte (lengths come from dec_off)
     uint32_t n_ids_table = 0;        // ids 0 .. n_ids_table-1 have an entry in the decode table (incl. special tokens)
+    int hb = 0;                      // compact ids: high bits per token above the 16-bit plane (jtk_compact_rules.h)
     JtkDeviceTables dt;
     std::vector<uint32_t> tok_len;   // byte length per id (0 = absent), for the maxTokens back-off
 };
@@ -129,6 +131,13 @@ struct jtk_batch {
     // where the host copy of the last job's result is: the buffers above, or inside h_small
     const int32_t* r_tokens = nullptr; const int64_t* r_tok_off = nullptr; int32_t* r_status = nullptr;
     bool have_host_result = false;
+    // JTK_ENCODE_COMPACT_IDS: the host copy is two planes -- lo in h_tokens (or inside h_small), hi in h_hi (or h_small) -- and
+    // there are no int32 ids in host memory; cp_stage: one chunk's planes on the device (lo | hi), compacted and copied on
+    // copy_stream (in order: the next chunk's pass follows this chunk's copies)
+    bool host_compact = false;
+    uint32_t* h_hi = nullptr; size_t h_hi_cap = 0;
+    const uint16_t* r_lo = nullptr; const uint32_t* r_hi = nullptr;
+    DevBuf cp_stage;
     // batch decode (jtk_batch_decode*)
     DevBuf dec_in_ids, dec_in_off, dec_zero, dec_tile, dec_pre, dec_out, dec_byte_off;
     DevBuf trunc_kept, trunc_flag;   // jtk_batch_truncate
@@ -246,7 +255,7 @@ int jtk_encoding_create(const char* name, int pattern_kind, const uint8_t* tikto
         const size_t l = strlen(special_literals[i]);
         if (l < 1 || l > JTK_SPECIAL_MAXLEN)
             return fail(JTK_ERR_INVALID_ARGUMENT, "special-token literals must be 1..65535 bytes long");
-        if (special_ids[i] < 0 || special_ids[i] > (int32_t)JTK_MAX_ID + (1 << 20))
+        if (special_ids[i] < 0 || special_ids[i] > JTK_MAX_SPECIAL_ID)
             return fail(JTK_ERR_INVALID_ARGUMENT, "special-token id out of range");
     }
     jtk_encoding* enc = new (std::nothrow) jtk_encoding();
@@ -256,6 +265,11 @@ int jtk_encoding_create(const char* name, int pattern_kind, const uint8_t* tikto
                               enc->host, err);
     if (rc != JTK_OK) { delete enc; return fail(rc, err); }
     enc->tok_len.assign((size_t)enc->host.max_id + 1 + (size_t)enc->host.n_missing, 1);     // (pseudo ids: one byte each)
+    {   // the largest id a result can hold: table ids, the pseudo ids above them, every special id
+        int64_t top = (int64_t)enc->host.max_id + (int64_t)enc->host.n_missing;
+        for (auto& sp : enc->host.specials) top = std::max<int64_t>(top, sp.second);
+        enc->hb = jtk_compact_hb(top);
+    }
     for (size_t i = 0; i <= (size_t)enc->host.max_id; i++) enc->tok_len[i] = (uint32_t)enc->host.id_to_bytes[i].size();
 
     int ndev = 0;
@@ -377,6 +391,7 @@ const char* jtk_encoding_name(const jtk_encoding* enc) { return enc ? enc->host.
 int jtk_encoding_device(const jtk_encoding* enc) { return enc ? enc->device : -1; }
 int64_t jtk_encoding_vocab_size(const jtk_encoding* enc) { return enc ? enc->host.n_tokens : 0; }
 int64_t jtk_encoding_pair_count(const jtk_encoding* enc) { return enc ? enc->host.n_pairs : 0; }
+int jtk_encoding_id_bits(const jtk_encoding* enc) { return enc ? 16 + enc->hb : 0; }
 
 int jtk_batch_create(const jtk_encoding* enc, jtk_batch** out) {
     if (!enc || !out) return fail(JTK_ERR_INVALID_ARGUMENT, "bad arguments");
@@ -436,6 +451,7 @@ void jtk_batch_destroy(jtk_batch* b) {
     if (b->ev_ck) (void)hipEventDestroy(b->ev_ck);
     if (b->host_plan) (void)hipHostFree(b->host_plan);
     if (b->h_tokens) (void)hipHostFree(b->h_tokens);
+    if (b->h_hi) (void)hipHostFree(b->h_hi);
     if (b->h_tok_off) (void)hipHostFree(b->h_tok_off);
     if (b->h_status) (void)hipHostFree(b->h_status);
     if (b->stream) (void)hipStreamDestroy(b->stream);
@@ -595,6 +611,12 @@ int run_job(jtk_batch* b, const uint8_t* d_text, const uint8_t* h_text, const in
             uint32_t flags, hipStream_t s, bool to_host, const PieceArgs* pieces = nullptr, const JtkMaxTokWork* mt = nullptr) {
     const jtk_encoding* enc = b->enc;
     const int n_chunks = (int)b->chunk_doc.size() - 1;
+    // JTK_ENCODE_COMPACT_IDS: what goes to pinned memory is the two planes of jtk_compact_rules.h instead of the int32 ids
+    // (a count-only job has no ids either way); the device-side result stays int32
+    const bool compact_req = to_host && (flags & JTK_ENCODE_COMPACT_IDS) != 0;
+    const bool compact = compact_req && !(flags & JTK_ENCODE_COUNT_ONLY);
+    const int hb = enc->hb;
+    flags &= ~(uint32_t)JTK_ENCODE_COMPACT_IDS;
     // (ids streamed to the host chunk by chunk: the host waits for a chunk's scan before it can issue that chunk's copy, one
     // chunk behind the enqueueing -- with two sets that wait stalls the pipeline: 404 ms per step on the headline corpus against
     // 163 with three, profiles/r03_experiments/r03bc_e2e_memcpy.txt -- so such a job takes three unless the caller chose)
@@ -605,7 +627,7 @@ int run_job(jtk_batch* b, const uint8_t* d_text, const uint8_t* h_text, const in
     const size_t status_bytes = align_up((size_t)(n_docs > 0 ? n_docs : 1) * 4, 16);
     const size_t job_bytes = align_up(64 + ((size_t)n_chunks + 2) * 8, 16);
     const size_t off_status = job_bytes, off_tok_off = off_status + status_bytes;
-    const size_t off_tokens = align_up(off_tok_off + ((size_t)n_docs + 1) * 8, 256);
+    size_t off_tokens = align_up(off_tok_off + ((size_t)n_docs + 1) * 8, 256);
     // a small single-chunk job (the per-call service's batches) copies its whole output block -- header, status, offsets and
     // the worst-case token range (one token per byte) -- right behind the kernels in ONE copy, instead of waiting for the
     // token count first: one host synchronisation and three copies less per batch
@@ -613,7 +635,15 @@ int run_job(jtk_batch* b, const uint8_t* d_text, const uint8_t* h_text, const in
     // r03: for the smallest of them (a per-call device batch) the output block IS pinned host memory -- pack, doc_offsets and the
     // status atomics write over the link, and the copy up (a DMA of 14 us for 27 documents) is gone.  JTK_TINY_COPY_OUT=1: the copy.
     static const bool copy_out_env = getenv("JTK_TINY_COPY_OUT") != nullptr;
-    const bool zero_copy_out = !copy_out_env && small_to_host && n_bytes <= TINY_JOB_BYTES && !h_text;
+    const bool zero_copy_out = !copy_out_env && small_to_host && n_bytes <= TINY_JOB_BYTES && !h_text && !compact;
+    // a small compact job: the planes lie between the offsets and the int32 ids, so that one copy of [0, off_tokens) takes
+    // header, status, offsets and both worst-case planes (and not the ids); the tiny job takes this copying path too
+    size_t off_lo = 0, off_hi = 0;
+    if (compact && small_to_host) {
+        off_lo = off_tokens;
+        off_hi = off_lo + align_up((size_t)jtk_compact_lo_bytes(n_bytes + 64), 256);
+        off_tokens = off_hi + align_up((size_t)jtk_compact_hi_words(n_bytes + 64, hb) * 4, 256);
+    }
     uint8_t* out_base;
     if (zero_copy_out) {
         if ((rc = ensure_pinned((void**)&b->h_small, &b->h_small_cap, off_tokens + ((size_t)n_bytes + 64) * 4 + 4096, 0))) return rc;
@@ -632,8 +662,22 @@ int run_job(jtk_batch* b, const uint8_t* d_text, const uint8_t* h_text, const in
     if (to_host && !small_to_host) {
         if ((rc = ensure_pinned((void**)&b->h_tok_off, &b->h_tok_off_cap, ((size_t)n_docs + 1) * 8, 0)) ||
             (rc = ensure_pinned((void**)&b->h_status, &b->h_status_cap, (size_t)(n_docs > 0 ? n_docs : 1) * 4, 0)) ||
-            (rc = ensure_pinned((void**)&b->h_tokens, &b->h_tokens_cap, (size_t)n_bytes * (n_bytes <= SMALL_JOB_BYTES ? 4 : 2) + 4096, 0)))     // grown as the chunks report
+            (rc = ensure_pinned((void**)&b->h_tokens, &b->h_tokens_cap, (size_t)n_bytes * (n_bytes <= SMALL_JOB_BYTES ? 4 : 2) / (compact ? 2 : 1) + 4096, 0)))     // grown as the chunks report
             return rc;
+    }
+    uint16_t* stage_lo = nullptr; uint32_t* stage_hi = nullptr;
+    if (compact && !small_to_host) {
+        // the same guess (a token per two bytes; per byte for a small job) for the hi plane; the staging planes hold the
+        // largest chunk at a token per byte, plus the tokens back to the range's start
+        int64_t max_chunk = 0;
+        for (int c = 0; c < n_chunks; c++) max_chunk = std::max(max_chunk, b->chunk_off[c + 1] - b->chunk_off[c]);
+        const int64_t cap_tok = max_chunk + 64 + JTK_CP_RANGE_ALIGN;
+        const size_t stage_lo_bytes = align_up((size_t)jtk_compact_lo_bytes(cap_tok), 256);
+        if ((hb && (rc = ensure_pinned((void**)&b->h_hi, &b->h_hi_cap, (size_t)jtk_compact_hi_words(n_bytes <= SMALL_JOB_BYTES ? n_bytes : n_bytes / 2, hb) * 4 + 4096, 0))) ||
+            (rc = b->cp_stage.ensure(stage_lo_bytes + (size_t)jtk_compact_hi_words(cap_tok, hb) * 4 + 16)))
+            return rc;
+        stage_lo = (uint16_t*)b->cp_stage.p;
+        stage_hi = (uint32_t*)((uint8_t*)b->cp_stage.p + stage_lo_bytes);
     }
     const bool prof = b->profiling;
     if (prof) {
@@ -665,7 +709,25 @@ int run_job(jtk_batch* b, const uint8_t* d_text, const uint8_t* h_text, const in
         ChunkSet& cs = b->set[c % n_sets];
         HIP_TRY(hipEventSynchronize(cs.ev_scan));
         const int64_t t0 = b->h_info[2 * c], t1 = b->h_info[2 * c + 1];
-        if (t1 > t0 && !(flags & JTK_ENCODE_COUNT_ONLY)) {
+        if (t1 > t0 && compact) {
+            // the range's planes: compacted into the staging planes from its start tb (a multiple of 32 tokens at or below t0:
+            // the words shared with the chunk before are rewritten whole, here and in pinned memory), then the two copies
+            const int64_t tb = jtk_compact_range_start(t0);
+            const int64_t w0 = jtk_compact_hi_word(tb, hb), w1 = jtk_compact_hi_words(t1, hb);
+            if ((size_t)t1 * 2 > b->h_tokens_cap || (size_t)w1 * 4 > b->h_hi_cap) {
+                // grow: earlier chunks' copies may still be in flight into the old buffers
+                HIP_TRY(hipStreamSynchronize(b->copy_stream));
+                const size_t rest = ((size_t)n_bytes - (size_t)b->chunk_off[c + 1]) / 2;        // tokens still expected
+                int rc2 = ensure_pinned((void**)&b->h_tokens, &b->h_tokens_cap, ((size_t)t1 + rest) * 2, (size_t)t0 * 2);
+                if (!rc2 && hb) rc2 = ensure_pinned((void**)&b->h_hi, &b->h_hi_cap, (size_t)jtk_compact_hi_words(t1 + (int64_t)rest, hb) * 4, (size_t)jtk_compact_hi_words(t0, hb) * 4);
+                if (rc2) return rc2;
+            }
+            HIP_TRY(hipStreamWaitEvent(b->copy_stream, cs.ev_done, 0));
+            jtk_launch_compact((const int32_t*)b->tokens.p, t0, t1, nullptr, stage_lo, stage_hi, tb, hb, b->copy_stream);
+            HIP_TRY(hipGetLastError());
+            HIP_TRY(hipMemcpyAsync((uint16_t*)b->h_tokens + t0, stage_lo + (t0 - tb), (size_t)(t1 - t0) * 2, hipMemcpyDeviceToHost, b->copy_stream));
+            if (hb) HIP_TRY(hipMemcpyAsync(b->h_hi + w0, stage_hi, (size_t)(w1 - w0) * 4, hipMemcpyDeviceToHost, b->copy_stream));
+        } else if (t1 > t0 && !(flags & JTK_ENCODE_COUNT_ONLY)) {
             if ((size_t)t1 * 4 > b->h_tokens_cap) {
                 // grow: earlier chunks' copies may still be in flight into the old buffer
                 HIP_TRY(hipStreamSynchronize(b->copy_stream));
@@ -759,7 +821,13 @@ int run_job(jtk_batch* b, const uint8_t* d_text, const uint8_t* h_text, const in
         HIP_TRY(hipGetLastError());
         if (small_to_host && !zero_copy_out) {
             // the whole answer in one copy: header, status, offsets and the worst-case token range (one token per byte)
-            const size_t total = (flags & JTK_ENCODE_COUNT_ONLY) ? off_tokens : off_tokens + (size_t)n_bytes * 4;
+            if (compact) {
+                // (the host does not know the token count yet: the pass reads it from the job's header)
+                jtk_launch_compact((const int32_t*)b->tokens.p, 0, n_bytes, &d_result->n_tokens, (uint16_t*)(out_base + off_lo),
+                                   (uint32_t*)(out_base + off_hi), 0, hb, cst);
+                HIP_TRY(hipGetLastError());
+            }
+            const size_t total = ((flags & JTK_ENCODE_COUNT_ONLY) || compact) ? off_tokens : off_tokens + (size_t)n_bytes * 4;
             if ((rc = ensure_pinned((void**)&b->h_small, &b->h_small_cap, total + 4096, 0))) return rc;
             HIP_TRY(hipMemcpyAsync(b->h_small, b->out.p, total, hipMemcpyDeviceToHost, cst));
         }
@@ -779,7 +847,8 @@ int run_job(jtk_batch* b, const uint8_t* d_text, const uint8_t* h_text, const in
         b->host_result = (JtkResult*)b->h_small;
         b->r_status = (int32_t*)(b->h_small + off_status);
         b->r_tok_off = (const int64_t*)(b->h_small + off_tok_off);
-        b->r_tokens = (const int32_t*)(b->h_small + off_tokens);
+        b->r_tokens = compact ? nullptr : (const int32_t*)(b->h_small + off_tokens);
+        b->r_lo = (const uint16_t*)(b->h_small + off_lo); b->r_hi = (const uint32_t*)(b->h_small + off_hi);
     } else {
         if (to_host) {
             HIP_TRY(hipMemcpyAsync(b->h_tok_off, b->tok_off.p, ((size_t)n_docs + 1) * 8, hipMemcpyDeviceToHost, s));
@@ -787,8 +856,10 @@ int run_job(jtk_batch* b, const uint8_t* d_text, const uint8_t* h_text, const in
         }
         b->host_result = b->host_result_own;
         HIP_TRY(hipMemcpyAsync(b->host_result, d_result, sizeof(JtkResult), hipMemcpyDeviceToHost, s));
-        b->r_status = b->h_status; b->r_tok_off = b->h_tok_off; b->r_tokens = b->h_tokens;
+        b->r_status = b->h_status; b->r_tok_off = b->h_tok_off; b->r_tokens = compact ? nullptr : b->h_tokens;
+        b->r_lo = (const uint16_t*)b->h_tokens; b->r_hi = b->h_hi;
     }
+    b->host_compact = compact_req;
     b->job_text = d_text;
     b->job_doc_off = d_doc_off;
     b->job_docs = n_docs;
@@ -850,7 +921,9 @@ int run_allow_special(jtk_batch* b, const uint8_t* d_text, const int64_t* d_doc_
                       hipStream_t s, int64_t cb) {
     const jtk_encoding* enc = b->enc;
     const bool to_host = (flags & JTK_ENCODE_TO_HOST) != 0, count_only = (flags & JTK_ENCODE_COUNT_ONLY) != 0;
-    const uint32_t base_flags = flags & ~(uint32_t)(JTK_ENCODE_ALLOW_SPECIAL | JTK_ENCODE_TO_HOST);
+    const uint32_t base_flags = flags & ~(uint32_t)(JTK_ENCODE_ALLOW_SPECIAL | JTK_ENCODE_TO_HOST);       // (keeps JTK_ENCODE_COMPACT_IDS)
+    const bool compact_req = to_host && (flags & JTK_ENCODE_COMPACT_IDS) != 0, compact = compact_req && !count_only;
+    const int hb = enc->hb;
     const int n_lits = (int)enc->host.specials.size();
     int rc;
     if (b->sp_dirty) {
@@ -924,6 +997,7 @@ int run_allow_special(jtk_batch* b, const uint8_t* d_text, const int64_t* d_doc_
     HIP_TRY(hipGetLastError());
     // encodeOrdinary of every sub-document (the literals' tokens are not used: their ids are written instead)
     const uint32_t sub_flags = JTK_ENCODE_ORDINARY | (flags & (JTK_ENCODE_VALIDATE_UTF8 | JTK_ENCODE_COUNT_ONLY));
+    flags &= ~(uint32_t)JTK_ENCODE_COMPACT_IDS;
     if ((rc = plan(w.sub_off, w.n_sub)) || (rc = run_job(b, d_text, nullptr, w.sub_off, w.n_sub, n_bytes, sub_flags, s, false))) return rc;
     // the stitched result: JtkResult | tok_off [n_docs + 1] | tokens (status: in the find scratch)
     const size_t o_tok_off = 64, o_tokens = align_up(o_tok_off + ((size_t)n_docs + 1) * 8, 256);
@@ -942,19 +1016,34 @@ int run_allow_special(jtk_batch* b, const uint8_t* d_text, const int64_t* d_doc_
     b->job_docs = n_docs;
     b->job_flags = flags & ~(uint32_t)JTK_ENCODE_TO_HOST;
     b->have_host_result = false;
+    b->host_compact = false;
     if (to_host) {
         // (the stitch comes after the last chunk: the ids go to the host in one copy behind it, not chunk by chunk)
         HIP_TRY(hipStreamSynchronize(s));
         const int64_t nt = b->host_result->n_tokens;
+        const size_t lo_bytes = align_up((size_t)jtk_compact_lo_bytes(nt), 256), hi_bytes = (size_t)jtk_compact_hi_words(nt, hb) * 4;
         if ((rc = ensure_pinned((void**)&b->h_tok_off, &b->h_tok_off_cap, ((size_t)n_docs + 1) * 8, 0)) ||
             (rc = ensure_pinned((void**)&b->h_status, &b->h_status_cap, (size_t)(n_docs > 0 ? n_docs : 1) * 4, 0)) ||
-            (rc = ensure_pinned((void**)&b->h_tokens, &b->h_tokens_cap, (size_t)nt * 4 + 4096, 0)))
+            (rc = ensure_pinned((void**)&b->h_tokens, &b->h_tokens_cap, (size_t)nt * (compact ? 2 : 4) + 4096, 0)))
             return rc;
         HIP_TRY(hipMemcpyAsync(b->h_tok_off, w.tok_off, ((size_t)n_docs + 1) * 8, hipMemcpyDeviceToHost, s));
         if (n_docs > 0) HIP_TRY(hipMemcpyAsync(b->h_status, w.status, (size_t)n_docs * 4, hipMemcpyDeviceToHost, s));
-        if (nt > 0 && !count_only) HIP_TRY(hipMemcpyAsync(b->h_tokens, w.tokens, (size_t)nt * 4, hipMemcpyDeviceToHost, s));
-        b->r_tokens = b->h_tokens; b->r_tok_off = b->h_tok_off; b->r_status = b->h_status;
+        if (compact) {
+            // the planes of the whole stitched result, compacted behind the stitch, in one copy each
+            if ((hb && (rc = ensure_pinned((void**)&b->h_hi, &b->h_hi_cap, hi_bytes + 4096, 0))) || (rc = b->cp_stage.ensure(lo_bytes + hi_bytes + 16))) return rc;
+            uint16_t* d_lo = (uint16_t*)b->cp_stage.p;
+            uint32_t* d_hi = (uint32_t*)((uint8_t*)b->cp_stage.p + lo_bytes);
+            if (nt > 0) {
+                jtk_launch_compact(w.tokens, 0, nt, nullptr, d_lo, d_hi, 0, hb, s);
+                HIP_TRY(hipGetLastError());
+                HIP_TRY(hipMemcpyAsync(b->h_tokens, d_lo, (size_t)nt * 2, hipMemcpyDeviceToHost, s));
+                if (hb) HIP_TRY(hipMemcpyAsync(b->h_hi, d_hi, hi_bytes, hipMemcpyDeviceToHost, s));
+            }
+        } else if (nt > 0 && !count_only) HIP_TRY(hipMemcpyAsync(b->h_tokens, w.tokens, (size_t)nt * 4, hipMemcpyDeviceToHost, s));
+        b->r_tokens = compact ? nullptr : b->h_tokens; b->r_tok_off = b->h_tok_off; b->r_status = b->h_status;
+        b->r_lo = (const uint16_t*)b->h_tokens; b->r_hi = b->h_hi;
         b->have_host_result = true;
+        b->host_compact = compact_req;
     }
     return JTK_OK;
 }
@@ -970,6 +1059,7 @@ int jtk_batch_encode_device(jtk_batch* b, const uint8_t* d_utf8, const int64_t* 
     if (((uintptr_t)d_utf8 & 15u) != 0) return fail(JTK_ERR_INVALID_ARGUMENT, "device text must be 16-byte aligned");
     if (n_bytes >= (int64_t)1 << 37) return fail(JTK_ERR_INVALID_ARGUMENT, "batch too large (128 GiB of text per call at most)");
     if (flags & JTK_ENCODE_TO_HOST) return fail(JTK_ERR_INVALID_ARGUMENT, "JTK_ENCODE_TO_HOST is for jtk_batch_encode (host buffers)");
+    if (flags & JTK_ENCODE_COMPACT_IDS) return fail(JTK_ERR_INVALID_ARGUMENT, "JTK_ENCODE_COMPACT_IDS is for jtk_batch_encode with JTK_ENCODE_TO_HOST (on the device: jtk_batch_compact)");
     HIP_TRY(hipSetDevice(b->enc->device));
     hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
     if ((flags & JTK_ENCODE_ALLOW_SPECIAL) && !sp_any_allowed(b)) flags &= ~(uint32_t)JTK_ENCODE_ALLOW_SPECIAL;   // empty set: today's call
@@ -1007,6 +1097,8 @@ int jtk_batch_encode_device(jtk_batch* b, const uint8_t* d_utf8, const int64_t* 
 int jtk_batch_encode(jtk_batch* b, const uint8_t* utf8, const int64_t* doc_off, int64_t n_docs,
                      uint32_t flags, int64_t* n_tokens) {
     if (!b || n_docs < 0 || !doc_off) return fail(JTK_ERR_INVALID_ARGUMENT, "bad arguments");
+    if ((flags & JTK_ENCODE_COMPACT_IDS) && !(flags & JTK_ENCODE_TO_HOST))
+        return fail(JTK_ERR_INVALID_ARGUMENT, "JTK_ENCODE_COMPACT_IDS needs JTK_ENCODE_TO_HOST (on the device: jtk_batch_compact)");
     if (doc_off[0] != 0) return fail(JTK_ERR_INVALID_ARGUMENT, "doc_off[0] must be 0");
     const int64_t n_bytes = doc_off[n_docs];
     if (n_bytes > 0 && !utf8) return fail(JTK_ERR_INVALID_ARGUMENT, "utf8 is NULL");
@@ -1074,6 +1166,8 @@ int jtk_batch_encode_pieces(jtk_batch* b, const uint8_t* utf8, const int64_t* do
     if (!b || n_docs < 0 || !doc_off || n_pieces < 0 || (n_pieces > 0 && (!piece_begin || !piece_end)))
         return fail(JTK_ERR_INVALID_ARGUMENT, "bad arguments");
     if (flags & JTK_ENCODE_ALLOW_SPECIAL) return fail(JTK_ERR_INVALID_ARGUMENT, "JTK_ENCODE_ALLOW_SPECIAL is for jtk_batch_encode / jtk_batch_encode_device");
+    if ((flags & JTK_ENCODE_COMPACT_IDS) && !(flags & JTK_ENCODE_TO_HOST))
+        return fail(JTK_ERR_INVALID_ARGUMENT, "JTK_ENCODE_COMPACT_IDS needs JTK_ENCODE_TO_HOST (on the device: jtk_batch_compact)");
     if (doc_off[0] != 0) return fail(JTK_ERR_INVALID_ARGUMENT, "doc_off[0] must be 0");
     const int64_t n_bytes = doc_off[n_docs];
     if (n_bytes > 0 && !utf8) return fail(JTK_ERR_INVALID_ARGUMENT, "utf8 is NULL");
@@ -1165,7 +1259,7 @@ int jtk_batch_fetch(jtk_batch* b, int32_t* tokens, int64_t tokens_cap, int64_t* 
         if (count_only) return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode was count-only: there are no token ids");
         if (tokens_cap < nt) return fail(JTK_ERR_CAPACITY, "tokens buffer too small");
         if (nt > 0) {
-            if (b->have_host_result) memcpy(tokens, b->r_tokens, (size_t)nt * 4);
+            if (b->have_host_result && !b->host_compact) memcpy(tokens, b->r_tokens, (size_t)nt * 4);
             else HIP_TRY(hipMemcpy(tokens, b->tokens.p, (size_t)nt * 4, hipMemcpyDefault));
         }
     }
@@ -1178,11 +1272,37 @@ int jtk_batch_fetch(jtk_batch* b, int32_t* tokens, int64_t tokens_cap, int64_t* 
 int jtk_batch_host_result(jtk_batch* b, const int32_t** tokens, const int64_t** tok_off, const int32_t** status) {
     if (!b || !b->have_result || !b->have_host_result)
         return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode on this batch did not run with JTK_ENCODE_TO_HOST");
+    if (b->host_compact)
+        return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode ran with JTK_ENCODE_COMPACT_IDS: host memory holds no int32 ids, read the planes with jtk_batch_host_result_compact()");
     HIP_TRY(hipSetDevice(b->enc->device));
     if (!b->synced) { HIP_TRY(hipStreamSynchronize(b->last_stream)); b->synced = true; }
     if (tokens) *tokens = (b->job_flags & JTK_ENCODE_COUNT_ONLY) ? nullptr : b->r_tokens;
     if (tok_off) *tok_off = b->r_tok_off;
     if (status) *status = b->r_status;
+    return JTK_OK;
+}
+
+int jtk_batch_host_result_compact(jtk_batch* b, const uint16_t** lo, const uint32_t** hi, int* id_bits, const int64_t** tok_off,
+                                  const int32_t** status) {
+    if (!b || !b->have_result || !b->have_host_result || !b->host_compact)
+        return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode on this batch did not run with JTK_ENCODE_TO_HOST | JTK_ENCODE_COMPACT_IDS");
+    HIP_TRY(hipSetDevice(b->enc->device));
+    if (!b->synced) { HIP_TRY(hipStreamSynchronize(b->last_stream)); b->synced = true; }
+    const bool count_only = (b->job_flags & JTK_ENCODE_COUNT_ONLY) != 0;
+    if (lo) *lo = count_only ? nullptr : b->r_lo;
+    if (hi) *hi = (count_only || !b->enc->hb) ? nullptr : b->r_hi;
+    if (id_bits) *id_bits = 16 + b->enc->hb;
+    if (tok_off) *tok_off = b->r_tok_off;
+    if (status) *status = b->r_status;
+    return JTK_OK;
+}
+
+int jtk_widen_ids(const uint16_t* lo, const uint32_t* hi, int id_bits, int64_t first, int64_t n, int32_t* out) {
+    if (!jtk_compact_valid_bits(id_bits)) return fail(JTK_ERR_INVALID_ARGUMENT, "id_bits must be 16, 17, 18, 20, 24 or 32");
+    const int hb = id_bits - 16;
+    if (first < 0 || n < 0 || (n > 0 && (!lo || !out || (hb && !hi)))) return fail(JTK_ERR_INVALID_ARGUMENT, "bad arguments");
+    if (!hb) for (int64_t k = 0; k < n; k++) out[k] = lo[first + k];
+    else for (int64_t k = 0; k < n; k++) out[k] = jtk_compact_widen(lo, hi, hb, first + k);
     return JTK_OK;
 }
 
@@ -1366,6 +1486,7 @@ int jtk_encode(jtk_batch* b, const uint8_t* utf8, int64_t len, uint32_t flags, i
                int32_t* tokens, int64_t tokens_cap, int64_t* n_tokens, int* truncated) {
     if (!b || len < 0) return fail(JTK_ERR_INVALID_ARGUMENT, "bad arguments");
     if (flags & JTK_ENCODE_ALLOW_SPECIAL) return fail(JTK_ERR_INVALID_ARGUMENT, "JTK_ENCODE_ALLOW_SPECIAL is for jtk_batch_encode / jtk_batch_encode_device");
+    if (flags & JTK_ENCODE_COMPACT_IDS) return fail(JTK_ERR_INVALID_ARGUMENT, "JTK_ENCODE_COMPACT_IDS is for jtk_batch_encode with JTK_ENCODE_TO_HOST");
     if (truncated) *truncated = 0;
     if (n_tokens) *n_tokens = 0;
     if (!utf8) return JTK_OK;                                    // text == null -> empty result
@@ -1774,6 +1895,22 @@ int jtk_batch_chunk_rows(jtk_batch* b, int32_t pad_id, int32_t* d_rows, void* st
     int rc;
     if ((rc = ck_order(b, b->ck_stream, s))) return rc;
     jtk_launch_chunk_rows(b->ck, pad_id, d_rows, s);
+    HIP_TRY(hipGetLastError());
+    return JTK_OK;
+}
+
+int jtk_batch_compact(jtk_batch* b, uint16_t* d_lo, uint32_t* d_hi, void* stream_or_null) {
+    if (!b || !b->have_result) return fail(JTK_ERR_INVALID_ARGUMENT, "no batch encode result on this batch (jtk_batch_encode_device_max_tokens leaves none)");
+    if (b->job_flags & JTK_ENCODE_COUNT_ONLY) return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode was count-only: there are no token ids");
+    if (((uintptr_t)d_lo & 1u) != 0 || ((uintptr_t)d_hi & 3u) != 0) return fail(JTK_ERR_INVALID_ARGUMENT, "d_lo must be 2-byte and d_hi 4-byte aligned");
+    int64_t nt = 0;
+    int rc;
+    if ((rc = jtk_batch_result(b, &nt, nullptr, nullptr))) return rc;
+    const int hb = b->enc->hb;
+    if (nt > 0 && (!d_lo || (hb && !d_hi))) return fail(JTK_ERR_INVALID_ARGUMENT, hb ? "d_lo or d_hi is NULL" : "d_lo is NULL");
+    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    if ((rc = ck_order(b, b->last_stream, s))) return rc;
+    jtk_launch_compact((const int32_t*)b->tokens.p, 0, nt, nullptr, d_lo, d_hi, 0, hb, s);
     HIP_TRY(hipGetLastError());
     return JTK_OK;
 }

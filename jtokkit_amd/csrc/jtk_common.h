@@ -45,6 +45,7 @@ enum { JTK_PAT_R50K = 0, JTK_PAT_CL100K = 1 };
 // Slot layout: key = id_left << 17 | id_right (34 bits) in the high bits, rank in the low 30.
 #define JTK_ID_BITS 17
 #define JTK_MAX_ID ((1u << JTK_ID_BITS) - 2)
+#define JTK_MAX_SPECIAL_ID ((1 << 25) - 1)   // special-token ids are not table ids: bounded only by the dense decode table (4 B per id)
 #define JTK_RANK_NONE 0x7FFFFFFFu          // Integer.MAX_VALUE of the reference
 #define JTK_ID_DEAD 0xFFFFFFFFu            // byte position that does not start a part
 #define JTK_PAIR_EMPTY 0xFFFFFFFFFFFFFFFFull

@@ -293,6 +293,12 @@ struct JtkPackWork {
 void jtk_launch_pack_plan(const JtkPackWork& w, hipStream_t s);        // units, scans, groups -> hdr
 void jtk_launch_pack_write(const JtkPackWork& w, int32_t pad_id, int32_t* rows, int32_t* positions, int32_t* cu_seqlens,
                            int64_t* seg_doc, hipStream_t s);           // (needs n_rows, n_seg)
+// Compact ids (jtk_compact.hip; the rule is jtk_compact_rules.h): the range [t0, t1) of the int32 stream `ids` (indexed from
+// token 0) into a uint16 plane and a plane of hb bits per token whose entry 0 is token `origin` (a multiple of 32; 0 for whole
+// planes).  Restarts at t0 rounded down to a multiple of 32 and rewrites the words there whole.  d_total != NULL: the range ends
+// at min(t1, *d_total).  hi may be NULL when hb == 0.
+void jtk_launch_compact(const int32_t* ids, int64_t t0, int64_t t1, const int64_t* d_total, uint16_t* lo, uint32_t* hi,
+                        int64_t origin, int hb, hipStream_t s);
 // Device-side state of an allow-special encode (jtk_special.hip, JTK_ENCODE_ALLOW_SPECIAL; the rule is jtk_special_rules.h).
 // Candidates (per position, the longest allowed literal there) are found in position order, resolved to the kept matches, and
 // the batch is cut into sub-documents that partition the text: per document a segment, then per candidate i two slots

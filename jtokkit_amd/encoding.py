@@ -90,6 +90,43 @@ class BatchResult:
         return len(self.tok_off) - 1
 
 
+def widen_ids(lo, hi, id_bits, first=0, n=None):
+    """jtk_widen_ids: int32 ids of tokens [first, first + n) from the planes of a compact result (jtk_compact_rules.h)."""
+    if n is None:
+        n = len(lo) - first
+    out = np.empty(max(n, 1), dtype=np.int32)
+    _check(N.lib().jtk_widen_ids(lo.ctypes.data if len(lo) else None, hi.ctypes.data if hi is not None and len(hi) else None,
+                                 int(id_bits), int(first), int(n), out.ctypes.data))
+    return out[:n]
+
+
+class CompactBatchResult:
+    """Packed result of a batch encode with compact ids: lo[uint16, n_tokens] holds id & 0xFFFF, hi[uint32] the id_bits - 16
+    bits above of every token back to back (None when id_bits == 16); tok_off and status as in BatchResult.  doc(d) widens
+    that document to int32, widen() the whole batch."""
+
+    def __init__(self, lo, hi, id_bits, tok_off, status):
+        self.lo = lo
+        self.hi = hi
+        self.id_bits = id_bits
+        self.tok_off = tok_off
+        self.status = status
+
+    def doc(self, d):
+        first = int(self.tok_off[d])
+        return widen_ids(self.lo, self.hi, self.id_bits, first, int(self.tok_off[d + 1]) - first)
+
+    def widen(self):
+        return widen_ids(self.lo, self.hi, self.id_bits, 0, len(self.lo))
+
+    @property
+    def tokens(self):
+        return self.widen()
+
+    def __len__(self):
+        return len(self.tok_off) - 1
+
+
 class HostBuffer:
     """Page-locked host memory (jtk_host_alloc) as a numpy array: input buffers the device reads by DMA."""
 
@@ -145,22 +182,25 @@ class Batch:
         arr = np.ascontiguousarray(list(ids), dtype=np.int32)
         _check(N.lib().jtk_batch_set_allowed_special(self._h, arr.ctypes.data if len(arr) else None, len(arr)))
 
-    def encode_host(self, text_u8, doc_off, ordinary=False, validate=False, count_only=False, to_host=False, allow_special=False):
+    def encode_host(self, text_u8, doc_off, ordinary=False, validate=False, count_only=False, to_host=False, allow_special=False,
+                    compact=False):
         """Host buffers in (numpy arrays, or anything with .ctypes.data such as a pinned HostBuffer view).  to_host: the result
         is streamed to the batch's pinned host memory while later chunks are encoded (read it with host_result()).
-        allow_special: the batch's allowed special-token literals become their ids (JTK_ENCODE_ALLOW_SPECIAL)."""
+        allow_special: the batch's allowed special-token literals become their ids (JTK_ENCODE_ALLOW_SPECIAL).
+        compact (with to_host): the ids go up as a 16-bit plane and a plane of the bits above (JTK_ENCODE_COMPACT_IDS; read
+        them with host_result_compact())."""
         text_u8 = np.ascontiguousarray(text_u8, dtype=np.uint8)
         doc_off = np.ascontiguousarray(doc_off, dtype=np.int64)
         nt = C.c_int64(0)
         flags = ((N.JTK_ENCODE_ORDINARY if ordinary else 0) | (N.JTK_ENCODE_VALIDATE_UTF8 if validate else 0)
                  | (N.JTK_ENCODE_COUNT_ONLY if count_only else 0) | (N.JTK_ENCODE_TO_HOST if to_host else 0)
-                 | (N.JTK_ENCODE_ALLOW_SPECIAL if allow_special else 0))
+                 | (N.JTK_ENCODE_ALLOW_SPECIAL if allow_special else 0) | (N.JTK_ENCODE_COMPACT_IDS if compact else 0))
         self._count_only = count_only
         _check(N.lib().jtk_batch_encode(self._h, text_u8.ctypes.data, doc_off.ctypes.data, len(doc_off) - 1,
                                         flags, C.byref(nt)))
         return nt.value
 
-    def encode_pieces(self, text_u8, doc_off, piece_begin, piece_end, ordinary=True, to_host=False):
+    def encode_pieces(self, text_u8, doc_off, piece_begin, piece_end, ordinary=True, to_host=False, compact=False):
         """jtk_batch_encode_pieces: the caller's own pattern has been matched on the host; piece i is
         text[piece_begin[i]:piece_end[i]] (positions in the whole batch).  Returns the token total."""
         text_u8 = np.ascontiguousarray(text_u8, dtype=np.uint8)
@@ -168,7 +208,8 @@ class Batch:
         pb = np.ascontiguousarray(piece_begin, dtype=np.int64)
         pe = np.ascontiguousarray(piece_end, dtype=np.int64)
         nt = C.c_int64(0)
-        flags = (N.JTK_ENCODE_ORDINARY if ordinary else 0) | (N.JTK_ENCODE_TO_HOST if to_host else 0)
+        flags = ((N.JTK_ENCODE_ORDINARY if ordinary else 0) | (N.JTK_ENCODE_TO_HOST if to_host else 0)
+                 | (N.JTK_ENCODE_COMPACT_IDS if compact else 0))
         self._count_only = False
         _check(N.lib().jtk_batch_encode_pieces(self._h, text_u8.ctypes.data, doc_off.ctypes.data, len(doc_off) - 1,
                                                pb.ctypes.data, pe.ctypes.data, len(pb), flags, C.byref(nt)))
@@ -187,6 +228,29 @@ class Batch:
             return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), shape=(n,))
         tokens = view(a.value, nt, C.c_int32, np.int32)
         return BatchResult(tokens, view(b.value, nd + 1, C.c_int64, np.int64), view(c.value, nd, C.c_int32, np.int32))
+
+    def host_result_compact(self):
+        """After encode_host(to_host=True, compact=True): zero-copy numpy views of the pinned planes as a CompactBatchResult
+        (valid until the next encode on this batch)."""
+        nt, nd, _ = self.result()
+        lo, hi, t, s = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        bits = C.c_int(0)
+        _check(N.lib().jtk_batch_host_result_compact(self._h, C.byref(lo), C.byref(hi), C.byref(bits), C.byref(t), C.byref(s)))
+
+        def view(ptr, n, ctype, dtype):
+            if not ptr or n == 0:
+                return np.zeros(0, dtype=dtype)
+            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), shape=(n,))
+        hb = bits.value - 16
+        n_lo = nt if lo.value else 0
+        return CompactBatchResult(view(lo.value, n_lo, C.c_uint16, np.uint16),
+                                  view(hi.value, (n_lo * hb + 31) // 32, C.c_uint32, np.uint32) if hb else None, bits.value,
+                                  view(t.value, nd + 1, C.c_int64, np.int64), view(s.value, nd, C.c_int32, np.int32))
+
+    def compact(self, d_lo_ptr, d_hi_ptr, stream=None):
+        """jtk_batch_compact on the last encode: uint16 [n_tokens] at d_lo_ptr and uint32 [ceil(n_tokens * (id_bits - 16) / 32)]
+        at d_hi_ptr (None when id_bits == 16), device pointers; waits for the token count, not for the pass."""
+        _check(N.lib().jtk_batch_compact(self._h, d_lo_ptr, d_hi_ptr, stream))
 
     def encode_device(self, d_text_ptr, d_doc_off_ptr, n_docs, n_bytes, ordinary=False, stream=None, sync=True,
                       allow_special=False, validate=False, count_only=False):
@@ -507,16 +571,70 @@ class HipEncoding:
         text = np.frombuffer(b"".join(bs), dtype=np.uint8) if doc_off[-1] else np.zeros(0, dtype=np.uint8)
         return self.encode_batch_packed(text, doc_off, ordinary, validate, allowed_special)
 
-    def encode_batch_packed(self, text_u8, doc_off, ordinary=False, validate=False, allowed_special=None):
+    def encode_batch_packed(self, text_u8, doc_off, ordinary=False, validate=False, allowed_special=None, compact=False):
+        """compact: the ids cross the link as two planes (JTK_ENCODE_COMPACT_IDS) and come back as a CompactBatchResult that
+        owns copies of them."""
         b = self._b()
         if self._allow(b, allowed_special):
-            b.encode_host(text_u8, doc_off, ordinary, validate, allow_special=True)
+            b.encode_host(text_u8, doc_off, ordinary, validate, allow_special=True, to_host=compact, compact=compact)
         elif self._host_pattern is not None:
             pb, pe = self._match_on_host(text_u8, doc_off)
-            b.encode_pieces(text_u8, doc_off, pb, pe, ordinary)
+            b.encode_pieces(text_u8, doc_off, pb, pe, ordinary, to_host=compact, compact=compact)
         else:
-            b.encode_host(text_u8, doc_off, ordinary, validate)
+            b.encode_host(text_u8, doc_off, ordinary, validate, to_host=compact, compact=compact)
+        if compact:
+            r = b.host_result_compact()
+            return CompactBatchResult(r.lo.copy(), None if r.hi is None else r.hi.copy(), r.id_bits, r.tok_off.copy(), r.status.copy())
         return b.fetch()
+
+    @property
+    def id_bits(self):
+        """Bits per id of the compact format: 16 + the high bits per token (jtk_encoding_id_bits)."""
+        return N.lib().jtk_encoding_id_bits(self._h)
+
+    def compact_batch_device(self, text, doc_off, ordinary=False, allowed_special=None):
+        """Encodes a device-resident batch and returns its ids compact, as CUDA tensors written on torch.cuda.current_stream():
+        (lo uint16 [n_tokens], hi int32 [ceil(n_tokens * (id_bits - 16) / 32)] or None when id_bits == 16 -- the bit pattern of
+        the format's uint32 words --, tok_off int64 [n_docs + 1], status int32 [n_docs]).  text: CUDA torch.uint8 tensor, doc_off:
+        CUDA torch.int64 tensor [n_docs + 1], on this encoding's device.  Waits once, for the token count (and, with
+        allowed_special -- as for encode_batch --, once more for the encode's count of literal candidates)."""
+        import torch
+        self._check_device_inputs("compact_batch_device", text, doc_off)
+        allow = self._allow(self._b(), allowed_special)
+        nd = doc_off.numel() - 1
+        if nd < 0:
+            raise ValueError("doc_off needs n_docs + 1 entries")
+        device = text.device
+        n = text.numel()
+        st = text.untyped_storage()
+        if text.data_ptr() % 16 or st.data_ptr() + st.nbytes() < text.data_ptr() + (n + 15) // 16 * 16:
+            # (the encode reads whole aligned 16-byte blocks)
+            buf = torch.zeros((n + 15) // 16 * 16 + 16, dtype=torch.uint8, device=device)
+            buf[:n].copy_(text)
+            text = buf
+        b = self._b()
+        cur = torch.cuda.current_stream(device)
+        side = None
+        if cur.cuda_stream == 0:
+            # (the legacy default stream: see chunk_batch_device)
+            side = torch.cuda.ExternalStream(b.stream(), device=device)
+            side.wait_stream(cur)
+        stream = (side or cur).cuda_stream
+        b.encode_device(text.data_ptr(), doc_off.data_ptr(), nd, n, ordinary, stream=stream, sync=False, allow_special=allow)
+        nt = b.result()[0]
+        hb = self.id_bits - 16
+        lo = torch.empty(nt, dtype=torch.uint16, device=device)
+        hi = torch.empty((nt * hb + 31) // 32, dtype=torch.int32, device=device) if hb else None
+        b.compact(lo.data_ptr() if nt else None, hi.data_ptr() if hb and nt else None, stream)
+        tok_off = torch.empty(nd + 1, dtype=torch.int64, device=device)
+        status = torch.empty(nd, dtype=torch.int32, device=device)
+        _, p_off, p_status = b.device_result()
+        for t, src in ((tok_off, p_off), (status, p_status)):
+            if t.numel():
+                _copy_d2d(t.data_ptr(), src, t.numel() * t.element_size(), stream)
+        if side is not None:
+            cur.wait_stream(side)
+        return lo, hi, tok_off, status
 
     def special_ids(self, allowed_special):
         """"all" or an iterable of special-token literals -> their ids (ValueError for a literal that is no special token)."""
