@@ -226,8 +226,9 @@ JTK_HD uint64_t jtk_split_block(const JtkBlk& cu, const JtkBlk& nx, JtkSplitCarr
         }
         slow = cand & undecided;
         if (cy.sw_unknown) {
-            // the chain's origin is not visible: its bytes, and the char right after it, go the slow way
-            const uint64_t after0 = (chain0 << 1) & wlead & ~cu.NL;
+            // the chain's origin is not visible: its bytes, and the char right after it, go the slow way -- also when the
+            // chain ends with the previous block, so that the char right after it is this block's first byte
+            const uint64_t after0 = ((chain0 << 1) | (cy.pNL >> 63)) & wlead & ~cu.NL;
             slow |= (chain0 & wlead) | after0;
         }
         // carry: does the chain at the end of this block still have an invisible origin?

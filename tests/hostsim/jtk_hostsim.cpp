@@ -202,6 +202,13 @@ uint32_t sim_class_byte(const uint8_t* text, int64_t n, int64_t p) {
 }
 }
 
+// class bytes (jtk_class_byte: class in the low two bits) at many positions of one text
+extern "C" void sim_class_bytes_at(const uint8_t* text, int64_t n, const int64_t* pos, int64_t n_pos, uint8_t* out) {
+    JtkUcTables u{jtk_uc_stage1_init, jtk_uc_stage2_init};
+    Txt txt{text, n};
+    for (int64_t i = 0; i < n_pos; i++) out[i] = (uint8_t)jtk_class_byte(txt, u, pos[i]);
+}
+
 // ---- rank tables + lane merge on the host -----------------------------------------------------------
 #include <string>
 #include "../../jtokkit_amd/csrc/jtk_merge_core.h"
