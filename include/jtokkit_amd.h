@@ -379,6 +379,53 @@ int jtk_batch_pack_write(jtk_batch* b, int32_t pad_id, int32_t* d_rows, int32_t*
 /* The same to host buffers (synchronises); any may be NULL. */
 int jtk_batch_pack_fetch(jtk_batch* b, int32_t pad_id, int32_t* rows, int32_t* positions, int32_t* cu_seqlens, int64_t* seg_doc);
 
+/* ---- labels of the packed rows from byte spans of the text, on the device --------------------------------------------
+ * Supervised fine-tuning trains on parts of each document only -- the assistant turns of a chat, the completion after a
+ * prompt -- and wants a labels tensor beside the rows, ignore_index everywhere else (the -100 labels a collator builds on the
+ * host from a tokenizer's offset mapping).  Two passes do it on the device; the rule is jtokkit_amd/csrc/jtk_label_rules.h.
+ *   Spans     [span_begin[i], span_end[i]), i < n_spans: byte positions in the batch text (the coordinates of byte_begin /
+ *             byte_end of jtk_batch_chunk), sorted and disjoint: begin[i] <= end[i] <= begin[i + 1].  A span may cross
+ *             document boundaries: membership goes by byte position alone.  An empty span holds no token.
+ *   Tokens    token t of the last encode occupies [p_t, q_t): p_t as jtk_batch_token_offsets defines it (doc_off[d] + the
+ *             decoded bytes of the document's tokens before it; a special token taken as an id counts its literal),
+ *             q_t = p_t + the token's decoded length.
+ *   tok_span  tok_span[t] = the lowest i for which the rule holds, or -1 (all -1 with n_spans == 0):
+ *               JTK_SPAN_WHOLE   begin[i] <= p_t && q_t <= end[i]   (no byte outside the span is ever trained on)
+ *               JTK_SPAN_START   begin[i] <= p_t && p_t < end[i]    (the usual offset-mapping rule)
+ *               JTK_SPAN_ANY     p_t < end[i] && q_t > begin[i]
+ *             Spans that are not sorted and disjoint give unspecified values of tok_span (and no access out of bounds).
+ *   Labels    the unshifted label of a cell of the packed rows is its id when it holds token t of a document and
+ *             tok_span[t] >= 0 (a NULL tok_span: every token is trainable); its id when it is an EOS-style separator
+ *             (sep_id >= 0 without JTK_PACK_SEP_FIRST), JTK_LABEL_SEP is set and the unit's last token is trainable -- this
+ *             teaches the model to stop; for a unit without tokens JTK_LABEL_SEP labels the separator only when tok_span is
+ *             NULL --; ignore_index otherwise: BOS-style separators and pad cells always.  With JTK_LABEL_SHIFT cell (r, c)
+ *             gets the unshifted label of cell (r, c + 1) when both lie in the same segment (the same row and the same unit,
+ *             as cu_seqlens delimits them), else ignore_index: next-token targets never cross a document boundary, a row
+ *             end, or into pad.  Without it labels[r][c] goes with rows[r][c] (models that shift inside their loss). */
+enum { JTK_SPAN_WHOLE = 0, JTK_SPAN_START = 1, JTK_SPAN_ANY = 2 };
+enum {
+    JTK_LABEL_SHIFT = 1u,         /* labels[r][c] = the label of the next cell of the segment (next-token targets) */
+    JTK_LABEL_SEP = 2u            /* an EOS-style separator after a trainable last token is a label too */
+};
+/* d_tok_span[n_tokens] (device, int32) for the tokens of the LAST batch encode on `b` (host- or device-input,
+ * JTK_ENCODE_ALLOW_SPECIAL included) from n_spans spans in device memory.
+ *   Input:  not after a count-only encode, jtk_batch_encode_pieces (its positions are positions in the decoded stream) or
+ *           jtk_batch_encode_device_max_tokens; rule one of JTK_SPAN_*; 0 <= n_spans < 2^31, the arrays non-NULL unless
+ *           n_spans == 0.  Any violation: JTK_ERR_INVALID_ARGUMENT.
+ *   Order:  queued after that encode on stream_or_null (or the batch's stream), as jtk_batch_token_offsets is.  Reuses the
+ *           byte scan of a jtk_batch_chunk or jtk_batch_token_offsets on the same encode; without one it waits once, for the
+ *           token count.  No [n_tokens] array of positions is written. */
+int jtk_batch_token_spans(jtk_batch* b, const int64_t* d_span_begin, const int64_t* d_span_end, int64_t n_spans,
+                          int rule, int32_t* d_tok_span, void* stream_or_null);
+/* d_labels[n_rows * seq_len] (device, int32) for the rows of the last jtk_batch_pack, from d_tok_span_or_null (the result of
+ * jtk_batch_token_spans on the same encode, or NULL: every token is trainable).  flags: JTK_LABEL_SHIFT, JTK_LABEL_SEP
+ * (other bits: JTK_ERR_INVALID_ARGUMENT).  Ordered after the plan on stream_or_null (or the batch's stream); does not wait. */
+int jtk_batch_pack_labels(jtk_batch* b, const int32_t* d_tok_span_or_null, int32_t ignore_index, uint32_t flags,
+                          int32_t* d_labels, void* stream_or_null);
+/* The same to a host buffer labels[n_rows * seq_len] (synchronises); d_tok_span_or_null stays a device pointer. */
+int jtk_batch_pack_labels_fetch(jtk_batch* b, const int32_t* d_tok_span_or_null, int32_t ignore_index, uint32_t flags,
+                                int32_t* labels);
+
 /* ---- batch decode on the device ---------------------------------------------------------------------
  * Replaces a loop of Encoding.decodeBytes(List<Integer>) (GptBytePairEncoding.java:137-151, 302-314; special-token
  * ids decode to their literals, :308-311) over n_seqs token lists: all ids back to back in `ids`, list q occupying

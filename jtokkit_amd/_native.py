@@ -34,6 +34,11 @@ JTK_ENCODE_COMPACT_IDS = 32
 JTK_PACK_WHOLE_DOCS = 1
 JTK_PACK_SEP_FIRST = 2
 JTK_PACK_DROP_LAST = 4
+JTK_SPAN_WHOLE = 0
+JTK_SPAN_START = 1
+JTK_SPAN_ANY = 2
+JTK_LABEL_SHIFT = 1
+JTK_LABEL_SEP = 2
 JTK_OPT_CHUNK_BYTES = 1
 JTK_OPT_CHUNKS_IN_FLIGHT = 2
 JTK_OPT_HOST_CHUNK_BYTES = 3
@@ -86,6 +91,9 @@ SIGNATURES = {
     "jtk_batch_pack": (C.c_int, [_p, _i64, C.c_int32, C.c_uint32, _p, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(C.c_int32)]),
     "jtk_batch_pack_write": (C.c_int, [_p, C.c_int32, _p, _p, _p, _p, _p]),
     "jtk_batch_pack_fetch": (C.c_int, [_p, C.c_int32, _p, _p, _p, _p]),
+    "jtk_batch_token_spans": (C.c_int, [_p, _p, _p, _i64, C.c_int, _p, _p]),
+    "jtk_batch_pack_labels": (C.c_int, [_p, _p, C.c_int32, C.c_uint32, _p, _p]),
+    "jtk_batch_pack_labels_fetch": (C.c_int, [_p, _p, C.c_int32, C.c_uint32, _p]),
     "jtk_batch_decode": (C.c_int, [_p, _p, _p, _i64, C.POINTER(_i64)]),
     "jtk_batch_decode_device": (C.c_int, [_p, _p, _p, _i64, _i64, _p, C.POINTER(_i64)]),
     "jtk_batch_decode_fetch": (C.c_int, [_p, _p, _i64, _p, _p]),

@@ -175,6 +175,7 @@ struct jtk_batch {
     int64_t job_docs = 0, job_bytes = 0;
     uint32_t job_flags = 0;
     bool have_result = false, synced = false;
+    bool job_pieces = false;             // the last encode took caller-supplied pieces (jtk_batch_encode_pieces)
     bool profiling = false;
     std::vector<hipEvent_t> prof_ev;     // [chunk][stage][start, end]
     int prof_chunks = 0;                 // chunks of the last job that recorded events
@@ -865,6 +866,7 @@ int run_job(jtk_batch* b, const uint8_t* d_text, const uint8_t* h_text, const in
     b->job_docs = n_docs;
     b->job_bytes = n_bytes;
     b->job_flags = flags;
+    b->job_pieces = pieces != nullptr;
     b->have_result = true;
     b->have_host_result = to_host;
     b->have_trunc = false;
@@ -2050,6 +2052,72 @@ int jtk_batch_pack_fetch(jtk_batch* b, int32_t pad_id, int32_t* rows, int32_t* p
     if (rc == JTK_OK && e == hipSuccess && positions && cells) e = hipMemcpy(positions, p + o_pos, cells * 4, hipMemcpyDeviceToHost);
     if (rc == JTK_OK && e == hipSuccess && cu_seqlens) e = hipMemcpy(cu_seqlens, p + o_cu, (ns + 1) * 4, hipMemcpyDeviceToHost);
     if (rc == JTK_OK && e == hipSuccess && seg_doc && ns) e = hipMemcpy(seg_doc, p + o_sd, ns * 8, hipMemcpyDeviceToHost);
+    tmp.release();
+    if (rc != JTK_OK) return rc;
+    HIP_TRY(e);
+    return JTK_OK;
+}
+
+
+// ---- labels of the packed rows from byte spans (jtk_label.hip) ---------------------------------------------------------
+int jtk_batch_token_spans(jtk_batch* b, const int64_t* d_span_begin, const int64_t* d_span_end, int64_t n_spans, int rule,
+                          int32_t* d_tok_span, void* stream_or_null) {
+    if (!b || !b->have_result) return fail(JTK_ERR_INVALID_ARGUMENT, "no batch encode result on this batch (jtk_batch_encode_device_max_tokens leaves none)");
+    if (b->job_flags & JTK_ENCODE_COUNT_ONLY) return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode was count-only: there are no token ids");
+    if (b->job_pieces)
+        return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode took caller-supplied pieces: its token positions are not positions in the text");
+    if (rule != JTK_SPAN_WHOLE && rule != JTK_SPAN_START && rule != JTK_SPAN_ANY)
+        return fail(JTK_ERR_INVALID_ARGUMENT, "rule: JTK_SPAN_WHOLE, JTK_SPAN_START or JTK_SPAN_ANY");
+    if (n_spans < 0 || n_spans > INT32_MAX) return fail(JTK_ERR_INVALID_ARGUMENT, "n_spans must be in [0, 2^31 - 1]");
+    if (n_spans > 0 && (!d_span_begin || !d_span_end)) return fail(JTK_ERR_INVALID_ARGUMENT, "d_span_begin or d_span_end is NULL");
+    if (((uintptr_t)d_span_begin & 7u) || ((uintptr_t)d_span_end & 7u) || ((uintptr_t)d_tok_span & 3u))
+        return fail(JTK_ERR_INVALID_ARGUMENT, "unaligned array (8-byte int64 spans, 4-byte int32 tok_span)");
+    HIP_TRY(hipSetDevice(b->enc->device));
+    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    int rc;
+    if (!b->have_tiles) {                   // no chunk plan or token offsets on this encode: the byte scan first
+        int64_t nt = 0;
+        if ((rc = jtk_batch_result(b, &nt, nullptr, nullptr)) || (rc = ck_order(b, b->last_stream, s)) || (rc = ck_setup(b))) return rc;
+        if ((rc = ck_tiles(b, nt, s))) return rc;
+        b->ck_stream = s;
+    } else if ((rc = ck_order(b, b->ck_stream, s))) {
+        return rc;
+    }
+    if (b->ck.n_tok > 0 && !d_tok_span) return fail(JTK_ERR_INVALID_ARGUMENT, "d_tok_span is NULL");
+    jtk_launch_label_spans(b->ck, d_span_begin, d_span_end, n_spans, rule, d_tok_span, s);
+    HIP_TRY(hipGetLastError());
+    return JTK_OK;
+}
+
+int jtk_batch_pack_labels(jtk_batch* b, const int32_t* d_tok_span_or_null, int32_t ignore_index, uint32_t flags,
+                          int32_t* d_labels, void* stream_or_null) {
+    if (!b || !b->have_pack) return fail(JTK_ERR_INVALID_ARGUMENT, "jtk_batch_pack has not run on the last encode of this batch");
+    if (flags & ~(uint32_t)(JTK_LABEL_SHIFT | JTK_LABEL_SEP)) return fail(JTK_ERR_INVALID_ARGUMENT, "flags: JTK_LABEL_SHIFT, JTK_LABEL_SEP");
+    if (b->pk.n_rows > 0 && !d_labels) return fail(JTK_ERR_INVALID_ARGUMENT, "d_labels is NULL");
+    if (((uintptr_t)d_tok_span_or_null & 3u) || ((uintptr_t)d_labels & 3u)) return fail(JTK_ERR_INVALID_ARGUMENT, "unaligned array (4-byte int32)");
+    HIP_TRY(hipSetDevice(b->enc->device));
+    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    int rc;
+    if ((rc = ck_order(b, b->pk_stream, s))) return rc;
+    JtkLabelView lv;
+    lv.tok_span = d_tok_span_or_null; lv.ignore_index = ignore_index; lv.label_sep = (flags & JTK_LABEL_SEP) != 0;
+    jtk_launch_label_pack(b->pk, lv, (flags & JTK_LABEL_SHIFT) != 0, d_labels, s);
+    HIP_TRY(hipGetLastError());
+    return JTK_OK;
+}
+
+int jtk_batch_pack_labels_fetch(jtk_batch* b, const int32_t* d_tok_span_or_null, int32_t ignore_index, uint32_t flags,
+                                int32_t* labels) {
+    if (!b || !b->have_pack) return fail(JTK_ERR_INVALID_ARGUMENT, "jtk_batch_pack has not run on the last encode of this batch");
+    const size_t cells = (size_t)(b->pk.n_rows * b->pk.v.L);
+    if (cells && !labels) return fail(JTK_ERR_INVALID_ARGUMENT, "labels is NULL");
+    HIP_TRY(hipSetDevice(b->enc->device));
+    DevBuf tmp;
+    int rc = tmp.ensure(cells * 4 + 16);
+    if (rc) return rc;
+    rc = jtk_batch_pack_labels(b, d_tok_span_or_null, ignore_index, flags, (int32_t*)tmp.p, b->pk_stream);
+    hipError_t e = rc == JTK_OK ? hipStreamSynchronize(b->pk_stream) : hipSuccess;
+    if (rc == JTK_OK && e == hipSuccess && cells) e = hipMemcpy(labels, tmp.p, cells * 4, hipMemcpyDeviceToHost);
     tmp.release();
     if (rc != JTK_OK) return rc;
     HIP_TRY(e);

@@ -7,6 +7,7 @@
 
 #include "jtk_common.h"
 #include "jtk_pack_rules.h"
+#include "jtk_label_rules.h"
 
 #define JTK_SPLIT_TILE 4096      // bytes per pretok_split workgroup
 #define JTK_SPLIT_HALO 64
@@ -293,6 +294,11 @@ struct JtkPackWork {
 void jtk_launch_pack_plan(const JtkPackWork& w, hipStream_t s);        // units, scans, groups -> hdr
 void jtk_launch_pack_write(const JtkPackWork& w, int32_t pad_id, int32_t* rows, int32_t* positions, int32_t* cu_seqlens,
                            int64_t* seg_doc, hipStream_t s);           // (needs n_rows, n_seg)
+// Labels (jtk_label.hip; the rule is jtk_label_rules.h).  tok_span[n_tok] of the chunk work's tokens from the spans
+// [begin[i], end[i]), i < n_spans (needs the tiles of jtk_launch_chunk_tiles); labels[n_rows * L] of the pack work's rows.
+void jtk_launch_label_spans(const JtkChunkWork& w, const int64_t* begin, const int64_t* end, int64_t n_spans, int rule,
+                            int32_t* tok_span, hipStream_t s);
+void jtk_launch_label_pack(const JtkPackWork& w, const JtkLabelView& lv, bool shift, int32_t* labels, hipStream_t s);
 // Compact ids (jtk_compact.hip; the rule is jtk_compact_rules.h): the range [t0, t1) of the int32 stream `ids` (indexed from
 // token 0) into a uint16 plane and a plane of hb bits per token whose entry 0 is token `origin` (a multiple of 32; 0 for whole
 // planes).  Restarts at t0 rounded down to a multiple of 32 and rewrites the words there whole.  d_total != NULL: the range ends

@@ -184,4 +184,13 @@ JTK_PK_HD JtkPackCell jtk_pack_cell(const JtkPackView& v, const JtkPackRow& row,
     return out;
 }
 
+// The source token of cell c of row `row`, as an index into the last encode's ids, with u the cursor that jtk_pack_cell has
+// just left on that cell: -1 for a separator and for a pad cell.
+JTK_PK_HD int64_t jtk_pack_cell_token(const JtkPackView& v, const JtkPackRow& row, int64_t c, const JtkPackUnit& u) {
+    const int64_t s = row.a + c;
+    if (s >= row.b) return -1;
+    const int64_t o = s - u.p0 - (v.sep_id >= 0 && v.sep_first ? 1 : 0);
+    return o >= 0 && o < u.n_ids ? u.tb + o : -1;
+}
+
 #endif

@@ -55,6 +55,50 @@ def _copy_d2d(dst, src, n_bytes, stream):
         raise EncodingError(N.JTK_ERR_HIP, "hipMemcpyAsync failed (%d)" % rc)
 
 
+_SPAN_RULES = {"whole": N.JTK_SPAN_WHOLE, "start": N.JTK_SPAN_START, "any": N.JTK_SPAN_ANY}
+
+
+def _span_rule(rule):
+    """"whole" / "start" / "any" -> JTK_SPAN_*; an int goes through (the library checks it)."""
+    if isinstance(rule, str):
+        if rule not in _SPAN_RULES:
+            raise ValueError("span rule must be 'whole', 'start' or 'any', not %r" % (rule,))
+        return _SPAN_RULES[rule]
+    return int(rule)
+
+
+class _DeviceArray:
+    """A numpy array's bytes in device memory of the HIP runtime the library is bound to, for host-input calls whose C entry
+    point takes device arrays (no torch needed).  fetch() copies back."""
+
+    def __init__(self, arr):
+        self._arr = np.ascontiguousarray(arr)
+        self.ptr = C.c_void_p()
+        L = N.lib()
+        for f, args in ((L.hipMalloc, [C.POINTER(C.c_void_p), C.c_size_t]), (L.hipFree, [C.c_void_p]),
+                        (L.hipMemcpy, [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int])):
+            f.restype, f.argtypes = C.c_int, args
+        self._check(L.hipMalloc(C.byref(self.ptr), max(self._arr.nbytes, 16)), "hipMalloc")
+        if self._arr.nbytes:
+            self._check(L.hipMemcpy(self.ptr, self._arr.ctypes.data, self._arr.nbytes, 1), "hipMemcpy")
+
+    @staticmethod
+    def _check(rc, what):
+        if rc != 0:
+            raise EncodingError(N.JTK_ERR_HIP, "%s failed (%d)" % (what, rc))
+
+    def fetch(self):
+        out = np.empty_like(self._arr)
+        if out.nbytes:
+            self._check(N.lib().hipMemcpy(out.ctypes.data, self.ptr, out.nbytes, 2), "hipMemcpy")
+        return out
+
+    def free(self):
+        if self.ptr:
+            N.lib().hipFree(self.ptr)
+            self.ptr = C.c_void_p()
+
+
 class EncodingResult:
     """api/EncodingResult.java"""
 
@@ -384,6 +428,27 @@ class Batch:
                                                                                                "seg_doc"))))
         f["seg_doc"] = f["seg_doc"][:ns]
         return f
+
+    # ---- labels of the packed rows from byte spans (device) ----------------------------------------------
+    def token_spans(self, d_begin, d_end, n_spans, rule, d_tok_span, stream=None):
+        """jtk_batch_token_spans on the last encode: int32 [n_tokens] at d_tok_span, per token the lowest of the n_spans spans
+        [begin[i], end[i]) (int64 device arrays, batch positions, sorted and disjoint) that holds it by `rule` ("whole",
+        "start", "any" or a JTK_SPAN_* value), or -1 (the rule is in jtk_label_rules.h)."""
+        _check(N.lib().jtk_batch_token_spans(self._h, d_begin, d_end, int(n_spans), _span_rule(rule), d_tok_span, stream))
+
+    def pack_labels(self, d_tok_span, ignore_index, d_labels, shift=False, label_sep=False, stream=None):
+        """jtk_batch_pack_labels on the last pack: int32 [n_rows, seq_len] at d_labels from d_tok_span (None: every token is
+        trainable); does not wait."""
+        flags = (N.JTK_LABEL_SHIFT if shift else 0) | (N.JTK_LABEL_SEP if label_sep else 0)
+        _check(N.lib().jtk_batch_pack_labels(self._h, d_tok_span, int(ignore_index), flags, d_labels, stream))
+
+    def pack_labels_fetch(self, d_tok_span, ignore_index=-100, shift=False, label_sep=False):
+        """The same on the host: labels int32 [n_rows, seq_len] (d_tok_span stays a device pointer, or None)."""
+        nr, L, _ = self._pack
+        out = np.zeros((nr, L), dtype=np.int32)
+        flags = (N.JTK_LABEL_SHIFT if shift else 0) | (N.JTK_LABEL_SEP if label_sep else 0)
+        _check(N.lib().jtk_batch_pack_labels_fetch(self._h, d_tok_span, int(ignore_index), flags, out.ctypes.data))
+        return out
 
     # ---- batch decode (device) -------------------------------------------------------------------------
     def decode_host(self, ids, seq_off):
@@ -845,37 +910,101 @@ class HipEncoding:
             return self._specials[key]
         return int(sep)
 
+    @staticmethod
+    def _batch_spans(train_spans, doc_off):
+        """Per-document (start, end) byte ranges -> sorted batch positions (begin, end int64), checked."""
+        nd = len(doc_off) - 1
+        if len(train_spans) != nd:
+            raise ValueError("train_spans needs one list of (start, end) per text (%d for %d texts)" % (len(train_spans), nd))
+        begin, end = [], []
+        for d, spans in enumerate(train_spans):
+            n, prev = int(doc_off[d + 1] - doc_off[d]), 0
+            for a, e in spans or ():
+                a, e = int(a), int(e)
+                if a < 0 or e < a or e > n:
+                    raise ValueError("train_spans[%d]: (%d, %d) is not a byte range inside the text (%d bytes)" % (d, a, e, n))
+                if a < prev:
+                    raise ValueError("train_spans[%d]: (%d, %d) starts before the previous range ends: ranges must be sorted "
+                                     "and must not overlap" % (d, a, e))
+                prev = e
+                begin.append(int(doc_off[d]) + a)
+                end.append(int(doc_off[d]) + e)
+        return np.array(begin, dtype=np.int64), np.array(end, dtype=np.int64)
+
     def pack_batch(self, texts, seq_len, sep=None, sep_first=False, whole_docs=False, drop_last=False, pad_id=-1, ordinary=False,
-                   allowed_special=None):
+                   allowed_special=None, train_spans=None, span_rule="whole", label_shift=False, label_sep=False,
+                   ignore_index=-100):
         """Every text encoded, then packed into rows of seq_len tokens (jtk_batch_pack; the rule is in jtk_pack_rules.h): a dict
         of numpy arrays rows, positions int32 [n_rows, seq_len], cu_seqlens int32 [n_segments + 1], seg_doc int64
         [n_segments], status int32 [n_docs] and max_seqlen (int).  sep: None, a token id or a special-token literal such as
         "<|endoftext|>", after each document (or before it with sep_first).  whole_docs: next-fit of whole documents instead of
         one concatenated stream; drop_last (concat only): omit a partial last row.  Documents with a negative status are left
-        out (they do not raise)."""
+        out (they do not raise).
+        train_spans: per text a list of (start, end) byte ranges inside that text, sorted and not overlapping (ValueError
+        otherwise; an empty list: nothing of the text is trained on).  The result then also holds labels int32
+        [n_rows, seq_len] -- a cell's id where its token lies in a range by span_rule ("whole": entirely inside, "start": its
+        first byte, "any": any byte), ignore_index elsewhere, on separators (unless label_sep, for a separator after a trainable
+        last token) and on pad; label_shift: next-token targets within each segment -- and tok_span int32 [n_tokens], each
+        token's range (numbered over the batch) or -1.  The rule is in jtk_label_rules.h."""
         bs = [t if isinstance(t, (bytes, bytearray)) else t.encode("utf-8") for t in texts]
         doc_off = np.zeros(len(bs) + 1, dtype=np.int64)
         if bs:
             np.cumsum([len(x) for x in bs], out=doc_off[1:])
         text = np.frombuffer(b"".join(bs), dtype=np.uint8) if doc_off[-1] else np.zeros(0, dtype=np.uint8)
         sep_id = self._sep_id(sep)
+        if train_spans is not None:
+            rule = _span_rule(span_rule)
+            begin, end = self._batch_spans(train_spans, doc_off)
         res = self.encode_batch_packed(text, doc_off, ordinary, False, allowed_special)
         b = self._b()
         _, _, mx = b.pack(seq_len, sep_id, whole_docs, sep_first, drop_last)
         f = b.pack_fetch(pad_id)
         f["status"] = res.status.copy()
         f["max_seqlen"] = mx
+        if train_spans is not None:
+            bufs = []
+            try:
+                for a in (begin, end, np.zeros(len(res.tokens), dtype=np.int32)):
+                    bufs.append(_DeviceArray(a))
+                b.token_spans(bufs[0].ptr, bufs[1].ptr, len(begin), rule, bufs[2].ptr)
+                f["labels"] = b.pack_labels_fetch(bufs[2].ptr, ignore_index, label_shift, label_sep)   # (synchronises)
+                f["tok_span"] = bufs[2].fetch()
+            finally:
+                for x in bufs:
+                    x.free()
         return f
 
+    def _check_device_spans(self, text, span_begin, span_end):
+        import torch
+        for name, t in (("span_begin", span_begin), ("span_end", span_end)):
+            if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != torch.int64 or t.dim() != 1:
+                raise ValueError("%s must be a 1-d CUDA tensor of torch.int64" % name)
+            if t.device != text.device:
+                raise ValueError("%s is on %s, the text on %s" % (name, t.device, text.device))
+            if not t.is_contiguous():
+                raise ValueError("%s must be contiguous" % name)
+        if span_begin.numel() != span_end.numel():
+            raise ValueError("span_begin and span_end must have the same length")
+
     def pack_batch_device(self, text, doc_off, seq_len, sep=None, sep_first=False, whole_docs=False, drop_last=False, pad_id=-1,
-                          ordinary=False, allowed_special=None):
+                          ordinary=False, allowed_special=None, span_begin=None, span_end=None, span_rule="whole",
+                          label_shift=False, label_sep=False, ignore_index=-100):
         """pack_batch for a device-resident batch.  text: CUDA torch.uint8 tensor, doc_off: CUDA torch.int64 tensor [n_docs + 1],
         on this encoding's device.  Returns a dict of CUDA tensors written on torch.cuda.current_stream(): rows int32
         [n_rows, seq_len], positions int32 [n_rows, seq_len], cu_seqlens int32 [n_segments + 1], seg_doc int64 [n_segments],
         status int32 [n_docs], and max_seqlen as a Python int -- what a varlen attention call takes.  The call waits once, for
-        the counts (and, with allowed_special, once more for the encode's count of literal candidates)."""
+        the counts (and, with allowed_special, once more for the encode's count of literal candidates).
+        span_begin / span_end: CUDA torch.int64 tensors of equal length, byte ranges [begin, end) in positions of `text`, sorted
+        and disjoint (not checked: ranges out of order give unspecified labels).  The dict then also holds labels int32
+        [n_rows, seq_len] and tok_span int32 [n_tokens], as pack_batch describes them, written on the same stream; the token
+        count costs one more wait."""
         import torch
         self._check_device_inputs("pack_batch_device", text, doc_off)
+        if (span_begin is None) != (span_end is None):
+            raise ValueError("span_begin and span_end go together")
+        if span_begin is not None:
+            self._check_device_spans(text, span_begin, span_end)
+            rule = _span_rule(span_rule)
         L = int(seq_len)
         if L < 1:
             raise ValueError("seq_len must be >= 1")
@@ -913,10 +1042,60 @@ class HipEncoding:
                      out["seg_doc"].data_ptr(), stream)
         if nd:
             _copy_d2d(out["status"].data_ptr(), b.device_result()[2], nd * 4, stream)
+        if span_begin is not None:
+            nt = b.result()[0]
+            out["tok_span"] = torch.empty(nt, dtype=torch.int32, device=device)
+            out["labels"] = torch.empty((nr, L), dtype=torch.int32, device=device)
+            b.token_spans(span_begin.data_ptr(), span_end.data_ptr(), span_begin.numel(), rule, out["tok_span"].data_ptr(), stream)
+            b.pack_labels(out["tok_span"].data_ptr(), ignore_index, out["labels"].data_ptr(), label_shift, label_sep, stream)
         if side is not None:
             cur.wait_stream(side)
         out["max_seqlen"] = mx
         return out
+
+    def token_spans_device(self, text, doc_off, span_begin, span_end, rule="whole", ordinary=False, allowed_special=None):
+        """For callers who do not pack: encodes a device-resident batch (text CUDA torch.uint8, doc_off CUDA torch.int64
+        [n_docs + 1]) and returns (tok_span int32 [n_tokens], tok_off int64 [n_docs + 1], status int32 [n_docs]) as CUDA tensors
+        written on torch.cuda.current_stream(): per token the lowest of the byte ranges [span_begin[i], span_end[i]) (CUDA
+        torch.int64, positions in `text`, sorted and disjoint) that holds it by `rule`, or -1 (jtk_label_rules.h).  The ids
+        stay in the batch (device_result).  Waits once, for the token count."""
+        import torch
+        self._check_device_inputs("token_spans_device", text, doc_off)
+        self._check_device_spans(text, span_begin, span_end)
+        rule = _span_rule(rule)
+        allow = self._allow(self._b(), allowed_special)
+        nd = doc_off.numel() - 1
+        if nd < 0:
+            raise ValueError("doc_off needs n_docs + 1 entries")
+        device = text.device
+        n = text.numel()
+        st = text.untyped_storage()
+        if text.data_ptr() % 16 or st.data_ptr() + st.nbytes() < text.data_ptr() + (n + 15) // 16 * 16:
+            # (the encode reads whole aligned 16-byte blocks)
+            buf = torch.zeros((n + 15) // 16 * 16 + 16, dtype=torch.uint8, device=device)
+            buf[:n].copy_(text)
+            text = buf
+        b = self._b()
+        cur = torch.cuda.current_stream(device)
+        side = None
+        if cur.cuda_stream == 0:
+            # (the legacy default stream: as in chunk_batch_device, the work goes to the batch's own stream explicitly)
+            side = torch.cuda.ExternalStream(b.stream(), device=device)
+            side.wait_stream(cur)
+        stream = (side or cur).cuda_stream
+        b.encode_device(text.data_ptr(), doc_off.data_ptr(), nd, n, ordinary, stream=stream, sync=False, allow_special=allow)
+        nt = b.result()[0]
+        tok_span = torch.empty(nt, dtype=torch.int32, device=device)
+        tok_off = torch.empty(nd + 1, dtype=torch.int64, device=device)
+        status = torch.empty(nd, dtype=torch.int32, device=device)
+        b.token_spans(span_begin.data_ptr(), span_end.data_ptr(), span_begin.numel(), rule, tok_span.data_ptr(), stream)
+        _, p_off, p_status = b.device_result()
+        _copy_d2d(tok_off.data_ptr(), p_off, (nd + 1) * 8, stream)
+        if nd:
+            _copy_d2d(status.data_ptr(), p_status, nd * 4, stream)
+        if side is not None:
+            cur.wait_stream(side)
+        return tok_span, tok_off, status
 
     def count_tokens_batch(self, texts, ordinary=False, allowed_special=None):
         """Encoding.countTokens / countTokensOrdinary for every text, one device call, no token ids written.  allowed_special:
