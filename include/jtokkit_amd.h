@@ -431,7 +431,9 @@ int jtk_batch_pack_labels_fetch(jtk_batch* b, const int32_t* d_tok_span_or_null,
  * ids decode to their literals, :308-311) over n_seqs token lists: all ids back to back in `ids`, list q occupying
  * [seq_off[q], seq_off[q+1]).  Result: the byte strings back to back, list q occupying [byte_off[q], byte_off[q+1]);
  * status[q] = JTK_OK or JTK_ERR_UNKNOWN_TOKEN (that list's bytes then omit the unknown ids).  Both calls synchronise
- * and leave the result on the device; *n_bytes receives the total byte count. */
+ * and leave the result on the device; *n_bytes receives the total byte count.  jtk_batch_decode checks seq_off (it starts at
+ * 0 and never decreases; JTK_ERR_INVALID_ARGUMENT otherwise); jtk_batch_decode_device does not validate d_seq_off, which must
+ * hold the same and end at n_ids. */
 int jtk_batch_decode(jtk_batch* b, const int32_t* ids, const int64_t* seq_off, int64_t n_seqs, int64_t* n_bytes);
 int jtk_batch_decode_device(jtk_batch* b, const int32_t* d_ids, const int64_t* d_seq_off, int64_t n_seqs, int64_t n_ids,
                             void* stream_or_null, int64_t* n_bytes);
