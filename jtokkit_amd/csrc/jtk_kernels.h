@@ -8,6 +8,7 @@
 #include "jtk_common.h"
 #include "jtk_pack_rules.h"
 #include "jtk_label_rules.h"
+#include "jtk_stage_rules.h"
 
 #define JTK_SPLIT_TILE 4096      // bytes per pretok_split workgroup
 #define JTK_SPLIT_HALO 64
@@ -47,13 +48,7 @@
 #define JTK_BIN_CAP4 (JTK_TILE / 32)   //           33..64 bytes
 #define JTK_BIN_CAP5 (JTK_TILE / 64)   //           65..128 bytes
 #define JTK_BIN_CAP6 (JTK_TILE / 128)  //           129..256 bytes
-// the head of a tile's slice of each bin's queue that pack stages in LDS: 32 + 16 + 16 results of the three classes of <= 16
-// bytes (staging slots 0..63), 8 of each longer bin (64..95); tiny pieces have a staging area of their own (JTK_PACK_TINY).
-// (Three times as much -- enough for every tile of CJK text -- made pack 3 % faster on mixed text and 10 % slower on prose.)
-#define JTK_PACK_TINY 128
-#define JTK_PACK_SLOTS 96
-#define JTK_PACK_CAP(bin) ((bin) == 0 ? 32 : (bin) <= 2 ? 16 : 8)
-#define JTK_PACK_OFF(bin) ((bin) == 0 ? 0 : (bin) == 1 ? 32 : (bin) == 2 ? 48 : 64 + ((bin) - 3) * 8)
+// (what pack stages of a tile's results in LDS, JTK_PACK_*: jtk_stage_rules.h)
 #define JTK_NBINS_BYTES 3              // bins 0..2: the queue entry carries the piece's bytes
 #define JTK_NBINS_LEAN 5               // bins 0..4: lean phases of the merge kernel; 5..6: state-machine phases
 #define JTK_BIN_MAXLEN 256            // longer pieces go to the wave-per-piece kernels

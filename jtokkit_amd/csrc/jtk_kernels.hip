@@ -1645,6 +1645,13 @@ __device__ __forceinline__ uint32_t hard_count(const JtkWork& w, int64_t pos) {
 }
 
 // c token ids from htok to the output, eight loads in flight per round trip (htok is padded by 16 words)
+// a wave-uniform pointer, held in scalar registers
+template <typename P> __device__ __forceinline__ P* uniform_ptr(P* p) {
+    const uint64_t v = reinterpret_cast<uint64_t>(p);
+    return reinterpret_cast<P*>((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)v) |
+                                (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)(v >> 32)) << 32);
+}
+
 struct __attribute__((packed, aligned(4))) U4Unaligned { uint32_t x, y, z, w; };
 __device__ __forceinline__ void pack_copy(uint32_t* dst, const uint32_t* src, uint32_t c) {
     for (uint32_t i = 0; i < c; i += 8) {
@@ -1668,9 +1675,6 @@ template <int I> __device__ __forceinline__ uint32_t res_tok(const uint4& r) {
     return (sh + 17 <= 32 ? (w0 >> sh) : __builtin_amdgcn_alignbit(w1, w0, sh)) & JTK_HT_ID_MASK;
 }
 
-#ifndef JTK_PACK_STAGE
-#define JTK_PACK_STAGE 768
-#endif
 constexpr int PACK_STAGE = JTK_PACK_STAGE;     // tokens of a tile assembled in LDS (ordinary text: a few hundred)
 constexpr int PQT = JTK_PACK_TINY;
 
@@ -1679,10 +1683,13 @@ __global__ void __launch_bounds__(64) k_pack_tokens(JtkWork w) {
     // of the tile's merge results (they are dense: the tile's slice of each bin's queue) and the document mask are all
     // requested before the first wait.  The tile's tokens are assembled in LDS (the few multi-token pieces make sparse
     // writes, cheap there and expensive in memory) and leave in full 256-byte stores.
-    __shared__ uint4 s_qe[JTK_PACK_SLOTS];
+    // Results and assembly words are one array of 16-byte slots (jtk_stage_rules.h): the slots that the tile's tokens leave
+    // free hold the results beyond the staged heads, so that a tile with many merged pieces finds them in LDS too.
+    __shared__ uint4 s_qe[JTK_PACK_SLOTS + JTK_PACK_OUT_SLOTS];
     __shared__ uint2 s_qt[PQT];                 // staged results of the tile's tiny pieces
     __shared__ uint64_t s_dm[TW];
-    __shared__ uint32_t s_out[PACK_STAGE];
+    __shared__ uint32_t s_ext[8];               // per bin: jtk_stage_word of its extension (tiles with results beyond the heads)
+    uint32_t* const s_out = reinterpret_cast<uint32_t*>(s_qe + JTK_PACK_SLOTS);
     const int lane = threadIdx.x;
     const int64_t tile = blockIdx.x;
     const int64_t B = tile * T;
@@ -1717,32 +1724,94 @@ __global__ void __launch_bounds__(64) k_pack_tokens(JtkWork w) {
     uint32_t e[8];
 #pragma unroll
     for (int j = 0; j < 8; j++) e[j] = plist[j * 64 + lane];          // (not waiting for np: entries beyond it are zeroed below)
+    // Everything else the tile needs is requested here, into registers, and written to LDS only after the last request: the
+    // wave waits for one round trip, not for one per kind of data.
+    uint64_t dmw = 0ull;
     if (lane < TW) {
         const int64_t dwd = (B >> 6) + lane;
-        s_dm[lane] = (dwd < w.n_words) ? w.docmask[dwd] : 0ull;
+        if (dwd < w.n_words) dmw = w.docmask[dwd];
     }
     // the tile's merge results: the head of its slice of every bin's queue is staged (one load per lane for the three
-    // classes of <= 16 bytes, one more for the longer bins if the tile has any), the rest is read on demand
+    // classes of <= 16 bytes, one more for the longer bins if the tile has any), then what the free slots hold of the rest
+    // (jtk_stage_rules.h); what is left is read on demand
     const int64_t shard = tile % JTK_Q_SHARDS;
+    uint4 rh = make_uint4(0, 0, 0, 0), rl = make_uint4(0, 0, 0, 0);
+    bool hv, lv = false;
     {
         const int bl = lane < 32 ? 0 : lane < 48 ? 1 : 2, il = lane < 32 ? lane : lane < 48 ? lane - 32 : lane - 48;
         const uint32_t qbv = (uint32_t)__shfl((int)meta, bl), nqv = (uint32_t)__shfl((int)meta, 8 + bl);
-        const uint4* src = (bl == 0 ? w.qd[0] + shard * w.q_cap[0] : bl == 1 ? w.qd[1] + shard * w.q_cap[1] : w.qd[2] + shard * w.q_cap[2]) + qbv;
-        if ((uint32_t)il < nqv) s_qe[lane] = src[il];
+        // (the bases as scalars: a queue pointer picked per lane becomes a vector load of the kernel arguments, a round trip)
+        const uint4* const p0 = uniform_ptr(w.qd[0] + shard * w.q_cap[0]), * const p1 = uniform_ptr(w.qd[1] + shard * w.q_cap[1]),
+                   * const p2 = uniform_ptr(w.qd[2] + shard * w.q_cap[2]);
+        const uint4* src = (bl == 0 ? p0 : bl == 1 ? p1 : p2) + qbv;
+        hv = (uint32_t)il < nqv;
+        if (hv) rh = src[il];
     }
     const uint32_t nq_hi = (uint32_t)__shfl((int)meta, 11) | (uint32_t)__shfl((int)meta, 12) | (uint32_t)__shfl((int)meta, 13) | (uint32_t)__shfl((int)meta, 14);
     if (nq_hi) {                                                          // wave-uniform; rare in ordinary text
         const int bq = 3 + ((lane >> 3) & 3), il = lane & 7;
         const uint32_t qb = (uint32_t)__shfl((int)meta, bq), nq = (uint32_t)__shfl((int)meta, 8 + bq);
-        if (lane < 32 && (uint32_t)il < nq) s_qe[JTK_PACK_OFF(3) + lane] = (w.qd[bq] + shard * w.q_cap[bq] + qb)[il];
+        lv = lane < 32 && (uint32_t)il < nq;
+        const uint4* const p3 = uniform_ptr(w.qd[3] + shard * w.q_cap[3]), * const p4 = uniform_ptr(w.qd[4] + shard * w.q_cap[4]),
+                   * const p5 = uniform_ptr(w.qd[5] + shard * w.q_cap[5]), * const p6 = uniform_ptr(w.qd[6] + shard * w.q_cap[6]);
+        if (lv) rl = ((bq == 3 ? p3 : bq == 4 ? p4 : bq == 5 ? p5 : p6) + qb)[il];
     }
     const uint32_t qb5 = (uint32_t)__shfl((int)meta, JTK_BIN_TINY), nq5 = (uint32_t)__shfl((int)meta, 8 + JTK_BIN_TINY);
     const uint2* const res5 = reinterpret_cast<const uint2*>(w.qt + shard * w.qt_cap + qb5);
+    uint2 rt[PQT / 64];
     if (nq5) {                                                            // wave-uniform
 #pragma unroll
         for (int r = 0; r < PQT / 64; r++) {
             const uint32_t i = (uint32_t)(r * 64 + lane);
-            if (i < nq5) s_qt[i] = res5[i];
+            rt[r] = make_uint2(0, 0);
+            if (i < nq5) rt[r] = res5[i];
+        }
+    }
+    // results beyond the heads (lanes 8..14 hold the bins' counts): lane l takes the free slots x0 + l, x0 + 64 + l, ...
+    constexpr int XR = JTK_PACK_OUT_SLOTS / 64;
+    const uint32_t over = (lane >= 8 && lane < 8 + JTK_NBINS_STAGE) ? jtk_stage_over(lane - 8, meta) : 0u;
+    const bool has_ext = __ballot(over != 0u) != 0ull;                    // wave-uniform; not in ordinary text
+    uint4 rx[XR];
+    uint32_t xend = 0;
+    const uint32_t x0 = (uint32_t)JTK_PACK_SLOTS + jtk_stage_first_free(total);
+    if (has_ext) {
+        const uint32_t inc = wave_incl_scan(over);
+        uint32_t xoff, xn;
+        jtk_stage_place(total, inc - over, over, &xoff, &xn);
+        if (lane >= 8 && lane < 16) s_ext[lane - 8] = lane < 8 + JTK_NBINS_STAGE ? jtk_stage_word(lane - 8, xoff, xn) : 0u;
+        xend = (uint32_t)__builtin_amdgcn_readlane((int)(xoff + xn), 8 + JTK_NBINS_STAGE - 1);
+#pragma unroll
+        for (int r = 0; r < XR; r++) {
+            rx[r] = make_uint4(0, 0, 0, 0);
+            if (x0 + r * 64 >= xend) break;                               // (wave-uniform)
+            const uint32_t slot = x0 + r * 64 + lane;
+            const uint4* src = nullptr;
+#pragma unroll
+            for (int b = 0; b < JTK_NBINS_STAGE; b++) {
+                const uint32_t n = (uint32_t)__builtin_amdgcn_readlane((int)xn, 8 + b);
+                if (n == 0u) continue;                                    // (wave-uniform)
+                const uint32_t o = (uint32_t)__builtin_amdgcn_readlane((int)xoff, 8 + b), qb = (uint32_t)__builtin_amdgcn_readlane((int)meta, b);
+                const uint4* base = w.qd[b] + shard * w.q_cap[b] + qb + JTK_PACK_CAP(b);
+                src = slot - o < n ? base + (slot - o) : src;
+            }
+            if (slot < xend) rx[r] = *src;
+        }
+    }
+    if (lane < TW) s_dm[lane] = dmw;
+    if (hv) s_qe[lane] = rh;
+    if (nq_hi) { if (lv) s_qe[JTK_PACK_OFF(3) + lane] = rl; }
+    if (nq5) {
+#pragma unroll
+        for (int r = 0; r < PQT / 64; r++) {
+            const uint32_t i = (uint32_t)(r * 64 + lane);
+            if (i < nq5) s_qt[i] = rt[r];
+        }
+    }
+    if (has_ext) {
+#pragma unroll
+        for (int r = 0; r < XR; r++) {
+            const uint32_t slot = x0 + r * 64 + lane;
+            if (slot < xend) s_qe[slot] = rx[r];
         }
     }
 #pragma unroll
@@ -1760,14 +1829,21 @@ __global__ void __launch_bounds__(64) k_pack_tokens(JtkWork w) {
         const bool queued = hard && !(ej & JTK_PL_NOQUEUE);
         const bool tinyp = bin == JTK_BIN_TINY;
         const bool staged = queued && (ej & JTK_PL_STAGED) != 0u;       // (piece_resolve knew: qi is the staging slot then)
-        const uint32_t sidx = staged && !tinyp ? qi : 0u;
+        uint32_t sidx = staged && !tinyp ? qi : 0u;
+        bool inlds = staged;                                             // ... or in the extension
+        if (has_ext) {
+            const uint32_t xw = s_ext[bin];
+            const bool x = queued && !staged && qi < (xw >> 16);
+            sidx = x ? (xw & 0xFFFFu) + qi : sidx;
+            inlds = staged || x;
+        }
         uint4 qe = s_qe[sidx];
         if (__ballot(queued && tinyp)) { if (staged && tinyp) qe = tiny_word(s_qt[qi]); }
         uint32_t c = valid ? (hard ? (qe.w >> 24) + 1u : 1u) : 0u;
         const uint32_t off = hard ? (ej & 2047u) : ((ej >> JTK_PL_OFF_SHIFT) & 2047u);
         const bool isdoc = valid && ((s_dm[off >> 6] >> (off & 63)) & 1ull);
         uint32_t pre;
-        if (!__ballot(valid && hard && (!staged || c > 7u))) {
+        if (!__ballot(valid && hard && (!inlds || c > 7u))) {
             // the common case, without divergent branches: exclusive scan of c (1 for most lanes, at most 7) by ballots of
             // the bits of c - 1, first tokens in one full store, the few further ones in sparse stores
             const uint32_t x = c ? c - 1u : 0u;
@@ -1795,10 +1871,10 @@ __global__ void __launch_bounds__(64) k_pack_tokens(JtkWork w) {
                 }
             }
         } else {
-            // general case: results beyond the staged head, results of more than 7 tokens (tokens in htok), pieces merged
+            // general case: results beyond what is staged, results of more than 7 tokens (tokens in htok), pieces merged
             // by the wave / workgroup phases (count and tokens in htok)
             const uint32_t qb = (uint32_t)__shfl((int)meta, (int)(bin < JTK_NBINS ? bin : 0u));   // (all lanes take part)
-            if (valid && queued && !staged) {
+            if (valid && queued && !inlds) {
                 qe = tinyp ? tiny_word(res5[qi]) : (w.qd[bin] + shard * w.q_cap[bin] + qb)[qi];
                 c = (qe.w >> 24) + 1u;
             } else if (valid && hard && !queued) c = hard_count(w, B + off);        // count in the htok header
