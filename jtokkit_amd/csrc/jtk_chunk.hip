@@ -18,6 +18,7 @@
 //   ck_tokpos        byte position of every token (tile scan + document base)
 // G(t) = bytes of the batch's tokens before token t = tile_off[t / 2048] + sub16[t / 16] + the lengths of < 16 tokens.
 #include "jtk_chunk_rules.h"
+#include "jtk_device_prims.h"
 #include "jtk_kernels.h"
 
 namespace {
@@ -27,10 +28,6 @@ constexpr int CK_LONG_CHUNKS = 32;             // documents with more chunks tha
 constexpr int CK_LONG_BLOCKS = 2048;           // persistent workgroups over the long documents
 static_assert(CT == 256 * 8 && CT % 16 == 0, "a tile is 256 lanes x 8 tokens");
 
-__device__ __forceinline__ uint32_t ck_len(const JtkChunkWork& w, int32_t id) {
-    // (ids past the decode table are the pseudo ids of bytes a rank map lacks: one byte each; their documents are refused)
-    return ((uint32_t)id < w.n_ids_table) ? w.tab_off[id + 1] - w.tab_off[id] : 1u;
-}
 __device__ __forceinline__ bool ck_bnd(const JtkChunkWork& w, int32_t id) {
     return (uint32_t)id >= w.n_ids_table || ((w.bnd[(uint32_t)id >> 5] >> ((uint32_t)id & 31)) & 1u);
 }
@@ -45,26 +42,7 @@ __device__ __forceinline__ bool ck_is_long(int64_t n, int64_t N, int64_t ov) {
 __device__ __forceinline__ int64_t ck_G(const JtkChunkWork& w, int64_t x) {
     if (x >= w.n_tok) return w.tile_off[w.n_tiles];
     int64_t v = w.tile_off[x / CT] + w.sub16[x >> 4];
-    for (int64_t y = x & ~(int64_t)15; y < x; y++) v += ck_len(w, w.tokens[y]);
-    return v;
-}
-
-__device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = (uint32_t)__shfl_up((int)v, d);
-        if (lane >= d) v += o;
-    }
-    return v;
-}
-__device__ __forceinline__ uint64_t wave_incl_scan_u64(uint64_t v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t o = __shfl_up(v, d);
-        if (lane >= d) v += o;
-    }
+    for (int64_t y = x & ~(int64_t)15; y < x; y++) v += jtk_tok_len(w.tab_off, w.n_ids_table, w.tokens[y], 1u);
     return v;
 }
 
@@ -160,54 +138,27 @@ __global__ void __launch_bounds__(256) k_ck_long(JtkChunkWork w) {
     }
 }
 
-// Exclusive scan of in[0, n) into out[0, n] (in may be out); one workgroup.  total (may be NULL) = the sum.
+// Exclusive scan of in[0, n) into out[0, n] (in may be out), out[n] = the sum, and *total (may be NULL); one workgroup
+// (jtk_block_scan_array).  hdr != NULL: the chunk count's epilogue, hdr[1] = tok_off[n_docs].
 template <class T>
 __global__ void __launch_bounds__(1024) k_ck_scan(const T* in, int64_t n, int64_t* out, int64_t* total, const int64_t* tok_off,
                                                   int64_t n_docs, int64_t* hdr) {
-    constexpr int PER = 16;
-    __shared__ uint64_t s_wsum[16];
-    __shared__ uint64_t s_base;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    if (tid == 0) s_base = 0;
-    __syncthreads();
-    for (int64_t c0 = 0; c0 < n; c0 += 1024 * PER) {
-        const int64_t i0 = c0 + (int64_t)tid * PER;
-        uint64_t v[PER];
-        uint64_t sum = 0;
-#pragma unroll
-        for (int j = 0; j < PER; j++) { v[j] = (i0 + j < n) ? (uint64_t)in[i0 + j] : 0u; sum += v[j]; }
-        const uint64_t inc = wave_incl_scan_u64(sum);
-        if (lane == 63) s_wsum[wv] = inc;
-        __syncthreads();
-        uint64_t run = s_base + inc - sum;
-        for (int k = 0; k < wv; k++) run += s_wsum[k];
-#pragma unroll
-        for (int j = 0; j < PER; j++) { if (i0 + j < n) out[i0 + j] = (int64_t)run; run += v[j]; }
-        __syncthreads();
-        if (tid == 1023) s_base = run;
-        __syncthreads();
-    }
-    if (tid == 0) {
-        out[n] = (int64_t)s_base;
-        if (total) *total = (int64_t)s_base;
+    const int64_t sum = (int64_t)jtk_block_scan_array(n, [&](int64_t i) { return in[i]; },
+                                                      [&](int64_t i, uint64_t v) { out[i] = (int64_t)v; });
+    if (threadIdx.x == 0) {
+        out[n] = sum;
+        if (total) *total = sum;
         if (hdr) hdr[1] = tok_off[n_docs];
     }
 }
 
 __global__ void __launch_bounds__(256) k_ck_tiles(JtkChunkWork w) {
-    __shared__ uint32_t s_wsum[4];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     const int64_t t0 = (int64_t)blockIdx.x * CT + tid * 8;
-    uint32_t len[8], sum = 0;
-#pragma unroll
-    for (int j = 0; j < 8; j++) { len[j] = (t0 + j < w.n_tok) ? ck_len(w, w.tokens[t0 + j]) : 0u; sum += len[j]; }
-    const uint32_t inc = wave_incl_scan_u32(sum);
-    if (lane == 63) s_wsum[wv] = inc;
-    __syncthreads();
-    uint32_t pre = inc - sum;
-    for (int k = 0; k < wv; k++) pre += s_wsum[k];
+    uint32_t len[8], tile_bytes;
+    const uint32_t pre = jtk_tile_tok_prefix(w.tokens, w.n_tok, t0, w.tab_off, w.n_ids_table, 1u, len, &tile_bytes);
     if ((tid & 1) == 0 && t0 < w.n_tok) w.sub16[t0 >> 4] = pre;           // (t0 of an even lane is a multiple of 16)
-    if (tid == 0) w.tile_bytes[blockIdx.x] = s_wsum[0] + s_wsum[1] + s_wsum[2] + s_wsum[3];
+    if (tid == 0) w.tile_bytes[blockIdx.x] = tile_bytes;
 }
 
 __global__ void __launch_bounds__(256) k_ck_dbase(JtkChunkWork w) {
@@ -253,26 +204,18 @@ __global__ void __launch_bounds__(256) k_ck_rows(JtkChunkWork w, int32_t pad_id,
     }
 }
 
-// the document that holds token t: the last d with tok_off[d] <= t
+// the document that holds token t: the last d in [0, n_docs) with tok_off[d] <= t (tok_off[0] <= t; the empty documents
+// before it share its offset and are passed over)
 __device__ __forceinline__ int64_t ck_doc_of(const JtkChunkWork& w, int64_t t) {
-    int64_t lo = 0, hi = w.n_docs;                                        // tok_off[lo] <= t < tok_off[hi]
-    while (hi - lo > 1) { const int64_t mid = (lo + hi) >> 1; if (w.tok_off[mid] <= t) lo = mid; else hi = mid; }
-    return lo;
+    return jtk_first_gt(w.tok_off, 1, w.n_docs, t) - 1;
 }
 
 __global__ void __launch_bounds__(256) k_ck_tokpos(JtkChunkWork w, int64_t* byte_pos) {
-    __shared__ uint32_t s_wsum[4];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int64_t t0 = (int64_t)blockIdx.x * CT + tid * 8;
-    uint32_t len[8], sum = 0;
-#pragma unroll
-    for (int j = 0; j < 8; j++) { len[j] = (t0 + j < w.n_tok) ? ck_len(w, w.tokens[t0 + j]) : 0u; sum += len[j]; }
-    const uint32_t inc = wave_incl_scan_u32(sum);
-    if (lane == 63) s_wsum[wv] = inc;
-    __syncthreads();
-    if (t0 >= w.n_tok) return;
-    int64_t pos = w.tile_off[blockIdx.x] + (inc - sum);
-    for (int k = 0; k < wv; k++) pos += s_wsum[k];
+    const int64_t t0 = (int64_t)blockIdx.x * CT + threadIdx.x * 8;
+    uint32_t len[8];
+    const uint32_t pre = jtk_tile_tok_prefix(w.tokens, w.n_tok, t0, w.tab_off, w.n_ids_table, 1u, len);
+    if (t0 >= w.n_tok) return;                                            // (behind the prefix: it holds a barrier)
+    int64_t pos = w.tile_off[blockIdx.x] + pre;
     int64_t d = ck_doc_of(w, t0);
     for (int j = 0; j < 8 && t0 + j < w.n_tok; j++) {
         const int64_t t = t0 + j;
@@ -282,12 +225,10 @@ __global__ void __launch_bounds__(256) k_ck_tokpos(JtkChunkWork w, int64_t* byte
     }
 }
 
-unsigned blocks_for(int64_t n, int per) { return (unsigned)((n + per - 1) / per > 0 ? (n + per - 1) / per : 1); }
-
 }  // namespace
 
 void jtk_launch_chunk_count(const JtkChunkWork& w, hipStream_t s) {
-    hipLaunchKernelGGL(k_ck_count_short, dim3(blocks_for(w.n_docs, 256)), dim3(256), 0, s, w);
+    hipLaunchKernelGGL(k_ck_count_short, dim3(jtk_blocks_for(w.n_docs, 256)), dim3(256), 0, s, w);
     hipLaunchKernelGGL(k_ck_long<false>, dim3(CK_LONG_BLOCKS), dim3(256), 0, s, w);
     hipLaunchKernelGGL(k_ck_scan<int64_t>, dim3(1), dim3(1024), 0, s, (const int64_t*)w.chunk_off, w.n_docs, w.chunk_off, &w.hdr[0],
                        w.tok_off, w.n_docs, w.hdr);
@@ -295,21 +236,20 @@ void jtk_launch_chunk_count(const JtkChunkWork& w, hipStream_t s) {
 
 void jtk_launch_chunk_tiles(const JtkChunkWork& w, hipStream_t s) {
     if (w.n_tok > 0) hipLaunchKernelGGL(k_ck_tiles, dim3((unsigned)w.n_tiles), dim3(256), 0, s, w);
-    hipLaunchKernelGGL(k_ck_scan<uint32_t>, dim3(1), dim3(1024), 0, s, (const uint32_t*)w.tile_bytes, w.n_tok > 0 ? w.n_tiles : (int64_t)0,
-                       w.tile_off, (int64_t*)nullptr, (const int64_t*)nullptr, (int64_t)0, (int64_t*)nullptr);
-    if (w.n_docs > 0) hipLaunchKernelGGL(k_ck_dbase, dim3(blocks_for(w.n_docs, 256)), dim3(256), 0, s, w);
+    jtk_launch_scan_u32(w.tile_bytes, w.n_tok > 0 ? w.n_tiles : (int64_t)0, w.tile_off, nullptr, s);
+    if (w.n_docs > 0) hipLaunchKernelGGL(k_ck_dbase, dim3(jtk_blocks_for(w.n_docs, 256)), dim3(256), 0, s, w);
 }
 
 void jtk_launch_chunk_write(const JtkChunkWork& w, hipStream_t s) {
     if (w.n_chunks <= 0) return;
-    hipLaunchKernelGGL(k_ck_write_short, dim3(blocks_for(w.n_docs, 256)), dim3(256), 0, s, w);
+    hipLaunchKernelGGL(k_ck_write_short, dim3(jtk_blocks_for(w.n_docs, 256)), dim3(256), 0, s, w);
     hipLaunchKernelGGL(k_ck_long<true>, dim3(CK_LONG_BLOCKS), dim3(256), 0, s, w);
-    hipLaunchKernelGGL(k_ck_bytes, dim3(blocks_for(w.n_chunks, 256)), dim3(256), 0, s, w);
+    hipLaunchKernelGGL(k_ck_bytes, dim3(jtk_blocks_for(w.n_chunks, 256)), dim3(256), 0, s, w);
 }
 
 void jtk_launch_chunk_rows(const JtkChunkWork& w, int32_t pad_id, int32_t* rows, hipStream_t s) {
     const int64_t total = w.n_chunks * w.N;
-    if (total > 0) hipLaunchKernelGGL(k_ck_rows, dim3(blocks_for(total, 1024)), dim3(256), 0, s, w, pad_id, rows, total);
+    if (total > 0) hipLaunchKernelGGL(k_ck_rows, dim3(jtk_blocks_for(total, 1024)), dim3(256), 0, s, w, pad_id, rows, total);
 }
 
 void jtk_launch_token_offsets(const JtkChunkWork& w, int64_t* byte_pos, hipStream_t s) {
@@ -319,4 +259,8 @@ void jtk_launch_token_offsets(const JtkChunkWork& w, int64_t* byte_pos, hipStrea
 void jtk_launch_scan_i64(int64_t* inout, int64_t n, int64_t* total, hipStream_t s) {
     hipLaunchKernelGGL(k_ck_scan<int64_t>, dim3(1), dim3(1024), 0, s, (const int64_t*)inout, n, inout, total, (const int64_t*)nullptr,
                        (int64_t)0, (int64_t*)nullptr);
+}
+void jtk_launch_scan_u32(const uint32_t* in, int64_t n, int64_t* out, int64_t* total, hipStream_t s) {
+    hipLaunchKernelGGL(k_ck_scan<uint32_t>, dim3(1), dim3(1024), 0, s, in, n, out, total, (const int64_t*)nullptr, (int64_t)0,
+                       (int64_t*)nullptr);
 }

@@ -269,8 +269,10 @@ void jtk_launch_chunk_tiles(const JtkChunkWork& w, hipStream_t s);      // tile 
 void jtk_launch_chunk_write(const JtkChunkWork& w, hipStream_t s);      // records (needs n_chunks and the tiles)
 void jtk_launch_chunk_rows(const JtkChunkWork& w, int32_t pad_id, int32_t* rows, hipStream_t s);
 void jtk_launch_token_offsets(const JtkChunkWork& w, int64_t* byte_pos, hipStream_t s);   // (needs the tiles)
-// exclusive scan of in[0, n) into out[0, n] in place (k_ck_scan, one workgroup); *total (may be NULL) = the sum
+// the one-workgroup exclusive scan (k_ck_scan of jtk_chunk.hip around jtk_block_scan_array): in[0, n) -> out[0, n), the sum
+// to out[n] and to *total (may be NULL).  _i64 scans in place.
 void jtk_launch_scan_i64(int64_t* inout, int64_t n, int64_t* total, hipStream_t s);
+void jtk_launch_scan_u32(const uint32_t* in, int64_t n, int64_t* out, int64_t* total, hipStream_t s);
 // Device-side state of jtk_batch_pack (jtk_pack.hip): the units of the last batch encode packed into rows of L tokens by the
 // rule of jtk_pack_rules.h.  The view's P, SEG, RS, flag and nxt point into the scratch below.
 struct JtkPackWork {

@@ -17,6 +17,7 @@
 
 #include <type_traits>
 
+#include "jtk_device_prims.h"
 #include "jtk_merge_core.h"
 #include "jtk_block_classify.h"
 #include "jtk_split_masks.h"
@@ -49,17 +50,6 @@ __device__ __forceinline__ uint32_t wave_min_u32(uint32_t v) {
     return v;
 }
 
-// inclusive prefix sum across the wave
-__device__ __forceinline__ uint32_t wave_incl_scan(uint32_t v) {
-    const unsigned lane = threadIdx.x & 63u;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = (uint32_t)__shfl_up((int)v, d);
-        if (lane >= (unsigned)d) v += o;
-    }
-    return v;
-}
-
 // ---------------------------------------------------------------------------------------------------
 // mark_docs: docmask bit for every doc_off[d], d = 0..n_docs (the last one is the end sentinel)
 // ---------------------------------------------------------------------------------------------------
@@ -77,15 +67,8 @@ __global__ void __launch_bounds__(256) k_mark_docs(JtkWork w) {
 
 // index of the document containing byte position p (skipping empty documents)
 __device__ int64_t find_doc(const JtkWork& w, int64_t p) {
-    const int64_t* doc_off = w.doc_off;
-    const int64_t n_docs = w.n_docs;
-    p += w.text_base;                            // doc_off holds positions in the whole batch
-    int64_t lo = 0, hi = n_docs;                 // first d with doc_off[d] > p
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (doc_off[mid] > p) hi = mid; else lo = mid + 1;
-    }
-    return lo - 1;
+    // doc_off holds positions in the whole batch; the one before the first d with doc_off[d] > p (-1: p is before all)
+    return jtk_first_gt(w.doc_off, 0, w.n_docs, p + w.text_base) - 1;
 }
 
 // ---------------------------------------------------------------------------------------------------
@@ -492,7 +475,7 @@ __global__ void __launch_bounds__(RES_THREADS) __attribute__((amdgpu_waves_per_e
     int np;
     {
         const uint32_t c = lane < TW ? (uint32_t)__popcll(s_pm[lane]) : 0u;
-        const uint32_t inc = wave_incl_scan(c);
+        const uint32_t inc = jtk_wave_incl_scan(c);
         np = (int)(uint32_t)__shfl((int)inc, 63);
         const uint32_t pre = inc - c;
         for (int wd = wv; wd < TW; wd += RES_WAVES) {
@@ -863,7 +846,7 @@ __device__ __forceinline__ void tiny_bin(const JtkWork& w, const LeanLds& L, uin
         // token counts per tile (as in lean_bin)
         const int64_t tile = have ? pos / T : -1;
         const uint32_t cc = have ? c : 0u;
-        const uint32_t inc = wave_incl_scan(cc);
+        const uint32_t inc = jtk_wave_incl_scan(cc);
         const uint32_t tlo = (uint32_t)tile, thi = (uint32_t)((uint64_t)tile >> 32);
         const uint32_t plo = (uint32_t)__shfl_up((int)tlo, 1), phi = (uint32_t)__shfl_up((int)thi, 1);
         const bool head = lane == 0 || plo != tlo || phi != thi;
@@ -980,7 +963,7 @@ __device__ __forceinline__ void lean_bin(const JtkWork& w, const JtkDeviceTables
         {
             const int64_t tile = have ? pos / T : -1;
             const uint32_t cc = have ? c : 0u;
-            const uint32_t inc = wave_incl_scan(cc);
+            const uint32_t inc = jtk_wave_incl_scan(cc);
             const uint32_t tlo = (uint32_t)tile, thi = (uint32_t)((uint64_t)tile >> 32);
             // (the shuffles are evaluated by ALL lanes, outside the condition: a lane that short-circuits an `||` leaves the
             // wave for the rest of the expression, and its neighbour would read a dead lane)
@@ -1614,7 +1597,7 @@ __global__ void __launch_bounds__(1024) k_tile_scan(JtkWork w) {
     uint32_t v[4];
     uint32_t sum = 0;
     for (int j = 0; j < 4; j++) { v[j] = (i0 + j < w.n_tiles) ? w.tile_tot[i0 + j] : 0u; sum += v[j]; }
-    const uint32_t inc = wave_incl_scan(sum);
+    const uint32_t inc = jtk_wave_incl_scan(sum);
     if (lane == 63) s_wsum[wv] = inc;
     __syncthreads();
     const uint64_t job_before = (uint64_t)*w.job_tokens;      // tokens of the batch's earlier chunks (their scans ran before this one)
@@ -1775,7 +1758,7 @@ __global__ void __launch_bounds__(64) k_pack_tokens(JtkWork w) {
     uint32_t xend = 0;
     const uint32_t x0 = (uint32_t)JTK_PACK_SLOTS + jtk_stage_first_free(total);
     if (has_ext) {
-        const uint32_t inc = wave_incl_scan(over);
+        const uint32_t inc = jtk_wave_incl_scan(over);
         uint32_t xoff, xn;
         jtk_stage_place(total, inc - over, over, &xoff, &xn);
         if (lane >= 8 && lane < 16) s_ext[lane - 8] = lane < 8 + JTK_NBINS_STAGE ? jtk_stage_word(lane - 8, xoff, xn) : 0u;
@@ -1878,7 +1861,7 @@ __global__ void __launch_bounds__(64) k_pack_tokens(JtkWork w) {
                 qe = tinyp ? tiny_word(res5[qi]) : (w.qd[bin] + shard * w.q_cap[bin] + qb)[qi];
                 c = (qe.w >> 24) + 1u;
             } else if (valid && hard && !queued) c = hard_count(w, B + off);        // count in the htok header
-            const uint32_t inc = wave_incl_scan(c);
+            const uint32_t inc = jtk_wave_incl_scan(c);
             pre = run + inc - c;
             run += (uint32_t)__shfl((int)inc, 63);
             if (valid) {
@@ -1993,15 +1976,8 @@ __global__ void __launch_bounds__(256) k_plan_chunks(const int64_t* doc_off, int
                                                      int64_t* out_doc, int64_t* out_off) {
     const int c = (int)(blockIdx.x * blockDim.x + threadIdx.x);
     if (c > n_chunks) return;
-    int64_t lo = 0, hi = n_docs;                              // first d with doc_off[d] >= c * chunk_bytes
-    if (c == n_chunks) lo = n_docs;
-    else {
-        const int64_t target = (int64_t)c * chunk_bytes;
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (doc_off[mid] >= target) hi = mid; else lo = mid + 1;
-        }
-    }
+    // first d with doc_off[d] >= c * chunk_bytes; n_docs for the end entry
+    const int64_t lo = c == n_chunks ? n_docs : jtk_first_ge(doc_off, 0, n_docs, (int64_t)c * chunk_bytes);
     out_doc[c] = lo;
     out_off[c] = doc_off[lo];
 }
@@ -2104,12 +2080,8 @@ __global__ void __launch_bounds__(256) k_flag_unencodable(JtkWork w, uint32_t ps
     if (i >= t1 || (uint32_t)w.tokens[i] < pseudo_base) return;
     // last document of the chunk whose first token is at or before i (empty documents share an offset: the last one with
     // tokens is the one that ends after i)
-    int64_t lo = 0, hi = w.n_docs;                                  // (this chunk's documents) tok_off[lo] <= i < tok_off[hi]
-    while (hi - lo > 1) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (w.tok_off[mid] <= i) lo = mid; else hi = mid;
-    }
-    atomicMin(&w.status[lo], -12 /* JTK_ERR_UNENCODABLE */);
+    const int64_t d = jtk_first_gt(w.tok_off, 1, w.n_docs, i) - 1;  // (this chunk's documents) tok_off[d] <= i < tok_off[d + 1]
+    atomicMin(&w.status[d], -12 /* JTK_ERR_UNENCODABLE */);
     atomicMin(&w.result->worst_status, -12);
 }
 

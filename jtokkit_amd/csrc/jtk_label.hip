@@ -1,7 +1,7 @@
 // jtk_label.hip -- training labels of the packed rows from byte spans of the batch text (jtk_batch_token_spans and
 // jtk_batch_pack_labels in jtk_abi.cpp), by the rule of jtk_label_rules.h.
 //
-//   lb_spans   per tile of 2048 tokens, 8 tokens per lane: the walk of k_ck_tokpos (token byte lengths, wave scan, tile_off and
+//   lb_spans   per tile of 2048 tokens, 8 tokens per lane: the walk of k_ck_tokpos (jtk_tile_tok_prefix, tile_off and
 //              dbase of the chunk work's byte scan), but the positions stay in registers: each lane finds the span cursor of
 //              its first token by one binary search over begin[], moves it forward by galloping for the other seven, and
 //              writes int32 tok_span -- 4 bytes per token, no [n_tokens] int64 array in between.
@@ -9,7 +9,8 @@
 //              cell's source token (jtk_pack_cell_token).  With shift a lane also maps the cell after its fourth, in the same
 //              lane (the lane after it may belong to another tile run, and a row's last cell needs no lookup), and hands every
 //              cell the label of its right neighbour within the segment.
-// Neither kernel shuffles inside a divergent expression: the wave scan of lb_spans runs before any lane leaves.
+// Neither kernel shuffles inside a divergent expression: the tile prefix of lb_spans runs before any lane leaves.
+#include "jtk_device_prims.h"
 #include "jtk_kernels.h"
 
 namespace {
@@ -19,41 +20,18 @@ constexpr int LB_TILE = 1024;         // cells per workgroup step (256 lanes x 4
 constexpr int LB_MAX_BLOCKS = 4096;   // workgroups of lb_pack; each takes a contiguous run of tiles
 static_assert(CT == 256 * 8, "a tile is 256 lanes x 8 tokens");
 
-__device__ __forceinline__ uint32_t lb_len(const JtkChunkWork& w, int32_t id) {
-    return ((uint32_t)id < w.n_ids_table) ? w.tab_off[id + 1] - w.tab_off[id] : 1u;      // (as ck_len of jtk_chunk.hip)
-}
-
-__device__ __forceinline__ uint32_t lb_wave_incl_scan(uint32_t v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = (uint32_t)__shfl_up((int)v, d);
-        if (lane >= d) v += o;
-    }
-    return v;
-}
-
-// the document that holds token t: the last d with tok_off[d] <= t
+// the document that holds token t: the last d in [0, n_docs) with tok_off[d] <= t (as ck_doc_of of jtk_chunk.hip)
 __device__ __forceinline__ int64_t lb_doc_of(const JtkChunkWork& w, int64_t t) {
-    int64_t lo = 0, hi = w.n_docs;                                        // tok_off[lo] <= t < tok_off[hi]
-    while (hi - lo > 1) { const int64_t mid = (lo + hi) >> 1; if (w.tok_off[mid] <= t) lo = mid; else hi = mid; }
-    return lo;
+    return jtk_first_gt(w.tok_off, 1, w.n_docs, t) - 1;
 }
 
 __global__ void __launch_bounds__(256) k_lb_spans(JtkChunkWork w, const int64_t* begin, const int64_t* end, int64_t n_spans,
                                                   int rule, int32_t* tok_span) {
-    __shared__ uint32_t s_wsum[4];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int64_t t0 = (int64_t)blockIdx.x * CT + tid * 8;
-    uint32_t len[8], sum = 0;
-#pragma unroll
-    for (int j = 0; j < 8; j++) { len[j] = (t0 + j < w.n_tok) ? lb_len(w, w.tokens[t0 + j]) : 0u; sum += len[j]; }
-    const uint32_t inc = lb_wave_incl_scan(sum);
-    if (lane == 63) s_wsum[wv] = inc;
-    __syncthreads();
-    if (t0 >= w.n_tok) return;
-    int64_t pos = w.tile_off[blockIdx.x] + (inc - sum);
-    for (int k = 0; k < wv; k++) pos += s_wsum[k];
+    const int64_t t0 = (int64_t)blockIdx.x * CT + threadIdx.x * 8;
+    uint32_t len[8];
+    const uint32_t pre = jtk_tile_tok_prefix(w.tokens, w.n_tok, t0, w.tab_off, w.n_ids_table, 1u, len);
+    if (t0 >= w.n_tok) return;                                            // (behind the prefix: it holds a barrier)
+    int64_t pos = w.tile_off[blockIdx.x] + pre;
     int64_t d = lb_doc_of(w, t0);
     int64_t cur = JTK_LB_FRESH;
     int32_t out[8];

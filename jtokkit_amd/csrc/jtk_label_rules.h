@@ -37,22 +37,14 @@
 #define JTK_LB_ANY 2
 #define JTK_LB_FRESH (-2)       // a span cursor that has not searched yet
 
-// the last i in [lo, hi] with begin[i] <= p, lo when there is none (lo may be -1: begin[-1] is never read)
-JTK_PK_HD int64_t jtk_label_last_le(const int64_t* begin, int64_t lo, int64_t hi, int64_t p) {
-    while (lo < hi) {
-        const int64_t mid = lo + (hi - lo + 1) / 2;
-        if (begin[mid] <= p) lo = mid; else hi = mid - 1;
-    }
-    return lo;
-}
-
 // The cursor k moved to the last span with begin <= p (-1: none).  From JTK_LB_FRESH, or from a span that begins after p, a
-// binary search over all spans; else galloping forward from k.
+// binary search over all spans (jtk_pack_last_le from lo = -1, its answer when there is none: begin[-1] is never read); else
+// galloping forward from k.
 JTK_PK_HD int64_t jtk_label_seek(const int64_t* begin, int64_t n, int64_t k, int64_t p) {
-    if (k < -1 || k >= n || (k >= 0 && begin[k] > p)) return jtk_label_last_le(begin, -1, n - 1, p);
+    if (k < -1 || k >= n || (k >= 0 && begin[k] > p)) return jtk_pack_last_le(begin, -1, n - 1, p);
     int64_t step = 1;
     while (k + step < n && begin[k + step] <= p) { k += step; step *= 2; }
-    return jtk_label_last_le(begin, k, k + step < n ? k + step - 1 : n - 1, p);
+    return jtk_pack_last_le(begin, k, k + step < n ? k + step - 1 : n - 1, p);
 }
 
 // tok_span of the token [p, q); k: the lane's cursor (JTK_LB_FRESH at first)

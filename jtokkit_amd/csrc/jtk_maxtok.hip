@@ -10,6 +10,7 @@
 //   maxtok_gather    the prefixes, back to back, from the caller text at any alignment (wide loads, byte shifts in registers)
 //   maxtok_decide    per chunk, behind run_job's doc_offsets: the last safe piece start from the chunk's piece mask, the
 //                    token bytes before it, the back-off (jtk_maxtok_rules.h), the row; undecided documents go round again
+#include "jtk_device_prims.h"
 #include "jtk_kernels.h"
 #include "jtk_maxtok_rules.h"
 
@@ -18,17 +19,6 @@ namespace {
 constexpr int MT_ITEMS = 4;                   // plan items per thread
 constexpr int MT_BLOCK = 256;
 constexpr int MT_PER_BLOCK = MT_ITEMS * MT_BLOCK;
-
-__device__ __forceinline__ uint32_t mt_tok_len(const JtkMaxTokWork& m, int32_t id) {
-    // (ids past the decode table are the pseudo ids of bytes a rank map lacks: one byte each; their documents are refused)
-    return ((uint32_t)id < m.n_ids_table) ? m.tab_off[id + 1] - m.tab_off[id] : 1u;
-}
-
-__device__ __forceinline__ uint32_t wave_sum_u32(uint32_t v) {
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) v += (uint32_t)__shfl_xor((int)v, d);
-    return v;
-}
 
 __global__ void __launch_bounds__(256) k_mt_check(JtkMaxTokWork m) {
     const int64_t d = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -39,12 +29,7 @@ __global__ void __launch_bounds__(256) k_mt_check(JtkMaxTokWork m) {
 
 // the document holding [p, p + len) whole, or -1 (a literal across two documents flags neither)
 __device__ int64_t mt_doc_of(const JtkMaxTokWork& m, int64_t p, int64_t len) {
-    int64_t lo = 0, hi = m.n_docs;                        // first d with doc_off[d] > p
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (m.doc_off[mid] > p) hi = mid; else lo = mid + 1;
-    }
-    const int64_t d = lo - 1;
+    const int64_t d = jtk_first_gt(m.doc_off, 0, m.n_docs, p) - 1;       // the one before the first d with doc_off[d] > p
     return (d >= 0 && p + len <= m.doc_off[d + 1]) ? d : -1;
 }
 
@@ -132,9 +117,8 @@ __global__ void __launch_bounds__(MT_BLOCK) k_mt_count(JtkMaxTokWork m) {
         int64_t d, p;
         if (mt_item(m, (int64_t)blockIdx.x * MT_PER_BLOCK + (int64_t)k * MT_BLOCK + tid, &d, &p)) { cnt++; bytes += p; }
     }
-    cnt = wave_sum_u32(cnt);
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) bytes += __shfl_xor(bytes, o);
+    cnt = jtk_wave_sum(cnt);
+    bytes = jtk_wave_sum(bytes);
     if (lane == 0) { s_cnt[wv] = cnt; s_bytes[wv] = bytes; }
     __syncthreads();
     if (tid == 0) {
@@ -145,39 +129,21 @@ __global__ void __launch_bounds__(MT_BLOCK) k_mt_count(JtkMaxTokWork m) {
     }
 }
 
-// one workgroup: exclusive scans of the block totals; the round's totals to hdr (and the end of the gather offsets)
+// one workgroup: exclusive scans of the block totals, counts then bytes, into the interleaved blk_base; the round's totals to
+// hdr (and the end of the gather offsets)
 __global__ void __launch_bounds__(1024) k_mt_scan(JtkMaxTokWork m) {
-    __shared__ int64_t s_c[1024], s_b[1024];
-    __shared__ int64_t s_base_c, s_base_b;
-    const int tid = threadIdx.x;
-    if (tid == 0) { s_base_c = 0; s_base_b = 0; }
-    __syncthreads();
-    for (int64_t c0 = 0; c0 < m.n_blk; c0 += 1024) {
-        const int64_t i = c0 + tid;
-        const int64_t vc = i < m.n_blk ? (int64_t)m.blk_cnt[i] : 0, vb = i < m.n_blk ? m.blk_bytes[i] : 0;
-        s_c[tid] = vc; s_b[tid] = vb;
-        __syncthreads();
-        for (int o = 1; o < 1024; o <<= 1) {                  // inclusive Hillis-Steele scan
-            const int64_t ac = tid >= o ? s_c[tid - o] : 0, ab = tid >= o ? s_b[tid - o] : 0;
-            __syncthreads();
-            s_c[tid] += ac; s_b[tid] += ab;
-            __syncthreads();
-        }
-        if (i < m.n_blk) { m.blk_base[2 * i] = s_base_c + s_c[tid] - vc; m.blk_base[2 * i + 1] = s_base_b + s_b[tid] - vb; }
-        __syncthreads();
-        if (tid == 1023) { s_base_c += s_c[1023]; s_base_b += s_b[1023]; }
-        __syncthreads();
-    }
-    if (tid == 0) {
-        m.hdr[0] = *m.bad ? -1 : s_base_c;
-        m.hdr[1] = s_base_b;
-        m.goff[s_base_c] = s_base_b;
+    const int64_t n_act = (int64_t)jtk_block_scan_array(m.n_blk, [&](int64_t i) { return m.blk_cnt[i]; },
+                                                        [&](int64_t i, uint64_t v) { m.blk_base[2 * i] = (int64_t)v; });
+    const int64_t n_bytes = (int64_t)jtk_block_scan_array(m.n_blk, [&](int64_t i) { return m.blk_bytes[i]; },
+                                                          [&](int64_t i, uint64_t v) { m.blk_base[2 * i + 1] = (int64_t)v; });
+    if (threadIdx.x == 0) {
+        m.hdr[0] = *m.bad ? -1 : n_act;
+        m.hdr[1] = n_bytes;
+        m.goff[n_act] = n_bytes;
     }
 }
 
 __global__ void __launch_bounds__(MT_BLOCK) k_mt_place(JtkMaxTokWork m) {
-    __shared__ uint32_t s_c[MT_BLOCK];
-    __shared__ int64_t s_b[MT_BLOCK];
     const int tid = threadIdx.x;
     // thread tid owns items [tid * MT_ITEMS, tid * MT_ITEMS + MT_ITEMS) of the block: slots stay in item order
     const int64_t j0 = (int64_t)blockIdx.x * MT_PER_BLOCK + (int64_t)tid * MT_ITEMS;
@@ -190,17 +156,11 @@ __global__ void __launch_bounds__(MT_BLOCK) k_mt_place(JtkMaxTokWork m) {
         on[k] = mt_item(m, j0 + k, &doc[k], &pb[k]);
         if (on[k]) { cnt++; bytes += pb[k]; }
     }
-    s_c[tid] = cnt; s_b[tid] = bytes;
-    __syncthreads();
-    for (int o = 1; o < MT_BLOCK; o <<= 1) {
-        const uint32_t ac = tid >= o ? s_c[tid - o] : 0u;
-        const int64_t ab = tid >= o ? s_b[tid - o] : 0;
-        __syncthreads();
-        s_c[tid] += ac; s_b[tid] += ab;
-        __syncthreads();
-    }
-    int64_t slot = m.blk_base[2 * blockIdx.x] + s_c[tid] - cnt;
-    int64_t off = m.blk_base[2 * blockIdx.x + 1] + s_b[tid] - bytes;
+    uint32_t c_pre;
+    int64_t b_pre;
+    jtk_block_excl_prefix<MT_BLOCK>(cnt, bytes, &c_pre, &b_pre);
+    int64_t slot = m.blk_base[2 * blockIdx.x] + c_pre;
+    int64_t off = m.blk_base[2 * blockIdx.x + 1] + b_pre;
 #pragma unroll
     for (int k = 0; k < MT_ITEMS; k++) {
         if (!on[k]) continue;
@@ -270,6 +230,8 @@ __global__ void __launch_bounds__(256) k_mt_decide(JtkWork w, JtkMaxTokWork m, i
     const int64_t t0 = w.tok_off[i], n = w.tok_off[i + 1] - t0;
     const int32_t* ids = w.tokens + t0;
     const int64_t mx = m.max_tokens;
+    // (ids past the decode table are the pseudo ids of bytes a rank map lacks: one byte each; their documents are refused)
+    auto tok_len = [&](int64_t j) { return jtk_tok_len(m.tab_off, m.n_ids_table, ids[j], 1u); };
     if (st != 0) {                                        // (the pipeline's status: no tokens, as on the host)
         mt_write_row(m, d, 0, nullptr, lane);
         if (lane == 0) { m.out_kept[d] = 0; m.out_truncated[d] = 0; m.out_status[d] = st; m.again[slot] = 0; }
@@ -278,7 +240,7 @@ __global__ void __launch_bounds__(256) k_mt_decide(JtkWork w, JtkMaxTokWork m, i
     int64_t k = -1, nb = 0;
     if (p == len) {
         k = n < mx ? n : mx;
-        for (int64_t b = 0; b < k; b += 64) nb += wave_sum_u32(b + lane < k ? mt_tok_len(m, ids[b + lane]) : 0u);
+        for (int64_t b = 0; b < k; b += 64) nb += jtk_wave_sum(b + lane < k ? tok_len(b + lane) : 0u);
     } else {
         // the last safe piece start q at or before p - JTK_MAXTOK_MARGIN: 64 mask words per step, backwards
         const int64_t base = g0 - w.text_base;            // the prefix in the chunk's piece mask
@@ -306,7 +268,7 @@ __global__ void __launch_bounds__(256) k_mt_decide(JtkWork w, JtkMaxTokWork m, i
         }
         if (q > 0 && n >= mx) {
             int64_t cum = 0;
-            for (int64_t b = 0; b < mx && cum <= q; b += 64) cum += wave_sum_u32(b + lane < mx ? mt_tok_len(m, ids[b + lane]) : 0u);
+            for (int64_t b = 0; b < mx && cum <= q; b += 64) cum += jtk_wave_sum(b + lane < mx ? tok_len(b + lane) : 0u);
             if (jtk_maxtok_decided(n, mx, cum, q)) { k = mx; nb = cum; }
         }
     }
@@ -315,7 +277,7 @@ __global__ void __launch_bounds__(256) k_mt_decide(JtkWork w, JtkMaxTokWork m, i
         return;
     }
     // the back-off reads the text around the cut from the prefix (every lane the same: uniform loads)
-    const JtkBackoff r = jtk_maxtok_backoff(t, len, k, nb, [&](int64_t j) { return (int64_t)mt_tok_len(m, ids[j]); });
+    const JtkBackoff r = jtk_maxtok_backoff(t, len, k, nb, [&](int64_t j) { return (int64_t)tok_len(j); });
     const int64_t avail = m.gbytes - g0;                 // (the gathered bytes from here on)
     const bool tr = r.ok && jtk_more_units_than(t, r.from, len < avail ? len : avail, r.units);
     mt_write_row(m, d, r.keep, ids, lane);

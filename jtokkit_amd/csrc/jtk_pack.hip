@@ -2,7 +2,7 @@
 // jtk_pack_rules.h: concat (the units one after another, cut every L cells) or whole (next-fit of the units' items), with
 // per-cell positions and flash-attention's varlen segments.
 //
-//   plan, both modes      pk_len          unit length per document -> P, then scan (k_ck_scan of jtk_chunk.hip)   |S| -> hdr[0]
+//   plan, both modes      pk_len          unit length per document -> P, then scan (jtk_launch_scan_i64)   |S| -> hdr[0]
 //   plan, concat          pk_cat_count    rows touched by each unit (arithmetic on P), longest segment -> SEG, scan
 //   plan, whole           pk_next         nxt(d) per unit (binary search over P) = up[0]; flag = HEAD at the first unit
 //                         pk_lift x K-1   up[k][d] = up[k-1][up[k-1][d]]: the head 2^k groups on
@@ -19,6 +19,7 @@
 //                                         holds a segment's first cell.
 // Scratch per document: P, SEG, RS (8 B each), flag (1 B), and the lifting table, 4 * K bytes, K = ceil(log2(n + 1)).  Every
 // round is a launch of its own: no data passes between workgroups inside one launch.
+#include "jtk_device_prims.h"
 #include "jtk_kernels.h"
 
 namespace {
@@ -150,29 +151,27 @@ __global__ void __launch_bounds__(256) k_pk_write(JtkPackWork w, int32_t pad_id,
     }
 }
 
-unsigned blocks_for(int64_t n, int per) { return (unsigned)((n + per - 1) / per > 0 ? (n + per - 1) / per : 1); }
-
 }  // namespace
 
 void jtk_launch_pack_plan(const JtkPackWork& w, hipStream_t s) {
     const int64_t n = w.v.n;
-    if (n > 0) hipLaunchKernelGGL(k_pk_len, dim3(blocks_for(n, 256)), dim3(256), 0, s, w);
+    if (n > 0) hipLaunchKernelGGL(k_pk_len, dim3(jtk_blocks_for(n, 256)), dim3(256), 0, s, w);
     jtk_launch_scan_i64(w.P, n, &w.hdr[0], s);
     if (!w.v.whole) {
-        if (n > 0) hipLaunchKernelGGL(k_pk_cat_count, dim3(blocks_for(n, 256)), dim3(256), 0, s, w);
+        if (n > 0) hipLaunchKernelGGL(k_pk_cat_count, dim3(jtk_blocks_for(n, 256)), dim3(256), 0, s, w);
         jtk_launch_scan_i64(w.SEG, n, &w.hdr[1], s);
         return;
     }
     const size_t stride = (size_t)n + 1;
-    hipLaunchKernelGGL(k_pk_next, dim3(blocks_for(n + 1, 256)), dim3(256), 0, s, w);
+    hipLaunchKernelGGL(k_pk_next, dim3(jtk_blocks_for(n + 1, 256)), dim3(256), 0, s, w);
     if (n > 0) {
         for (int k = 1; k < w.K; k++)
-            hipLaunchKernelGGL(k_pk_lift, dim3(blocks_for(n + 1, 256)), dim3(256), 0, s, (const int32_t*)(w.up + (k - 1) * stride),
+            hipLaunchKernelGGL(k_pk_lift, dim3(jtk_blocks_for(n + 1, 256)), dim3(256), 0, s, (const int32_t*)(w.up + (k - 1) * stride),
                                w.up + k * stride, n);
         for (int k = w.K - 1; k >= 0; k--)
-            hipLaunchKernelGGL(k_pk_mark, dim3(blocks_for(n, 256)), dim3(256), 0, s, (const int32_t*)(w.up + k * stride), w.flag, n);
-        hipLaunchKernelGGL(k_pk_groups, dim3(blocks_for(n, 256)), dim3(256), 0, s, w);
-        hipLaunchKernelGGL(k_pk_whole_count, dim3(blocks_for(n, 256)), dim3(256), 0, s, w);
+            hipLaunchKernelGGL(k_pk_mark, dim3(jtk_blocks_for(n, 256)), dim3(256), 0, s, (const int32_t*)(w.up + k * stride), w.flag, n);
+        hipLaunchKernelGGL(k_pk_groups, dim3(jtk_blocks_for(n, 256)), dim3(256), 0, s, w);
+        hipLaunchKernelGGL(k_pk_whole_count, dim3(jtk_blocks_for(n, 256)), dim3(256), 0, s, w);
     }
     jtk_launch_scan_i64(w.RS, n, &w.hdr[2], s);
     jtk_launch_scan_i64(w.SEG, n, &w.hdr[1], s);

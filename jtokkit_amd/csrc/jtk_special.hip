@@ -6,7 +6,7 @@
 //   sp_find      one lane per 16 bytes (a workgroup per JTK_SPECIAL_BLOCK): candidate bytes from the first-byte bitmap, a
 //                ballot skips the waves without one; per candidate the longest allowed literal that ends inside its document,
 //                and (encode()) whether a literal outside the allowed set matches there (atomicMin of the document's status)
-//   scan         exclusive scan of the per-workgroup counts (one workgroup) -> hdr[0] = candidates, read by the host
+//   scan         exclusive scan of the per-workgroup counts (jtk_launch_scan_i64) -> hdr[0] = candidates, read by the host
 //   sp_find      again, writing the candidates in position order (workgroup base + lane scan)
 //   sp_resolve   one lane per candidate: kept for certain, or part of a chain
 //   sp_walk      one lane per chain: the greedy walk from the certain candidate before it
@@ -18,6 +18,7 @@
 //   scan         exclusive scan of the counts
 //   sp_offsets   one lane per document: tok_off, worst status, token total
 //   sp_gather    16 output tokens per lane: segment ids copied, special ids written
+#include "jtk_device_prims.h"
 #include "jtk_kernels.h"
 #include "jtk_special_rules.h"
 
@@ -28,34 +29,10 @@ static_assert(FT * 16 == JTK_SPECIAL_BLOCK, "a find workgroup covers JTK_SPECIAL
 constexpr int GT = 256, GPER = 16;         // gather: lanes per workgroup, output tokens per lane
 constexpr int GATHER_BLOCKS_MAX = 65536;
 
-__device__ __forceinline__ uint32_t sp_wave_incl_scan(uint32_t v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint32_t o = (uint32_t)__shfl_up((int)v, d);
-        if (lane >= d) v += o;
-    }
-    return v;
-}
-__device__ __forceinline__ uint64_t sp_wave_incl_scan64(uint64_t v) {
-    const int lane = threadIdx.x & 63;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const uint64_t o = __shfl_up(v, d);
-        if (lane >= d) v += o;
-    }
-    return v;
-}
-
 // the document that holds byte p (empty documents skipped); clamped to a valid index, so that bad offsets are never followed
 // out of range (the call then discards the find pass)
 __device__ __forceinline__ int64_t sp_find_doc(const JtkSpecialWork& w, int64_t p) {
-    int64_t lo = 0, hi = w.n_docs + 1;                     // first k with doc_off[k] > p
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (w.doc_off[mid] > p) hi = mid; else lo = mid + 1;
-    }
-    int64_t d = lo - 1;
+    int64_t d = jtk_first_gt(w.doc_off, 0, w.n_docs + 1, p) - 1;      // the one before the first k with doc_off[k] > p
     if (d < 0) d = 0;
     if (d > w.n_docs - 1) d = w.n_docs - 1;
     return d;
@@ -87,8 +64,7 @@ __device__ __forceinline__ bool sp_at(const JtkSpecialWork& w, int64_t p, int* l
 template <bool WRITE>
 __global__ void __launch_bounds__(FT) k_sp_find(JtkSpecialWork w) {
     __shared__ uint32_t s_first[8];
-    __shared__ uint32_t s_wsum[FT / 64];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     if (tid < 8) s_first[tid] = w.first[tid];
     __syncthreads();
     const int64_t p0 = (int64_t)blockIdx.x * JTK_SPECIAL_BLOCK + (int64_t)tid * 16;
@@ -122,15 +98,13 @@ __global__ void __launch_bounds__(FT) k_sp_find(JtkSpecialWork w) {
             }
         }
     }
-    const uint32_t inc = sp_wave_incl_scan(n_here);
-    if (lane == 63) s_wsum[wv] = inc;
-    __syncthreads();
+    uint32_t n_blk_here;
+    const uint32_t pre = jtk_block_excl_prefix<FT>(n_here, &n_blk_here);
     if (!WRITE) {
-        if (tid == 0) w.blk[blockIdx.x] = (int64_t)(s_wsum[0] + s_wsum[1] + s_wsum[2] + s_wsum[3]);
+        if (tid == 0) w.blk[blockIdx.x] = (int64_t)n_blk_here;
         return;
     }
-    int64_t idx = w.blk[blockIdx.x] + (int64_t)(inc - n_here);
-    for (int k = 0; k < wv; k++) idx += s_wsum[k];
+    int64_t idx = w.blk[blockIdx.x] + (int64_t)pre;
     for (uint32_t m = found; m; idx++) {
         const int j = __builtin_ctz(m);
         m &= m - 1;
@@ -143,37 +117,6 @@ __global__ void __launch_bounds__(FT) k_sp_find(JtkSpecialWork w) {
         w.cand_len[idx] = len;
         w.cand_id[idx] = w.lit_id[lit];
         w.cand_doc[idx] = d;
-    }
-}
-
-// Exclusive scan of a[0, n) in place, a[n] = the sum (and *total); one workgroup.
-__global__ void __launch_bounds__(1024) k_sp_scan(int64_t* a, int64_t n, int64_t* total) {
-    constexpr int PER = 16;
-    __shared__ uint64_t s_wsum[16];
-    __shared__ uint64_t s_base;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    if (tid == 0) s_base = 0;
-    __syncthreads();
-    for (int64_t c0 = 0; c0 < n; c0 += 1024 * PER) {
-        const int64_t i0 = c0 + (int64_t)tid * PER;
-        uint64_t v[PER];
-        uint64_t sum = 0;
-#pragma unroll
-        for (int j = 0; j < PER; j++) { v[j] = (i0 + j < n) ? (uint64_t)a[i0 + j] : 0u; sum += v[j]; }
-        const uint64_t inc = sp_wave_incl_scan64(sum);
-        if (lane == 63) s_wsum[wv] = inc;
-        __syncthreads();
-        uint64_t run = s_base + inc - sum;
-        for (int k = 0; k < wv; k++) run += s_wsum[k];
-#pragma unroll
-        for (int j = 0; j < PER; j++) { if (i0 + j < n) a[i0 + j] = (int64_t)run; run += v[j]; }
-        __syncthreads();
-        if (tid == 1023) s_base = run;
-        __syncthreads();
-    }
-    if (tid == 0) {
-        a[n] = (int64_t)s_base;
-        if (total) *total = (int64_t)s_base;
     }
 }
 
@@ -202,12 +145,7 @@ __global__ void __launch_bounds__(256) k_sp_docs(JtkSpecialWork w) {
     if (d > w.n_docs) return;
     if (d == w.n_docs) { w.sub_off[w.n_sub] = w.doc_off[w.n_docs]; return; }
     const int64_t q = w.doc_off[d];
-    int64_t lo = 0, hi = w.n_cand;                         // candidates before the document
-    while (lo < hi) {
-        const int64_t mid = (lo + hi) >> 1;
-        if (w.cand_pos[mid] < q) lo = mid + 1; else hi = mid;
-    }
-    const int64_t f = d + 2 * lo;
+    const int64_t f = d + 2 * jtk_first_ge(w.cand_pos, 0, w.n_cand, q);   // (the candidates before the document: two slots each)
     w.doc_first[d] = f;
     w.sub_off[f] = q;
     w.sub_lit[f] = -1;
@@ -271,15 +209,9 @@ __global__ void __launch_bounds__(256) k_sp_offsets(JtkSpecialWork w) {
 // next token lies past it.  16 consecutive tokens per lane with a search each took 6.4 ms on the headline corpus, this 2.9)
 __global__ void __launch_bounds__(GT) k_sp_gather(JtkSpecialWork w) {
     const int64_t total = w.cnt[w.n_sub];
-    // the sub-document that holds output token t, searched from lo: last k in [lo - 1, n_sub) with cnt[k] <= t
-    auto locate = [&](int64_t lo, int64_t t) {
-        int64_t hi = w.n_sub;                              // first k with cnt[k] > t (cnt[n_sub] = total > t)
-        while (lo < hi) {
-            const int64_t mid = (lo + hi) >> 1;
-            if (w.cnt[mid] > t) hi = mid; else lo = mid + 1;
-        }
-        return lo - 1;
-    };
+    // the sub-document that holds output token t, searched from lo: last k in [lo - 1, n_sub) with cnt[k] <= t, the one before
+    // the first k with cnt[k] > t (cnt[n_sub] = total > t)
+    auto locate = [&](int64_t lo, int64_t t) { return jtk_first_gt(w.cnt, lo, w.n_sub, t) - 1; };
     for (int64_t base = (int64_t)blockIdx.x * GT * GPER; base < total; base += (int64_t)gridDim.x * GT * GPER) {
         int64_t j = -1;
         for (int k = 0; k < GPER; k++) {
@@ -292,30 +224,28 @@ __global__ void __launch_bounds__(GT) k_sp_gather(JtkSpecialWork w) {
     }
 }
 
-inline unsigned blocks_for(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
-
 }  // namespace
 
 void jtk_launch_special_find(const JtkSpecialWork& w, hipStream_t s) {
-    hipLaunchKernelGGL(k_sp_check, dim3(blocks_for(w.n_docs + 1, 256)), dim3(256), 0, s, w);
+    hipLaunchKernelGGL(k_sp_check, dim3(jtk_blocks_for(w.n_docs + 1, 256)), dim3(256), 0, s, w);
     if (w.n_blk > 0 && w.n_docs > 0) hipLaunchKernelGGL(k_sp_find<false>, dim3((unsigned)w.n_blk), dim3(FT), 0, s, w);
     else if (w.n_blk > 0) (void)hipMemsetAsync(w.blk, 0, (size_t)w.n_blk * 8, s);
-    hipLaunchKernelGGL(k_sp_scan, dim3(1), dim3(1024), 0, s, w.blk, w.n_blk, &w.hdr[0]);
+    jtk_launch_scan_i64(w.blk, w.n_blk, &w.hdr[0], s);
 }
 
 void jtk_launch_special_write(const JtkSpecialWork& w, hipStream_t s) {
     hipLaunchKernelGGL(k_sp_find<true>, dim3((unsigned)w.n_blk), dim3(FT), 0, s, w);
-    hipLaunchKernelGGL(k_sp_resolve, dim3(blocks_for(w.n_cand, 256)), dim3(256), 0, s, w);
-    hipLaunchKernelGGL(k_sp_walk, dim3(blocks_for(w.n_cand, 256)), dim3(256), 0, s, w);
-    hipLaunchKernelGGL(k_sp_docs, dim3(blocks_for(w.n_docs + 1, 256)), dim3(256), 0, s, w);
-    hipLaunchKernelGGL(k_sp_subs, dim3(blocks_for(w.n_cand, 256)), dim3(256), 0, s, w);
+    hipLaunchKernelGGL(k_sp_resolve, dim3(jtk_blocks_for(w.n_cand, 256)), dim3(256), 0, s, w);
+    hipLaunchKernelGGL(k_sp_walk, dim3(jtk_blocks_for(w.n_cand, 256)), dim3(256), 0, s, w);
+    hipLaunchKernelGGL(k_sp_docs, dim3(jtk_blocks_for(w.n_docs + 1, 256)), dim3(256), 0, s, w);
+    hipLaunchKernelGGL(k_sp_subs, dim3(jtk_blocks_for(w.n_cand, 256)), dim3(256), 0, s, w);
 }
 
 void jtk_launch_special_stitch(const JtkSpecialWork& w, hipStream_t s) {
-    hipLaunchKernelGGL(k_sp_status, dim3(blocks_for(w.n_sub, 256)), dim3(256), 0, s, w);
-    hipLaunchKernelGGL(k_sp_count, dim3(blocks_for(w.n_sub, 256)), dim3(256), 0, s, w);
-    hipLaunchKernelGGL(k_sp_scan, dim3(1), dim3(1024), 0, s, w.cnt, w.n_sub, (int64_t*)nullptr);
-    hipLaunchKernelGGL(k_sp_offsets, dim3(blocks_for(w.n_docs + 1, 256)), dim3(256), 0, s, w);
+    hipLaunchKernelGGL(k_sp_status, dim3(jtk_blocks_for(w.n_sub, 256)), dim3(256), 0, s, w);
+    hipLaunchKernelGGL(k_sp_count, dim3(jtk_blocks_for(w.n_sub, 256)), dim3(256), 0, s, w);
+    jtk_launch_scan_i64(w.cnt, w.n_sub, nullptr, s);
+    hipLaunchKernelGGL(k_sp_offsets, dim3(jtk_blocks_for(w.n_docs + 1, 256)), dim3(256), 0, s, w);
     if (!w.count_only) {
         int64_t g = w.n_bytes / (4 * GT * GPER) + 1;       // (about one token per 4 bytes; the loop takes any total)
         if (g > GATHER_BLOCKS_MAX) g = GATHER_BLOCKS_MAX;

@@ -298,8 +298,8 @@ def test_batch_decode_unknown_and_special_ids(jt):
 
 def test_batch_decode_full_size_round_trip(jt):
     """cfg-2-sized corpus: device decode of the device encode, document by document == the input bytes; mixed-script
-    corpus likewise.  The english corpus has more than 4,096 tiles, so it reaches the second iteration of k_dec_scan; both
-    corpora run the staged path of k_dec_scatter on natural text (no tile of theirs exceeds 7 KB, so none takes the direct
+    corpus likewise.  The english corpus has more than 4,096 tiles, which is still one step of the shared one-workgroup scan
+    (16,384 tiles per step; tests/test_scan_edges_gpu.py takes decode through the second step); both corpora run the staged path of k_dec_scatter on natural text (no tile of theirs exceeds 7 KB, so none takes the direct
     path past the 16 KB LDS stage: tests/test_decode_gpu.py builds those)."""
     from jtokkit_amd import corpus
     enc = jt.get_encoding("cl100k_base")
