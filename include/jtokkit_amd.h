@@ -443,6 +443,42 @@ int jtk_batch_decode_fetch(jtk_batch* b, uint8_t* out, int64_t out_cap, int64_t*
 /* Device pointers of the last decode (valid until the next decode on this batch). */
 int jtk_batch_decode_device_result(jtk_batch* b, const uint8_t** d_out, const int64_t** d_byte_off, const int32_t** d_status);
 
+/* ---- decode of an id matrix on the device --------------------------------------------------------------
+ * Replaces a loop of Encoding.decodeBytes(List<Integer>) (GptBytePairEncoding.java:137-151, 302-314) over the rows of a matrix
+ * of token ids, as a model's generate() or this library's padded rows (jtk_batch_encode_device_max_tokens, jtk_batch_chunk_rows)
+ * hand them out: n_rows x width ids of id_bytes (4 or 8) bytes each, signed, row r starting at element r * row_stride
+ * (row_stride >= width); the pointer is aligned to id_bytes, nothing more.  For row r (the rule is jtk_decode_rows_rules.h):
+ *   window  [b, e) = begin[r] / end[r] clamped into [0, width]; 0 and width where the array is NULL; empty when e <= b.
+ *   stop    s = the first column in [b, e) that holds one of the n_stop (<= JTK_DECODE_MAX_STOP_IDS) stop ids.  The row ends
+ *           at e' = s, or at s + 1 with JTK_DECODE_KEEP_STOP; without such a column e' = e.  Stop ids left of b are not seen.
+ *           The stop test comes before the pad test: a pad that is a stop id ends the row.
+ *   cells   cell c contributes the byte string of its id when b <= c < e' and not (JTK_DECODE_SKIP_PAD and id == pad_id).
+ *           A contributing cell whose id has no entry (negative, at or above the table, a hole, any 64-bit value outside
+ *           int32: 2^32 + id is not id) contributes nothing and gives its row, and no other, JTK_ERR_UNKNOWN_TOKEN (:313).
+ *           A skipped pad, a cell outside [b, e') and a stop id that is not kept never do.
+ *   result  as a flat decode's, read with jtk_batch_decode_fetch / jtk_batch_decode_device_result with n_seqs = n_rows: the
+ *           rows' bytes back to back, byte_off[n_rows + 1], status[n_rows].  cell_byte[n_rows * width] (optional, dense):
+ *           the output position of the first byte of cell (r, c); for a cell without bytes, where the next byte of the matrix
+ *           goes -- so cell_byte never decreases, and cell_byte[r * width] == byte_off[r] when b == 0.
+ * Without stop ids, begin, end and JTK_DECODE_SKIP_PAD a row decodes exactly as jtk_batch_decode_device decodes it as a list.
+ * Both calls synchronise as jtk_batch_decode_device does (once for the size of the output, once at the end) and leave the
+ * result on the device; *n_bytes receives the total.  n_rows == 0 and width == 0 are valid (empty rows).  stop_ids is a host
+ * array in both.  JTK_ERR_INVALID_ARGUMENT, before any device work: id_bytes not 4 or 8, row_stride < width, a negative size,
+ * n_stop outside 0..JTK_DECODE_MAX_STOP_IDS, n_stop > 0 with stop_ids NULL, unknown flag bits, rows NULL with cells.
+ * jtk_batch_decode_rows takes the matrix, begin, end and cell_byte_or_null in host memory. */
+enum { JTK_DECODE_MAX_STOP_IDS = 8 };
+enum {
+    JTK_DECODE_SKIP_PAD = 1u,     /* cells that hold pad_id contribute nothing (and are never unknown) */
+    JTK_DECODE_KEEP_STOP = 2u     /* the first stop id of a row is decoded too */
+};
+int jtk_batch_decode_rows_device(jtk_batch* b, const void* d_rows, int id_bytes, int64_t n_rows, int64_t width, int64_t row_stride,
+                                 const int64_t* d_begin_or_null, const int64_t* d_end_or_null, int64_t pad_id,
+                                 const int64_t* stop_ids, int n_stop, uint32_t flags, int64_t* d_cell_byte_or_null,
+                                 void* stream_or_null, int64_t* n_bytes);
+int jtk_batch_decode_rows(jtk_batch* b, const void* rows, int id_bytes, int64_t n_rows, int64_t width, int64_t row_stride,
+                          const int64_t* begin_or_null, const int64_t* end_or_null, int64_t pad_id, const int64_t* stop_ids,
+                          int n_stop, uint32_t flags, int64_t* cell_byte_or_null, int64_t* n_bytes);
+
 /* ---- per-call service: many caller threads, one device batch at a time -------------------------------------------
  * The reference is called per document from many threads (api/Encoding.java; its benchmark is one task per document on a
  * pool of 1..64 threads, benchmark/.../AbstractMultiThreadedBenchmark.java:35-45).  A jtk_service coalesces such callers:

@@ -16,6 +16,7 @@
 #include "../../include/jtokkit_amd.h"
 #include "jtk_chunk_rules.h"
 #include "jtk_compact_rules.h"
+#include "jtk_decode_rows_rules.h"
 #include "jtk_kernels.h"
 #include "jtk_maxtok_rules.h"
 #include "jtk_tables.h"
@@ -140,6 +141,7 @@ struct jtk_batch {
     DevBuf cp_stage;
     // batch decode (jtk_batch_decode*)
     DevBuf dec_in_ids, dec_in_off, dec_zero, dec_tile, dec_pre, dec_out, dec_byte_off;
+    DevBuf dec_first, dec_in_win, dec_cell;   // jtk_batch_decode_rows*: first stop column per row | host begin, end | cell_byte for the host
     DevBuf trunc_kept, trunc_flag;   // jtk_batch_truncate
     DevBuf mt_scratch, mt_gather;    // jtk_batch_encode_device_max_tokens: per-document state of the rounds | the gathered prefixes
     int64_t* h_mt = nullptr; size_t h_mt_cap = 0;   // pinned: the round's (open documents, gathered bytes)
@@ -432,7 +434,7 @@ void jtk_batch_destroy(jtk_batch* b) {
         if (cs.stream) (void)hipStreamDestroy(cs.stream);
     }
     DevBuf* bufs[] = {&b->in_text, &b->in_off, &b->in_pieces, &b->out, &b->plan, &b->dec_in_ids, &b->dec_in_off,
-                      &b->dec_zero, &b->dec_tile, &b->dec_pre, &b->dec_out, &b->dec_byte_off, &b->trunc_kept, &b->trunc_flag,
+                      &b->dec_zero, &b->dec_tile, &b->dec_pre, &b->dec_out, &b->dec_byte_off, &b->dec_first, &b->dec_in_win, &b->dec_cell, &b->trunc_kept, &b->trunc_flag,
                       &b->mt_scratch, &b->mt_gather, &b->ck_scratch, &b->ck_tiles, &b->ck_rec, &b->pk_scratch, &b->sp_lits, &b->sp_find,
                       &b->sp_cand, &b->sp_out};
     for (DevBuf* d : bufs) d->release();
@@ -1453,6 +1455,108 @@ int jtk_batch_decode_device_result(jtk_batch* b, const uint8_t** d_out, const in
     if (d_out) *d_out = b->dwork.out;
     if (d_byte_off) *d_byte_off = b->dwork.byte_off;
     if (d_status) *d_status = b->dwork.status;
+    return JTK_OK;
+}
+
+// ---- decode of an id matrix (jtk_decode_rows.hip) -----------------------------------------------------
+static_assert(JTK_DECODE_MAX_STOP_IDS == JTK_DR_MAX_STOP, "the rule header holds as many stop ids as the ABI takes");
+
+// the argument checks both entries share; *n_cells = n_rows * width
+static int decode_rows_args(jtk_batch* b, const void* rows, int id_bytes, int64_t n_rows, int64_t width, int64_t row_stride,
+                            const int64_t* stop_ids, int n_stop, uint32_t flags, int64_t* n_cells) {
+    if (!b) return fail(JTK_ERR_INVALID_ARGUMENT, "batch is NULL");
+    if (id_bytes != 4 && id_bytes != 8) return fail(JTK_ERR_INVALID_ARGUMENT, "id_bytes must be 4 or 8");
+    if (n_rows < 0 || width < 0 || row_stride < 0) return fail(JTK_ERR_INVALID_ARGUMENT, "negative size");
+    if (row_stride < width) return fail(JTK_ERR_INVALID_ARGUMENT, "row_stride is smaller than width");
+    if (n_stop < 0 || n_stop > JTK_DECODE_MAX_STOP_IDS) return fail(JTK_ERR_INVALID_ARGUMENT, "n_stop must be 0..JTK_DECODE_MAX_STOP_IDS");
+    if (n_stop > 0 && !stop_ids) return fail(JTK_ERR_INVALID_ARGUMENT, "stop_ids is NULL");
+    if (flags & ~(uint32_t)(JTK_DECODE_SKIP_PAD | JTK_DECODE_KEEP_STOP)) return fail(JTK_ERR_INVALID_ARGUMENT, "unknown flag bits");
+    const int64_t lim = (int64_t)1 << 58;                              // (element and byte counts stay far inside 64 bits)
+    if (n_rows > 0 && row_stride > lim / n_rows) return fail(JTK_ERR_INVALID_ARGUMENT, "matrix too large");
+    *n_cells = n_rows * width;
+    if (*n_cells / JTK_DEC_TILE >= ((int64_t)1 << 31) - 1) return fail(JTK_ERR_INVALID_ARGUMENT, "matrix too large");
+    if (*n_cells > 0 && !rows) return fail(JTK_ERR_INVALID_ARGUMENT, "rows is NULL");
+    return JTK_OK;
+}
+
+int jtk_batch_decode_rows_device(jtk_batch* b, const void* d_rows, int id_bytes, int64_t n_rows, int64_t width, int64_t row_stride,
+                                 const int64_t* d_begin_or_null, const int64_t* d_end_or_null, int64_t pad_id,
+                                 const int64_t* stop_ids, int n_stop, uint32_t flags, int64_t* d_cell_byte_or_null,
+                                 void* stream_or_null, int64_t* n_bytes) {
+    int64_t n_cells = 0;
+    int rc;
+    if ((rc = decode_rows_args(b, d_rows, id_bytes, n_rows, width, row_stride, stop_ids, n_stop, flags, &n_cells))) return rc;
+    const jtk_encoding* enc = b->enc;
+    HIP_TRY(hipSetDevice(enc->device));
+    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    JtkDecodeRowsWork w{};
+    w.rows = d_rows; w.id_bytes = id_bytes; w.n_rows = n_rows; w.width = width; w.row_stride = row_stride; w.n_cells = n_cells;
+    w.n_tiles = (n_cells + JTK_DEC_TILE - 1) / JTK_DEC_TILE;
+    w.begin = d_begin_or_null; w.end = d_end_or_null;
+    w.rule.pad_id = pad_id; w.rule.n_stop = n_stop;
+    for (int k = 0; k < n_stop; k++) w.rule.stop[k] = stop_ids[k];
+    w.rule.skip_pad = (flags & JTK_DECODE_SKIP_PAD) != 0; w.rule.keep_stop = (flags & JTK_DECODE_KEEP_STOP) != 0;
+    w.tab_off = (const uint32_t*)enc->dec_off.p; w.tab_blob = (const uint8_t*)enc->dec_blob.p; w.n_ids_table = enc->n_ids_table;
+    const size_t nt = (size_t)(w.n_tiles > 0 ? w.n_tiles : 1);
+    const size_t status_bytes = align_up((size_t)(n_rows > 0 ? n_rows : 1) * 4, 16);
+    const size_t zero_bytes = status_bytes + 16;
+    if ((rc = b->dec_zero.ensure(zero_bytes)) || (rc = b->dec_tile.ensure(nt * 4 + (nt + 1) * 8 + 16)) ||
+        (rc = b->dec_byte_off.ensure(((size_t)n_rows + 1) * 8)) || (n_stop > 0 && (rc = b->dec_first.ensure((size_t)(n_rows > 0 ? n_rows : 1) * 8))))
+        return rc;
+    uint8_t* z = (uint8_t*)b->dec_zero.p;
+    w.status = (int32_t*)z;
+    w.total = (int64_t*)(z + status_bytes);
+    w.tile_off = (int64_t*)b->dec_tile.p;
+    w.tile_bytes = (uint32_t*)((uint8_t*)b->dec_tile.p + (nt + 1) * 8);
+    w.byte_off = (int64_t*)b->dec_byte_off.p;
+    w.cell_byte = d_cell_byte_or_null;
+    w.first_stop = n_stop > 0 ? (unsigned long long*)b->dec_first.p : nullptr;
+    // phase 1: sizes (the output is allocated once they are known)
+    b->have_decode = false;
+    HIP_TRY(hipMemsetAsync(z, 0, zero_bytes, s));
+    int64_t total = 0;
+    if (n_cells > 0) {
+        if (w.first_stop) HIP_TRY(hipMemsetAsync(w.first_stop, 0xFF, (size_t)n_rows * 8, s));      // JTK_DR_NO_STOP
+        jtk_launch_decode_rows_count(w, s);
+        HIP_TRY(hipMemcpyAsync(&total, w.total, 8, hipMemcpyDeviceToHost, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    if ((rc = b->dec_out.ensure((size_t)total + 64))) return rc;
+    w.out = (uint8_t*)b->dec_out.p;
+    // phase 2: bytes, per-row offsets, per-cell offsets (a matrix without cells: every row is empty)
+    if (n_cells > 0) jtk_launch_decode_rows_scatter(w, s);
+    else HIP_TRY(hipMemsetAsync(w.byte_off, 0, ((size_t)n_rows + 1) * 8, s));
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));
+    // the result is read as a flat decode's: jtk_batch_decode_fetch / jtk_batch_decode_device_result with n_seqs = n_rows
+    b->dwork.n_seqs = n_rows; b->dwork.out = w.out; b->dwork.byte_off = w.byte_off; b->dwork.status = w.status;
+    b->dec_total = total;
+    b->have_decode = true;
+    if (n_bytes) *n_bytes = total;
+    return JTK_OK;
+}
+
+int jtk_batch_decode_rows(jtk_batch* b, const void* rows, int id_bytes, int64_t n_rows, int64_t width, int64_t row_stride,
+                          const int64_t* begin_or_null, const int64_t* end_or_null, int64_t pad_id, const int64_t* stop_ids,
+                          int n_stop, uint32_t flags, int64_t* cell_byte_or_null, int64_t* n_bytes) {
+    int64_t n_cells = 0;
+    int rc;
+    if ((rc = decode_rows_args(b, rows, id_bytes, n_rows, width, row_stride, stop_ids, n_stop, flags, &n_cells))) return rc;
+    HIP_TRY(hipSetDevice(b->enc->device));
+    const size_t n_elem = n_cells > 0 ? (size_t)(n_rows - 1) * (size_t)row_stride + (size_t)width : 0;   // the last row's tail is not read
+    const size_t row_bytes = (size_t)(n_rows > 0 ? n_rows : 1) * 8;
+    if ((rc = b->dec_in_ids.ensure(n_elem * (size_t)id_bytes + 64)) || (rc = b->dec_in_win.ensure(2 * row_bytes)) ||
+        (cell_byte_or_null && (rc = b->dec_cell.ensure((size_t)n_cells * 8 + 8))))
+        return rc;
+    int64_t* d_begin = begin_or_null ? (int64_t*)b->dec_in_win.p : nullptr;
+    int64_t* d_end = end_or_null ? (int64_t*)((uint8_t*)b->dec_in_win.p + row_bytes) : nullptr;
+    if (n_elem > 0) HIP_TRY(hipMemcpyAsync(b->dec_in_ids.p, rows, n_elem * (size_t)id_bytes, hipMemcpyHostToDevice, b->stream));
+    if (d_begin && n_rows > 0) HIP_TRY(hipMemcpyAsync(d_begin, begin_or_null, (size_t)n_rows * 8, hipMemcpyHostToDevice, b->stream));
+    if (d_end && n_rows > 0) HIP_TRY(hipMemcpyAsync(d_end, end_or_null, (size_t)n_rows * 8, hipMemcpyHostToDevice, b->stream));
+    if ((rc = jtk_batch_decode_rows_device(b, b->dec_in_ids.p, id_bytes, n_rows, width, row_stride, d_begin, d_end, pad_id, stop_ids, n_stop,
+                                           flags, cell_byte_or_null ? (int64_t*)b->dec_cell.p : nullptr, nullptr, n_bytes)))
+        return rc;
+    if (cell_byte_or_null && n_cells > 0) HIP_TRY(hipMemcpy(cell_byte_or_null, b->dec_cell.p, (size_t)n_cells * 8, hipMemcpyDeviceToHost));
     return JTK_OK;
 }
 

@@ -117,6 +117,24 @@ public:
         check(jtk_batch_decode_fetch(batch_, (uint8_t*)&bytes[0], nb, byteOff.data(), status.data()));
     }
 
+    // batch decodeBytes of the rows of an id matrix (IdT = int32_t or int64_t; nRows x width, row r at element r * rowStride): each
+    // row's window [begin[r], end[r]) (empty vectors: the whole row), cut at its first stop id, pad cells skipped with
+    // JTK_DECODE_SKIP_PAD in flags -> bytes back to back + nRows+1 byte offsets + status (+ the byte position of every cell)
+    template <class IdT>
+    void decodeRows(const IdT* rows, int64_t nRows, int64_t width, int64_t rowStride, const std::vector<int64_t>& begin,
+                    const std::vector<int64_t>& end, int64_t padId, const std::vector<int64_t>& stopIds, uint32_t flags,
+                    std::string& bytes, std::vector<int64_t>& byteOff, std::vector<int32_t>& status,
+                    std::vector<int64_t>* cellByte = nullptr) {
+        static_assert(sizeof(IdT) == 4 || sizeof(IdT) == 8, "ids are 32 or 64 bits");
+        int64_t nb = 0;
+        if (cellByte) cellByte->resize((size_t)(nRows * width));
+        check(jtk_batch_decode_rows(batch_, rows, (int)sizeof(IdT), nRows, width, rowStride, begin.empty() ? nullptr : begin.data(),
+                                    end.empty() ? nullptr : end.data(), padId, stopIds.empty() ? nullptr : stopIds.data(),
+                                    (int)stopIds.size(), flags, cellByte ? cellByte->data() : nullptr, &nb));
+        bytes.resize((size_t)nb); byteOff.resize((size_t)nRows + 1); status.resize((size_t)nRows);
+        check(jtk_batch_decode_fetch(batch_, (uint8_t*)&bytes[0], nb, byteOff.data(), status.data()));
+    }
+
 private:
     EncodingResult run(const std::string& text, uint32_t flags, int64_t maxTokens) {
         EncodingResult r{std::vector<int32_t>(text.size() + 1), false};

@@ -9,6 +9,7 @@
 #include "jtk_pack_rules.h"
 #include "jtk_label_rules.h"
 #include "jtk_stage_rules.h"
+#include "jtk_decode_rows_rules.h"
 
 #define JTK_SPLIT_TILE 4096      // bytes per pretok_split workgroup
 #define JTK_SPLIT_HALO 64
@@ -181,6 +182,30 @@ struct JtkDecodeWork {
     uint8_t* out;               // NULL in the sizing phase
     int64_t* byte_off;          // [n_seqs + 1]
 };
+// Device-side working set of one decode of an id matrix (jtk_decode_rows.hip; the rule is jtk_decode_rows_rules.h).  Cells are
+// numbered t = r * width + c; tiles of JTK_DEC_TILE cells.
+struct JtkDecodeRowsWork {
+    const void* rows;           // ids of id_bytes (4 or 8) bytes, row r at element r * row_stride; aligned to id_bytes only
+    int id_bytes;
+    int64_t n_rows, width, row_stride, n_cells, n_tiles;
+    const int64_t* begin;       // [n_rows] or NULL
+    const int64_t* end;         // [n_rows] or NULL
+    JtkDecodeRowsRule rule;
+    const uint32_t* tab_off;    // as in JtkDecodeWork
+    const uint8_t* tab_blob;
+    uint32_t n_ids_table;
+    unsigned long long* first_stop;   // [n_rows] first stop column inside the window (set to JTK_DR_NO_STOP per call); NULL
+                                      // without stop ids
+    uint32_t* tile_bytes;       // [n_tiles]
+    int64_t* tile_off;          // [n_tiles + 1]
+    int32_t* status;            // [n_rows] (zeroed per call)
+    int64_t* total;
+    uint8_t* out;
+    int64_t* byte_off;          // [n_rows + 1]
+    int64_t* cell_byte;         // [n_rows * width] or NULL
+};
+void jtk_launch_decode_rows_count(const JtkDecodeRowsWork& w, hipStream_t s);     // row ends (with stop ids), count, scan
+void jtk_launch_decode_rows_scatter(const JtkDecodeRowsWork& w, hipStream_t s);   // bytes, byte_off, cell_byte
 struct JtkTruncWork {
     const int32_t* tokens;      // result of the last batch encode
     const int64_t* tok_off;

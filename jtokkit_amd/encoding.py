@@ -474,6 +474,57 @@ class Batch:
         _check(N.lib().jtk_batch_decode_fetch(self._h, out.ctypes.data, nb, byte_off.ctypes.data, status.ctypes.data))
         return out[:nb], byte_off, status[:ns]
 
+    # ---- decode of an id matrix (device); the result is read with decode_fetch ----------------------------
+    @staticmethod
+    def _rows_options(stop_ids, skip_pad, keep_stop):
+        stop = np.ascontiguousarray(list(stop_ids), dtype=np.int64)
+        flags = (N.JTK_DECODE_SKIP_PAD if skip_pad else 0) | (N.JTK_DECODE_KEEP_STOP if keep_stop else 0)
+        return stop, flags
+
+    def decode_rows_device(self, d_rows_ptr, id_bytes, n_rows, width, row_stride=None, d_begin_ptr=None, d_end_ptr=None, pad_id=-1,
+                           stop_ids=(), skip_pad=False, keep_stop=False, d_cell_byte_ptr=None, stream=None):
+        """jtk_batch_decode_rows_device: n_rows x width ids of id_bytes bytes at d_rows_ptr -> total byte count (result on the
+        device)."""
+        stop, flags = self._rows_options(stop_ids, skip_pad, keep_stop)
+        nb = C.c_int64(0)
+        _check(N.lib().jtk_batch_decode_rows_device(self._h, d_rows_ptr, id_bytes, n_rows, width, width if row_stride is None else row_stride,
+                                                    d_begin_ptr, d_end_ptr, int(pad_id), stop.ctypes.data if len(stop) else None,
+                                                    len(stop), flags, d_cell_byte_ptr, stream, C.byref(nb)))
+        self._dec_shape = (nb.value, n_rows)
+        return nb.value
+
+    def decode_rows_host(self, rows, begin=None, end=None, pad_id=-1, stop_ids=(), skip_pad=False, keep_stop=False, cell_byte=False):
+        """jtk_batch_decode_rows: rows is a 2-d numpy int32 / int64 matrix whose rows are contiguous (a row-strided view is passed
+        as it is) -> total byte count, or (total, cell_byte int64 [n_rows, width]) when cell_byte is asked for."""
+        rows = np.asarray(rows)
+        if rows.ndim != 2 or rows.dtype not in (np.dtype(np.int32), np.dtype(np.int64)):
+            raise ValueError("rows must be a 2-d int32 or int64 array")
+        nr, width = rows.shape
+        isz = rows.itemsize
+        if nr > 1 and width > 0 and rows.strides[1] == isz and rows.strides[0] % isz == 0 and rows.strides[0] >= width * isz:
+            stride = rows.strides[0] // isz
+        else:
+            rows, stride = np.ascontiguousarray(rows), width
+        win = [None if a is None else np.ascontiguousarray(a, dtype=np.int64) for a in (begin, end)]
+        for a in win:
+            if a is not None and a.shape != (nr,):
+                raise ValueError("begin / end need one entry per row")
+        stop, flags = self._rows_options(stop_ids, skip_pad, keep_stop)
+        cells = np.zeros((nr, width), dtype=np.int64) if cell_byte else None
+        nb = C.c_int64(0)
+        _check(N.lib().jtk_batch_decode_rows(self._h, rows.ctypes.data if rows.size else None, isz, nr, width, stride,
+                                             None if win[0] is None else win[0].ctypes.data, None if win[1] is None else win[1].ctypes.data,
+                                             int(pad_id), stop.ctypes.data if len(stop) else None, len(stop), flags,
+                                             cells.ctypes.data if cell_byte else None, C.byref(nb)))
+        self._dec_shape = (nb.value, nr)
+        return (nb.value, cells) if cell_byte else nb.value
+
+    def decode_device_result(self):
+        """jtk_batch_decode_device_result: device pointers (out, byte_off, status) of the last decode."""
+        p = [C.c_void_p() for _ in range(3)]
+        _check(N.lib().jtk_batch_decode_device_result(self._h, *(C.byref(x) for x in p)))
+        return tuple(x.value for x in p)
+
     def set_profiling(self, on=True):
         _check(N.lib().jtk_batch_set_profiling(self._h, 1 if on else 0))
 
@@ -1127,6 +1178,85 @@ class HipEncoding:
             raise EncodingError(int(status[q]), "Unknown token for decoding (list %d)" % q)
         raw = out.tobytes()
         return [raw[byte_off[q]:byte_off[q + 1]] for q in range(len(token_lists))]
+
+    def _stop_ids(self, stop):
+        """Ids or special-token literals -> ids (at most JTK_DECODE_MAX_STOP_IDS)."""
+        if isinstance(stop, (int, np.integer, str, bytes, bytearray)):
+            stop = (stop,)
+        ids = [self._sep_id(x) for x in stop]
+        if len(ids) > N.JTK_DECODE_MAX_STOP_IDS:
+            raise ValueError("at most %d stop ids" % N.JTK_DECODE_MAX_STOP_IDS)
+        return ids
+
+    def decode_rows_device(self, rows, begin=None, end=None, pad_id=None, stop=(), keep_stop=False, cell_offsets=False):
+        """Encoding.decodeBytes for every row of a device-resident id matrix, as generate() or this library's padded rows hand
+        it out (jtk_batch_decode_rows_device; the rule is in jtk_decode_rows_rules.h).  rows: 2-d CUDA torch.int32 / int64
+        tensor on this encoding's device with stride(1) == 1 (a row-strided view is read in place); begin / end: CUDA int64
+        [n_rows] or None, the window of columns of every row; pad_id: cells holding it are skipped (None: no cell is); stop:
+        ids or special-token literals, the first of which ends its row (keep_stop: and is decoded too).  Returns a dict of CUDA
+        tensors written on torch.cuda.current_stream(): bytes uint8, byte_off int64 [n_rows + 1], status int32 [n_rows] (0 or
+        JTK_ERR_UNKNOWN_TOKEN; rows do not raise) and, with cell_offsets, cell_byte int64 [n_rows, width]: where in `bytes`
+        every cell's bytes start.  The call waits as decode does: once for the size of the output, once at the end."""
+        import torch
+        dev = N.lib().jtk_encoding_device(self._h)
+        if (not isinstance(rows, torch.Tensor) or rows.device.type != "cuda" or rows.dim() != 2
+                or rows.dtype not in (torch.int32, torch.int64)):
+            raise ValueError("rows must be a 2-d CUDA tensor of torch.int32 or torch.int64")
+        if rows.device.index != dev:
+            raise ValueError("rows is on cuda:%s, the encoding on cuda:%d" % (rows.device.index, dev))
+        nr, width = rows.shape
+        stride = width
+        if nr > 1 and width > 0:
+            if rows.stride(1) != 1 or rows.stride(0) < width:
+                raise ValueError("rows must have stride(1) == 1 and stride(0) >= width")
+            stride = rows.stride(0)
+        elif width > 1 and rows.stride(1) != 1:
+            raise ValueError("rows must have stride(1) == 1 and stride(0) >= width")
+        device = rows.device
+        for name, t in (("begin", begin), ("end", end)):
+            if t is None:
+                continue
+            if (not isinstance(t, torch.Tensor) or t.device != device or t.dtype != torch.int64 or t.dim() != 1 or t.numel() != nr
+                    or not t.is_contiguous()):
+                raise ValueError("%s must be a contiguous CUDA int64 tensor of n_rows entries on %s" % (name, device))
+        stop_ids = self._stop_ids(stop)
+        b = self._b()
+        cur = torch.cuda.current_stream(device)
+        side = None
+        if cur.cuda_stream == 0:
+            # (the legacy default stream: see chunk_batch_device)
+            side = torch.cuda.ExternalStream(b.stream(), device=device)
+            side.wait_stream(cur)
+        stream = (side or cur).cuda_stream
+        cells = torch.empty((nr, width), dtype=torch.int64, device=device) if cell_offsets else None
+        nb = b.decode_rows_device(rows.data_ptr() if nr * width else None, rows.element_size(), nr, width, stride,
+                                  None if begin is None else begin.data_ptr(), None if end is None else end.data_ptr(),
+                                  0 if pad_id is None else int(pad_id), stop_ids, pad_id is not None, keep_stop,
+                                  cells.data_ptr() if cell_offsets and nr * width else None, stream)
+        out = dict(bytes=torch.empty(nb, dtype=torch.uint8, device=device), byte_off=torch.empty(nr + 1, dtype=torch.int64, device=device),
+                   status=torch.empty(nr, dtype=torch.int32, device=device))
+        for key, src in zip(("bytes", "byte_off", "status"), b.decode_device_result()):
+            t = out[key]
+            if t.numel():
+                _copy_d2d(t.data_ptr(), src, t.numel() * t.element_size(), stream)
+        if cell_offsets:
+            out["cell_byte"] = cells
+        if side is not None:
+            cur.wait_stream(side)
+        return out
+
+    def decode_rows(self, rows, begin=None, end=None, pad_id=None, stop=(), keep_stop=False, strict=True):
+        """The same for a numpy id matrix (2-d, int32 or int64) -> list of bytes, one per row.  strict: raise for a row with an
+        unknown id among its decoded cells, as decode_batch does."""
+        b = self._b()
+        rows = np.asarray(rows)
+        b.decode_rows_host(rows, begin, end, 0 if pad_id is None else int(pad_id), self._stop_ids(stop), pad_id is not None, keep_stop)
+        out, byte_off, status = b.decode_fetch()
+        if strict and len(status) and status.min() < 0:
+            q = int(np.argmin(status))
+            raise EncodingError(int(status[q]), "Unknown token for decoding (row %d)" % q)
+        raw = out.tobytes()
+        return [raw[byte_off[q]:byte_off[q + 1]] for q in range(rows.shape[0])]
 
     def vocab_size(self):
         return N.lib().jtk_encoding_vocab_size(self._h)
