@@ -344,6 +344,51 @@ int jtk_batch_chunk_rows(jtk_batch* b, int32_t pad_id, int32_t* d_rows, void* st
  * same encode; without one it synchronises once for the token count.  Not after a count-only encode. */
 int jtk_batch_token_offsets(jtk_batch* b, int64_t* d_byte_pos, void* stream_or_null);
 
+/* ---- character positions: UTF-16 and code-point offsets, on the device -------------------------------------------------
+ * Every position above is a byte position in String.getBytes(UTF_8).  These calls convert between the byte positions of the
+ * LAST batch encode's text and indices into the documents as a Java String (JTK_UNIT_UTF16: what substring takes) or a Python
+ * str (JTK_UNIT_CODEPOINT: what tiktoken's decode_with_offsets and an offset_mapping hold).  The rule
+ * (jtokkit_amd/csrc/jtk_charpos_rules.h) is per byte and defined for any bytes: a byte that is no continuation byte
+ * ((x & 0xC0) != 0x80) counts 1, a byte >= 0xF0 one more in UTF-16 units (a surrogate pair), every byte 1 with JTK_UNIT_BYTE.
+ * The sums equal new String(bytes, UTF_8) indices and Python str indices for WELL-FORMED documents only; for others they are
+ * still the sums of these weights (no U+FFFD accounting) -- encode with JTK_ENCODE_VALIDATE_UTF8 to find such documents
+ * (JTK_ERR_BAD_UTF8).
+ *   Coordinates  byte positions are batch positions (those of byte_begin and jtk_batch_token_offsets); character positions
+ *                are relative to their document [a, e) = [doc_off[d], doc_off[d + 1]).
+ *   Rounding     a boundary is a, e, or a byte that is no continuation byte.  JTK_CHAR_FLOOR takes the nearest boundary at or
+ *                before the position (the index of the character that holds the byte: tiktoken's convention for a token that
+ *                starts inside a character), JTK_CHAR_CEIL the nearest at or after it (a partly covered character counts: the
+ *                exclusive end); looked for within 3 bytes and inside [a, e], else the position itself.
+ *   Forward      d_char_pos[i] = the units of [a, snap(d_byte_pos[i])) of document d_doc_or_null[i] -- without the array, of
+ *                the last document with doc_off[d] <= the position (a document edge belongs to the document that starts there,
+ *                n_bytes to the last document).  -1 for a position outside [a, e] or a bad document.
+ *   Inverse      d_byte_pos[i] = the largest boundary q of document d_doc[i] with at most d_char_pos[i] units in [a, q): -1
+ *                for a negative index or a bad document, e for an index at or past the document's length.  A UTF-16 index that
+ *                points at a low surrogate gives the first byte of its 4-byte character.
+ *   Index        the first call after an encode builds a rank / select index over the text (about 3.3 % of its size) for the
+ *                unit; later calls with that unit reuse it, a call with another unit rebuilds it, a new encode of any kind
+ *                drops it.  jtk_batch_char_index builds it ahead of time and, with d_doc_units_or_null [n_docs], writes every
+ *                document's length (String.length(), len(str)).
+ *   Tokens       jtk_batch_token_char_offsets: per token of the last encode, d_begin = FLOOR of its first byte and
+ *                d_end_or_null = CEIL of its end, both relative to the token's document.  Reuses the byte scan of a
+ *                jtk_batch_chunk / _token_offsets / _token_spans on the same encode; without one it waits once, for the token
+ *                count.
+ *   Order        queued after the last encode on stream_or_null (or the batch's stream); the calls do not wait (but for the
+ *                token count above).  They READ THE TEXT: with device input (jtk_batch_encode_device) the caller's text and
+ *                offsets must stay valid and unchanged until these calls have run, as for jtk_batch_truncate.
+ *   Errors       JTK_ERR_INVALID_ARGUMENT without an encode result (jtk_batch_encode_device_max_tokens leaves none), for an
+ *                unknown unit or rounding, a NULL array with n > 0, after jtk_batch_encode_pieces (its positions are positions
+ *                in the decoded stream), and for jtk_batch_token_char_offsets after a count-only encode.  The other three
+ *                work after a count-only encode: they read only the text.  n == 0 and n_docs == 0 launch nothing. */
+enum { JTK_UNIT_BYTE = 0, JTK_UNIT_UTF16 = 1, JTK_UNIT_CODEPOINT = 2 };
+enum { JTK_CHAR_FLOOR = 0, JTK_CHAR_CEIL = 1 };
+int jtk_batch_char_index(jtk_batch* b, int unit, int64_t* d_doc_units_or_null /* [n_docs], device */, void* stream_or_null);
+int jtk_batch_char_positions(jtk_batch* b, int unit, int round, const int64_t* d_doc_or_null, const int64_t* d_byte_pos,
+                             int64_t n, int64_t* d_char_pos, void* stream_or_null);
+int jtk_batch_byte_positions(jtk_batch* b, int unit, const int64_t* d_doc, const int64_t* d_char_pos, int64_t n,
+                             int64_t* d_byte_pos, void* stream_or_null);
+int jtk_batch_token_char_offsets(jtk_batch* b, int unit, int64_t* d_begin, int64_t* d_end_or_null, void* stream_or_null);
+
 /* ---- packed training rows, on the device ---------------------------------------------------------------------------
  * The documents of the LAST batch encode on `b` packed into rows of seq_len (L) tokens, as a pretraining or fine-tuning
  * loader does, with the document boundaries inside every row for a varlen attention call.  The rule

@@ -37,6 +37,11 @@ JTK_PACK_DROP_LAST = 4
 JTK_SPAN_WHOLE = 0
 JTK_SPAN_START = 1
 JTK_SPAN_ANY = 2
+JTK_UNIT_BYTE = 0
+JTK_UNIT_UTF16 = 1
+JTK_UNIT_CODEPOINT = 2
+JTK_CHAR_FLOOR = 0
+JTK_CHAR_CEIL = 1
 JTK_LABEL_SHIFT = 1
 JTK_LABEL_SEP = 2
 JTK_DECODE_MAX_STOP_IDS = 8
@@ -91,6 +96,10 @@ SIGNATURES = {
     "jtk_batch_chunk_device_result": (C.c_int, [_p] + [C.POINTER(_p)] * 7),
     "jtk_batch_chunk_rows": (C.c_int, [_p, C.c_int32, _p, _p]),
     "jtk_batch_token_offsets": (C.c_int, [_p, _p, _p]),
+    "jtk_batch_char_index": (C.c_int, [_p, C.c_int, _p, _p]),
+    "jtk_batch_char_positions": (C.c_int, [_p, C.c_int, C.c_int, _p, _p, _i64, _p, _p]),
+    "jtk_batch_byte_positions": (C.c_int, [_p, C.c_int, _p, _p, _i64, _p, _p]),
+    "jtk_batch_token_char_offsets": (C.c_int, [_p, C.c_int, _p, _p, _p]),
     "jtk_batch_pack": (C.c_int, [_p, _i64, C.c_int32, C.c_uint32, _p, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(C.c_int32)]),
     "jtk_batch_pack_write": (C.c_int, [_p, C.c_int32, _p, _p, _p, _p, _p]),
     "jtk_batch_pack_fetch": (C.c_int, [_p, C.c_int32, _p, _p, _p, _p]),

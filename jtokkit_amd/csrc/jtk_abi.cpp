@@ -159,6 +159,13 @@ struct jtk_batch {
     JtkPackWork pk{};
     bool have_pack = false;
     hipStream_t pk_stream = nullptr;     // stream of the last pack plan
+    // jtk_batch_char_*: the rank / select index over the last encode's text for cp_unit (-1: none; a new encode drops it, a call
+    // with another unit rebuilds it): sup [n_sup + 1] | dunit [n_docs + 1] (i64) | superblock totals [n_sup] (u32) | sub (u16)
+    DevBuf cp_buf;
+    JtkCharIndex cp{};
+    int64_t* cp_dunit = nullptr;
+    int cp_unit = -1;
+    hipStream_t cp_stream = nullptr;     // stream of the last call that built or read the index
     // JTK_ENCODE_ALLOW_SPECIAL (jtk_special.hip): the allowed set per literal of the encoding (a new batch allows all) and its
     // device copy; find scratch (hdr | the stitched status | per-block counts), candidates and sub-documents, the stitched result
     std::vector<uint8_t> sp_allowed;
@@ -436,7 +443,7 @@ void jtk_batch_destroy(jtk_batch* b) {
     DevBuf* bufs[] = {&b->in_text, &b->in_off, &b->in_pieces, &b->out, &b->plan, &b->dec_in_ids, &b->dec_in_off,
                       &b->dec_zero, &b->dec_tile, &b->dec_pre, &b->dec_out, &b->dec_byte_off, &b->dec_first, &b->dec_in_win, &b->dec_cell, &b->trunc_kept, &b->trunc_flag,
                       &b->mt_scratch, &b->mt_gather, &b->ck_scratch, &b->ck_tiles, &b->ck_rec, &b->pk_scratch, &b->sp_lits, &b->sp_find,
-                      &b->sp_cand, &b->sp_out};
+                      &b->sp_cand, &b->sp_out, &b->cp_buf};
     for (DevBuf* d : bufs) d->release();
     if (b->h_sp) (void)hipHostFree(b->h_sp);
     for (hipEvent_t ev : b->prof_ev) (void)hipEventDestroy(ev);
@@ -875,6 +882,7 @@ int run_job(jtk_batch* b, const uint8_t* d_text, const uint8_t* h_text, const in
     b->have_chunk = false;
     b->have_tiles = false;
     b->have_pack = false;
+    b->cp_unit = -1;
     b->synced = false;
     b->last_stream = s;
     b->prof_chunks = prof ? n_chunks : 0;
@@ -1791,6 +1799,7 @@ int jtk_batch_encode_device_max_tokens(jtk_batch* b, const uint8_t* d_utf8, cons
     b->have_chunk = false;
     b->have_tiles = false;
     b->have_pack = false;
+    b->cp_unit = -1;
     b->plan_doc_off = nullptr;
     if (n_docs == 0) return JTK_OK;
     hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
@@ -2225,6 +2234,118 @@ int jtk_batch_pack_labels_fetch(jtk_batch* b, const int32_t* d_tok_span_or_null,
     tmp.release();
     if (rc != JTK_OK) return rc;
     HIP_TRY(e);
+    return JTK_OK;
+}
+
+
+// ---- character positions of the last encode's text (jtk_charpos.hip; the rule is jtk_charpos_rules.h) -----------------------
+static_assert(JTK_UNIT_BYTE == JTK_CP_UNIT_BYTE && JTK_UNIT_UTF16 == JTK_CP_UNIT_UTF16 && JTK_UNIT_CODEPOINT == JTK_CP_UNIT_CODEPOINT &&
+              JTK_CHAR_FLOOR == JTK_CP_FLOOR && JTK_CHAR_CEIL == JTK_CP_CEIL, "the rule header's values are the ABI's");
+static int cp_check(jtk_batch* b, int unit) {
+    if (!b || !b->have_result) return fail(JTK_ERR_INVALID_ARGUMENT, "no batch encode result on this batch (jtk_batch_encode_device_max_tokens leaves none)");
+    if (b->job_pieces)
+        return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode took caller-supplied pieces: its positions are positions in the decoded stream, not in the text");
+    if (!jtk_cp_valid_unit(unit)) return fail(JTK_ERR_INVALID_ARGUMENT, "unit: JTK_UNIT_BYTE, JTK_UNIT_UTF16 or JTK_UNIT_CODEPOINT");
+    return JTK_OK;
+}
+
+// the index of the last encode's text for `unit`, ready on s: the cached one, or a new build behind the encode
+static int cp_index(jtk_batch* b, int unit, hipStream_t s) {
+    int rc;
+    if (b->cp_unit == unit) {
+        if ((rc = ck_order(b, b->cp_stream, s))) return rc;
+        b->cp_stream = s;
+        return JTK_OK;
+    }
+    if ((rc = ck_order(b, b->last_stream, s))) return rc;
+    if (b->cp_stream && (rc = ck_order(b, b->cp_stream, s))) return rc;       // (readers of the index that this one replaces)
+    b->cp_unit = -1;
+    const int64_t n_bytes = b->job_bytes, nd = b->job_docs;
+    const int64_t n_sup = (n_bytes + JTK_CP_SUPER - 1) / JTK_CP_SUPER;
+    const size_t o_dunit = ((size_t)n_sup + 1) * 8, o_cnt = o_dunit + ((size_t)nd + 1) * 8, o_sub = align_up(o_cnt + (size_t)n_sup * 4 + 4, 16);
+    if ((rc = b->cp_buf.ensure(o_sub + (size_t)n_sup * JTK_CP_BLOCKS_PER_SUPER * 2 + 16))) return rc;
+    uint8_t* z = (uint8_t*)b->cp_buf.p;
+    JtkCharIndex& ix = b->cp;
+    ix.text = b->job_text; ix.n_bytes = n_bytes; ix.n_sup = n_sup; ix.unit = unit;
+    ix.sup = (const int64_t*)z; ix.sub = (const uint16_t*)(z + o_sub);
+    b->cp_dunit = (int64_t*)(z + o_dunit);
+    jtk_launch_charpos_build(ix, (uint32_t*)(z + o_cnt), (int64_t*)z, (uint16_t*)(z + o_sub), b->job_doc_off, nd, b->cp_dunit, s);
+    HIP_TRY(hipGetLastError());
+    b->cp_unit = unit;
+    b->cp_stream = s;
+    return JTK_OK;
+}
+
+int jtk_batch_char_index(jtk_batch* b, int unit, int64_t* d_doc_units_or_null, void* stream_or_null) {
+    int rc;
+    if ((rc = cp_check(b, unit))) return rc;
+    if ((uintptr_t)d_doc_units_or_null & 7u) return fail(JTK_ERR_INVALID_ARGUMENT, "unaligned array (8-byte int64)");
+    if (b->job_docs == 0) return JTK_OK;
+    HIP_TRY(hipSetDevice(b->enc->device));
+    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    if ((rc = cp_index(b, unit, s))) return rc;
+    if (d_doc_units_or_null) {
+        jtk_launch_charpos_doc_units(b->job_doc_off, b->cp_dunit, b->job_docs, d_doc_units_or_null, s);
+        HIP_TRY(hipGetLastError());
+    }
+    return JTK_OK;
+}
+
+int jtk_batch_char_positions(jtk_batch* b, int unit, int round, const int64_t* d_doc_or_null, const int64_t* d_byte_pos, int64_t n,
+                             int64_t* d_char_pos, void* stream_or_null) {
+    int rc;
+    if ((rc = cp_check(b, unit))) return rc;
+    if (!jtk_cp_valid_round(round)) return fail(JTK_ERR_INVALID_ARGUMENT, "round: JTK_CHAR_FLOOR or JTK_CHAR_CEIL");
+    if (n < 0) return fail(JTK_ERR_INVALID_ARGUMENT, "n must not be negative");
+    if (n > 0 && (!d_byte_pos || !d_char_pos)) return fail(JTK_ERR_INVALID_ARGUMENT, "d_byte_pos or d_char_pos is NULL");
+    if (((uintptr_t)d_doc_or_null & 7u) || ((uintptr_t)d_byte_pos & 7u) || ((uintptr_t)d_char_pos & 7u))
+        return fail(JTK_ERR_INVALID_ARGUMENT, "unaligned array (8-byte int64)");
+    if (n == 0) return JTK_OK;
+    HIP_TRY(hipSetDevice(b->enc->device));
+    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    if ((rc = cp_index(b, unit, s))) return rc;
+    jtk_launch_charpos_rank(b->cp, b->job_doc_off, b->cp_dunit, b->job_docs, round, d_doc_or_null, d_byte_pos, n, d_char_pos, s);
+    HIP_TRY(hipGetLastError());
+    return JTK_OK;
+}
+
+int jtk_batch_byte_positions(jtk_batch* b, int unit, const int64_t* d_doc, const int64_t* d_char_pos, int64_t n, int64_t* d_byte_pos,
+                             void* stream_or_null) {
+    int rc;
+    if ((rc = cp_check(b, unit))) return rc;
+    if (n < 0) return fail(JTK_ERR_INVALID_ARGUMENT, "n must not be negative");
+    if (n > 0 && (!d_doc || !d_char_pos || !d_byte_pos)) return fail(JTK_ERR_INVALID_ARGUMENT, "d_doc, d_char_pos or d_byte_pos is NULL");
+    if (((uintptr_t)d_doc & 7u) || ((uintptr_t)d_char_pos & 7u) || ((uintptr_t)d_byte_pos & 7u))
+        return fail(JTK_ERR_INVALID_ARGUMENT, "unaligned array (8-byte int64)");
+    if (n == 0) return JTK_OK;
+    HIP_TRY(hipSetDevice(b->enc->device));
+    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    if ((rc = cp_index(b, unit, s))) return rc;
+    jtk_launch_charpos_select(b->cp, b->job_doc_off, b->cp_dunit, b->job_docs, d_doc, d_char_pos, n, d_byte_pos, s);
+    HIP_TRY(hipGetLastError());
+    return JTK_OK;
+}
+
+int jtk_batch_token_char_offsets(jtk_batch* b, int unit, int64_t* d_begin, int64_t* d_end_or_null, void* stream_or_null) {
+    int rc;
+    if ((rc = cp_check(b, unit))) return rc;
+    if (b->job_flags & JTK_ENCODE_COUNT_ONLY) return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode was count-only: there are no token ids");
+    if (((uintptr_t)d_begin & 7u) || ((uintptr_t)d_end_or_null & 7u)) return fail(JTK_ERR_INVALID_ARGUMENT, "unaligned array (8-byte int64)");
+    HIP_TRY(hipSetDevice(b->enc->device));
+    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    if (!b->have_tiles) {                   // no chunk plan, token offsets or spans on this encode: the byte scan first
+        int64_t nt = 0;
+        if ((rc = jtk_batch_result(b, &nt, nullptr, nullptr)) || (rc = ck_order(b, b->last_stream, s)) || (rc = ck_setup(b))) return rc;
+        if ((rc = ck_tiles(b, nt, s))) return rc;
+        b->ck_stream = s;
+    } else if ((rc = ck_order(b, b->ck_stream, s))) {
+        return rc;
+    }
+    if (b->ck.n_tok == 0) return JTK_OK;
+    if (!d_begin) return fail(JTK_ERR_INVALID_ARGUMENT, "d_begin is NULL");
+    if ((rc = cp_index(b, unit, s))) return rc;
+    jtk_launch_charpos_tokens(b->ck, b->cp, b->cp_dunit, d_begin, d_end_or_null, s);
+    HIP_TRY(hipGetLastError());
     return JTK_OK;
 }
 

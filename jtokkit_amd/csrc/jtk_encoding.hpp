@@ -107,6 +107,22 @@ public:
         check(jtk_batch_fetch_truncated(batch_, kept.data(), truncated.data()));
     }
 
+    // character positions of the last encodeBatch's text (device arrays; unit JTK_UNIT_UTF16 for indices into a Java String):
+    // every document's length, byte positions -> indices, indices -> byte positions, and every token's [begin, end)
+    void charIndex(int unit, int64_t* dDocUnits = nullptr, void* stream = nullptr) {
+        check(jtk_batch_char_index(batch_, unit, dDocUnits, stream));
+    }
+    void charPositions(int unit, int round, const int64_t* dDoc, const int64_t* dBytePos, int64_t n, int64_t* dCharPos,
+                       void* stream = nullptr) {
+        check(jtk_batch_char_positions(batch_, unit, round, dDoc, dBytePos, n, dCharPos, stream));
+    }
+    void bytePositions(int unit, const int64_t* dDoc, const int64_t* dCharPos, int64_t n, int64_t* dBytePos, void* stream = nullptr) {
+        check(jtk_batch_byte_positions(batch_, unit, dDoc, dCharPos, n, dBytePos, stream));
+    }
+    void tokenCharOffsets(int unit, int64_t* dBegin, int64_t* dEnd = nullptr, void* stream = nullptr) {
+        check(jtk_batch_token_char_offsets(batch_, unit, dBegin, dEnd, stream));
+    }
+
     // batch decodeBytes: token lists back to back in `ids`, n+1 offsets -> bytes back to back + n+1 byte offsets + status
     void decodeBatch(const int32_t* ids, const std::vector<int64_t>& seqOff, std::string& bytes,
                      std::vector<int64_t>& byteOff, std::vector<int32_t>& status) {

@@ -10,6 +10,7 @@
 #include "jtk_label_rules.h"
 #include "jtk_stage_rules.h"
 #include "jtk_decode_rows_rules.h"
+#include "jtk_charpos_rules.h"
 
 #define JTK_SPLIT_TILE 4096      // bytes per pretok_split workgroup
 #define JTK_SPLIT_HALO 64
@@ -321,6 +322,19 @@ void jtk_launch_pack_write(const JtkPackWork& w, int32_t pad_id, int32_t* rows, 
 void jtk_launch_label_spans(const JtkChunkWork& w, const int64_t* begin, const int64_t* end, int64_t n_spans, int rule,
                             int32_t* tok_span, hipStream_t s);
 void jtk_launch_label_pack(const JtkPackWork& w, const JtkLabelView& lv, bool shift, int32_t* labels, hipStream_t s);
+// Character positions (jtk_charpos.hip; the rule and the index are jtk_charpos_rules.h).  build: the index of ix.text for ix.unit
+// into sup_cnt [n_sup] (scratch), sup [n_sup + 1] and sub [n_sup * 64] (ix.sup / ix.sub point at them), then dunit[d] =
+// rank(doc_off[d]) for d = 0 .. n_docs.  The queries take the built index; tokens: begin / end (may be NULL) [n_tok] of the chunk
+// work's tokens (needs the tiles of jtk_launch_chunk_tiles).
+void jtk_launch_charpos_build(const JtkCharIndex& ix, uint32_t* sup_cnt, int64_t* sup, uint16_t* sub, const int64_t* doc_off,
+                              int64_t n_docs, int64_t* dunit, hipStream_t s);
+void jtk_launch_charpos_doc_units(const int64_t* doc_off, const int64_t* dunit, int64_t n_docs, int64_t* doc_units, hipStream_t s);
+void jtk_launch_charpos_rank(const JtkCharIndex& ix, const int64_t* doc_off, const int64_t* dunit, int64_t n_docs, int round,
+                             const int64_t* doc, const int64_t* byte_pos, int64_t n, int64_t* char_pos, hipStream_t s);
+void jtk_launch_charpos_select(const JtkCharIndex& ix, const int64_t* doc_off, const int64_t* dunit, int64_t n_docs, const int64_t* doc,
+                               const int64_t* char_pos, int64_t n, int64_t* byte_pos, hipStream_t s);
+void jtk_launch_charpos_tokens(const JtkChunkWork& w, const JtkCharIndex& ix, const int64_t* dunit, int64_t* begin, int64_t* end,
+                               hipStream_t s);
 // Compact ids (jtk_compact.hip; the rule is jtk_compact_rules.h): the range [t0, t1) of the int32 stream `ids` (indexed from
 // token 0) into a uint16 plane and a plane of hb bits per token whose entry 0 is token `origin` (a multiple of 32; 0 for whole
 // planes).  Restarts at t0 rounded down to a multiple of 32 and rewrites the words there whole.  d_total != NULL: the range ends

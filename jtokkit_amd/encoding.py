@@ -67,6 +67,37 @@ def _span_rule(rule):
     return int(rule)
 
 
+_UNITS = {"byte": N.JTK_UNIT_BYTE, "utf16": N.JTK_UNIT_UTF16, "char": N.JTK_UNIT_CODEPOINT}
+_ROUNDS = {"floor": N.JTK_CHAR_FLOOR, "ceil": N.JTK_CHAR_CEIL}
+
+
+def _unit(unit):
+    """"byte" / "utf16" (indices into a Java String) / "char" (code points: indices into a Python str) -> JTK_UNIT_*; an int
+    goes through (the library checks it)."""
+    if isinstance(unit, str):
+        if unit not in _UNITS:
+            raise ValueError("unit must be 'byte', 'utf16' or 'char', not %r" % (unit,))
+        return _UNITS[unit]
+    return int(unit)
+
+
+def _round(rnd):
+    if isinstance(rnd, str):
+        if rnd not in _ROUNDS:
+            raise ValueError("round must be 'floor' or 'ceil', not %r" % (rnd,))
+        return _ROUNDS[rnd]
+    return int(rnd)
+
+
+def _stream_sync(stream):
+    """hipStreamSynchronize of the HIP runtime the library is bound to."""
+    f = N.lib().hipStreamSynchronize
+    f.restype, f.argtypes = C.c_int, [C.c_void_p]
+    rc = f(stream)
+    if rc != 0:
+        raise EncodingError(N.JTK_ERR_HIP, "hipStreamSynchronize failed (%d)" % rc)
+
+
 class _DeviceArray:
     """A numpy array's bytes in device memory of the HIP runtime the library is bound to, for host-input calls whose C entry
     point takes device arrays (no torch needed).  fetch() copies back."""
@@ -450,6 +481,29 @@ class Batch:
         _check(N.lib().jtk_batch_pack_labels_fetch(self._h, d_tok_span, int(ignore_index), flags, out.ctypes.data))
         return out
 
+    # ---- character positions of the last encode's text (device) ------------------------------------------
+    def char_index(self, unit, d_doc_units_ptr=None, stream=None):
+        """jtk_batch_char_index: builds the index of the last encode's text for `unit` ("utf16", "char", "byte" or a
+        JTK_UNIT_* value); int64 [n_docs] at d_doc_units_ptr (may be None): every document's length in that unit."""
+        _check(N.lib().jtk_batch_char_index(self._h, _unit(unit), d_doc_units_ptr, stream))
+
+    def char_positions(self, unit, d_byte_pos_ptr, n, d_char_pos_ptr, round="floor", d_doc_ptr=None, stream=None):
+        """jtk_batch_char_positions: int64 [n] at d_char_pos_ptr, the index in its document of each of the n batch byte
+        positions at d_byte_pos_ptr, rounded down ("floor") or up ("ceil") to a character; d_doc_ptr (int64 [n], or None: the
+        document that holds the position) names the documents.  -1 outside the document."""
+        _check(N.lib().jtk_batch_char_positions(self._h, _unit(unit), _round(round), d_doc_ptr, d_byte_pos_ptr, int(n), d_char_pos_ptr,
+                                                stream))
+
+    def byte_positions(self, unit, d_doc_ptr, d_char_pos_ptr, n, d_byte_pos_ptr, stream=None):
+        """jtk_batch_byte_positions: int64 [n] at d_byte_pos_ptr, the batch byte position of index d_char_pos[i] of document
+        d_doc[i] (an index past the document: its end; a negative one: -1)."""
+        _check(N.lib().jtk_batch_byte_positions(self._h, _unit(unit), d_doc_ptr, d_char_pos_ptr, int(n), d_byte_pos_ptr, stream))
+
+    def token_char_offsets(self, unit, d_begin_ptr, d_end_ptr=None, stream=None):
+        """jtk_batch_token_char_offsets: int64 [n_tokens] at d_begin_ptr and d_end_ptr (may be None): every token's range
+        [begin, end) in its document, in `unit`."""
+        _check(N.lib().jtk_batch_token_char_offsets(self._h, _unit(unit), d_begin_ptr, d_end_ptr, stream))
+
     # ---- batch decode (device) -------------------------------------------------------------------------
     def decode_host(self, ids, seq_off):
         """ids int32[n], seq_off int64[n_seqs+1] -> total byte count (result stays on the device)."""
@@ -703,6 +757,52 @@ class HipEncoding:
             return CompactBatchResult(r.lo.copy(), None if r.hi is None else r.hi.copy(), r.id_bits, r.tok_off.copy(), r.status.copy())
         return b.fetch()
 
+    def _char_unit(self, unit, what):
+        """JTK_UNIT_* of `unit`; None for bytes.  A custom split pattern has no positions in the text to convert."""
+        u = _unit(unit)
+        if u == N.JTK_UNIT_BYTE:
+            return None
+        if self._host_pattern is not None:
+            raise ValueError("%s: character positions are not defined for this encoding's custom split pattern" % what)
+        return u
+
+    def encode_batch_with_offsets(self, texts, unit="char", ordinary=False, allowed_special=None):
+        """encode_batch plus every token's range in its text: (BatchResult, begin int64 [n_tokens], end int64 [n_tokens]).
+        unit "char": indices into the Python str (text[begin:end] holds the token's characters; a token that starts inside a
+        character begins at that character, one that ends inside a character ends after it -- tiktoken's decode_with_offsets
+        convention for begin); "utf16": indices into a Java String; "byte": the token's own bytes, unrounded."""
+        bs = [t if isinstance(t, (bytes, bytearray)) else t.encode("utf-8") for t in texts]
+        doc_off = np.zeros(len(bs) + 1, dtype=np.int64)
+        if bs:
+            np.cumsum([len(b) for b in bs], out=doc_off[1:])
+        text = np.frombuffer(b"".join(bs), dtype=np.uint8) if doc_off[-1] else np.zeros(0, dtype=np.uint8)
+        u = self._char_unit(unit, "encode_batch_with_offsets")
+        res = self.encode_batch_packed(text, doc_off, ordinary, False, allowed_special)
+        nt = len(res.tokens)
+        b = self._b()
+        bufs = []
+        try:
+            for _ in range(2):
+                bufs.append(_DeviceArray(np.zeros(nt, dtype=np.int64)))
+            if u is None:
+                b.token_offsets(bufs[0].ptr)
+                _stream_sync(b.stream())
+                pos = bufs[0].fetch()
+                counts = np.diff(res.tok_off)
+                doc = np.repeat(np.arange(len(bs)), counts)
+                begin = pos - doc_off[doc]
+                end = np.empty_like(begin)
+                end[:-1] = pos[1:] - doc_off[doc[:-1]]                          # a token ends where the next one begins ...
+                last = res.tok_off[1:][counts > 0] - 1
+                end[last] = (doc_off[1:] - doc_off[:-1])[doc[last]]             # ... a document's last token at its end
+                return res, begin, end
+            b.token_char_offsets(u, bufs[0].ptr, bufs[1].ptr)
+            _stream_sync(b.stream())
+            return res, bufs[0].fetch(), bufs[1].fetch()
+        finally:
+            for x in bufs:
+                x.free()
+
     @property
     def id_bits(self):
         """Bits per id of the compact format: 16 + the high bits per token (jtk_encoding_id_bits)."""
@@ -873,12 +973,15 @@ class HipEncoding:
             if not t.is_contiguous():
                 raise ValueError("%s must be contiguous" % name)
 
-    def chunk_batch(self, texts, chunk_tokens, overlap=0, ordinary=False, allowed_special=None):
+    def chunk_batch(self, texts, chunk_tokens, overlap=0, ordinary=False, allowed_special=None, unit="byte"):
         """Every text cut into consecutive chunks of at most chunk_tokens tokens (overlapping by up to `overlap` tokens), each a
         whole number of characters unless the tokens do not allow it: per document a list of (tokens, start, end, split), with
         start / end byte positions in that document (jtk_batch_chunk; the rule is in jtk_chunk_rules.h).  The chunks are
         slices of encode(text); with overlap 0 they concatenate to it.  A document that cannot be encoded raises.
-        allowed_special: as for encode_batch (a special token's byte span is its literal)."""
+        allowed_special: as for encode_batch (a special token's byte span is its literal).
+        unit: "byte" (default), "char" -- start / end are indices into the Python str, text[start:end] is the chunk's text -- or
+        "utf16", indices into a Java String (start rounds down, end up, to a character for a split chunk)."""
+        u = self._char_unit(unit, "chunk_batch")
         bs = [t if isinstance(t, (bytes, bytearray)) else t.encode("utf-8") for t in texts]
         doc_off = np.zeros(len(bs) + 1, dtype=np.int64)
         if bs:
@@ -890,22 +993,39 @@ class HipEncoding:
         b = self._b()
         b.chunk(chunk_tokens, overlap)
         f = b.chunk_fetch()
+        nc = len(f["doc"])
+        start, end = f["byte_begin"] - doc_off[f["doc"]], f["byte_end"] - doc_off[f["doc"]]
+        if u is not None and nc:
+            p_doc, p_bb, p_be = (b.chunk_device_result()[i] for i in (1, 4, 5))
+            bufs = []
+            try:
+                for _ in range(2):
+                    bufs.append(_DeviceArray(np.zeros(nc, dtype=np.int64)))
+                b.char_positions(u, p_bb, nc, bufs[0].ptr, "floor", p_doc)
+                b.char_positions(u, p_be, nc, bufs[1].ptr, "ceil", p_doc)
+                _stream_sync(b.stream())
+                start, end = bufs[0].fetch(), bufs[1].fetch()
+            finally:
+                for x in bufs:
+                    x.free()
         out = [[] for _ in bs]
-        for c in range(len(f["doc"])):
+        for c in range(nc):
             d, tb, n = int(f["doc"][c]), int(f["tok_begin"][c]), int(f["n_tok"][c])
-            out[d].append((res.tokens[tb:tb + n].tolist(), int(f["byte_begin"][c] - doc_off[d]), int(f["byte_end"][c] - doc_off[d]),
-                           bool(f["split"][c])))
+            out[d].append((res.tokens[tb:tb + n].tolist(), int(start[c]), int(end[c]), bool(f["split"][c])))
         return out
 
-    def chunk_batch_device(self, text, doc_off, chunk_tokens, overlap=0, ordinary=False, pad_id=-1, allowed_special=None):
+    def chunk_batch_device(self, text, doc_off, chunk_tokens, overlap=0, ordinary=False, pad_id=-1, allowed_special=None, unit=None):
         """chunk_batch for a device-resident batch, in a model's layout.  text: CUDA torch.uint8 tensor, doc_off: CUDA torch.int64
         tensor [n_docs + 1], on this encoding's device.  Returns a dict of CUDA tensors written on torch.cuda.current_stream():
         rows int32 [n_chunks, chunk_tokens] (the chunk's ids, then pad_id), n_tok int32, doc int64, byte_begin / byte_end int64
         (positions in `text`), split bool [n_chunks], chunk_off int64 [n_docs + 1] and the per-document status int32 (documents
         with a negative status have no chunks; they do not raise).  The call waits once, for the chunk count (and, with
-        allowed_special -- as for encode_batch --, once more for the encode's count of literal candidates)."""
+        allowed_special -- as for encode_batch --, once more for the encode's count of literal candidates).
+        unit ("char", "utf16" or a JTK_UNIT_* value): the dict also holds char_begin / char_end int64 [n_chunks], the chunk's
+        range in that unit, relative to its document (begin rounded down, end up); byte_begin / byte_end stay as they are."""
         import torch
         self._check_device_inputs("chunk_batch_device", text, doc_off)
+        u = None if unit is None else _unit(unit)
         allow = self._allow(self._b(), allowed_special)
         N_, ov = int(chunk_tokens), int(overlap)
         if N_ < 1 or not 0 <= ov < N_:
@@ -946,6 +1066,12 @@ class HipEncoding:
             t = out[key]
             if t.numel():
                 _copy_d2d(t.data_ptr(), src, t.numel() * t.element_size(), stream)
+        if u is not None:
+            out["char_begin"] = torch.empty(nc, dtype=torch.int64, device=device)
+            out["char_end"] = torch.empty(nc, dtype=torch.int64, device=device)
+            if nc:
+                b.char_positions(u, p_bb, nc, out["char_begin"].data_ptr(), "floor", p_doc, stream)
+                b.char_positions(u, p_be, nc, out["char_end"].data_ptr(), "ceil", p_doc, stream)
         if side is not None:
             cur.wait_stream(side)
         return out
@@ -962,29 +1088,37 @@ class HipEncoding:
         return int(sep)
 
     @staticmethod
-    def _batch_spans(train_spans, doc_off):
-        """Per-document (start, end) byte ranges -> sorted batch positions (begin, end int64), checked."""
+    def _batch_spans(train_spans, doc_off, doc_units=None):
+        """Per-document (start, end) byte ranges -> sorted batch positions (begin, end int64), checked.  With doc_units (the
+        documents' lengths in characters or UTF-16 units) the ranges are in that unit: (doc, begin, end int64), begin / end
+        still relative to their document, for jtk_batch_byte_positions."""
         nd = len(doc_off) - 1
         if len(train_spans) != nd:
             raise ValueError("train_spans needs one list of (start, end) per text (%d for %d texts)" % (len(train_spans), nd))
-        begin, end = [], []
+        begin, end, doc = [], [], []
         for d, spans in enumerate(train_spans):
-            n, prev = int(doc_off[d + 1] - doc_off[d]), 0
+            n, prev = int(doc_off[d + 1] - doc_off[d]) if doc_units is None else int(doc_units[d]), 0
             for a, e in spans or ():
                 a, e = int(a), int(e)
                 if a < 0 or e < a or e > n:
+                    if doc_units is not None:
+                        raise ValueError("train_spans[%d]: (%d, %d) is not a character range inside the text (%d units)" % (d, a, e, n))
                     raise ValueError("train_spans[%d]: (%d, %d) is not a byte range inside the text (%d bytes)" % (d, a, e, n))
                 if a < prev:
                     raise ValueError("train_spans[%d]: (%d, %d) starts before the previous range ends: ranges must be sorted "
                                      "and must not overlap" % (d, a, e))
                 prev = e
-                begin.append(int(doc_off[d]) + a)
-                end.append(int(doc_off[d]) + e)
+                base = int(doc_off[d]) if doc_units is None else 0
+                begin.append(base + a)
+                end.append(base + e)
+                doc.append(d)
+        if doc_units is not None:
+            return np.array(doc, dtype=np.int64), np.array(begin, dtype=np.int64), np.array(end, dtype=np.int64)
         return np.array(begin, dtype=np.int64), np.array(end, dtype=np.int64)
 
     def pack_batch(self, texts, seq_len, sep=None, sep_first=False, whole_docs=False, drop_last=False, pad_id=-1, ordinary=False,
                    allowed_special=None, train_spans=None, span_rule="whole", label_shift=False, label_sep=False,
-                   ignore_index=-100):
+                   ignore_index=-100, span_unit="byte"):
         """Every text encoded, then packed into rows of seq_len tokens (jtk_batch_pack; the rule is in jtk_pack_rules.h): a dict
         of numpy arrays rows, positions int32 [n_rows, seq_len], cu_seqlens int32 [n_segments + 1], seg_doc int64
         [n_segments], status int32 [n_docs] and max_seqlen (int).  sep: None, a token id or a special-token literal such as
@@ -996,7 +1130,10 @@ class HipEncoding:
         [n_rows, seq_len] -- a cell's id where its token lies in a range by span_rule ("whole": entirely inside, "start": its
         first byte, "any": any byte), ignore_index elsewhere, on separators (unless label_sep, for a separator after a trainable
         last token) and on pad; label_shift: next-token targets within each segment -- and tok_span int32 [n_tokens], each
-        token's range (numbered over the batch) or -1.  The rule is in jtk_label_rules.h."""
+        token's range (numbered over the batch) or -1.  The rule is in jtk_label_rules.h.
+        span_unit: "byte" (default), or "char" / "utf16": train_spans are ranges of the Python str / of a Java String, checked
+        against the texts' lengths in that unit and converted on the device (jtk_batch_byte_positions)."""
+        su = self._char_unit(span_unit, "pack_batch") if train_spans is not None else None
         bs = [t if isinstance(t, (bytes, bytearray)) else t.encode("utf-8") for t in texts]
         doc_off = np.zeros(len(bs) + 1, dtype=np.int64)
         if bs:
@@ -1005,7 +1142,10 @@ class HipEncoding:
         sep_id = self._sep_id(sep)
         if train_spans is not None:
             rule = _span_rule(span_rule)
-            begin, end = self._batch_spans(train_spans, doc_off)
+            if su is None:
+                begin, end = self._batch_spans(train_spans, doc_off)
+            elif len(train_spans) != len(bs):
+                self._batch_spans(train_spans, doc_off)                     # (raises: one list per text)
         res = self.encode_batch_packed(text, doc_off, ordinary, False, allowed_special)
         b = self._b()
         _, _, mx = b.pack(seq_len, sep_id, whole_docs, sep_first, drop_last)
@@ -1015,11 +1155,25 @@ class HipEncoding:
         if train_spans is not None:
             bufs = []
             try:
-                for a in (begin, end, np.zeros(len(res.tokens), dtype=np.int32)):
-                    bufs.append(_DeviceArray(a))
-                b.token_spans(bufs[0].ptr, bufs[1].ptr, len(begin), rule, bufs[2].ptr)
-                f["labels"] = b.pack_labels_fetch(bufs[2].ptr, ignore_index, label_shift, label_sep)   # (synchronises)
-                f["tok_span"] = bufs[2].fetch()
+                if su is not None:
+                    # the ranges are checked against the documents' lengths in the unit, then become byte positions on the device
+                    units = _DeviceArray(np.zeros(max(len(bs), 1), dtype=np.int64))
+                    bufs.append(units)
+                    b.char_index(su, units.ptr)
+                    _stream_sync(b.stream())
+                    doc, begin, end = self._batch_spans(train_spans, doc_off, units.fetch()[:len(bs)])
+                    d_doc, d_begin, d_end = _DeviceArray(doc), _DeviceArray(begin), _DeviceArray(end)
+                    bufs += [d_doc, d_begin, d_end]
+                    b.byte_positions(su, d_doc.ptr, d_begin.ptr, len(doc), d_begin.ptr)     # (in place: one lane per entry)
+                    b.byte_positions(su, d_doc.ptr, d_end.ptr, len(doc), d_end.ptr)
+                else:
+                    d_begin, d_end = _DeviceArray(begin), _DeviceArray(end)
+                    bufs += [d_begin, d_end]
+                d_span = _DeviceArray(np.zeros(len(res.tokens), dtype=np.int32))
+                bufs.append(d_span)
+                b.token_spans(d_begin.ptr, d_end.ptr, len(begin), rule, d_span.ptr)
+                f["labels"] = b.pack_labels_fetch(d_span.ptr, ignore_index, label_shift, label_sep)   # (synchronises)
+                f["tok_span"] = d_span.fetch()
             finally:
                 for x in bufs:
                     x.free()
@@ -1147,6 +1301,50 @@ class HipEncoding:
         if side is not None:
             cur.wait_stream(side)
         return tok_span, tok_off, status
+
+    def token_offsets_device(self, text, doc_off, unit="char", ordinary=False, allowed_special=None):
+        """Encodes a device-resident batch (text CUDA torch.uint8, doc_off CUDA torch.int64 [n_docs + 1]) and returns (begin int64
+        [n_tokens], end int64 [n_tokens], tok_off int64 [n_docs + 1], status int32 [n_docs]) as CUDA tensors written on
+        torch.cuda.current_stream(): every token's range in its document in `unit` ("char", "utf16", "byte" or a JTK_UNIT_*
+        value), begin rounded down and end up to a character (jtk_batch_token_char_offsets).  The ids stay in the batch
+        (device_result).  Waits once, for the token count."""
+        import torch
+        self._check_device_inputs("token_offsets_device", text, doc_off)
+        u = _unit(unit)
+        allow = self._allow(self._b(), allowed_special)
+        nd = doc_off.numel() - 1
+        if nd < 0:
+            raise ValueError("doc_off needs n_docs + 1 entries")
+        device = text.device
+        n = text.numel()
+        st = text.untyped_storage()
+        if text.data_ptr() % 16 or st.data_ptr() + st.nbytes() < text.data_ptr() + (n + 15) // 16 * 16:
+            # (the encode reads whole aligned 16-byte blocks)
+            buf = torch.zeros((n + 15) // 16 * 16 + 16, dtype=torch.uint8, device=device)
+            buf[:n].copy_(text)
+            text = buf
+        b = self._b()
+        cur = torch.cuda.current_stream(device)
+        side = None
+        if cur.cuda_stream == 0:
+            # (the legacy default stream: as in chunk_batch_device, the work goes to the batch's own stream explicitly)
+            side = torch.cuda.ExternalStream(b.stream(), device=device)
+            side.wait_stream(cur)
+        stream = (side or cur).cuda_stream
+        b.encode_device(text.data_ptr(), doc_off.data_ptr(), nd, n, ordinary, stream=stream, sync=False, allow_special=allow)
+        nt = b.result()[0]
+        begin = torch.empty(nt, dtype=torch.int64, device=device)
+        end = torch.empty(nt, dtype=torch.int64, device=device)
+        tok_off = torch.empty(nd + 1, dtype=torch.int64, device=device)
+        status = torch.empty(nd, dtype=torch.int32, device=device)
+        b.token_char_offsets(u, begin.data_ptr() if nt else None, end.data_ptr() if nt else None, stream)
+        _, p_off, p_status = b.device_result()
+        _copy_d2d(tok_off.data_ptr(), p_off, (nd + 1) * 8, stream)
+        if nd:
+            _copy_d2d(status.data_ptr(), p_status, nd * 4, stream)
+        if side is not None:
+            cur.wait_stream(side)
+        return begin, end, tok_off, status
 
     def count_tokens_batch(self, texts, ordinary=False, allowed_special=None):
         """Encoding.countTokens / countTokensOrdinary for every text, one device call, no token ids written.  allowed_special:
