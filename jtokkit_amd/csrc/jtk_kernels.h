@@ -55,7 +55,7 @@
 #define JTK_NBINS_LEAN 5               // bins 0..4: lean phases of the merge kernel; 5..6: state-machine phases
 #define JTK_BIN_MAXLEN 256            // longer pieces go to the wave-per-piece kernels
 #define JTK_M_WGS_PER_SHARD 4
-#define JTK_MID_CAP 512          // wave-per-piece kernel, small bin: pieces of 65..512 bytes
+#define JTK_MID_CAP 512          // wave-per-piece kernel, small bin: pieces of 257..512 bytes (up to 256: the bins)
 #define JTK_LONG_CAP 8192        // wave-per-piece kernel, large bin
 #define JTK_GIANT_CAP (1 << 20)  // workgroup-per-piece kernel with parts in global scratch (= JTK_MAX_PIECE_BYTES)
 #define JTK_GIANT_CHUNK 256      // positions per cached chunk minimum
@@ -149,7 +149,7 @@ struct JtkWork {
     int64_t qt_cap;
     uint32_t* q_count;              // [JTK_NBINS + 1][JTK_Q_SHARDS], one counter per 128-byte line: JTK_QC(bin, shard)
     uint32_t* q_meta;               // [n_tiles][16]: [k] where in its shard the tile's entries of bin k start, [8 + k] how many
-    JtkLongPiece* mid_list; // pieces of 65..JTK_MID_CAP bytes
+    JtkLongPiece* mid_list; // pieces of 257..JTK_MID_CAP bytes (JTK_BIN_MAXLEN + 1 ..)
     JtkLongPiece* long_list;// longer pieces
     JtkLongPiece* giant_list;// pieces longer than JTK_LONG_CAP
     uint32_t* mid_count;

@@ -270,3 +270,67 @@ int sim_merge_piece(void* h, const uint8_t* piece, int len, int32_t* out) {
     return n;
 }
 }
+
+// The same merge with the pair lookups counted as lean_steps of the lean merge bins makes them: the first ranks of a piece come
+// from the direct two-byte table; every later lookup reads the key's primary bucket and goes on to the secondary one only after a
+// miss in a bucket flagged JTK_PAIR_OVERFLOW.  Pieces of up to 16 bytes (bins 0..2, lean_piece16) run with SKIP_WHOLE: a pair
+// that would be the whole piece is not looked up at all -- the piece is known to be no table entry, and must be none here.
+// stats[0]: lookups answered from the secondary bucket; stats[1]: lookups that missed in a flagged primary bucket and in the
+// secondary one as well; stats[2]: all lookups made.  Returns the token count (tokens in out), -1 for a bad length, -2 if the
+// tokens differ from jtk_merge_piece_lane's.
+extern "C" int sim_merge_piece_stats(void* h, const uint8_t* piece, int len, int32_t* out, int64_t* stats) {
+    JtkHostTables* t = (JtkHostTables*)h;
+    if (len < 1 || len > 64) return -1;
+    stats[0] = stats[1] = stats[2] = 0;
+    const bool skip_whole = len <= 16;
+    const JtkPairTable pt{t->pair_buckets.data(), t->pair_bits};
+    auto lookup = [&](uint32_t a, uint32_t b) {
+        const uint64_t key = jtk_pair_key(a, b);
+        const uint32_t m = jtk_pair_mix(a, b);
+        const JtkPairBucket v1 = pt.buckets[jtk_reduce32(m, pt.bits)];
+        uint32_t r = jtk_pair_match(v1, key);
+        stats[2]++;
+        if (r == JTK_RANK_NONE && (v1.r0 & JTK_PAIR_OVERFLOW)) {
+            r = jtk_pair_match(pt.buckets[jtk_reduce32(jtk_pair_mix2(m), pt.bits)], key);
+            stats[r == JTK_RANK_NONE ? 1 : 0]++;
+        }
+        return r;
+    };
+    uint32_t ids[64], rk[64];
+    for (int i = 0; i < len; i++) {
+        ids[i] = t->byte_rank[piece[i]];
+        rk[i] = i + 1 < len ? t->bp_rank[((uint32_t)piece[i] << 8) | piece[i + 1]] : JTK_RANK_NONE;
+    }
+    uint64_t alive = (len >= 64) ? ~0ull : ((1ull << len) - 1ull);
+    for (;;) {
+        uint32_t minr = JTK_RANK_NONE;
+        int mini = 0;
+        for (int j = 0; j < len; j++) if (((alive >> j) & 1ull) && rk[j] < minr) { minr = rk[j]; mini = j; }
+        if (minr == JTK_RANK_NONE) break;
+        const uint64_t above = alive & ~((2ull << mini) - 1ull);
+        const int nxt = jtk_ctz64(above);
+        const uint64_t above2 = above & (above - 1);
+        const uint64_t below = alive & ((1ull << mini) - 1ull);
+        const int pv = below ? 63 - jtk_clz64(below) : mini;
+        bool want1 = above2 != 0, want2 = below != 0;
+        if (skip_whole) {                                            // as lean_steps<.., SKIP_WHOLE = true>
+            want1 = want1 && !(mini == 0 && (above2 & (above2 - 1)) == 0);
+            want2 = want2 && !(pv == 0 && above2 == 0);
+        }
+        const uint32_t r1 = want1 ? lookup(minr, ids[jtk_ctz64(above2)]) : JTK_RANK_NONE;
+        if (below) rk[pv] = want2 ? lookup(ids[pv], minr) : JTK_RANK_NONE;
+        ids[mini] = minr;
+        rk[mini] = r1;
+        ids[nxt] = JTK_ID_DEAD;
+        alive &= ~(1ull << nxt);
+    }
+    uint32_t ids2[64], rk2[64];
+    for (int i = 0; i < len; i++) ids2[i] = t->byte_rank[piece[i]];
+    jtk_merge_piece_lane(ids2, rk2, len, pt);
+    int n = 0;
+    for (int i = 0; i < len; i++) {
+        if (ids[i] != ids2[i]) return -2;
+        if (ids[i] != JTK_ID_DEAD) out[n++] = (int32_t)ids[i];
+    }
+    return n;
+}
