@@ -19,6 +19,7 @@
 
 #include "jtk_device_prims.h"
 #include "jtk_merge_core.h"
+#include "jtk_merge_order_rules.h"
 #include "jtk_block_classify.h"
 #include "jtk_split_masks.h"
 #include "jtk_split_rules.h"
@@ -702,9 +703,10 @@ __global__ void __launch_bounds__(RES_THREADS) __attribute__((amdgpu_waves_per_e
 // but a handful of the pieces that need merging -- ONE LANE PER PIECE, no state machine: a wave takes 64 consecutive
 // queue entries, expands them (byte -> id and the 2-byte-token ranks from LDS tables), then all lanes step together:
 // leftmost minimum over the pair keys (:234-240), the two neighbour lookups in the (left id, right id) pair table,
-// update (:248-259); a lane whose piece is finished idles until the wave's last piece is.  Entries of one wave come
-// from the same stretch of text, so their lengths are alike; the slots scanned per step are bounded by the wave's
-// longest piece (NS: a compile-time unrolled scan, all LDS reads of a step in flight together).
+// update (:248-259); a lane whose piece is finished idles until the wave's last piece is.  The bins are length classes,
+// and a long queue is taken in windows of 4 x 64 entries in order of length (lean_window, jtk_merge_order_rules.h), so a
+// wave's pieces are of nearly one length; the slots scanned per step are bounded by the bin's longest piece (NS: a
+// compile-time unrolled scan, all LDS reads of a step in flight together).
 // What bounds the kernel is the number of scattered cache-line fetches (tools/microbench/gather_rate.hip: a CU
 // sustains one per ~2.3 clocks), so a step fetches as few as it can: the pair table is primary-first (jtk_common.h) --
 // ONE 16-byte load per lookup, issued for both lookups together; only lanes that miss in a bucket flagged "overflowed"
@@ -861,6 +863,135 @@ __device__ __forceinline__ void tiny_bin(const JtkWork& w, const LeanLds& L, uin
     }
 }
 
+// emit (:270-273): one result word per piece; more than seven tokens go to htok
+template <int THREADS, class M>
+__device__ __forceinline__ uint4 lean_emit(const JtkWork& w, const uint32_t* id, M alive, uint32_t c, int64_t pos) {
+    uint32_t r0 = 0, r1 = 0, r2 = 0, r3 = (c - 1u) << 24;
+    if (c <= 7u) {
+        M m = alive;
+        uint32_t tk[7];
+#pragma unroll
+        for (int i = 0; i < 7; i++) {
+            const uint32_t j = m ? (sizeof(M) == 8 ? (uint32_t)jtk_ctz64((uint64_t)m) : (uint32_t)__builtin_ctz((uint32_t)m)) : 0u;
+            tk[i] = m ? id[j * THREADS] : 0u;
+            m &= m - (M)1;
+        }
+        // 17 bits each from bit 0: token i at bit 17 * i
+        r0 = tk[0] | (tk[1] << 17);
+        r1 = (tk[1] >> 15) | (tk[2] << 2) | (tk[3] << 19);
+        r2 = (tk[3] >> 13) | (tk[4] << 4) | (tk[5] << 21);
+        r3 |= (tk[5] >> 11) | (tk[6] << 6);
+    } else {
+        uint32_t* dst = w.htok + pos;
+        uint32_t idx = 0;
+        for (M m = alive; m;) {
+            const uint32_t j = sizeof(M) == 8 ? (uint32_t)jtk_ctz64((uint64_t)m) : (uint32_t)__builtin_ctz((uint32_t)m);
+            m &= m - (M)1;
+            dst[idx++] = id[j * THREADS];
+        }
+    }
+    return make_uint4(r0, r1, r2, r3);
+}
+
+// token counts per tile: entries of a tile are consecutive, so a wave sees a few runs of equal tiles; the first
+// lane of each run adds the run's sum.  Evaluated by all lanes of the wave.
+__device__ __forceinline__ void lean_tile_counts(const JtkWork& w, bool have, int64_t pos, uint32_t c, int lane) {
+    const int64_t tile = have ? pos / T : -1;
+    const uint32_t cc = have ? c : 0u;
+    const uint32_t inc = jtk_wave_incl_scan(cc);
+    const uint32_t tlo = (uint32_t)tile, thi = (uint32_t)((uint64_t)tile >> 32);
+    // (the shuffles are evaluated by ALL lanes, outside the condition: a lane that short-circuits an `||` leaves the
+    // wave for the rest of the expression, and its neighbour would read a dead lane)
+    const uint32_t plo = (uint32_t)__shfl_up((int)tlo, 1), phi = (uint32_t)__shfl_up((int)thi, 1);
+    const bool head = lane == 0 || plo != tlo || phi != thi;
+    const uint64_t heads = __ballot(head);
+    const uint64_t later = heads & ~((2ull << lane) - 1ull);                  // run heads after this lane
+    const int last = later ? jtk_ctz64(later) - 1 : 63;                        // last lane of this lane's run
+    const uint32_t run_end = (uint32_t)__shfl((int)inc, last);
+    if (head && have) {
+        const uint32_t sum = run_end - (inc - cc);
+        if (sum) atomicAdd(&w.tile_tot[tile], sum);
+    }
+}
+
+// A window of 64 * R (R = 2 or 4, wave-uniform) consecutive entries of the queue of 4..8-byte pieces, all present, taken by
+// one wave in stable order of length (jtk_merge_order_rules.h): a round's 64 pieces are of nearly one length, so few of
+// its steps serve finished lanes.  The window comes in and its results go out in entry order, with the coalesced loads and
+// stores of a pass of R = 1; in between the 16-byte entries stay in the wave's columns of slots 8..15 of both part arrays
+// (idle while 8 slots are merged: 2 x 8 x 64 words = 256 entries), entry e in the four words from (e & 15) * 4 of slot
+// 8 + (e >> 4 & 7) of id (e < 128) or rk, where each result replaces its entry as it does in memory.  The queue words stay
+// with the lanes that loaded them; the lane that merges an entry is told its index and length through slots 0..3.
+template <int THREADS>
+__device__ __forceinline__ void lean_window(const JtkWork& w, const JtkDeviceTables& t, const LeanLds& L, const uint64_t* qm, uint4* qd,
+                                            uint32_t wbase, uint32_t R) {
+    constexpr uint32_t LO = 4, NC = 5;                                          // 4..8 bytes
+    const int tid = threadIdx.x, lane = tid & 63, col0 = tid & ~63;
+    uint32_t* const id = L.id + tid;
+    uint32_t* const rk = L.rk + tid;
+    uint32_t* const park_lo = L.id + 8 * THREADS + col0;
+    uint32_t* const park_hi = L.rk + 8 * THREADS + col0;
+    uint64_t meta[JTK_MO_RMAX];
+    uint32_t key[JTK_MO_RMAX], place[JTK_MO_RMAX];
+#pragma unroll
+    for (uint32_t s = 0; s < JTK_MO_RMAX; s++) {
+        meta[s] = 0; key[s] = NC; place[s] = 0;
+        if (s < R) {
+            const uint32_t e = s * 64u + (uint32_t)lane;
+            meta[s] = qm[wbase + e];
+            const uint4 by = qd[wbase + e];
+            *reinterpret_cast<uint4*>((s < 2 ? park_lo : park_hi) + ((e >> 4) & 7u) * THREADS + (e & 15u) * 4u) = by;
+            key[s] = jtk_mo_class((uint32_t)((meta[s] >> JTK_QE_LEN_SHIFT) & 255u) + 1u, LO, NC);
+        }
+    }
+    uint32_t before = 0;
+#pragma unroll
+    for (uint32_t c = 0; c < NC; c++) {
+#pragma unroll
+        for (uint32_t s = 0; s < JTK_MO_RMAX; s++) {
+            const uint64_t b = __ballot(key[s] == c);
+            if (key[s] == c) place[s] = jtk_mo_place(b, (uint32_t)lane, before);
+            before += (uint32_t)__popcll(b);
+        }
+    }
+#pragma unroll
+    for (uint32_t s = 0; s < JTK_MO_RMAX; s++) {
+        if (s < R) {
+            const uint32_t len = (uint32_t)((meta[s] >> JTK_QE_LEN_SHIFT) & 255u) + 1u;
+            L.id[(place[s] >> 6) * THREADS + col0 + (place[s] & 63u)] = (s * 64u + (uint32_t)lane) | (len << 8);
+        }
+    }
+    wave_lds_fence();
+    // 16 bits per round: index in the window, length
+    const uint64_t mine = (uint64_t)(id[0] | (id[THREADS] << 16)) | ((uint64_t)(id[2 * THREADS] | (id[3 * THREADS] << 16)) << 32);
+#pragma unroll 1
+    for (uint32_t r = 0; r < R; r++) {
+        const uint32_t el = (uint32_t)(mine >> (16u * r)) & 0xFFFFu, e = el & 255u;
+        const int len = (int)(el >> 8);
+        uint4* const slot = reinterpret_cast<uint4*>(((e & 128u) ? park_hi : park_lo) + ((e >> 4) & 7u) * THREADS + (e & 15u) * 4u);
+        const uint4 by = *slot;
+        const uint32_t d4[3] = {by.x, by.y, by.z};
+        uint32_t b[9];
+#pragma unroll
+        for (int j = 0; j < 9; j++) b[j] = (d4[j >> 2] >> (8 * (j & 3))) & 255u;
+        const uint32_t alive = lean_piece16<8, THREADS>(L, id, rk, b, len, t);
+        const uint32_t c = (uint32_t)__popc(alive);
+        int64_t pos = 0;
+        if (c > 7u) pos = (int64_t)(qm[wbase + e] & JTK_QE_POS_MASK);          // (eight bytes, no merge at all)
+        *slot = lean_emit<THREADS, uint32_t>(w, id, alive, c, pos);
+    }
+    wave_lds_fence();
+#pragma unroll
+    for (uint32_t s = 0; s < JTK_MO_RMAX; s++) {
+        if (s < R) {
+            const uint32_t e = s * 64u + (uint32_t)lane;
+            const uint4 res = *reinterpret_cast<const uint4*>((s < 2 ? park_lo : park_hi) + ((e >> 4) & 7u) * THREADS + (e & 15u) * 4u);
+            qd[wbase + e] = res;
+            lean_tile_counts(w, true, (int64_t)(meta[s] & JTK_QE_POS_MASK), (res.w >> 24) + 1u, lane);
+        }
+    }
+    wave_lds_fence();               // (the words read here are other lanes' slots 8..15, which the next phase may write)
+}
+
 template <int SLOTS, int THREADS, int BIN>
 __device__ __forceinline__ void lean_bin(const JtkWork& w, const JtkDeviceTables& t, const LeanLds& L, uint32_t count, uint32_t kq, uint32_t K) {
     typedef typename std::conditional<(SLOTS > 32), uint64_t, uint32_t>::type M;
@@ -872,7 +1003,16 @@ __device__ __forceinline__ void lean_bin(const JtkWork& w, const JtkDeviceTables
     const uint64_t* const qm = w.qm[BIN] + (int64_t)shard * w.q_cap[BIN];
     uint4* const qd = w.qd[BIN] + (int64_t)shard * w.q_cap[BIN];
 
-    for (uint32_t base = kq * THREADS; base < count; base += K * THREADS) {
+    // passes of 4 or 2 rounds while the queue gives every wave of the shard a full window of that many (jtk_mo_rounds), each
+    // window taken in order of length; what is left is taken 64 consecutive entries per wave
+    uint32_t taken = 0;
+    if (BIN == 0) {
+        const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)count);
+        const uint32_t span = (uint32_t)__builtin_amdgcn_readfirstlane((int)(K * THREADS));
+        for (uint32_t R; (R = jtk_mo_rounds(n - taken, span)) > 1u; taken += R * span)
+            lean_window<THREADS>(w, t, L, qm, qd, taken + R * (kq * THREADS + (uint32_t)(tid & ~63)), R);
+    }
+    for (uint32_t base = taken + kq * THREADS; base < count; base += K * THREADS) {
         const uint32_t qi = base + (uint32_t)tid;
         bool have = qi < count;
         uint64_t meta = 0;
@@ -931,53 +1071,8 @@ __device__ __forceinline__ void lean_bin(const JtkWork& w, const JtkDeviceTables
 
         // ---- emit (:270-273): one result word per piece; more than seven tokens go to htok
         const uint32_t c = sizeof(M) == 8 ? (uint32_t)__popcll((uint64_t)alive) : (uint32_t)__popc((uint32_t)alive);
-        if (have) {
-            uint32_t r0 = 0, r1 = 0, r2 = 0, r3 = (c - 1u) << 24;
-            if (c <= 7u) {
-                M m = alive;
-                uint32_t tk[7];
-#pragma unroll
-                for (int i = 0; i < 7; i++) {
-                    const uint32_t j = m ? (sizeof(M) == 8 ? (uint32_t)jtk_ctz64((uint64_t)m) : (uint32_t)__builtin_ctz((uint32_t)m)) : 0u;
-                    tk[i] = m ? id[j * THREADS] : 0u;
-                    m &= m - (M)1;
-                }
-                // 17 bits each from bit 0: token i at bit 17 * i
-                r0 = tk[0] | (tk[1] << 17);
-                r1 = (tk[1] >> 15) | (tk[2] << 2) | (tk[3] << 19);
-                r2 = (tk[3] >> 13) | (tk[4] << 4) | (tk[5] << 21);
-                r3 |= (tk[5] >> 11) | (tk[6] << 6);
-            } else {
-                uint32_t* dst = w.htok + pos;
-                uint32_t idx = 0;
-                for (M m = alive; m;) {
-                    const uint32_t j = sizeof(M) == 8 ? (uint32_t)jtk_ctz64((uint64_t)m) : (uint32_t)__builtin_ctz((uint32_t)m);
-                    m &= m - (M)1;
-                    dst[idx++] = id[j * THREADS];
-                }
-            }
-            qd[qi] = make_uint4(r0, r1, r2, r3);
-        }
-        // token counts per tile: entries of a tile are consecutive, so a wave sees a few runs of equal tiles; the first
-        // lane of each run adds the run's sum
-        {
-            const int64_t tile = have ? pos / T : -1;
-            const uint32_t cc = have ? c : 0u;
-            const uint32_t inc = jtk_wave_incl_scan(cc);
-            const uint32_t tlo = (uint32_t)tile, thi = (uint32_t)((uint64_t)tile >> 32);
-            // (the shuffles are evaluated by ALL lanes, outside the condition: a lane that short-circuits an `||` leaves the
-            // wave for the rest of the expression, and its neighbour would read a dead lane)
-            const uint32_t plo = (uint32_t)__shfl_up((int)tlo, 1), phi = (uint32_t)__shfl_up((int)thi, 1);
-            const bool head = lane == 0 || plo != tlo || phi != thi;
-            const uint64_t heads = __ballot(head);
-            const uint64_t later = heads & ~((2ull << lane) - 1ull);                  // run heads after this lane
-            const int last = later ? jtk_ctz64(later) - 1 : 63;                        // last lane of this lane's run
-            const uint32_t run_end = (uint32_t)__shfl((int)inc, last);
-            if (head && have) {
-                const uint32_t sum = run_end - (inc - cc);
-                if (sum) atomicAdd(&w.tile_tot[tile], sum);
-            }
-        }
+        if (have) qd[qi] = lean_emit<THREADS, M>(w, id, alive, c, pos);
+        lean_tile_counts(w, have, pos, c, lane);
     }
 }
 
@@ -1487,8 +1582,8 @@ __device__ void merge_giant(const JtkWork& w, const JtkDeviceTables& t, const Gi
 // on ordinary text the later phases find empty queues and cost nothing.
 // ---------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(ML_THREADS) k_bpe_merge(JtkWork w, JtkDeviceTables t) {
-    __shared__ uint32_t s_id[ML_WORDS];
-    __shared__ uint32_t s_rk[ML_WORDS];
+    __shared__ alignas(16) uint32_t s_id[ML_WORDS];        // (16 bytes: lean_window parks whole queue entries in them)
+    __shared__ alignas(16) uint32_t s_rk[ML_WORDS];
     __shared__ uint64_t s_bpbits[1024];
     __shared__ uint32_t s_bpranks[JTK_BP_MAX];
     __shared__ uint16_t s_bpcum[1024];
