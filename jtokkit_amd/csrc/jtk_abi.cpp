@@ -63,7 +63,7 @@ int jtk_fail_msg(int code, const std::string& msg) { return fail(code, msg); }  
 struct jtk_encoding {
     JtkHostTables host;
     int device = 0;
-    DevBuf uc1, uc2, brank, pairs, tok8, tok16, bprank, bpbits, bpcum, bpranks, pairin, dec_off, dec_blob, longtok, longblob, specials;
+    DevBuf uc1, uc2, uclds, splittab, brank, pairs, tok8, tok16, bprank, bpbits, bpcum, bpranks, pairin, dec_off, dec_blob, longtok, longblob, specials;
     DevBuf bnd;                      // jtk_batch_chunk: one bit per id of the decode table, set when its byte string does not start
                                      // with a UTF-8 continuation byte (lengths come from dec_off)
     uint32_t n_ids_table = 0;        // ids 0 .. n_ids_table-1 have an entry in the decode table (incl. special tokens)
@@ -289,11 +289,19 @@ int jtk_encoding_create(const char* name, int pattern_kind, const uint8_t* tikto
     }
     if (device < 0 || device >= ndev) { delete enc; return fail(JTK_ERR_INVALID_ARGUMENT, "device index out of range"); }
     enc->device = device;
-    auto cleanup = [&]() { enc->uc1.release(); enc->uc2.release(); enc->brank.release(); enc->pairs.release(); enc->tok8.release(); enc->tok16.release(); enc->bprank.release(); enc->bpbits.release(); enc->bpcum.release(); enc->bpranks.release(); enc->pairin.release(); enc->dec_off.release(); enc->dec_blob.release(); enc->longtok.release(); enc->longblob.release(); enc->specials.release(); enc->bnd.release(); delete enc; };
+    auto cleanup = [&]() { enc->uc1.release(); enc->uc2.release(); enc->uclds.release(); enc->splittab.release(); enc->brank.release(); enc->pairs.release(); enc->tok8.release(); enc->tok16.release(); enc->bprank.release(); enc->bpbits.release(); enc->bpcum.release(); enc->bpranks.release(); enc->pairin.release(); enc->dec_off.release(); enc->dec_blob.release(); enc->longtok.release(); enc->longblob.release(); enc->specials.release(); enc->bnd.release(); delete enc; };
 #define ENC_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { cleanup(); return fail(JTK_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } } while (0)
     ENC_TRY(hipSetDevice(device));
     const size_t tok8_bytes = (enc->host.tok8.size() * sizeof(JtkTok8Slot) + 31) & ~(size_t)31;
+    // the Unicode class table as pretok_split stages it in LDS (JtkDeviceTables::uc_lds_image)
+    std::vector<uint8_t> uc_image;
+    if (sizeof(jtk_uc_stage1_init) <= JTK_UC_LDS_STAGE1 && JTK_UC_LDS_STAGE1 + sizeof(jtk_uc_stage2_init) <= (size_t)JTK_UC_LDS_UNITS * 16) {
+        uc_image.assign((size_t)JTK_UC_LDS_UNITS * 16, 0);
+        memcpy(uc_image.data(), jtk_uc_stage1_init, sizeof(jtk_uc_stage1_init));
+        memcpy(uc_image.data() + JTK_UC_LDS_STAGE1, jtk_uc_stage2_init, sizeof(jtk_uc_stage2_init));
+    }
     if (enc->uc1.ensure(sizeof(jtk_uc_stage1_init)) || enc->uc2.ensure(sizeof(jtk_uc_stage2_init)) ||
+        enc->uclds.ensure(uc_image.size() + 16) || enc->splittab.ensure(256 * sizeof(JtkCode4)) ||
         enc->brank.ensure(256 * 4) || enc->pairs.ensure(enc->host.pair_buckets.size() * sizeof(JtkPairBucket)) ||
         // the two whole-piece tables live in one allocation (tok8 slots, then tok16 slots): piece_resolve addresses both with
         // one base and a 32-bit offset; + 32: a 9..16-byte probe of the last slot may read 16 bytes past a 16-byte slot
@@ -302,6 +310,7 @@ int jtk_encoding_create(const char* name, int pattern_kind, const uint8_t* tikto
         enc->bpbits.ensure(1024 * 8) || enc->bpcum.ensure(1024 * 2) || enc->bpranks.ensure(JTK_BP_MAX * 4) || enc->pairin.ensure(2048 * 4)) { cleanup(); return JTK_ERR_OUT_OF_MEMORY; }
     ENC_TRY(hipMemcpy(enc->uc1.p, jtk_uc_stage1_init, sizeof(jtk_uc_stage1_init), hipMemcpyHostToDevice));
     ENC_TRY(hipMemcpy(enc->uc2.p, jtk_uc_stage2_init, sizeof(jtk_uc_stage2_init), hipMemcpyHostToDevice));
+    if (!uc_image.empty()) ENC_TRY(hipMemcpy(enc->uclds.p, uc_image.data(), uc_image.size(), hipMemcpyHostToDevice));
     ENC_TRY(hipMemcpy(enc->brank.p, enc->host.byte_rank, 256 * 4, hipMemcpyHostToDevice));
     ENC_TRY(hipMemcpy(enc->pairs.p, enc->host.pair_buckets.data(), enc->host.pair_buckets.size() * sizeof(JtkPairBucket), hipMemcpyHostToDevice));
     ENC_TRY(hipMemcpy(enc->tok8.p, enc->host.tok8.data(), enc->host.tok8.size() * sizeof(JtkTok8Slot), hipMemcpyHostToDevice));
@@ -345,8 +354,8 @@ int jtk_encoding_create(const char* name, int pattern_kind, const uint8_t* tikto
     dt.longtok.max_len = enc->host.long_max_len;
     dt.uc.stage1 = (const uint8_t*)enc->uc1.p;
     dt.uc.stage2 = (const uint32_t*)enc->uc2.p;
-    dt.uc_stage1_len = JTK_UC_STAGE1_LEN;
-    dt.uc_stage2_words = JTK_UC_STAGE2_WORDS;
+    dt.uc_lds_image = uc_image.empty() ? nullptr : (const uint32_t*)enc->uclds.p;
+    dt.split_tab = (const uint32_t*)enc->splittab.p;
     dt.byte_rank = (const uint32_t*)enc->brank.p;
     dt.pairs.buckets = (const JtkPairBucket*)enc->pairs.p;
     dt.pairs.bits = enc->host.pair_bits;
@@ -359,10 +368,6 @@ int jtk_encoding_create(const char* name, int pattern_kind, const uint8_t* tikto
     dt.bp.cum = (const uint16_t*)enc->bpcum.p;
     dt.bp.ranks = (const uint32_t*)enc->bpranks.p;
     dt.pair_in_token = (const uint32_t*)enc->pairin.p;
-    {
-        const JtkUcTables host_uc{jtk_uc_stage1_init, jtk_uc_stage2_init};
-        for (uint32_t b = 0; b < 256; b++) if (jtk_lead_all_letters(host_uc, b)) dt.lead_letters[b >> 5] |= 1u << (b & 31);
-    }
     dt.kind = pattern_kind;
     dt.pseudo_base = enc->host.n_missing ? enc->host.pseudo_base : 0u;
     dt.n_specials = n_specials;
@@ -383,6 +388,14 @@ int jtk_encoding_create(const char* name, int pattern_kind, const uint8_t* tikto
         dt.special_off = (const uint32_t*)enc->specials.p;
         dt.special_blob = (const uint8_t*)enc->specials.p + off_bytes;
     }
+    {   // pretok_split's per-byte flag table, with the literals' first bytes and the all-letter lead bytes in it
+        const JtkUcTables host_uc{jtk_uc_stage1_init, jtk_uc_stage2_init};
+        uint32_t lead_letters[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+        for (uint32_t b = 0; b < 256; b++) if (jtk_lead_all_letters(host_uc, b)) lead_letters[b >> 5] |= 1u << (b & 31);
+        JtkCode4 tab[256];
+        jtk_build_code4_table(pattern_kind == JTK_PAT_CL100K, dt.special_first, lead_letters, tab);
+        ENC_TRY(hipMemcpy(enc->splittab.p, tab, sizeof(tab), hipMemcpyHostToDevice));
+    }
 #undef ENC_TRY
     *out = enc;
     return JTK_OK;
@@ -391,7 +404,7 @@ int jtk_encoding_create(const char* name, int pattern_kind, const uint8_t* tikto
 void jtk_encoding_destroy(jtk_encoding* enc) {
     if (!enc) return;
     (void)hipSetDevice(enc->device);
-    enc->uc1.release(); enc->uc2.release(); enc->brank.release(); enc->pairs.release();
+    enc->uc1.release(); enc->uc2.release(); enc->uclds.release(); enc->splittab.release(); enc->brank.release(); enc->pairs.release();
     enc->tok8.release(); enc->tok16.release(); enc->bprank.release(); enc->bpbits.release(); enc->bpcum.release(); enc->bpranks.release(); enc->pairin.release();
     enc->dec_off.release(); enc->dec_blob.release(); enc->longtok.release(); enc->longblob.release(); enc->specials.release();
     enc->bnd.release();

@@ -20,8 +20,8 @@ enum : uint32_t {
     JTK_F_L = 1u << 0, JTK_F_N = 1u << 1, JTK_F_W = 1u << 2, JTK_F_NL = 1u << 3, JTK_F_SP = 1u << 4, JTK_F_AP = 1u << 5,
     JTK_F_CONT = 1u << 6, JTK_F_LEAD = 1u << 7,          // LEAD: first byte of a non-ASCII character
     JTK_F_S1 = 1u << 8, JTK_F_RV = 1u << 9, JTK_F_E = 1u << 10, JTK_F_LL = 1u << 11, JTK_F_C5 = 1u << 12, JTK_F_BF = 1u << 13,
-    JTK_F_LT = 1u << 14,                                  // a byte a special-token literal starts with (set by the kernel from the encoding's literals)
-    JTK_F_ULL = 1u << 15                                  // lead byte of characters that are all letters (jtk_lead_all_letters; set by the kernel)
+    JTK_F_LT = 1u << 14,                                  // a byte a special-token literal starts with (set from the encoding's literals)
+    JTK_F_ULL = 1u << 15                                  // lead byte of characters that are all letters (jtk_lead_all_letters)
 };
 
 JTK_HD uint32_t jtk_byte_code(uint32_t b, bool case_insensitive) {
@@ -154,27 +154,61 @@ JTK_HD uint64_t jtk_with_cont_bytes(uint64_t x, uint64_t cont) {
     return x | c1 | c2 | c3;
 }
 
+// The table the split kernel stages: jtk_code4 of every byte value's flag code, with JTK_F_LT / JTK_F_ULL from the two
+// 256-bit sets.  Built once per encoding on the host; 4 KB.
+inline void jtk_build_code4_table(bool case_insensitive, const uint32_t (&special_first)[8], const uint32_t (&lead_letters)[8],
+                                  JtkCode4 (&out)[256]) {
+    for (uint32_t b = 0; b < 256; b++) {
+        uint32_t code = jtk_byte_code(b, case_insensitive);
+        if ((special_first[b >> 5] >> (b & 31)) & 1u) code |= JTK_F_LT;
+        if ((lead_letters[b >> 5] >> (b & 31)) & 1u) code |= JTK_F_ULL;
+        out[b] = jtk_code4(code);
+    }
+}
+
+// The code point a 2-, 3- or 4-byte UTF-8 form encodes, from the 4 bytes w that start at its lead byte (0xC0..0xFF; leads
+// >= 0xF8 take the 4-byte form), without branches: the length n is the count of leading one bits of the lead, all four
+// bytes are packed as if the form had 4 bytes, and the 4 - n bytes too many are shifted out again.  Bytes that are no
+// continuation bytes contribute their low 6 bits (malformed text: some class, never an out-of-range access).
+JTK_HD uint32_t jtk_decode_lead_word(uint32_t w) {
+    const uint32_t b0 = w & 255u;
+#if defined(__HIP_DEVICE_COMPILE__)
+    uint32_t n = (uint32_t)__clz((int)~(b0 << 24));
+#else
+    uint32_t n = (uint32_t)__builtin_clz(~(b0 << 24));
+#endif
+    n = n > 4u ? 4u : n;
+    const uint32_t t = (b0 << 18) | ((w >> 8) & 0x3Fu) << 12 | ((w >> 16) & 0x3Fu) << 6 | ((w >> 24) & 0x3Fu);
+    return (t >> (24u - 6u * n)) & ((2u << (5u * n)) - 1u);
+}
+
 // Non-ASCII characters that START in this block.  Leads in `ull` are letters without a look at the other bytes; the
-// others are decoded (txt.word(j): the 4 bytes that start at byte j of the block, zero beyond the text) and classified
-// one by one.  A character's class goes to its lead and the continuation bytes that directly follow it inside the
-// block.  spill_cls: the class of a character that runs up to the block's last byte (for the leading continuation
-// bytes of the next block; if the character ended there the next block has none), else JTK_CLS_O.
+// others are decoded (txt.word(j): the 4 bytes that start at byte j of the block, zero beyond the text) and classified,
+// two per trip: the byte fetches of both go first, then both stage-1 reads, then both stage-2 reads, so a pair waits
+// three times for its reads, not six (in the kernel they are LDS reads).  An odd last character is taken twice (OR-ing
+// its class bits in again changes nothing).  A character's class goes to its lead and the continuation bytes that
+// directly follow it inside the block.  spill_cls: the class of a character that runs up to the block's last byte (for
+// the leading continuation bytes of the next block; if the character ended there the next block has none), else JTK_CLS_O.
 template <class Txt4>
 JTK_HD void jtk_block_fix_nonascii(const Txt4& txt, const JtkUcTables& uc, uint64_t lead, uint64_t ull, JtkBlk& k,
                                    uint32_t& spill_cls) {
     uint64_t c0 = ull & lead, c1 = 0;                                  // class bits 0 / 1 at the lead positions
     for (uint64_t m = lead & ~ull; m;) {
-        const int j = jtk_ctz64(m);
+        const int ja = jtk_ctz64(m);
         m &= m - 1;
-        const uint32_t w = txt.word(j);
-        const uint32_t b0 = w & 255u, b1 = (w >> 8) & 0x3Fu, b2 = (w >> 16) & 0x3Fu, b3 = (w >> 24) & 0x3Fu;
-        uint32_t cp;
-        if (b0 < 0xE0u) cp = ((b0 & 0x1Fu) << 6) | b1;
-        else if (b0 < 0xF0u) cp = ((b0 & 0x0Fu) << 12) | (b1 << 6) | b2;
-        else cp = ((b0 & 0x07u) << 18) | (b1 << 12) | (b2 << 6) | b3;
-        const uint32_t cls = jtk_class_of_cp(uc, cp);
-        c0 |= (uint64_t)(cls & 1u) << j;
-        c1 |= (uint64_t)(cls >> 1) << j;
+        const int jb = m ? jtk_ctz64(m) : ja;
+        m &= m - 1;                                                    // (0 stays 0)
+        const uint32_t wa = txt.word(ja), wb = txt.word(jb);
+        const uint32_t cpa = jtk_decode_lead_word(wa), cpb = jtk_decode_lead_word(wb);
+        // jtk_class_of_cp for both.  Values past U+10FFFF (malformed text only) are looked up as U+10FFFF, a noncharacter and
+        // so class O like them: no branch stands between the two chains of reads.
+        const uint32_t ca = cpa < 0x10FFFFu ? cpa : 0x10FFFFu, cb = cpb < 0x10FFFFu ? cpb : 0x10FFFFu;
+        const uint32_t blka = uc.stage1[ca >> 8], blkb = uc.stage1[cb >> 8];
+        const uint32_t wda = uc.stage2[blka * 16 + ((ca & 255u) >> 4)], wdb = uc.stage2[blkb * 16 + ((cb & 255u) >> 4)];
+        const uint32_t clsa = (wda >> (2 * (ca & 15u))) & 3u, clsb = (wdb >> (2 * (cb & 15u))) & 3u;
+        // (64-bit shifts: two per character; 32-bit halves picked by bit 5 of the position take more instructions)
+        c0 |= ((uint64_t)(clsa & 1u) << ja) | ((uint64_t)(clsb & 1u) << jb);
+        c1 |= ((uint64_t)(clsa >> 1) << ja) | ((uint64_t)(clsb >> 1) << jb);
     }
     spill_cls = JTK_CLS_O;
     if (lead) {

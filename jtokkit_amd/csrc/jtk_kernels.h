@@ -62,12 +62,16 @@
 #define JTK_MAX_SPECIALS 65536           // special-token literals live in a device blob: the bounds are sanity checks only
 #define JTK_SPECIAL_MAXLEN 65535
 
-#define JTK_UC_LDS_STAGE1 4352    // capacity of the LDS copy of the Unicode class table (pretok_split)
-#define JTK_UC_LDS_STAGE2 2048
+#define JTK_UC_LDS_UNITS 768      // capacity of the LDS copy of the Unicode class table (pretok_split), in 16-byte units:
+                                  // a copying wave moves whole rows of 64 units, a few at a time
+#define JTK_UC_LDS_STAGE1 4352    // bytes of it that hold stage 1 (a multiple of 16); stage 2 follows
 
 struct JtkDeviceTables {
     JtkUcTables uc;
-    uint32_t uc_stage1_len, uc_stage2_words;
+    // The same table as pretok_split stages it in LDS, JTK_UC_LDS_UNITS units of 16 bytes: stage 1 in the first
+    // JTK_UC_LDS_STAGE1 bytes, then stage 2, zero-filled to the end.  Null: the table does not fit.
+    const uint32_t* uc_lds_image;
+    const uint32_t* split_tab;   // [256 * 4] jtk_build_code4_table: the per-byte flag table of pretok_split, 16 bytes per byte value
     const uint32_t* byte_rank;   // [256]
     JtkPairTable pairs;
     JtkTok8Table tok8;
@@ -75,7 +79,6 @@ struct JtkDeviceTables {
     const uint32_t* bp_rank;     // [65536]
     JtkBpLds bp;                 // the same, compressed (staged into LDS by bpe_merge)
     const uint32_t* pair_in_token;   // [2048] bit (b0 << 8 | b1): adjacent inside some table entry
-    uint32_t lead_letters[8];        // bit b: every character whose UTF-8 form starts with byte b is a letter (jtk_lead_all_letters)
     JtkLongTokTable longtok;         // table entries of > 16 bytes that merging does not reproduce (n == 0 for the shipped tables)
     int kind;
     uint32_t pseudo_base;            // ids from here on stand for single bytes that are no tokens (0: the table has all 256)

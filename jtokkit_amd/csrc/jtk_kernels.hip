@@ -185,6 +185,8 @@ struct SlowWin {
     }
 };
 
+constexpr int UC_ROWS = 4;                             // rows of 64 16-byte units a wave has in flight when it copies the class table
+static_assert(JTK_UC_LDS_UNITS % (64 * UC_ROWS) == 0, "the class table moves in whole groups of rows");
 constexpr int SPW = 62;                                // blocks a wave emits
 constexpr int SPLIT_BYTES = (SPLIT_THREADS / 64) * SPW * 64;   // bytes per workgroup
 
@@ -198,23 +200,19 @@ __device__ __forceinline__ uint64_t lo_from_next_lane(uint64_t v) {      // only
 template <int KIND>
 __global__ void __launch_bounds__(SPLIT_THREADS) __attribute__((amdgpu_waves_per_eu(4, 4))) k_pretok_split(JtkWork w, JtkDeviceTables t) {
     __shared__ __attribute__((aligned(16))) JtkCode4 s_tab[256];   // per-byte flags, laid out for shift-or accumulation (jtk_block_classify.h)
-    __shared__ uint32_t s_pin[2048];           // byte pairs that occur inside some table entry
+    __shared__ __attribute__((aligned(16))) uint32_t s_pin[2048];   // byte pairs that occur inside some table entry
     __shared__ uint32_t s_blk[17 * SPLIT_THREADS];   // the lanes' blocks, [dword][lane] (staged only for text outside ASCII)
-    __shared__ __attribute__((aligned(4))) uint8_t s_uc1[JTK_UC_LDS_STAGE1];
-    __shared__ uint32_t s_uc2[JTK_UC_LDS_STAGE2];
+    __shared__ uint4 s_uc[JTK_UC_LDS_UNITS];         // the Unicode class table: stage 1, then stage 2 (JtkDeviceTables::uc_lds_image)
     __shared__ uint32_t s_uc_ready;
+    static_assert(SPLIT_THREADS * 4 == 2048 && SPLIT_THREADS >= 256, "the prologue moves one 16-byte unit per thread");
 
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int64_t B = (int64_t)blockIdx.x * SPLIT_BYTES;
     const int64_t n = w.n_bytes;
-    if (tid < 256) {
-        uint32_t code = jtk_byte_code((uint32_t)tid, KIND == JTK_PAT_CL100K);
-        if ((t.special_first[tid >> 5] >> (tid & 31)) & 1u) code |= JTK_F_LT;
-        if ((t.lead_letters[tid >> 5] >> (tid & 31)) & 1u) code |= JTK_F_ULL;
-        s_tab[tid] = jtk_code4(code);
-    }
+    // both tables come ready-made from the host (jtk_abi.cpp): 16 bytes per thread each
+    if (tid < 256) reinterpret_cast<uint4*>(s_tab)[tid] = reinterpret_cast<const uint4*>(t.split_tab)[tid];
+    reinterpret_cast<uint4*>(s_pin)[tid] = reinterpret_cast<const uint4*>(t.pair_in_token)[tid];
     if (tid == 0) s_uc_ready = 0;
-    for (int i = tid; i < 2048; i += SPLIT_THREADS) s_pin[i] = t.pair_in_token[i];
     __syncthreads();
 
     // ---- this lane's block
@@ -249,23 +247,31 @@ __global__ void __launch_bounds__(SPLIT_THREADS) __attribute__((amdgpu_waves_per
         // that needs in LDS -- the Unicode class table (12 KB) and each lane's 64 bytes -- so that the per-character
         // chain is LDS reads, not global loads (the kernel runs at 2 waves per SIMD: nothing hides a global latency).
         uint32_t spill = JTK_CLS_O;
-        const bool lds_ok = t.uc_stage1_len <= JTK_UC_LDS_STAGE1 && t.uc_stage2_words <= JTK_UC_LDS_STAGE2;
+        const bool lds_ok = t.uc_lds_image != nullptr;
         // leads of characters that are letters whatever follows (CJK ideographs, Hangul, ...) need no decode: `ull`
         if (__ballot((lead & ~ull) != 0)) {                           // per wave: no workgroup barrier on the ASCII path
             if (lds_ok) {
-                // the first wave that needs the table copies it; a wave that does not see the flag yet copies it again
-                // (same values: a benign race), so no barrier is needed
-                if (*(volatile uint32_t*)&s_uc_ready == 0u) {
-                    for (uint32_t i = lane; i < t.uc_stage1_len / 4; i += 64) reinterpret_cast<uint32_t*>(s_uc1)[i] = reinterpret_cast<const uint32_t*>(t.uc.stage1)[i];
-                    for (uint32_t i = lane; i < t.uc_stage2_words; i += 64) s_uc2[i] = t.uc.stage2[i];
-                }
+                // (the block goes first: its 16 registers are free while the table moves)
 #pragma unroll
                 for (int q = 0; q < 16; q++) s_blk[q * SPLIT_THREADS + tid] = d[q];
                 s_blk[16 * SPLIT_THREADS + tid] = (uint32_t)__shfl_down((int)d[0], 1);   // lane 63: its own (a halo block: only its low bits are used)
+                // the first wave that needs the table copies it; a wave that does not see the flag yet copies it again
+                // (same values: a benign race), so no barrier is needed.  16 bytes per lane and move, UC_ROWS moves in flight.
+                if (*(volatile uint32_t*)&s_uc_ready == 0u) {
+                    const uint4* src = reinterpret_cast<const uint4*>(t.uc_lds_image);
+                    for (uint32_t i0 = 0; i0 < (uint32_t)JTK_UC_LDS_UNITS; i0 += 64 * UC_ROWS) {
+                        uint4 v[UC_ROWS];
+#pragma unroll
+                        for (int q = 0; q < UC_ROWS; q++) v[q] = src[i0 + 64u * q + (uint32_t)lane];
+#pragma unroll
+                        for (int q = 0; q < UC_ROWS; q++) s_uc[i0 + 64u * q + lane] = v[q];
+                    }
+                }
                 wave_lds_fence();
                 if (lane == 0) *(volatile uint32_t*)&s_uc_ready = 1u;
                 const LdsBlockWords bw{s_blk, tid};
-                const JtkUcTables ucl{s_uc1, s_uc2};
+                const uint8_t* uc_lds = reinterpret_cast<const uint8_t*>(s_uc);
+                const JtkUcTables ucl{uc_lds, reinterpret_cast<const uint32_t*>(uc_lds + JTK_UC_LDS_STAGE1)};
                 jtk_block_fix_nonascii(bw, ucl, lead, ull, cu, spill);
             } else {
                 const GlobalBlockWords bw{w.text, n, p0};
@@ -359,11 +365,13 @@ __global__ void __launch_bounds__(SPLIT_THREADS) __attribute__((amdgpu_waves_per
     if ((lead | cu.CONT) != 0 || __popcll(ms) < 6) {
         // The block's bytes are read again here (a cache hit) rather than kept in 16 registers through the rules above.
         uint32_t dd[16];
+        const uint8_t* text_again = w.text;
+        asm volatile("" : "+s"(text_again));       // not the first read's address kept in (spilled) registers: one add
 #pragma unroll
         for (int q = 0; q < 4; q++) {
             const int64_t p = p0 + 16 * q;
             uint4 v = make_uint4(0, 0, 0, 0);
-            if (p >= 0 && p + 16 <= n) v = *reinterpret_cast<const uint4*>(w.text + p);
+            if (p >= 0 && p + 16 <= n) v = *reinterpret_cast<const uint4*>(text_again + p);
             else if (p >= 0 && p < n) {
                 uint32_t tmp[4] = {0, 0, 0, 0};
                 for (int r = 0; r < 16; r++) if (p + r < n) tmp[r >> 2] |= (uint32_t)w.text[p + r] << (8 * (r & 3));
