@@ -524,6 +524,56 @@ int jtk_batch_decode_rows(jtk_batch* b, const void* rows, int id_bytes, int64_t 
                           const int64_t* begin_or_null, const int64_t* end_or_null, int64_t pad_id, const int64_t* stop_ids,
                           int n_stop, uint32_t flags, int64_t* cell_byte_or_null, int64_t* n_bytes);
 
+/* ---- UTF-16 in and out, on the device ---------------------------------------------------------------------------------
+ * A Java String is UTF-16: these entry points take char[] and hand back char[], so that no host codec stands in front of or
+ * behind the device passes.  Units are uint16 in the byte order of host and device (little-endian); no BOM handling: a U+FEFF
+ * is a character.  Both rules are jtokkit_amd/csrc/jtk_utf16_rules.h.
+ *   In (the rule of String.getBytes(UTF_8))   document d is units [unit_off[d], unit_off[d + 1]).  A unit below 0x80 gives 1
+ *       byte, below 0x800 2 bytes, any other non-surrogate 3; a high surrogate whose next unit is in the same document and is a
+ *       low surrogate gives the 4 bytes of the pair's code point and that low surrogate none; every other surrogate gives the
+ *       single byte '?' (a lone high, a lone low, a high that ends its document even if the next document starts with a low,
+ *       the first high of high high low).  Units outside [unit_off[0], unit_off[n_docs]) belong to no document.  doc_off[d]
+ *       (int64 [n_docs + 1]) = the bytes of the units before unit_off[d].  For the transcoded text the JTK_UNIT_UTF16 length
+ *       of every document (jtk_batch_char_index) is its original unit count, so every UTF-16 position the library hands out
+ *       after jtk_batch_encode_utf16* is an index into the caller's char[].
+ *   jtk_batch_transcode_utf16_device   runs it into buffers the batch owns: UTF-8 text, 16-byte aligned and readable to the next
+ *       multiple of 16 (what jtk_batch_encode_device demands of its input), and doc_off.  d_units must be 2-byte aligned
+ *       (JTK_ERR_INVALID_ARGUMENT otherwise); a 16-byte aligned d_units takes the fast path, which reads whole 16-byte granules
+ *       up to the one that holds the last unit; any other alignment reads the n_units units alone and gives the same result.
+ *       d_unit_off is checked on the device: it starts at or above 0, never decreases and ends at or below n_units
+ *       (JTK_ERR_INVALID_ARGUMENT otherwise, nothing written).  The call waits once, for the byte count and that check; the
+ *       write pass is queued on stream_or_null (or the batch's stream).
+ *   jtk_batch_utf8_device_result   device pointers of the last transcode (of this call or inside jtk_batch_encode_utf16*), valid
+ *       until the next transcode of the same kind on the batch.
+ *   jtk_batch_encode_utf16_device   the transcode, then jtk_batch_encode_device on the owned text on the same stream.  That
+ *       text is "the last encode's text" for every post-pass (chunk, pack, labels, character positions, token offsets) and
+ *       stays alive until the next jtk_batch_encode_utf16*.  Flags JTK_ENCODE_ORDINARY, _VALIDATE_UTF8, _COUNT_ONLY and
+ *       _ALLOW_SPECIAL are accepted; JTK_ENCODE_TO_HOST and JTK_ENCODE_COMPACT_IDS give JTK_ERR_INVALID_ARGUMENT (the result
+ *       stays on the device: jtk_batch_fetch, jtk_batch_compact).
+ *   jtk_batch_encode_utf16   the same for host buffers; n_units = unit_off[n_docs].  The offsets are validated on the host
+ *       before anything is launched; then ONE upload and the device call: it is not chunk-pipelined as jtk_batch_encode is.
+ *   Out (the rule of new String(bytes, UTF_8))   jtk_batch_decode_utf16 is a post-pass over the LAST decode of the batch, flat
+ *       or rows: sequence q, bytes [byte_off[q], byte_off[q + 1]), becomes units [unit_off[q], unit_off[q + 1]).  Well-formed
+ *       characters (Unicode Table 3-7) give their unit, or a surrogate pair for a 4-byte character; every maximal ill-formed
+ *       subpart gives one U+FFFD: a lead with the continuation bytes that its row of the table accepts, up to the first byte it
+ *       rejects or the end of the sequence; any other byte on its own (a stray continuation byte, C0, C1, F5..FF).  A character
+ *       cut by a sequence edge gives U+FFFD on both sides.  This is CPython's bytes.decode("utf-8", "replace"), the codec that
+ *       stands for new String(bytes, UTF_8) here (no JVM is at hand).  status is the decode's: a sequence with an unknown id
+ *       keeps JTK_ERR_UNKNOWN_TOKEN and transcodes what was decoded.  The call waits as a decode does (once for the size, once
+ *       at the end) and leaves units (uint16) and unit_off (int64 [n_seqs + 1]) in buffers the batch owns, valid until the next
+ *       jtk_batch_decode_utf16; a new decode drops them.  _fetch and _device_result mirror jtk_batch_decode_fetch and
+ *       jtk_batch_decode_device_result. */
+int jtk_batch_transcode_utf16_device(jtk_batch* b, const uint16_t* d_units, const int64_t* d_unit_off, int64_t n_docs, int64_t n_units,
+                                     void* stream_or_null, int64_t* n_bytes);
+int jtk_batch_utf8_device_result(jtk_batch* b, const uint8_t** d_utf8, const int64_t** d_doc_off, int64_t* n_bytes);
+int jtk_batch_encode_utf16_device(jtk_batch* b, const uint16_t* d_units, const int64_t* d_unit_off, int64_t n_docs, int64_t n_units,
+                                  uint32_t flags, void* stream_or_null, int64_t* n_tokens);
+int jtk_batch_encode_utf16(jtk_batch* b, const uint16_t* units, const int64_t* unit_off, int64_t n_docs, uint32_t flags,
+                           int64_t* n_tokens);
+int jtk_batch_decode_utf16(jtk_batch* b, void* stream_or_null, int64_t* n_units);
+int jtk_batch_decode_utf16_fetch(jtk_batch* b, uint16_t* units, int64_t units_cap, int64_t* unit_off, int32_t* status);
+int jtk_batch_decode_utf16_device_result(jtk_batch* b, const uint16_t** d_units, const int64_t** d_unit_off, const int32_t** d_status);
+
 /* ---- per-call service: many caller threads, one device batch at a time -------------------------------------------
  * The reference is called per document from many threads (api/Encoding.java; its benchmark is one task per document on a
  * pool of 1..64 threads, benchmark/.../AbstractMultiThreadedBenchmark.java:35-45).  A jtk_service coalesces such callers:

@@ -113,6 +113,13 @@ SIGNATURES = {
     "jtk_batch_decode_rows_device": (C.c_int, [_p, _p, C.c_int, _i64, _i64, _i64, _p, _p, _i64, _p, C.c_int, C.c_uint32, _p, _p,
                                                C.POINTER(_i64)]),
     "jtk_batch_decode_rows": (C.c_int, [_p, _p, C.c_int, _i64, _i64, _i64, _p, _p, _i64, _p, C.c_int, C.c_uint32, _p, C.POINTER(_i64)]),
+    "jtk_batch_transcode_utf16_device": (C.c_int, [_p, _p, _p, _i64, _i64, _p, C.POINTER(_i64)]),
+    "jtk_batch_utf8_device_result": (C.c_int, [_p, C.POINTER(_p), C.POINTER(_p), C.POINTER(_i64)]),
+    "jtk_batch_encode_utf16_device": (C.c_int, [_p, _p, _p, _i64, _i64, C.c_uint32, _p, C.POINTER(_i64)]),
+    "jtk_batch_encode_utf16": (C.c_int, [_p, _p, _p, _i64, C.c_uint32, C.POINTER(_i64)]),
+    "jtk_batch_decode_utf16": (C.c_int, [_p, _p, C.POINTER(_i64)]),
+    "jtk_batch_decode_utf16_fetch": (C.c_int, [_p, _p, _i64, _p, _p]),
+    "jtk_batch_decode_utf16_device_result": (C.c_int, [_p, C.POINTER(_p), C.POINTER(_p), C.POINTER(_p)]),
     "jtk_service_create": (C.c_int, [_p, C.c_int, C.POINTER(_p)]),
     "jtk_service_destroy": (None, [_p]),
     "jtk_service_encode": (C.c_int, [_p, _p, _i64, C.c_uint32, _i64, _p, _i64, C.POINTER(_i64), C.POINTER(C.c_int)]),

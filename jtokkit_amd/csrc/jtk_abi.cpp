@@ -166,6 +166,16 @@ struct jtk_batch {
     int64_t* cp_dunit = nullptr;
     int cp_unit = -1;
     hipStream_t cp_stream = nullptr;     // stream of the last call that built or read the index
+    // UTF-16 in and out (jtk_utf16.hip).  E: scratch (hdr | tile_off | tile counts | sub), the host form's input (units |
+    // offsets), and two results, each UTF-8 text + doc_off: u16_tx_* of the last jtk_batch_transcode_utf16_device (valid until the
+    // next one), u16_enc_* of the last jtk_batch_encode_utf16* (the encode's text: alive until the next such encode, whatever is
+    // transcoded in between).  D: scratch and the units + unit_off of the last jtk_batch_decode_utf16.
+    DevBuf u16_scratch, u16_in, u16_tx_text, u16_tx_off, u16_enc_text, u16_enc_off, u16_dscratch, u16_units, u16_unit_off;
+    const uint8_t* u16_last_text = nullptr;   // jtk_batch_utf8_device_result: the last transcode of either kind
+    const int64_t* u16_last_off = nullptr;
+    int64_t u16_last_bytes = 0, u16_dec_units = 0, u16_dec_seqs = 0;
+    bool have_u16 = false, have_u16_dec = false;
+    hipStream_t u16_stream = nullptr;    // stream of the last transcode: the next one, on another stream, reuses its scratch behind it
     // JTK_ENCODE_ALLOW_SPECIAL (jtk_special.hip): the allowed set per literal of the encoding (a new batch allows all) and its
     // device copy; find scratch (hdr | the stitched status | per-block counts), candidates and sub-documents, the stitched result
     std::vector<uint8_t> sp_allowed;
@@ -456,7 +466,8 @@ void jtk_batch_destroy(jtk_batch* b) {
     DevBuf* bufs[] = {&b->in_text, &b->in_off, &b->in_pieces, &b->out, &b->plan, &b->dec_in_ids, &b->dec_in_off,
                       &b->dec_zero, &b->dec_tile, &b->dec_pre, &b->dec_out, &b->dec_byte_off, &b->dec_first, &b->dec_in_win, &b->dec_cell, &b->trunc_kept, &b->trunc_flag,
                       &b->mt_scratch, &b->mt_gather, &b->ck_scratch, &b->ck_tiles, &b->ck_rec, &b->pk_scratch, &b->sp_lits, &b->sp_find,
-                      &b->sp_cand, &b->sp_out, &b->cp_buf};
+                      &b->sp_cand, &b->sp_out, &b->cp_buf, &b->u16_scratch, &b->u16_in, &b->u16_tx_text, &b->u16_tx_off, &b->u16_enc_text, &b->u16_enc_off,
+                      &b->u16_dscratch, &b->u16_units, &b->u16_unit_off};
     for (DevBuf* d : bufs) d->release();
     if (b->h_sp) (void)hipHostFree(b->h_sp);
     for (hipEvent_t ev : b->prof_ev) (void)hipEventDestroy(ev);
@@ -1440,6 +1451,7 @@ int jtk_batch_decode_device(jtk_batch* b, const int32_t* d_ids, const int64_t* d
     HIP_TRY(hipStreamSynchronize(s));
     b->dec_total = total;
     b->have_decode = true;
+    b->have_u16_dec = false;
     if (n_bytes) *n_bytes = total;
     return JTK_OK;
 }
@@ -1553,6 +1565,7 @@ int jtk_batch_decode_rows_device(jtk_batch* b, const void* d_rows, int id_bytes,
     b->dwork.n_seqs = n_rows; b->dwork.out = w.out; b->dwork.byte_off = w.byte_off; b->dwork.status = w.status;
     b->dec_total = total;
     b->have_decode = true;
+    b->have_u16_dec = false;
     if (n_bytes) *n_bytes = total;
     return JTK_OK;
 }
@@ -2359,6 +2372,152 @@ int jtk_batch_token_char_offsets(jtk_batch* b, int unit, int64_t* d_begin, int64
     if ((rc = cp_index(b, unit, s))) return rc;
     jtk_launch_charpos_tokens(b->ck, b->cp, b->cp_dunit, d_begin, d_end_or_null, s);
     HIP_TRY(hipGetLastError());
+    return JTK_OK;
+}
+
+// ---- UTF-16 in and out (jtk_utf16.hip; the rules are jtk_utf16_rules.h) -------------------------------------------------------
+// E into (text, off) of the batch: count, the one wait (size of the output, offsets check), write
+static int u16_transcode(jtk_batch* b, DevBuf& text, DevBuf& off, const uint16_t* d_units, const int64_t* d_unit_off, int64_t n_docs,
+                         int64_t n_units, hipStream_t s, int64_t* n_bytes) {
+    if (!b || n_docs < 0 || n_units < 0 || (n_units > 0 && !d_units) || !d_unit_off) return fail(JTK_ERR_INVALID_ARGUMENT, "bad arguments");
+    if ((uintptr_t)d_units & 1u) return fail(JTK_ERR_INVALID_ARGUMENT, "d_units must be 2-byte aligned");
+    if ((uintptr_t)d_unit_off & 7u) return fail(JTK_ERR_INVALID_ARGUMENT, "unaligned array (8-byte int64)");
+    if (n_units >= (int64_t)1 << 35) return fail(JTK_ERR_INVALID_ARGUMENT, "batch too large (32 Gi units per call at most)");
+    HIP_TRY(hipSetDevice(b->enc->device));
+    JtkU16EncWork w{};
+    w.units = d_units; w.n_units = n_units; w.unit_off = d_unit_off; w.n_docs = n_docs;
+    w.n_tiles = (n_units + JTK_U16_E_TILE - 1) / JTK_U16_E_TILE;
+    const size_t nt = (size_t)w.n_tiles;
+    const size_t o_cnt = 16 + (nt + 1) * 8, o_sub = o_cnt + align_up(nt * 4 + 4, 16);
+    int rc;
+    if ((rc = b->u16_scratch.ensure(o_sub + nt * JTK_U16_LANES * 2 + 16)) || (rc = off.ensure(((size_t)n_docs + 1) * 8))) return rc;
+    uint8_t* z = (uint8_t*)b->u16_scratch.p;
+    w.hdr = (int64_t*)z; w.tile_off = (int64_t*)(z + 16); w.tile_cnt = (uint32_t*)(z + o_cnt); w.sub = (uint16_t*)(z + o_sub);
+    w.doc_off = (int64_t*)off.p;
+    const bool aligned = ((uintptr_t)d_units & 15u) == 0;
+    b->have_u16 = false;
+    if (b->u16_stream && (rc = ck_order(b, b->u16_stream, s))) return rc;    // (the last write pass still reads sub and tile_off)
+    b->u16_stream = s;
+    HIP_TRY(hipMemsetAsync(w.hdr, 0, 16, s));
+    jtk_launch_u16_enc_count(w, aligned, s);
+    HIP_TRY(hipGetLastError());
+    int64_t hdr[2] = {0, 0};
+    HIP_TRY(hipMemcpyAsync(hdr, w.hdr, 16, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if (hdr[1] != 0) return fail(JTK_ERR_INVALID_ARGUMENT, "unit_off must start at or above 0, never decrease and end at or below n_units");
+    if ((rc = text.ensure((size_t)hdr[0] + 64))) return rc;
+    w.out = (uint8_t*)text.p;
+    jtk_launch_u16_enc_write(w, aligned, s);
+    HIP_TRY(hipGetLastError());
+    b->u16_last_text = w.out; b->u16_last_off = w.doc_off; b->u16_last_bytes = hdr[0];
+    b->have_u16 = true;
+    if (n_bytes) *n_bytes = hdr[0];
+    return JTK_OK;
+}
+
+int jtk_batch_transcode_utf16_device(jtk_batch* b, const uint16_t* d_units, const int64_t* d_unit_off, int64_t n_docs, int64_t n_units,
+                                     void* stream_or_null, int64_t* n_bytes) {
+    if (!b) return fail(JTK_ERR_INVALID_ARGUMENT, "batch is NULL");
+    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    return u16_transcode(b, b->u16_tx_text, b->u16_tx_off, d_units, d_unit_off, n_docs, n_units, s, n_bytes);
+}
+
+int jtk_batch_utf8_device_result(jtk_batch* b, const uint8_t** d_utf8, const int64_t** d_doc_off, int64_t* n_bytes) {
+    if (!b || !b->have_u16) return fail(JTK_ERR_INVALID_ARGUMENT, "no UTF-16 transcode has run on this batch");
+    if (d_utf8) *d_utf8 = b->u16_last_text;
+    if (d_doc_off) *d_doc_off = b->u16_last_off;
+    if (n_bytes) *n_bytes = b->u16_last_bytes;
+    return JTK_OK;
+}
+
+static int u16_encode_flags(uint32_t flags) {
+    if (flags & (JTK_ENCODE_TO_HOST | JTK_ENCODE_COMPACT_IDS))
+        return fail(JTK_ERR_INVALID_ARGUMENT, "JTK_ENCODE_TO_HOST and JTK_ENCODE_COMPACT_IDS are not for the UTF-16 entry points (the result stays on the device: jtk_batch_fetch, jtk_batch_compact)");
+    return JTK_OK;
+}
+
+int jtk_batch_encode_utf16_device(jtk_batch* b, const uint16_t* d_units, const int64_t* d_unit_off, int64_t n_docs, int64_t n_units,
+                                  uint32_t flags, void* stream_or_null, int64_t* n_tokens) {
+    if (!b) return fail(JTK_ERR_INVALID_ARGUMENT, "batch is NULL");
+    int rc;
+    if ((rc = u16_encode_flags(flags))) return rc;
+    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    int64_t n_bytes = 0;
+    if ((rc = u16_transcode(b, b->u16_enc_text, b->u16_enc_off, d_units, d_unit_off, n_docs, n_units, s, &n_bytes))) return rc;
+    return jtk_batch_encode_device(b, (const uint8_t*)b->u16_enc_text.p, (const int64_t*)b->u16_enc_off.p, n_docs, n_bytes, flags, (void*)s, n_tokens);
+}
+
+int jtk_batch_encode_utf16(jtk_batch* b, const uint16_t* units, const int64_t* unit_off, int64_t n_docs, uint32_t flags, int64_t* n_tokens) {
+    if (!b || n_docs < 0 || !unit_off) return fail(JTK_ERR_INVALID_ARGUMENT, "bad arguments");
+    int rc;
+    if ((rc = u16_encode_flags(flags))) return rc;
+    if (unit_off[0] < 0) return fail(JTK_ERR_INVALID_ARGUMENT, "unit_off must not be negative");
+    for (int64_t d = 0; d < n_docs; d++)
+        if (unit_off[d + 1] < unit_off[d]) return fail(JTK_ERR_INVALID_ARGUMENT, "unit_off must be non-decreasing");
+    const int64_t n_units = unit_off[n_docs];                             // (the units behind the last document are not read)
+    if (n_units > 0 && !units) return fail(JTK_ERR_INVALID_ARGUMENT, "units is NULL");
+    if (n_units >= (int64_t)1 << 35) return fail(JTK_ERR_INVALID_ARGUMENT, "batch too large (32 Gi units per call at most)");
+    HIP_TRY(hipSetDevice(b->enc->device));
+    // one upload: units | offsets, then the device call (not chunk-pipelined)
+    const size_t o_off = align_up((size_t)n_units * 2 + 16, 256);
+    if ((rc = b->u16_in.ensure(o_off + ((size_t)n_docs + 1) * 8))) return rc;
+    uint8_t* z = (uint8_t*)b->u16_in.p;
+    if (n_units > 0) HIP_TRY(hipMemcpyAsync(z, units, (size_t)n_units * 2, hipMemcpyHostToDevice, b->stream));
+    HIP_TRY(hipMemcpyAsync(z + o_off, unit_off, ((size_t)n_docs + 1) * 8, hipMemcpyHostToDevice, b->stream));
+    int64_t nt = 0;
+    if ((rc = jtk_batch_encode_utf16_device(b, (const uint16_t*)z, (const int64_t*)(z + o_off), n_docs, n_units, flags, nullptr, &nt))) return rc;
+    if (n_tokens) *n_tokens = nt;
+    return JTK_OK;
+}
+
+int jtk_batch_decode_utf16(jtk_batch* b, void* stream_or_null, int64_t* n_units) {
+    if (!b || !b->have_decode) return fail(JTK_ERR_INVALID_ARGUMENT, "no decode has run on this batch");
+    HIP_TRY(hipSetDevice(b->enc->device));
+    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    JtkU16DecWork w{};
+    w.text = b->dwork.out; w.n_bytes = b->dec_total; w.byte_off = b->dwork.byte_off; w.n_seqs = b->dwork.n_seqs;
+    w.n_tiles = (w.n_bytes + JTK_U16_D_TILE - 1) / JTK_U16_D_TILE;
+    const size_t nt = (size_t)w.n_tiles;
+    const size_t o_cnt = 16 + (nt + 1) * 8, o_sub = o_cnt + align_up(nt * 4 + 4, 16);
+    int rc;
+    if ((rc = b->u16_dscratch.ensure(o_sub + nt * JTK_U16_LANES * 2 + 16)) || (rc = b->u16_unit_off.ensure(((size_t)w.n_seqs + 1) * 8))) return rc;
+    uint8_t* z = (uint8_t*)b->u16_dscratch.p;
+    w.hdr = (int64_t*)z; w.tile_off = (int64_t*)(z + 16); w.tile_cnt = (uint32_t*)(z + o_cnt); w.sub = (uint16_t*)(z + o_sub);
+    w.unit_off = (int64_t*)b->u16_unit_off.p;
+    b->have_u16_dec = false;
+    jtk_launch_u16_dec_count(w, s);
+    HIP_TRY(hipGetLastError());
+    int64_t total = 0;
+    HIP_TRY(hipMemcpyAsync(&total, w.hdr, 8, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    if ((rc = b->u16_units.ensure((size_t)total * 2 + 64))) return rc;
+    w.out = (uint16_t*)b->u16_units.p;
+    jtk_launch_u16_dec_write(w, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s));                                     // (as decode: the fetch copies on no stream)
+    b->u16_dec_units = total; b->u16_dec_seqs = w.n_seqs;
+    b->have_u16_dec = true;
+    if (n_units) *n_units = total;
+    return JTK_OK;
+}
+
+int jtk_batch_decode_utf16_fetch(jtk_batch* b, uint16_t* units, int64_t units_cap, int64_t* unit_off, int32_t* status) {
+    if (!b || !b->have_u16_dec) return fail(JTK_ERR_INVALID_ARGUMENT, "no jtk_batch_decode_utf16 has run on the last decode of this batch");
+    HIP_TRY(hipSetDevice(b->enc->device));
+    if (units) {
+        if (units_cap < b->u16_dec_units) return fail(JTK_ERR_CAPACITY, "output buffer too small");
+        if (b->u16_dec_units > 0) HIP_TRY(hipMemcpy(units, b->u16_units.p, (size_t)b->u16_dec_units * 2, hipMemcpyDeviceToHost));
+    }
+    if (unit_off) HIP_TRY(hipMemcpy(unit_off, b->u16_unit_off.p, ((size_t)b->u16_dec_seqs + 1) * 8, hipMemcpyDeviceToHost));
+    if (status && b->u16_dec_seqs > 0) HIP_TRY(hipMemcpy(status, b->dwork.status, (size_t)b->u16_dec_seqs * 4, hipMemcpyDeviceToHost));
+    return JTK_OK;
+}
+
+int jtk_batch_decode_utf16_device_result(jtk_batch* b, const uint16_t** d_units, const int64_t** d_unit_off, const int32_t** d_status) {
+    if (!b || !b->have_u16_dec) return fail(JTK_ERR_INVALID_ARGUMENT, "no jtk_batch_decode_utf16 has run on the last decode of this batch");
+    if (d_units) *d_units = (const uint16_t*)b->u16_units.p;
+    if (d_unit_off) *d_unit_off = (const int64_t*)b->u16_unit_off.p;
+    if (d_status) *d_status = b->dwork.status;
     return JTK_OK;
 }
 

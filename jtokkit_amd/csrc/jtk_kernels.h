@@ -11,6 +11,7 @@
 #include "jtk_stage_rules.h"
 #include "jtk_decode_rows_rules.h"
 #include "jtk_charpos_rules.h"
+#include "jtk_utf16_rules.h"
 
 #define JTK_SPLIT_TILE 4096      // bytes per pretok_split workgroup
 #define JTK_SPLIT_HALO 64
@@ -338,6 +339,39 @@ void jtk_launch_charpos_select(const JtkCharIndex& ix, const int64_t* doc_off, c
                                const int64_t* char_pos, int64_t n, int64_t* byte_pos, hipStream_t s);
 void jtk_launch_charpos_tokens(const JtkChunkWork& w, const JtkCharIndex& ix, const int64_t* dunit, int64_t* begin, int64_t* end,
                                hipStream_t s);
+// UTF-16 in and out (jtk_utf16.hip; the rules are jtk_utf16_rules.h).  E: the documents unit_off[0 .. n_docs] of units[n_units]
+// to UTF-8 in out, doc_off[n_docs + 1].  D: the sequences byte_off[0 .. n_seqs] of text[n_bytes] (16-byte aligned, readable to
+// the next multiple of 16) to UTF-16 units in out, unit_off[n_seqs + 1].  Tiles of 256 lanes: tile_cnt [n_tiles] (scratch),
+// tile_off [n_tiles + 1], sub [n_tiles * 256].  count: sub, tile_off and hdr[0] = the size of the output (E: hdr[1], zeroed by
+// the caller, != 0 for bad offsets); write (needs out, 16-byte aligned): the output and its offsets.
+struct JtkU16EncWork {
+    const uint16_t* units;
+    int64_t n_units;
+    const int64_t* unit_off;
+    int64_t n_docs, n_tiles;
+    uint32_t* tile_cnt;
+    int64_t* tile_off;
+    uint16_t* sub;
+    int64_t* hdr;
+    uint8_t* out;
+    int64_t* doc_off;
+};
+struct JtkU16DecWork {
+    const uint8_t* text;
+    int64_t n_bytes;
+    const int64_t* byte_off;
+    int64_t n_seqs, n_tiles;
+    uint32_t* tile_cnt;
+    int64_t* tile_off;
+    uint16_t* sub;
+    int64_t* hdr;
+    uint16_t* out;
+    int64_t* unit_off;
+};
+void jtk_launch_u16_enc_count(const JtkU16EncWork& w, bool aligned, hipStream_t s);   // aligned: units is 16-byte aligned
+void jtk_launch_u16_enc_write(const JtkU16EncWork& w, bool aligned, hipStream_t s);
+void jtk_launch_u16_dec_count(const JtkU16DecWork& w, hipStream_t s);
+void jtk_launch_u16_dec_write(const JtkU16DecWork& w, hipStream_t s);
 // Compact ids (jtk_compact.hip; the rule is jtk_compact_rules.h): the range [t0, t1) of the int32 stream `ids` (indexed from
 // token 0) into a uint16 plane and a plane of hb bits per token whose entry 0 is token `origin` (a multiple of 32; 0 for whole
 // planes).  Restarts at t0 rounded down to a multiple of 32 and rewrites the words there whole.  d_total != NULL: the range ends

@@ -579,6 +579,72 @@ class Batch:
         _check(N.lib().jtk_batch_decode_device_result(self._h, *(C.byref(x) for x in p)))
         return tuple(x.value for x in p)
 
+    # ---- UTF-16 in and out (device; the rules are jtk_utf16_rules.h) --------------------------------------
+    def transcode_utf16_device(self, d_units_ptr, d_unit_off_ptr, n_docs, n_units, stream=None):
+        """jtk_batch_transcode_utf16_device: uint16 units and int64 offsets on the device -> the byte count of the UTF-8 text the
+        batch now owns (utf8_device_result)."""
+        nb = C.c_int64(0)
+        _check(N.lib().jtk_batch_transcode_utf16_device(self._h, d_units_ptr, d_unit_off_ptr, n_docs, n_units, stream, C.byref(nb)))
+        return nb.value
+
+    def utf8_device_result(self):
+        """jtk_batch_utf8_device_result: (device pointer of the UTF-8 text, of doc_off int64 [n_docs + 1], n_bytes) of the last
+        transcode."""
+        a, o, nb = C.c_void_p(), C.c_void_p(), C.c_int64(0)
+        _check(N.lib().jtk_batch_utf8_device_result(self._h, C.byref(a), C.byref(o), C.byref(nb)))
+        return a.value, o.value, nb.value
+
+    @staticmethod
+    def _utf16_flags(ordinary, allow_special, validate, count_only, to_host):
+        return ((N.JTK_ENCODE_ORDINARY if ordinary else 0) | (N.JTK_ENCODE_ALLOW_SPECIAL if allow_special else 0)
+                | (N.JTK_ENCODE_VALIDATE_UTF8 if validate else 0) | (N.JTK_ENCODE_COUNT_ONLY if count_only else 0)
+                | (N.JTK_ENCODE_TO_HOST if to_host else 0))
+
+    def encode_utf16_device(self, d_units_ptr, d_unit_off_ptr, n_docs, n_units, ordinary=False, stream=None, sync=True,
+                            allow_special=False, validate=False, count_only=False, to_host=False):
+        """jtk_batch_encode_utf16_device: the transcode, then the encode of the owned text (to_host: the library refuses it)."""
+        nt = C.c_int64(0)
+        flags = self._utf16_flags(ordinary, allow_special, validate, count_only, to_host)
+        self._count_only = count_only
+        _check(N.lib().jtk_batch_encode_utf16_device(self._h, d_units_ptr, d_unit_off_ptr, n_docs, n_units, flags, stream,
+                                                     C.byref(nt) if sync else None))
+        return nt.value if sync else None
+
+    def encode_utf16_host(self, units, unit_off, ordinary=False, allow_special=False, validate=False, count_only=False, to_host=False):
+        """jtk_batch_encode_utf16: numpy uint16 units and int64 offsets in host memory -> the token total."""
+        units = np.ascontiguousarray(units, dtype=np.uint16)
+        unit_off = np.ascontiguousarray(unit_off, dtype=np.int64)
+        if len(unit_off) < 1 or unit_off[-1] > len(units):
+            # (the C entry takes n_units = unit_off[n_docs]: only here is the length of the array known)
+            raise ValueError("unit_off needs n_docs + 1 entries and must end at or below len(units)")
+        nt = C.c_int64(0)
+        flags = self._utf16_flags(ordinary, allow_special, validate, count_only, to_host)
+        self._count_only = count_only
+        _check(N.lib().jtk_batch_encode_utf16(self._h, units.ctypes.data if len(units) else None, unit_off.ctypes.data, len(unit_off) - 1,
+                                              flags, C.byref(nt)))
+        return nt.value
+
+    def decode_utf16(self, stream=None):
+        """jtk_batch_decode_utf16 over the last decode (flat or rows) -> the unit total (result on the device)."""
+        nu = C.c_int64(0)
+        _check(N.lib().jtk_batch_decode_utf16(self._h, stream, C.byref(nu)))
+        self._dec16_shape = (nu.value, self._dec_shape[1])
+        return nu.value
+
+    def decode_utf16_fetch(self):
+        nu, ns = self._dec16_shape
+        units = np.empty(max(nu, 1), dtype=np.uint16)
+        unit_off = np.empty(ns + 1, dtype=np.int64)
+        status = np.zeros(max(ns, 1), dtype=np.int32)
+        _check(N.lib().jtk_batch_decode_utf16_fetch(self._h, units.ctypes.data, nu, unit_off.ctypes.data, status.ctypes.data))
+        return units[:nu], unit_off, status[:ns]
+
+    def decode_utf16_device_result(self):
+        """jtk_batch_decode_utf16_device_result: device pointers (units, unit_off, status)."""
+        p = [C.c_void_p() for _ in range(3)]
+        _check(N.lib().jtk_batch_decode_utf16_device_result(self._h, *(C.byref(x) for x in p)))
+        return tuple(x.value for x in p)
+
     def set_profiling(self, on=True):
         _check(N.lib().jtk_batch_set_profiling(self._h, 1 if on else 0))
 
@@ -1455,6 +1521,130 @@ class HipEncoding:
             raise EncodingError(int(status[q]), "Unknown token for decoding (row %d)" % q)
         raw = out.tobytes()
         return [raw[byte_off[q]:byte_off[q + 1]] for q in range(rows.shape[0])]
+
+    # ---- UTF-16 in and out: a Java String's char[] crosses as it is (the rules are jtk_utf16_rules.h) -------------
+    def encode_batch_utf16(self, units, unit_off, ordinary=False, allowed_special=None):
+        """numpy uint16 units (a String's chars, documents back to back) and int64 unit_off [n_docs + 1] -> BatchResult: the
+        tokens of String.getBytes(UTF_8) of every document, transcoded and encoded on the device (jtk_batch_encode_utf16: one
+        upload, not chunk-pipelined).  allowed_special: as for encode_batch."""
+        if self._host_pattern is not None:
+            raise ValueError("encode_batch_utf16: the device cannot run this encoding's custom split pattern")
+        b = self._b()
+        b.encode_utf16_host(units, unit_off, ordinary, allow_special=self._allow(b, allowed_special))
+        return b.fetch()
+
+    def _check_utf16_inputs(self, what, units, unit_off):
+        import torch
+        if self._host_pattern is not None:
+            raise ValueError("%s: the device cannot run this encoding's custom split pattern" % what)
+        dev = N.lib().jtk_encoding_device(self._h)
+        for name, t, dt in (("units", units, torch.uint16), ("unit_off", unit_off, torch.int64)):
+            if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != dt or t.dim() != 1:
+                raise ValueError("%s must be a 1-d CUDA tensor of %s" % (name, dt))
+            if t.device.index != dev:
+                raise ValueError("%s is on cuda:%s, the encoding on cuda:%d" % (name, t.device.index, dev))
+            if not t.is_contiguous():
+                raise ValueError("%s must be contiguous" % name)
+        if unit_off.numel() < 1:
+            raise ValueError("unit_off needs n_docs + 1 entries")
+
+    def _torch_stream(self, b, device):
+        """(current stream, side stream or None, raw handle): the work goes to torch's current stream, or, when that is the legacy
+        default stream, to the batch's own stream explicitly (as in chunk_batch_device)."""
+        import torch
+        cur = torch.cuda.current_stream(device)
+        side = None
+        if cur.cuda_stream == 0:
+            side = torch.cuda.ExternalStream(b.stream(), device=device)
+            side.wait_stream(cur)
+        return cur, side, (side or cur).cuda_stream
+
+    def transcode_utf16_device(self, units, unit_off):
+        """Device-resident UTF-16 (units CUDA torch.uint16, any 2-byte alignment; unit_off CUDA torch.int64 [n_docs + 1]) ->
+        (utf8 uint8 [n_bytes], doc_off int64 [n_docs + 1]) as CUDA tensors written on torch.cuda.current_stream(): the rule of
+        String.getBytes(UTF_8) per document (jtk_batch_transcode_utf16_device).  Waits once, for the byte count and the check of
+        the offsets (EncodingError JTK_ERR_INVALID_ARGUMENT for offsets that decrease or leave [0, n_units])."""
+        import torch
+        self._check_utf16_inputs("transcode_utf16_device", units, unit_off)
+        device, nd = units.device, unit_off.numel() - 1
+        b = self._b()
+        cur, side, stream = self._torch_stream(b, device)
+        nb = b.transcode_utf16_device(units.data_ptr() if units.numel() else None, unit_off.data_ptr(), nd, units.numel(), stream)
+        utf8 = torch.empty(nb, dtype=torch.uint8, device=device)
+        doc_off = torch.empty(nd + 1, dtype=torch.int64, device=device)
+        p_text, p_off, _ = b.utf8_device_result()
+        if nb:
+            _copy_d2d(utf8.data_ptr(), p_text, nb, stream)
+        _copy_d2d(doc_off.data_ptr(), p_off, (nd + 1) * 8, stream)
+        if side is not None:
+            cur.wait_stream(side)
+        return utf8, doc_off
+
+    def encode_batch_utf16_device(self, units, unit_off, ordinary=False, allowed_special=None):
+        """Encodes device-resident UTF-16 (as transcode_utf16_device takes it) -> (tokens int32 [n_tokens], tok_off int64
+        [n_docs + 1], status int32 [n_docs], doc_off int64 [n_docs + 1]) as CUDA tensors written on torch.cuda.current_stream().
+        doc_off are the documents' byte offsets in the transcoded text, which the batch keeps as the encode's text for the
+        post-passes (chunk, pack, character positions: positions in "utf16" index the caller's units).  Waits for the byte
+        count and the token count."""
+        import torch
+        self._check_utf16_inputs("encode_batch_utf16_device", units, unit_off)
+        b = self._b()
+        allow = self._allow(b, allowed_special)
+        device, nd = units.device, unit_off.numel() - 1
+        cur, side, stream = self._torch_stream(b, device)
+        nt = b.encode_utf16_device(units.data_ptr() if units.numel() else None, unit_off.data_ptr(), nd, units.numel(), ordinary,
+                                   stream=stream, allow_special=allow)
+        tokens = torch.empty(nt, dtype=torch.int32, device=device)
+        tok_off = torch.empty(nd + 1, dtype=torch.int64, device=device)
+        status = torch.empty(nd, dtype=torch.int32, device=device)
+        doc_off = torch.empty(nd + 1, dtype=torch.int64, device=device)
+        p_tok, p_off, p_status = b.device_result()
+        if nt:
+            _copy_d2d(tokens.data_ptr(), p_tok, nt * 4, stream)
+        _copy_d2d(tok_off.data_ptr(), p_off, (nd + 1) * 8, stream)
+        if nd:
+            _copy_d2d(status.data_ptr(), p_status, nd * 4, stream)
+        _copy_d2d(doc_off.data_ptr(), b.utf8_device_result()[1], (nd + 1) * 8, stream)
+        if side is not None:
+            cur.wait_stream(side)
+        return tokens, tok_off, status, doc_off
+
+    def decode_batch_utf16(self, token_lists, strict=True):
+        """List of token-id lists -> list of str: new String(decodeBytes(tokens), UTF_8) for each, decoded and transcoded to
+        UTF-16 units on the device (jtk_batch_decode_utf16: one U+FFFD per maximal ill-formed subpart).  strict: as decode_batch."""
+        seq_off = np.zeros(len(token_lists) + 1, dtype=np.int64)
+        if token_lists:
+            np.cumsum([len(t) for t in token_lists], out=seq_off[1:])
+        ids = np.fromiter((i for t in token_lists for i in t), dtype=np.int32, count=int(seq_off[-1]))
+        b = self._b()
+        b.decode_host(ids, seq_off)
+        b.decode_utf16()
+        units, unit_off, status = b.decode_utf16_fetch()
+        if strict and len(status) and status.min() < 0:
+            q = int(np.argmin(status))
+            raise EncodingError(int(status[q]), "Unknown token for decoding (list %d)" % q)
+        raw = units.tobytes()
+        return [raw[2 * unit_off[q]:2 * unit_off[q + 1]].decode("utf-16-le", "surrogatepass") for q in range(len(token_lists))]
+
+    def decode_rows_utf16_device(self, rows, begin=None, end=None, pad_id=None, stop=(), keep_stop=False, cell_offsets=False):
+        """decode_rows_device, then the rows' bytes as UTF-16 units (jtk_batch_decode_utf16).  Returns its dict with, added, units
+        uint16 and unit_off int64 [n_rows + 1] (CUDA tensors written on torch.cuda.current_stream()): row r is
+        units[unit_off[r]:unit_off[r + 1]], new String(bytes of row r, UTF_8).  status is the decode's."""
+        import torch
+        out = self.decode_rows_device(rows, begin, end, pad_id, stop, keep_stop, cell_offsets)
+        device, nr = rows.device, rows.shape[0]
+        b = self._b()
+        cur, side, stream = self._torch_stream(b, device)
+        nu = b.decode_utf16(stream)
+        out["units"] = torch.empty(nu, dtype=torch.uint16, device=device)
+        out["unit_off"] = torch.empty(nr + 1, dtype=torch.int64, device=device)
+        p_units, p_off, _ = b.decode_utf16_device_result()
+        if nu:
+            _copy_d2d(out["units"].data_ptr(), p_units, nu * 2, stream)
+        _copy_d2d(out["unit_off"].data_ptr(), p_off, (nr + 1) * 8, stream)
+        if side is not None:
+            cur.wait_stream(side)
+        return out
 
     def vocab_size(self):
         return N.lib().jtk_encoding_vocab_size(self._h)
