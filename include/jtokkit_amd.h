@@ -344,6 +344,39 @@ int jtk_batch_chunk_rows(jtk_batch* b, int32_t pad_id, int32_t* d_rows, void* st
  * same encode; without one it synchronises once for the token count.  Not after a count-only encode. */
 int jtk_batch_token_offsets(jtk_batch* b, int64_t* d_byte_pos, void* stream_or_null);
 
+/* ---- chunks that end at paragraph, line, sentence and word boundaries, on the device -----------------------------------
+ * jtk_batch_chunk cuts at the last character boundary inside the budget; this call fills the budget and then backs off to the
+ * best boundary in a window, as text splitters for RAG and embedding pipelines do.  The rule
+ * (jtokkit_amd/csrc/jtk_chunk_prefer_rules.h): every cut between two tokens of a document has a level -- 0 SPLIT (inside a
+ * character), 1 CHAR, 2 WORD (white space on either side), 3 SENTENCE (after . ! ? and white space, or after one of the CJK
+ * stops U+3002 U+FF01 U+FF1F), 4 LINE (after \n, not before \n or \r), 5 PARAGRAPH (LINE after \n\n or \n\r\n) --, the highest
+ * class that holds among those enabled in `prefer`; the document's two ends have level 6.  The bytes are those of the
+ * decoded token stream (a special id counts as its literal); a cut's level looks back at most three bytes and never into the
+ * document before.  A chunk that starts at token s ends at the document's end if that is within N = chunk_tokens tokens, else
+ * at the last cut of the highest level in [s + min_tokens, s + N] (the back-off of jtk_batch_chunk if all are SPLIT); the next
+ * chunk starts at the first cut of the highest level in [max(e - overlap, s + 1), e), or at e.  With prefer == 0 and
+ * min_tokens == 1 the chunks are those of jtk_batch_chunk.  Chunks are exact slices of encode(doc), have at most N tokens,
+ * and with overlap 0 concatenate to encode(doc).
+ *   Input, order and spans: as jtk_batch_chunk.  1 <= min_tokens <= chunk_tokens and prefer within 15, else
+ *           JTK_ERR_INVALID_ARGUMENT.  Does not read the text: it works after device-input encodes whose text is gone.
+ *   Waits:  once to read *n_chunks, as jtk_batch_chunk; before that for the encode itself if the caller has not yet (the
+ *           level plane is sized by its token count, as in jtk_batch_token_offsets).
+ *   Result: replaces the batch's chunk result: jtk_batch_chunk_fetch, _device_result, _rows and jtk_batch_token_offsets read
+ *           it as they read jtk_batch_chunk's; jtk_batch_chunk_levels adds the level of every chunk's end. */
+enum { JTK_CUT_WORD = 1u, JTK_CUT_SENTENCE = 2u, JTK_CUT_LINE = 4u, JTK_CUT_PARAGRAPH = 8u };
+enum { JTK_LEVEL_SPLIT = 0, JTK_LEVEL_CHAR, JTK_LEVEL_WORD, JTK_LEVEL_SENTENCE, JTK_LEVEL_LINE, JTK_LEVEL_PARAGRAPH, JTK_LEVEL_DOC_END };
+int jtk_batch_chunk_prefer(jtk_batch* b, int64_t chunk_tokens, int64_t overlap, int64_t min_tokens, uint32_t prefer,
+                           void* stream_or_null, int64_t* n_chunks);
+/* end_level[n_chunks] of the last jtk_batch_chunk_prefer: to a host buffer (synchronises) and / or as a device pointer (valid
+ * until the next encode or chunk call on this batch); either may be NULL.  JTK_ERR_INVALID_ARGUMENT when the batch's chunk
+ * result comes from a plain jtk_batch_chunk. */
+int jtk_batch_chunk_levels(jtk_batch* b, uint8_t* end_level_or_null /* host [n_chunks] */, const uint8_t** d_end_level_or_null);
+/* d_level[n_tokens] (device): for every token of the last encode the level of the cut before it under `prefer` (within 15), 6
+ * for the first token of a document.  Queued after the encode on stream_or_null (or the batch's stream); waits only for the
+ * encode, if the caller has not yet (jtk_batch_result).  Leaves the batch's chunk result as it is.  Not after a count-only encode or jtk_batch_encode_device_max_tokens.  Entries of documents with a negative status carry no
+ * meaning. */
+int jtk_batch_token_cut_levels(jtk_batch* b, uint32_t prefer, uint8_t* d_level /* device [n_tokens] */, void* stream_or_null);
+
 /* ---- character positions: UTF-16 and code-point offsets, on the device -------------------------------------------------
  * Every position above is a byte position in String.getBytes(UTF_8).  These calls convert between the byte positions of the
  * LAST batch encode's text and indices into the documents as a Java String (JTK_UNIT_UTF16: what substring takes) or a Python

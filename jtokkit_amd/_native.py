@@ -34,6 +34,17 @@ JTK_ENCODE_COMPACT_IDS = 32
 JTK_PACK_WHOLE_DOCS = 1
 JTK_PACK_SEP_FIRST = 2
 JTK_PACK_DROP_LAST = 4
+JTK_CUT_WORD = 1
+JTK_CUT_SENTENCE = 2
+JTK_CUT_LINE = 4
+JTK_CUT_PARAGRAPH = 8
+JTK_LEVEL_SPLIT = 0
+JTK_LEVEL_CHAR = 1
+JTK_LEVEL_WORD = 2
+JTK_LEVEL_SENTENCE = 3
+JTK_LEVEL_LINE = 4
+JTK_LEVEL_PARAGRAPH = 5
+JTK_LEVEL_DOC_END = 6
 JTK_SPAN_WHOLE = 0
 JTK_SPAN_START = 1
 JTK_SPAN_ANY = 2
@@ -96,6 +107,9 @@ SIGNATURES = {
     "jtk_batch_chunk_device_result": (C.c_int, [_p] + [C.POINTER(_p)] * 7),
     "jtk_batch_chunk_rows": (C.c_int, [_p, C.c_int32, _p, _p]),
     "jtk_batch_token_offsets": (C.c_int, [_p, _p, _p]),
+    "jtk_batch_chunk_prefer": (C.c_int, [_p, _i64, _i64, _i64, C.c_uint32, _p, C.POINTER(_i64)]),
+    "jtk_batch_chunk_levels": (C.c_int, [_p, _p, C.POINTER(_p)]),
+    "jtk_batch_token_cut_levels": (C.c_int, [_p, C.c_uint32, _p, _p]),
     "jtk_batch_char_index": (C.c_int, [_p, C.c_int, _p, _p]),
     "jtk_batch_char_positions": (C.c_int, [_p, C.c_int, C.c_int, _p, _p, _i64, _p, _p]),
     "jtk_batch_byte_positions": (C.c_int, [_p, C.c_int, _p, _p, _i64, _p, _p]),

@@ -15,6 +15,7 @@
 
 #include "../../include/jtokkit_amd.h"
 #include "jtk_chunk_rules.h"
+#include "jtk_chunk_prefer_rules.h"
 #include "jtk_compact_rules.h"
 #include "jtk_decode_rows_rules.h"
 #include "jtk_kernels.h"
@@ -148,6 +149,8 @@ struct jtk_batch {
     bool have_trunc = false;
     // jtk_batch_chunk: hdr | per-document scan, long list, bases | tiles of the byte scan | records
     DevBuf ck_scratch, ck_tiles, ck_rec;
+    DevBuf ck_plane;                     // jtk_batch_chunk_prefer: the level of the cut before every token
+    const uint8_t* ck_end_level = nullptr;   // end_level[n_chunks] in ck_rec when the chunk result is jtk_batch_chunk_prefer's
     int64_t* h_ck = nullptr; size_t h_ck_cap = 0;   // pinned: (chunks, tokens) read once per call
     JtkChunkWork ck{};
     bool have_chunk = false, have_tiles = false;
@@ -465,7 +468,7 @@ void jtk_batch_destroy(jtk_batch* b) {
     }
     DevBuf* bufs[] = {&b->in_text, &b->in_off, &b->in_pieces, &b->out, &b->plan, &b->dec_in_ids, &b->dec_in_off,
                       &b->dec_zero, &b->dec_tile, &b->dec_pre, &b->dec_out, &b->dec_byte_off, &b->dec_first, &b->dec_in_win, &b->dec_cell, &b->trunc_kept, &b->trunc_flag,
-                      &b->mt_scratch, &b->mt_gather, &b->ck_scratch, &b->ck_tiles, &b->ck_rec, &b->pk_scratch, &b->sp_lits, &b->sp_find,
+                      &b->mt_scratch, &b->mt_gather, &b->ck_scratch, &b->ck_tiles, &b->ck_rec, &b->ck_plane, &b->pk_scratch, &b->sp_lits, &b->sp_find,
                       &b->sp_cand, &b->sp_out, &b->cp_buf, &b->u16_scratch, &b->u16_in, &b->u16_tx_text, &b->u16_tx_off, &b->u16_enc_text, &b->u16_enc_off,
                       &b->u16_dscratch, &b->u16_units, &b->u16_unit_off};
     for (DevBuf* d : bufs) d->release();
@@ -1927,6 +1930,7 @@ static int ck_setup(jtk_batch* b) {
     if ((rc = b->ck_scratch.ensure(32 + (3 * nd + 1) * 8))) return rc;
     JtkChunkWork& w = b->ck;
     w = JtkChunkWork{};
+    b->ck_end_level = nullptr;
     w.tokens = (const int32_t*)b->tokens.p; w.tok_off = (const int64_t*)b->tok_off.p; w.status = (const int32_t*)b->status.p;
     w.doc_off = b->job_doc_off; w.n_docs = b->job_docs;
     w.bnd = (const uint32_t*)b->enc->bnd.p; w.tab_off = (const uint32_t*)b->enc->dec_off.p; w.n_ids_table = b->enc->n_ids_table;
@@ -2073,6 +2077,89 @@ int jtk_batch_token_offsets(jtk_batch* b, int64_t* d_byte_pos, void* stream_or_n
     if (b->ck.n_tok > 0 && !d_byte_pos) return fail(JTK_ERR_INVALID_ARGUMENT, "d_byte_pos is NULL");
     jtk_launch_token_offsets(b->ck, d_byte_pos, s);
     HIP_TRY(hipGetLastError());
+    return JTK_OK;
+}
+
+
+int jtk_batch_token_cut_levels(jtk_batch* b, uint32_t prefer, uint8_t* d_level, void* stream_or_null) {
+    if (!b || !b->have_result) return fail(JTK_ERR_INVALID_ARGUMENT, "no batch encode result on this batch (jtk_batch_encode_device_max_tokens leaves none)");
+    if (b->job_flags & JTK_ENCODE_COUNT_ONLY) return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode was count-only: there are no token ids");
+    if (prefer & ~15u) return fail(JTK_ERR_INVALID_ARGUMENT, "prefer holds bits outside JTK_CUT_WORD | _SENTENCE | _LINE | _PARAGRAPH");
+    int64_t nt = 0;
+    int rc;
+    if ((rc = jtk_batch_result(b, &nt, nullptr, nullptr))) return rc;
+    if (nt > 0 && !d_level) return fail(JTK_ERR_INVALID_ARGUMENT, "d_level is NULL");
+    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    if ((rc = ck_order(b, b->last_stream, s))) return rc;
+    // (a view of the last encode of its own: the batch's chunk result stays as it is)
+    JtkChunkWork w{};
+    w.tokens = (const int32_t*)b->tokens.p; w.tok_off = (const int64_t*)b->tok_off.p; w.n_docs = b->job_docs;
+    w.tab_off = (const uint32_t*)b->enc->dec_off.p; w.n_ids_table = b->enc->n_ids_table;
+    if (nt > 0) jtk_launch_cut_levels(w, (const uint8_t*)b->enc->dec_blob.p, prefer, d_level, s);
+    HIP_TRY(hipGetLastError());
+    return JTK_OK;
+}
+
+int jtk_batch_chunk_prefer(jtk_batch* b, int64_t chunk_tokens, int64_t overlap, int64_t min_tokens, uint32_t prefer,
+                           void* stream_or_null, int64_t* n_chunks) {
+    if (!b || !n_chunks) return fail(JTK_ERR_INVALID_ARGUMENT, "bad arguments");
+    *n_chunks = 0;
+    if (!b->have_result) return fail(JTK_ERR_INVALID_ARGUMENT, "no batch encode result on this batch (jtk_batch_encode_device_max_tokens leaves none)");
+    if (b->job_flags & JTK_ENCODE_COUNT_ONLY) return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode was count-only: there are no token ids");
+    if (chunk_tokens < 1 || chunk_tokens > INT32_MAX) return fail(JTK_ERR_INVALID_ARGUMENT, "chunk_tokens must be in [1, 2^31 - 1]");
+    if (overlap < 0 || overlap >= chunk_tokens) return fail(JTK_ERR_INVALID_ARGUMENT, "overlap must be in [0, chunk_tokens)");
+    if (min_tokens < 1 || min_tokens > chunk_tokens) return fail(JTK_ERR_INVALID_ARGUMENT, "min_tokens must be in [1, chunk_tokens]");
+    if (prefer & ~15u) return fail(JTK_ERR_INVALID_ARGUMENT, "prefer holds bits outside JTK_CUT_WORD | _SENTENCE | _LINE | _PARAGRAPH");
+    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    int rc;
+    int64_t nt = 0;
+    if ((rc = jtk_batch_result(b, &nt, nullptr, nullptr))) return rc;      // (the plane is sized by the token count)
+    b->have_chunk = false;
+    b->have_tiles = false;
+    if ((rc = ck_order(b, b->last_stream, s)) || (rc = ck_setup(b)) || (rc = ensure_pinned((void**)&b->h_ck, &b->h_ck_cap, 32, 0)) ||
+        (rc = b->ck_plane.ensure((size_t)nt + 16))) return rc;
+    JtkChunkPreferWork p{};
+    JtkChunkWork& w = b->ck;
+    w.N = chunk_tokens; w.overlap = overlap;
+    p.plane = (const uint8_t*)b->ck_plane.p; p.min_tokens = min_tokens; p.prefer = prefer;
+    // plane, count per document, scan; the wait: (chunks, tokens)
+    HIP_TRY(hipMemsetAsync(w.hdr, 0, 32, s));
+    if (nt > 0) jtk_launch_cut_levels(w, (const uint8_t*)b->enc->dec_blob.p, prefer, (uint8_t*)b->ck_plane.p, s);
+    p.w = w;
+    jtk_launch_chunk_prefer_count(p, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(b->h_ck, w.hdr, 16, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const int64_t nc = b->h_ck[0];
+    if ((rc = ck_tiles(b, nt, s))) return rc;
+    // records: chunk_doc | tok_begin | byte_begin | byte_end (i64) | n_tok (i32) | split (u8) | end_level (u8)
+    const size_t n = (size_t)(nc > 0 ? nc : 1), o_i32 = 4 * n * 8, o_u8 = align_up(o_i32 + n * 4, 16);
+    if ((rc = b->ck_rec.ensure(o_u8 + 2 * n))) return rc;
+    int64_t* r64 = (int64_t*)b->ck_rec.p;
+    w.chunk_doc = r64; w.tok_begin = r64 + n; w.byte_begin = r64 + 2 * n; w.byte_end = r64 + 3 * n;
+    w.n_tok_out = (int32_t*)((uint8_t*)b->ck_rec.p + o_i32);
+    w.split = (uint8_t*)b->ck_rec.p + o_u8;
+    p.end_level = w.split + n;
+    w.n_chunks = nc;
+    p.w = w;
+    jtk_launch_chunk_prefer_write(p, s);
+    HIP_TRY(hipGetLastError());
+    b->ck_end_level = p.end_level;
+    b->have_chunk = true;
+    b->ck_stream = s;
+    *n_chunks = nc;
+    return JTK_OK;
+}
+
+int jtk_batch_chunk_levels(jtk_batch* b, uint8_t* end_level_or_null, const uint8_t** d_end_level_or_null) {
+    if (!b || !b->have_chunk) return fail(JTK_ERR_INVALID_ARGUMENT, "jtk_batch_chunk_prefer has not run on the last encode of this batch");
+    if (!b->ck_end_level) return fail(JTK_ERR_INVALID_ARGUMENT, "the last chunk call was jtk_batch_chunk: it has no levels");
+    if (d_end_level_or_null) *d_end_level_or_null = b->ck_end_level;
+    if (end_level_or_null && b->ck.n_chunks > 0) {
+        HIP_TRY(hipSetDevice(b->enc->device));
+        HIP_TRY(hipStreamSynchronize(b->ck_stream));
+        HIP_TRY(hipMemcpy(end_level_or_null, b->ck_end_level, (size_t)b->ck.n_chunks, hipMemcpyDeviceToHost));
+    }
     return JTK_OK;
 }
 

@@ -247,6 +247,10 @@ void jtk_launch_chunk_write(const JtkChunkWork& w, hipStream_t s) {
     hipLaunchKernelGGL(k_ck_bytes, dim3(jtk_blocks_for(w.n_chunks, 256)), dim3(256), 0, s, w);
 }
 
+void jtk_launch_chunk_bytes(const JtkChunkWork& w, hipStream_t s) {
+    if (w.n_chunks > 0) hipLaunchKernelGGL(k_ck_bytes, dim3(jtk_blocks_for(w.n_chunks, 256)), dim3(256), 0, s, w);
+}
+
 void jtk_launch_chunk_rows(const JtkChunkWork& w, int32_t pad_id, int32_t* rows, hipStream_t s) {
     const int64_t total = w.n_chunks * w.N;
     if (total > 0) hipLaunchKernelGGL(k_ck_rows, dim3(jtk_blocks_for(total, 1024)), dim3(256), 0, s, w, pad_id, rows, total);

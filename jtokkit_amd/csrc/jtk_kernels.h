@@ -303,6 +303,22 @@ void jtk_launch_token_offsets(const JtkChunkWork& w, int64_t* byte_pos, hipStrea
 // to out[n] and to *total (may be NULL).  _i64 scans in place.
 void jtk_launch_scan_i64(int64_t* inout, int64_t n, int64_t* total, hipStream_t s);
 void jtk_launch_scan_u32(const uint32_t* in, int64_t n, int64_t* out, int64_t* total, hipStream_t s);
+// Device-side state of jtk_batch_chunk_prefer (jtk_chunk_prefer.hip): the chunk work above (same scratch, same records) plus
+// the level plane and the level of every chunk's end, by the rule of jtk_chunk_prefer_rules.h.  A document of more than
+// JTK_CP_LONG_TOKENS tokens (and more than one chunk) is walked by a workgroup, any other by one lane.
+#define JTK_CP_LONG_TOKENS 8192
+struct JtkChunkPreferWork {
+    JtkChunkWork w;
+    const uint8_t* plane;       // [n_tok] level of the cut before every token (6: first token of a document)
+    uint8_t* end_level;         // [n_chunks]
+    int64_t min_tokens;
+    uint32_t prefer;            // JTK_CUT_* mask
+};
+// the level plane of w's tokens (reads w.tokens, tok_off, n_docs and the decode table; the token count stays on the device)
+void jtk_launch_cut_levels(const JtkChunkWork& w, const uint8_t* tab_blob, uint32_t prefer, uint8_t* plane, hipStream_t s);
+void jtk_launch_chunk_prefer_count(const JtkChunkPreferWork& p, hipStream_t s);   // count per document, scan -> hdr (needs the plane)
+void jtk_launch_chunk_prefer_write(const JtkChunkPreferWork& p, hipStream_t s);   // records (needs n_chunks and the tiles)
+void jtk_launch_chunk_bytes(const JtkChunkWork& w, hipStream_t s);      // byte_begin / byte_end of written records (k_ck_bytes)
 // Device-side state of jtk_batch_pack (jtk_pack.hip): the units of the last batch encode packed into rows of L tokens by the
 // rule of jtk_pack_rules.h.  The view's P, SEG, RS, flag and nxt point into the scratch below.
 struct JtkPackWork {

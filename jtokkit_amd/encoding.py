@@ -81,6 +81,26 @@ def _unit(unit):
     return int(unit)
 
 
+_CUTS = {"word": N.JTK_CUT_WORD, "sentence": N.JTK_CUT_SENTENCE, "line": N.JTK_CUT_LINE, "paragraph": N.JTK_CUT_PARAGRAPH}
+
+
+def prefer_mask(prefer):
+    """An iterable of "word" / "sentence" / "line" / "paragraph", the string "all", or an int mask -> JTK_CUT_* bits (the
+    library checks an int)."""
+    if isinstance(prefer, str):
+        if prefer == "all":
+            return 15
+        prefer = (prefer,)
+    if isinstance(prefer, int):
+        return prefer & 0xFFFFFFFF
+    mask = 0
+    for name in prefer:
+        if name not in _CUTS:
+            raise ValueError("prefer takes 'word', 'sentence', 'line', 'paragraph' or 'all', not %r" % (name,))
+        mask |= _CUTS[name]
+    return mask
+
+
 def _round(rnd):
     if isinstance(rnd, str):
         if rnd not in _ROUNDS:
@@ -432,6 +452,36 @@ class Batch:
     def token_offsets(self, d_byte_pos_ptr, stream=None):
         """jtk_batch_token_offsets: int64 [n_tokens] at d_byte_pos_ptr, each token's byte position in the batch text."""
         _check(N.lib().jtk_batch_token_offsets(self._h, d_byte_pos_ptr, stream))
+
+    def chunk_prefer(self, chunk_tokens, overlap=0, min_tokens=None, prefer="all", stream=None):
+        """jtk_batch_chunk_prefer on the last encode: chunks of at most chunk_tokens tokens that end at the best paragraph, line,
+        sentence or word boundary in [min_tokens, chunk_tokens] (jtk_chunk_prefer_rules.h).  min_tokens defaults to
+        (chunk_tokens + 1) // 2.  The result replaces chunk()'s: chunk_fetch, chunk_device_result and chunk_rows read it.
+        Returns n_chunks."""
+        n = C.c_int64(0)
+        mt = (int(chunk_tokens) + 1) // 2 if min_tokens is None else int(min_tokens)
+        _check(N.lib().jtk_batch_chunk_prefer(self._h, int(chunk_tokens), int(overlap), mt, prefer_mask(prefer), stream, C.byref(n)))
+        self._n_chunks = n.value
+        return n.value
+
+    def chunk_levels(self):
+        """(end_level uint8 [n_chunks] on the host, its device pointer) of the last chunk_prefer call (JTK_LEVEL_*)."""
+        nc = self._n_chunks
+        lv = np.zeros(max(nc, 1), dtype=np.uint8)
+        p = C.c_void_p()
+        _check(N.lib().jtk_batch_chunk_levels(self._h, lv.ctypes.data, C.byref(p)))
+        return lv[:nc], p.value
+
+    def chunk_levels_device(self):
+        """Device pointer of end_level uint8 [n_chunks] of the last chunk_prefer call (does not wait)."""
+        p = C.c_void_p()
+        _check(N.lib().jtk_batch_chunk_levels(self._h, None, C.byref(p)))
+        return p.value
+
+    def token_cut_levels(self, prefer, d_level_ptr, stream=None):
+        """jtk_batch_token_cut_levels: uint8 [n_tokens] at d_level_ptr, the level of the cut before every token under `prefer`
+        (6 for the first token of a document)."""
+        _check(N.lib().jtk_batch_token_cut_levels(self._h, prefer_mask(prefer), d_level_ptr, stream))
 
     # ---- packed training rows (device) -------------------------------------------------------------------
     def pack(self, seq_len, sep_id=-1, whole_docs=False, sep_first=False, drop_last=False, stream=None):
@@ -1039,15 +1089,21 @@ class HipEncoding:
             if not t.is_contiguous():
                 raise ValueError("%s must be contiguous" % name)
 
-    def chunk_batch(self, texts, chunk_tokens, overlap=0, ordinary=False, allowed_special=None, unit="byte"):
+    def chunk_batch(self, texts, chunk_tokens, overlap=0, ordinary=False, allowed_special=None, unit="byte", prefer=None,
+                    min_tokens=None):
         """Every text cut into consecutive chunks of at most chunk_tokens tokens (overlapping by up to `overlap` tokens), each a
         whole number of characters unless the tokens do not allow it: per document a list of (tokens, start, end, split), with
         start / end byte positions in that document (jtk_batch_chunk; the rule is in jtk_chunk_rules.h).  The chunks are
         slices of encode(text); with overlap 0 they concatenate to it.  A document that cannot be encoded raises.
         allowed_special: as for encode_batch (a special token's byte span is its literal).
         unit: "byte" (default), "char" -- start / end are indices into the Python str, text[start:end] is the chunk's text -- or
-        "utf16", indices into a Java String (start rounds down, end up, to a character for a split chunk)."""
+        "utf16", indices into a Java String (start rounds down, end up, to a character for a split chunk).
+        prefer (an iterable of "word", "sentence", "line", "paragraph", the string "all", or a JTK_CUT_* mask) and / or
+        min_tokens (default (chunk_tokens + 1) // 2): the chunks end at the best such boundary between min_tokens and
+        chunk_tokens and overlaps start on one (jtk_batch_chunk_prefer; the rule is in jtk_chunk_prefer_rules.h), and the tuples
+        gain a fifth field, the JTK_LEVEL_* of the chunk's end (6: the document's end)."""
         u = self._char_unit(unit, "chunk_batch")
+        leveled = prefer is not None or min_tokens is not None
         bs = [t if isinstance(t, (bytes, bytearray)) else t.encode("utf-8") for t in texts]
         doc_off = np.zeros(len(bs) + 1, dtype=np.int64)
         if bs:
@@ -1057,8 +1113,12 @@ class HipEncoding:
         if len(res.status) and res.status.min() < 0:
             _check(int(res.status.min()))
         b = self._b()
-        b.chunk(chunk_tokens, overlap)
+        if leveled:
+            b.chunk_prefer(chunk_tokens, overlap, min_tokens, 0 if prefer is None else prefer)
+        else:
+            b.chunk(chunk_tokens, overlap)
         f = b.chunk_fetch()
+        level = b.chunk_levels()[0] if leveled else None
         nc = len(f["doc"])
         start, end = f["byte_begin"] - doc_off[f["doc"]], f["byte_end"] - doc_off[f["doc"]]
         if u is not None and nc:
@@ -1077,10 +1137,12 @@ class HipEncoding:
         out = [[] for _ in bs]
         for c in range(nc):
             d, tb, n = int(f["doc"][c]), int(f["tok_begin"][c]), int(f["n_tok"][c])
-            out[d].append((res.tokens[tb:tb + n].tolist(), int(start[c]), int(end[c]), bool(f["split"][c])))
+            rec = (res.tokens[tb:tb + n].tolist(), int(start[c]), int(end[c]), bool(f["split"][c]))
+            out[d].append(rec + (int(level[c]),) if leveled else rec)
         return out
 
-    def chunk_batch_device(self, text, doc_off, chunk_tokens, overlap=0, ordinary=False, pad_id=-1, allowed_special=None, unit=None):
+    def chunk_batch_device(self, text, doc_off, chunk_tokens, overlap=0, ordinary=False, pad_id=-1, allowed_special=None, unit=None,
+                           prefer=None, min_tokens=None):
         """chunk_batch for a device-resident batch, in a model's layout.  text: CUDA torch.uint8 tensor, doc_off: CUDA torch.int64
         tensor [n_docs + 1], on this encoding's device.  Returns a dict of CUDA tensors written on torch.cuda.current_stream():
         rows int32 [n_chunks, chunk_tokens] (the chunk's ids, then pad_id), n_tok int32, doc int64, byte_begin / byte_end int64
@@ -1088,9 +1150,13 @@ class HipEncoding:
         with a negative status have no chunks; they do not raise).  The call waits once, for the chunk count (and, with
         allowed_special -- as for encode_batch --, once more for the encode's count of literal candidates).
         unit ("char", "utf16" or a JTK_UNIT_* value): the dict also holds char_begin / char_end int64 [n_chunks], the chunk's
-        range in that unit, relative to its document (begin rounded down, end up); byte_begin / byte_end stay as they are."""
+        range in that unit, relative to its document (begin rounded down, end up); byte_begin / byte_end stay as they are.
+        prefer / min_tokens: as for chunk_batch (jtk_batch_chunk_prefer); the dict then also holds level uint8 [n_chunks], the
+        JTK_LEVEL_* of every chunk's end, and the call waits for the encode before it waits for the chunk count."""
         import torch
         self._check_device_inputs("chunk_batch_device", text, doc_off)
+        leveled = prefer is not None or min_tokens is not None
+        mask = prefer_mask(0 if prefer is None else prefer)
         u = None if unit is None else _unit(unit)
         allow = self._allow(self._b(), allowed_special)
         N_, ov = int(chunk_tokens), int(overlap)
@@ -1117,7 +1183,7 @@ class HipEncoding:
             side.wait_stream(cur)
         stream = (side or cur).cuda_stream
         b.encode_device(text.data_ptr(), doc_off.data_ptr(), nd, n, ordinary, stream=stream, sync=False, allow_special=allow)
-        nc = b.chunk(N_, ov, stream)
+        nc = b.chunk_prefer(N_, ov, min_tokens, mask, stream) if leveled else b.chunk(N_, ov, stream)
         out = dict(rows=torch.empty((nc, N_), dtype=torch.int32, device=device),
                    n_tok=torch.empty(nc, dtype=torch.int32, device=device), doc=torch.empty(nc, dtype=torch.int64, device=device),
                    byte_begin=torch.empty(nc, dtype=torch.int64, device=device),
@@ -1132,6 +1198,10 @@ class HipEncoding:
             t = out[key]
             if t.numel():
                 _copy_d2d(t.data_ptr(), src, t.numel() * t.element_size(), stream)
+        if leveled:
+            out["level"] = torch.empty(nc, dtype=torch.uint8, device=device)
+            if nc:
+                _copy_d2d(out["level"].data_ptr(), b.chunk_levels_device(), nc, stream)
         if u is not None:
             out["char_begin"] = torch.empty(nc, dtype=torch.int64, device=device)
             out["char_end"] = torch.empty(nc, dtype=torch.int64, device=device)
