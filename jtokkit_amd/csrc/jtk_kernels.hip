@@ -411,6 +411,7 @@ __global__ void __launch_bounds__(SPLIT_THREADS) __attribute__((amdgpu_waves_per
 constexpr int T = JTK_TILE;
 constexpr int TW = T / 64;                                          // mask words per tile
 static_assert(TW <= 64, "tile scans assume at most 64 mask words");
+static_assert((T & (T - 1)) == 0, "piece_resolve wraps positions into the tile with a mask");
 
 // this tile's queued pieces by bin, in LDS until its slices of the queues are claimed
 __host__ __device__ __forceinline__ constexpr int q_off(int bin) {
@@ -430,14 +431,15 @@ static_assert(RES_THREADS >= (T + 16) / 16 && RES_THREADS > 64, "the prologue's 
 
 __global__ void __launch_bounds__(RES_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) k_piece_resolve(JtkWork w, JtkDeviceTables t) {
     __shared__ __attribute__((aligned(16))) uint8_t s_tx[T + 16];
-    __shared__ uint16_t s_plist[T + 1];
+    __shared__ uint16_t s_plist[T + 64];       // piece starts, then where the last piece ends, repeated to the end of the last chunk
     __shared__ uint64_t s_pm[TW];
     __shared__ uint64_t s_gap[TW];
     __shared__ uint32_t s_q[Q_TOTAL];          // this tile's pieces for the merge kernels, by bin: offset | (len - 1) << 11 | index in this list << 19
     __shared__ uint32_t s_qn[JTK_NBINS + 1], s_qb[JTK_NBINS + 1], s_binc[JTK_NBINS + 1], s_nhard;
     __shared__ int64_t s_next_after;           // first piece start at or after B + T (global position)
 
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);          // the same in all lanes: a scalar, as is what follows from it
     const int64_t tile = blockIdx.x;
     const int64_t B = tile * T;
     const int64_t n = w.n_bytes;
@@ -485,7 +487,7 @@ __global__ void __launch_bounds__(RES_THREADS) __attribute__((amdgpu_waves_per_e
     {
         const uint32_t c = lane < TW ? (uint32_t)__popcll(s_pm[lane]) : 0u;
         const uint32_t inc = jtk_wave_incl_scan(c);
-        np = (int)(uint32_t)__shfl((int)inc, 63);
+        np = __builtin_amdgcn_readlane((int)inc, 63);                 // a scalar: the chunk loop's bounds and branches are too
         const uint32_t pre = inc - c;
         for (int wd = wv; wd < TW; wd += RES_WAVES) {
             const uint64_t m = s_pm[wd];
@@ -493,11 +495,12 @@ __global__ void __launch_bounds__(RES_THREADS) __attribute__((amdgpu_waves_per_e
             if ((m >> lane) & 1ull)
                 s_plist[base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = (uint16_t)(wd * 64 + lane);
         }
-        if (tid == 0) {
+        if (wv == 0) {
             // where the last piece ends: the sentinel (bit n) or the next tile's first piece; a piece of more than 64 KB only
-            // needs to look longer than every bin (its length is taken again, exactly, where it is queued)
+            // needs to look longer than every bin (its length is taken again, exactly, where it is queued).  Written 64 times:
+            // a lane beyond the list finds a piece of length 0 there (the last chunk's lanes read up to entry np + 63)
             const int64_t e = (n - B < T) ? (n - B) : (s_next_after - B);
-            s_plist[np] = (uint16_t)(e < 0xFFFF ? e : 0xFFFF);
+            s_plist[np + lane] = (uint16_t)(e < 0xFFFF ? e : 0xFFFF);
         }
     }
     __syncthreads();
@@ -532,13 +535,11 @@ __global__ void __launch_bounds__(RES_THREADS) __attribute__((amdgpu_waves_per_e
         return (h << (small ? 4u : 5u)) + (small ? 0u : rel16);
     };
     auto issue = [&](int k, Probe& pr) {
-        const bool have = k < np;
-        const int kk = have ? k : np - 1;                             // np >= 1 here
-        const uint32_t s0 = s_plist[kk], e0 = s_plist[kk + 1];        // s_plist[np] = where the tile's last piece ends (clamped)
-        pr.s = have ? s0 : 0u;
-        pr.len = have ? e0 - s0 : 0u;
-        // up to 16 bytes of the piece, zero beyond its length
-        const uint32_t a = pr.s >> 2, sh = pr.s & 3u;
+        pr.s = s_plist[k];                                            // s_plist[np ..] = where the tile's last piece ends (clamped):
+        pr.len = s_plist[k + 1] - pr.s;                               // length 0 for a lane beyond the list
+        // up to 16 bytes of the piece, zero beyond its length.  A piece starts inside the tile; the end position that a lane
+        // beyond the list holds may lie anywhere, and its word index wraps into the tile: those bytes are all masked away
+        const uint32_t a = (pr.s >> 2) & (uint32_t)(T / 4 - 1), sh = pr.s & 3u;
         const uint32_t w0 = tw[a], w1 = tw[a + 1], w2 = tw[a + 2], w3 = tw[a + 3], w4 = tw[a + 4];
         const uint32_t len = pr.len < 16u ? pr.len : 16u;
         const uint64_t run = ~0ull >> ((0u - 8u * len) & 63u);        // 8 len ones (len 8 and 16: all 64)
@@ -571,73 +572,96 @@ __global__ void __launch_bounds__(RES_THREADS) __attribute__((amdgpu_waves_per_e
         pr.ka = *reinterpret_cast<const uint4*>(sa);
         if (!small) pr.ma = *reinterpret_cast<const uint2*>(sa + 16);
     };
-    auto resolve = [&](int k, const Probe& pr, uint32_t id) {
-        if (pr.len == 0u) return;
-        const uint32_t s = pr.s, len = pr.len;
-        const bool gap = gaps && ((s_gap[s >> 6] >> (s & 63u)) & 1ull);
-        uint32_t entry = id | (s << JTK_PL_OFF_SHIFT);                 // (a hit implies len <= 16)
-        if (gap || id == JTK_RANK_NONE) {
-            entry = JTK_PL_HARD | JTK_PL_NOQUEUE | s;
-            if (gap) {
-                // text the caller's pattern did not match: no tokens (an htok header with count 0)
-                w.htok[B + s] = 0u;
-                atomicAdd(&s_nhard, 1u);
-            } else if (len <= (uint32_t)JTK_BIN_MAXLEN) {
-                // bin by length: 2..3 tiny, 4..8, 9..12, 13..16 (three bits per length from a constant), then 17..32, ..64, ..128, ..256
-                // (a 1-byte piece is always a table entry)
-                constexpr uint64_t BIN16 = (7ull << 6) | (7ull << 9) | (1ull << 27) | (1ull << 30) | (1ull << 33) | (1ull << 36) |
-                                           (2ull << 39) | (2ull << 42) | (2ull << 45) | (2ull << 48);
-                const uint32_t bin = len <= 16u ? (uint32_t)(BIN16 >> (3u * len)) & 7u : 30u - (uint32_t)__builtin_clz(len - 1u);
-                const uint32_t bc = s_binc[bin];                           // q_off | staging cap << 12 | staging offset << 21
-                const uint32_t i = atomicAdd(&s_qn[bin], 1u);
-                s_q[(bc & 0xFFFu) + i] = s | ((len - 1u) << 11) | (i << 19);
-                // pack finds the result of one of the tile's first few pieces of a bin in its LDS staging area: say where
-                const bool st = i < ((bc >> 12) & 0x1FFu);
-                const uint32_t idx = st ? (bc >> 21) + i : i;
-                entry = JTK_PL_HARD | (st ? JTK_PL_STAGED : 0u) | (bin << JTK_PL_BIN_SHIFT) | (idx << JTK_PL_QI_SHIFT) | s;
-            } else {
-                const int64_t len64 = piece_len(k, (int)s);
-                if (len64 <= JTK_MID_CAP) w.mid_list[atomicAdd(w.mid_count, 1u)] = JtkLongPiece{B + s, len64};
-                else if (len64 <= JTK_LONG_CAP) w.long_list[atomicAdd(w.long_count, 1u)] = JtkLongPiece{B + s, len64};
+    // The kinds of piece that ordinary text has next to none of: text the caller's pattern left over (a gap piece), and a piece of
+    // more than JTK_BIN_MAXLEN bytes (no table entry is that long).  Which pieces these are does not depend on the probe, so the
+    // chunk passes only mark them in the list and note that the wave has met one; a sweep of its own after the passes, entered
+    // under that one wave-uniform test, does the rest.
+    bool any_rare = false;                                             // wave-uniform
+    auto is_rare = [&](uint32_t s, uint32_t len, bool& gap) -> bool {
+        gap = gaps && ((s_gap[(s >> 6) & (uint32_t)(TW - 1)] >> (s & 63u)) & 1ull);
+        return len != 0u && (gap || len > (uint32_t)JTK_BIN_MAXLEN);    // (length 0: a lane beyond the list, s is the end position)
+    };
+    auto resolve_rare = [&](int k, uint32_t s, bool gap) {
+        if (gap) {
+            // text the caller's pattern did not match: no tokens (an htok header with count 0)
+            w.htok[B + s] = 0u;
+        } else {
+            const int64_t len64 = piece_len(k, (int)s);
+            if (len64 <= JTK_MID_CAP) w.mid_list[atomicAdd(w.mid_count, 1u)] = JtkLongPiece{B + s, len64};
+            else if (len64 <= JTK_LONG_CAP) w.long_list[atomicAdd(w.long_count, 1u)] = JtkLongPiece{B + s, len64};
+            else {
+                // giant piece (a run of one byte value, mostly): merged by a whole workgroup in the last phase of
+                // k_bpe_merge; its token count goes to docpre[pos + 1] (a position inside the piece: no document starts
+                // there, so pack never writes that word), the htok header only says so
+                w.docpre[B + s + 1] = 0u;
+                if (len64 <= JTK_GIANT_CAP) w.giant_list[atomicAdd(w.n_giant, 1u)] = JtkLongPiece{B + s, len64};
                 else {
-                    // giant piece (a run of one byte value, mostly): merged by a whole workgroup in the last phase of
-                    // k_bpe_merge; its token count goes to docpre[pos + 1] (a position inside the piece: no document starts
-                    // there, so pack never writes that word), the htok header only says so
-                    w.docpre[B + s + 1] = 0u;
-                    if (len64 <= JTK_GIANT_CAP) w.giant_list[atomicAdd(w.n_giant, 1u)] = JtkLongPiece{B + s, len64};
-                    else {
-                        const int64_t d = find_doc(w, B + s);
-                        if (d >= 0) atomicMin(&w.status[d], -10 /* JTK_ERR_PIECE_TOO_LONG */);
-                    }
-                    w.htok[B + s] = (uint32_t)JTK_HT_ESCAPE << JTK_HT_CNT_SHIFT;         // count: docpre[pos + 1]
+                    const int64_t d = find_doc(w, B + s);
+                    if (d >= 0) atomicMin(&w.status[d], -10 /* JTK_ERR_PIECE_TOO_LONG */);
                 }
-                atomicAdd(&s_nhard, 1u);
+                w.htok[B + s] = (uint32_t)JTK_HT_ESCAPE << JTK_HT_CNT_SHIFT;         // count: docpre[pos + 1]
             }
         }
-        plist[k] = entry;
+        atomicAdd(&s_nhard, 1u);
+    };
+    auto resolve = [&](int k, const Probe& pr, uint32_t id) {
+        const uint32_t s = pr.s, len = pr.len;
+        bool gap;
+        const bool rare = is_rare(s, len, gap);
+        any_rare |= __ballot(rare) != 0ull;
+        const bool live = len != 0u, miss = id == JTK_RANK_NONE;
+        uint32_t entry = rare ? JTK_PL_HARD | JTK_PL_NOQUEUE | s : id | (s << JTK_PL_OFF_SHIFT);      // (a hit implies len <= 16)
+        if (live && miss && !rare) {
+            // bin by length: 2..3 tiny, 4..8, 9..12, 13..16 (three bits per length from a constant), then 17..32, ..64, ..128, ..256
+            // (a 1-byte piece is always a table entry)
+            constexpr uint64_t BIN16 = (7ull << 6) | (7ull << 9) | (1ull << 27) | (1ull << 30) | (1ull << 33) | (1ull << 36) |
+                                       (2ull << 39) | (2ull << 42) | (2ull << 45) | (2ull << 48);
+            const uint32_t bin = len <= 16u ? (uint32_t)(BIN16 >> (3u * len)) & 7u : 30u - (uint32_t)__builtin_clz(len - 1u);
+            const uint32_t bc = s_binc[bin];                           // q_off | staging cap << 12 | staging offset << 21
+            const uint32_t i = atomicAdd(&s_qn[bin], 1u);
+            s_q[(bc & 0xFFFu) + i] = s | ((len - 1u) << 11) | (i << 19);
+            // pack finds the result of one of the tile's first few pieces of a bin in its LDS staging area: say where
+            const bool st = i < ((bc >> 12) & 0x1FFu);
+            const uint32_t idx = st ? (bc >> 21) + i : i;
+            entry = JTK_PL_HARD | (st ? JTK_PL_STAGED : 0u) | (bin << JTK_PL_BIN_SHIFT) | (idx << JTK_PL_QI_SHIFT) | s;
+        }
+        if (live) plist[k] = entry;
     };
     // Pieces are taken in chunks of 64 (chunk c: pieces 64 c .. 64 c + 63); wave wv takes chunks wv, wv + RES_WAVES, ... two at
     // a time while there are two (so that two probes per lane are in flight), one otherwise: a tile of 530 pieces costs nine
-    // chunk passes, not the sixteen of two full rounds of 512.
-    for (int c0 = wv; c0 * 64 < np; c0 += 2 * RES_WAVES) {
-        const bool two = (c0 + RES_WAVES) * 64 < np;                       // wave-uniform
+    // chunk passes, not the sixteen of two full rounds of 512.  wv and np are scalars, so the loop's bounds and branches are
+    // scalar code; the body is instantiated for two chunks and for one: pair passes, then at most one single pass, which
+    // carries no second probe.
+    auto pass = [&](int c0, auto two) {                                     // c0: wave-uniform; two: std::true_type or false_type
+        constexpr bool TWO = decltype(two)::value;
         const int ka = c0 * 64 + lane, kb = (c0 + RES_WAVES) * 64 + lane;
         Probe p0, p1;
         issue(ka, p0);
-        if (two) issue(kb, p1); else { p1.s = 0; p1.len = 0; p1.ka = make_uint4(0, 0, 0, 0); p1.ma = make_uint2(0, 0); p1.k0 = p1.k1 = p1.k2 = p1.k3 = p1.mix = 0; }
+        if constexpr (TWO) issue(kb, p1);
         uint32_t id0, id1 = JTK_RANK_NONE;
         bool more0, more1 = false;
         check(p0, id0, more0);
-        if (two) check(p1, id1, more1);
+        if constexpr (TWO) check(p1, id1, more1);
         if (__ballot(more0 || more1)) {
             if (more0) issue2(p0);
-            if (more1) issue2(p1);
+            if constexpr (TWO) { if (more1) issue2(p1); }
             bool dummy;
             if (more0) check(p0, id0, dummy);
-            if (more1) check(p1, id1, dummy);
+            if constexpr (TWO) { if (more1) check(p1, id1, dummy); }
         }
         resolve(ka, p0, id0);
-        if (two) resolve(kb, p1, id1);
+        if constexpr (TWO) resolve(kb, p1, id1);
+    };
+    int c0 = wv;
+    for (; (c0 + RES_WAVES) * 64 < np; c0 += 2 * RES_WAVES) pass(c0, std::true_type{});
+    if (c0 * 64 < np) pass(c0, std::false_type{});
+    if (any_rare) {
+        for (int c = wv; c * 64 < np; c += RES_WAVES) {
+            const int k = c * 64 + lane;
+            const uint32_t s = s_plist[k], len = s_plist[k + 1] - s;
+            bool gap;
+            if (is_rare(s, len, gap)) resolve_rare(k, s, gap);
+        }
     }
     __syncthreads();
     // The tile's slices of its queue shards are claimed with one returning atomic per bin (a device-wide atomic:
