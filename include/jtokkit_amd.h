@@ -557,6 +557,39 @@ int jtk_batch_decode_rows(jtk_batch* b, const void* rows, int id_bytes, int64_t 
                           const int64_t* begin_or_null, const int64_t* end_or_null, int64_t pad_id, const int64_t* stop_ids,
                           int n_stop, uint32_t flags, int64_t* cell_byte_or_null, int64_t* n_bytes);
 
+/* ---- stop strings over the last decode, on the device -------------------------------------------------
+ * Replaces a loop of bytes.find per row and per string over decoded text copied to the host, as a server does for OpenAI's
+ * `stop` or vLLM / TGI `stop_sequences`.  A stop string is a property of the decoded text, not of the ids: the search is a
+ * post-pass over the LAST decode of the batch, flat or rows, from host or device input (bytes `out`, byte_off[n_seqs + 1]),
+ * and changes nothing of it.  n_strings strings back to back in `strings`, string i occupying [str_off[i], str_off[i + 1]),
+ * both in host memory, in the caller's order of preference.  For sequence q (the rule is jtk_stop_rules.h):
+ *   range   [S, E): S = byte_off[q] + d_from[q] clamped into [0, the sequence's length] (d_from_or_null NULL: 0),
+ *           E = byte_off[q + 1].  String i of length L matches at p when S <= p, p + L <= E and the bytes are equal: a match
+ *           never reaches into the next sequence, and one that starts before S does not count.
+ *   match   the match with the smallest p, among those the smallest i (duplicate strings are allowed): stop_pos[q] = p, a
+ *           position in `out` -- the cut text is out[byte_off[q], stop_pos[q]) --, stop_which[q] = i, hold[q] = 0.
+ *   none    stop_pos[q] = E, stop_which[q] = -1, hold[q] = E - p* for the smallest p* in [max(S, E - (maxlen - 1)), E) at
+ *           which out[p*, E) is a proper prefix of some string, 0 without one: the trailing bytes a streaming server must not
+ *           emit yet (always below maxlen, the longest string's length).
+ *   column  with d_cell_byte_or_null, the dense cell_byte [n_rows, width] of the rows decode, and a match: stop_col[q] = the
+ *           largest column c with cell_byte[q * width + c] <= stop_pos[q], the cell that holds the byte at stop_pos (the
+ *           row's kept cells end before it).  -1 without a match or without cell_byte.
+ * Positions are bytes; UTF-16 positions of stops are not computed.  jtk_batch_decode_find_stops is ordered after the decode
+ * on stream_or_null (or the batch's stream) and does not wait.  Results live in buffers the batch owns, valid until the next
+ * jtk_batch_decode_find_stops; a new decode drops them.  n_strings == 0 is valid (no sequence matches, all holds 0), and so
+ * are n_seqs == 0 and an empty `out` (nothing is launched).  JTK_ERR_INVALID_ARGUMENT, before any device work: no decode result
+ * on the batch, n_strings outside 0..JTK_STOP_MAX_STRINGS, a string that is empty or longer than JTK_STOP_MAX_BYTES, str_off
+ * not increasing from 0, NULL arrays with n_strings > 0, and d_cell_byte_or_null with width < 1 or after a decode that is not
+ * a rows decode of exactly this width (a flat decode has no cells: cell_byte is refused after it, whatever the width).
+ * _fetch copies to host arrays of n_seqs entries (any may be NULL) and synchronises; _device_result hands out the pointers. */
+enum { JTK_STOP_MAX_STRINGS = 16, JTK_STOP_MAX_BYTES = 64 };
+int jtk_batch_decode_find_stops(jtk_batch* b, const uint8_t* strings, const uint32_t* str_off, int n_strings,
+                                const int64_t* d_from_or_null, const int64_t* d_cell_byte_or_null, int64_t width,
+                                void* stream_or_null);
+int jtk_batch_decode_stops_fetch(jtk_batch* b, int64_t* stop_pos, int32_t* stop_which, int32_t* hold, int64_t* stop_col);
+int jtk_batch_decode_stops_device_result(jtk_batch* b, const int64_t** d_stop_pos, const int32_t** d_stop_which,
+                                         const int32_t** d_hold, const int64_t** d_stop_col);
+
 /* ---- UTF-16 in and out, on the device ---------------------------------------------------------------------------------
  * A Java String is UTF-16: these entry points take char[] and hand back char[], so that no host codec stands in front of or
  * behind the device passes.  Units are uint16 in the byte order of host and device (little-endian); no BOM handling: a U+FEFF

@@ -58,6 +58,8 @@ JTK_LABEL_SEP = 2
 JTK_DECODE_MAX_STOP_IDS = 8
 JTK_DECODE_SKIP_PAD = 1
 JTK_DECODE_KEEP_STOP = 2
+JTK_STOP_MAX_STRINGS = 16
+JTK_STOP_MAX_BYTES = 64
 JTK_OPT_CHUNK_BYTES = 1
 JTK_OPT_CHUNKS_IN_FLIGHT = 2
 JTK_OPT_HOST_CHUNK_BYTES = 3
@@ -134,6 +136,9 @@ SIGNATURES = {
     "jtk_batch_decode_utf16": (C.c_int, [_p, _p, C.POINTER(_i64)]),
     "jtk_batch_decode_utf16_fetch": (C.c_int, [_p, _p, _i64, _p, _p]),
     "jtk_batch_decode_utf16_device_result": (C.c_int, [_p, C.POINTER(_p), C.POINTER(_p), C.POINTER(_p)]),
+    "jtk_batch_decode_find_stops": (C.c_int, [_p, _p, _p, C.c_int, _p, _p, _i64, _p]),
+    "jtk_batch_decode_stops_fetch": (C.c_int, [_p, _p, _p, _p, _p]),
+    "jtk_batch_decode_stops_device_result": (C.c_int, [_p, C.POINTER(_p), C.POINTER(_p), C.POINTER(_p), C.POINTER(_p)]),
     "jtk_service_create": (C.c_int, [_p, C.c_int, C.POINTER(_p)]),
     "jtk_service_destroy": (None, [_p]),
     "jtk_service_encode": (C.c_int, [_p, _p, _i64, C.c_uint32, _i64, _p, _i64, C.POINTER(_i64), C.POINTER(C.c_int)]),

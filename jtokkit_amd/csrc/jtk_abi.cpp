@@ -189,6 +189,12 @@ struct jtk_batch {
     JtkDecodeWork dwork{};
     bool have_decode = false;
     int64_t dec_total = 0;
+    int64_t dec_rows_width = -1;         // width of the last decode when it was a rows decode, -1 after a flat one
+    // jtk_batch_decode_find_stops: keys [2 n] | stop_pos [n] | stop_col [n] (i64) | stop_which [n] | hold [n] (i32)
+    DevBuf stop_buf;
+    JtkStopWork stop{};
+    bool have_stops = false;
+    hipStream_t stop_stream = nullptr;   // stream of the last find_stops: the fetch waits for it
     JtkResult* host_result = nullptr;   // pinned: host_result_own, or the head of h_small after a small job
     JtkResult* host_result_own = nullptr;
     // the last job
@@ -470,7 +476,7 @@ void jtk_batch_destroy(jtk_batch* b) {
                       &b->dec_zero, &b->dec_tile, &b->dec_pre, &b->dec_out, &b->dec_byte_off, &b->dec_first, &b->dec_in_win, &b->dec_cell, &b->trunc_kept, &b->trunc_flag,
                       &b->mt_scratch, &b->mt_gather, &b->ck_scratch, &b->ck_tiles, &b->ck_rec, &b->ck_plane, &b->pk_scratch, &b->sp_lits, &b->sp_find,
                       &b->sp_cand, &b->sp_out, &b->cp_buf, &b->u16_scratch, &b->u16_in, &b->u16_tx_text, &b->u16_tx_off, &b->u16_enc_text, &b->u16_enc_off,
-                      &b->u16_dscratch, &b->u16_units, &b->u16_unit_off};
+                      &b->u16_dscratch, &b->u16_units, &b->u16_unit_off, &b->stop_buf};
     for (DevBuf* d : bufs) d->release();
     if (b->h_sp) (void)hipHostFree(b->h_sp);
     for (hipEvent_t ev : b->prof_ev) (void)hipEventDestroy(ev);
@@ -1453,8 +1459,10 @@ int jtk_batch_decode_device(jtk_batch* b, const int32_t* d_ids, const int64_t* d
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s));
     b->dec_total = total;
+    b->dec_rows_width = -1;
     b->have_decode = true;
     b->have_u16_dec = false;
+    b->have_stops = false;
     if (n_bytes) *n_bytes = total;
     return JTK_OK;
 }
@@ -1567,8 +1575,10 @@ int jtk_batch_decode_rows_device(jtk_batch* b, const void* d_rows, int id_bytes,
     // the result is read as a flat decode's: jtk_batch_decode_fetch / jtk_batch_decode_device_result with n_seqs = n_rows
     b->dwork.n_seqs = n_rows; b->dwork.out = w.out; b->dwork.byte_off = w.byte_off; b->dwork.status = w.status;
     b->dec_total = total;
+    b->dec_rows_width = width;
     b->have_decode = true;
     b->have_u16_dec = false;
+    b->have_stops = false;
     if (n_bytes) *n_bytes = total;
     return JTK_OK;
 }
@@ -2605,6 +2615,76 @@ int jtk_batch_decode_utf16_device_result(jtk_batch* b, const uint16_t** d_units,
     if (d_units) *d_units = (const uint16_t*)b->u16_units.p;
     if (d_unit_off) *d_unit_off = (const int64_t*)b->u16_unit_off.p;
     if (d_status) *d_status = b->dwork.status;
+    return JTK_OK;
+}
+
+// ---- stop strings over the last decode (jtk_stop.hip) -------------------------------------------------
+static_assert(JTK_STOP_MAX_STRINGS == JTK_ST_MAX_STRINGS && JTK_STOP_MAX_BYTES == JTK_ST_MAX_BYTES, "the rule header holds what the ABI takes");
+
+int jtk_batch_decode_find_stops(jtk_batch* b, const uint8_t* strings, const uint32_t* str_off, int n_strings,
+                                const int64_t* d_from_or_null, const int64_t* d_cell_byte_or_null, int64_t width,
+                                void* stream_or_null) {
+    if (!b || !b->have_decode) return fail(JTK_ERR_INVALID_ARGUMENT, "no decode has run on this batch");
+    JtkStopWork& w = b->stop;
+    b->have_stops = false;
+    if (!jtk_stop_set_init(&w.set, strings, str_off, n_strings))
+        return fail(JTK_ERR_INVALID_ARGUMENT, "stop strings: 0..16 strings of 1..64 bytes, str_off increasing from 0");
+    // cell_byte belongs to a rows decode: the last decode must be one, of this width (after a flat decode there are no cells)
+    if (d_cell_byte_or_null && (width < 1 || width != b->dec_rows_width))
+        return fail(JTK_ERR_INVALID_ARGUMENT, "cell_byte needs the width of the rows decode it came from");
+    HIP_TRY(hipSetDevice(b->enc->device));
+    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    const int64_t n = b->dwork.n_seqs;
+    w.out = b->dwork.out; w.n_bytes = b->dec_total; w.byte_off = b->dwork.byte_off; w.n_seqs = n;
+    w.n_tiles = (w.n_bytes + JTK_STOP_TILE - 1) / JTK_STOP_TILE;
+    if (w.n_tiles >= ((int64_t)1 << 31) - 1) return fail(JTK_ERR_INVALID_ARGUMENT, "output too large");
+    w.from = d_from_or_null; w.cell_byte = d_cell_byte_or_null; w.width = width;
+    const size_t nn = (size_t)(n > 0 ? n : 1);
+    int rc;
+    if ((rc = b->stop_buf.ensure(nn * (4 * 8 + 2 * 4)))) return rc;
+    uint8_t* z = (uint8_t*)b->stop_buf.p;
+    w.keys = (unsigned long long*)z;
+    w.stop_pos = (int64_t*)(z + nn * 16);
+    w.stop_col = (int64_t*)(z + nn * 24);
+    w.stop_which = (int32_t*)(z + nn * 32);
+    w.hold = (int32_t*)(z + nn * 36);
+    if (n > 0 && w.n_bytes == 0) {
+        // every sequence is empty: stop_pos = E = 0, no match, nothing held, no column
+        HIP_TRY(hipMemsetAsync(w.stop_pos, 0, nn * 8, s));
+        HIP_TRY(hipMemsetAsync(w.stop_col, 0xFF, nn * 8 + nn * 4, s));         // stop_col | stop_which: -1
+        HIP_TRY(hipMemsetAsync(w.hold, 0, nn * 4, s));
+    } else if (n > 0) {
+        HIP_TRY(hipMemsetAsync(w.keys, 0xFF, nn * 16, s));                      // JTK_STOP_NONE
+        jtk_launch_stop_find(w, s);
+        HIP_TRY(hipGetLastError());
+    }
+    b->stop_stream = s;
+    b->have_stops = true;
+    return JTK_OK;
+}
+
+int jtk_batch_decode_stops_fetch(jtk_batch* b, int64_t* stop_pos, int32_t* stop_which, int32_t* hold, int64_t* stop_col) {
+    if (!b || !b->have_decode || !b->have_stops)
+        return fail(JTK_ERR_INVALID_ARGUMENT, "no jtk_batch_decode_find_stops has run on the last decode of this batch");
+    HIP_TRY(hipSetDevice(b->enc->device));
+    HIP_TRY(hipStreamSynchronize(b->stop_stream));
+    const size_t n = (size_t)b->stop.n_seqs;
+    if (n == 0) return JTK_OK;
+    if (stop_pos) HIP_TRY(hipMemcpy(stop_pos, b->stop.stop_pos, n * 8, hipMemcpyDeviceToHost));
+    if (stop_which) HIP_TRY(hipMemcpy(stop_which, b->stop.stop_which, n * 4, hipMemcpyDeviceToHost));
+    if (hold) HIP_TRY(hipMemcpy(hold, b->stop.hold, n * 4, hipMemcpyDeviceToHost));
+    if (stop_col) HIP_TRY(hipMemcpy(stop_col, b->stop.stop_col, n * 8, hipMemcpyDeviceToHost));
+    return JTK_OK;
+}
+
+int jtk_batch_decode_stops_device_result(jtk_batch* b, const int64_t** d_stop_pos, const int32_t** d_stop_which,
+                                         const int32_t** d_hold, const int64_t** d_stop_col) {
+    if (!b || !b->have_decode || !b->have_stops)
+        return fail(JTK_ERR_INVALID_ARGUMENT, "no jtk_batch_decode_find_stops has run on the last decode of this batch");
+    if (d_stop_pos) *d_stop_pos = b->stop.stop_pos;
+    if (d_stop_which) *d_stop_which = b->stop.stop_which;
+    if (d_hold) *d_hold = b->stop.hold;
+    if (d_stop_col) *d_stop_col = b->stop.stop_col;
     return JTK_OK;
 }
 

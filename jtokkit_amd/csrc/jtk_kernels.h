@@ -12,6 +12,7 @@
 #include "jtk_decode_rows_rules.h"
 #include "jtk_charpos_rules.h"
 #include "jtk_utf16_rules.h"
+#include "jtk_stop_rules.h"
 
 #define JTK_SPLIT_TILE 4096      // bytes per pretok_split workgroup
 #define JTK_SPLIT_HALO 64
@@ -388,6 +389,25 @@ void jtk_launch_u16_enc_count(const JtkU16EncWork& w, bool aligned, hipStream_t 
 void jtk_launch_u16_enc_write(const JtkU16EncWork& w, bool aligned, hipStream_t s);
 void jtk_launch_u16_dec_count(const JtkU16DecWork& w, hipStream_t s);
 void jtk_launch_u16_dec_write(const JtkU16DecWork& w, hipStream_t s);
+// Stop strings over the last decode (jtk_stop.hip; the rule is jtk_stop_rules.h): out (16-byte aligned, readable up to the next
+// multiple of 16 past n_bytes) and byte_off of that decode.  keys [2 * n_seqs], all bytes 0xFF before the launch: per sequence
+// the smallest match key, then the smallest proper-prefix tail.  Launched only with n_seqs > 0 and n_bytes > 0.
+struct JtkStopWork {
+    const uint8_t* out;
+    int64_t n_bytes;
+    const int64_t* byte_off;    // [n_seqs + 1]
+    int64_t n_seqs, n_tiles;    // tiles of JTK_STOP_TILE bytes
+    const int64_t* from;        // [n_seqs] or NULL
+    const int64_t* cell_byte;   // [n_seqs * width] of the rows decode, or NULL
+    int64_t width;
+    unsigned long long* keys;
+    int64_t* stop_pos;          // [n_seqs] each
+    int32_t* stop_which;
+    int32_t* hold;
+    int64_t* stop_col;
+    JtkStopSet set;
+};
+void jtk_launch_stop_find(const JtkStopWork& w, hipStream_t s);      // find (with strings), then finish
 // Compact ids (jtk_compact.hip; the rule is jtk_compact_rules.h): the range [t0, t1) of the int32 stream `ids` (indexed from
 // token 0) into a uint16 plane and a plane of hb bits per token whose entry 0 is token `origin` (a multiple of 32; 0 for whole
 // planes).  Restarts at t0 rounded down to a multiple of 32 and rewrites the words there whole.  d_total != NULL: the range ends

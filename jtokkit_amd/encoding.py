@@ -118,6 +118,18 @@ def _stream_sync(stream):
         raise EncodingError(N.JTK_ERR_HIP, "hipStreamSynchronize failed (%d)" % rc)
 
 
+def _stop_blob(stop_strings):
+    """Stop strings (bytes or str, a str as its UTF-8 bytes; one alone is a list of one) -> (blob uint8, str_off uint32
+    [n + 1]).  The library checks counts and lengths."""
+    if isinstance(stop_strings, (str, bytes, bytearray)):
+        stop_strings = (stop_strings,)
+    bs = [s.encode("utf-8") if isinstance(s, str) else bytes(s) for s in stop_strings]
+    str_off = np.zeros(len(bs) + 1, dtype=np.uint32)
+    if bs:
+        np.cumsum([len(x) for x in bs], out=str_off[1:])
+    return np.frombuffer(b"".join(bs), dtype=np.uint8), str_off
+
+
 class _DeviceArray:
     """A numpy array's bytes in device memory of the HIP runtime the library is bound to, for host-input calls whose C entry
     point takes device arrays (no torch needed).  fetch() copies back."""
@@ -693,6 +705,29 @@ class Batch:
         """jtk_batch_decode_utf16_device_result: device pointers (units, unit_off, status)."""
         p = [C.c_void_p() for _ in range(3)]
         _check(N.lib().jtk_batch_decode_utf16_device_result(self._h, *(C.byref(x) for x in p)))
+        return tuple(x.value for x in p)
+
+    # ---- stop strings over the last decode (device; the rule is jtk_stop_rules.h) --------------------------
+    def decode_find_stops(self, stop_strings, d_from_ptr=None, d_cell_byte_ptr=None, width=0, stream=None):
+        """jtk_batch_decode_find_stops over the last decode (flat or rows): stop_strings is a sequence of bytes / str (a str
+        is its UTF-8 bytes) in order of preference; d_from_ptr int64 [n_seqs] and d_cell_byte_ptr int64 [n_rows, width] are
+        device pointers or None.  Queued on stream (None: the batch's); does not wait."""
+        blob, str_off = _stop_blob(stop_strings)
+        _check(N.lib().jtk_batch_decode_find_stops(self._h, blob.ctypes.data if len(blob) else None, str_off.ctypes.data, len(str_off) - 1,
+                                                   d_from_ptr, d_cell_byte_ptr, width, stream))
+
+    def decode_stops_fetch(self):
+        """jtk_batch_decode_stops_fetch -> (stop_pos int64, stop_which int32, hold int32, stop_col int64), each [n_seqs]."""
+        ns = self._dec_shape[1]
+        pos, col = np.zeros(max(ns, 1), dtype=np.int64), np.zeros(max(ns, 1), dtype=np.int64)
+        which, hold = np.zeros(max(ns, 1), dtype=np.int32), np.zeros(max(ns, 1), dtype=np.int32)
+        _check(N.lib().jtk_batch_decode_stops_fetch(self._h, pos.ctypes.data, which.ctypes.data, hold.ctypes.data, col.ctypes.data))
+        return pos[:ns], which[:ns], hold[:ns], col[:ns]
+
+    def decode_stops_device_result(self):
+        """jtk_batch_decode_stops_device_result: device pointers (stop_pos, stop_which, hold, stop_col)."""
+        p = [C.c_void_p() for _ in range(4)]
+        _check(N.lib().jtk_batch_decode_stops_device_result(self._h, *(C.byref(x) for x in p)))
         return tuple(x.value for x in p)
 
     def set_profiling(self, on=True):
@@ -1497,9 +1532,10 @@ class HipEncoding:
             _check(int(status.min()))
         return counts.tolist()
 
-    def decode_batch(self, token_lists, strict=True):
+    def decode_batch(self, token_lists, strict=True, stop_strings=None, search_from=None, keep_stop_string=False):
         """List of token-id lists -> list of bytes (Encoding.decodeBytes for each), one device call.
-        strict: raise for a list with an unknown id, as the reference does (GptBytePairEncoding.java:313)."""
+        strict: raise for a list with an unknown id, as the reference does (GptBytePairEncoding.java:313).
+        stop_strings, search_from, keep_stop_string: as for decode_rows."""
         seq_off = np.zeros(len(token_lists) + 1, dtype=np.int64)
         if token_lists:
             np.cumsum([len(t) for t in token_lists], out=seq_off[1:])
@@ -1511,6 +1547,8 @@ class HipEncoding:
             q = int(np.argmin(status))
             raise EncodingError(int(status[q]), "Unknown token for decoding (list %d)" % q)
         raw = out.tobytes()
+        if stop_strings is not None:
+            return self._cut_at_stops(b, raw, byte_off, len(token_lists), stop_strings, search_from, keep_stop_string)
         return [raw[byte_off[q]:byte_off[q + 1]] for q in range(len(token_lists))]
 
     def _stop_ids(self, stop):
@@ -1522,7 +1560,8 @@ class HipEncoding:
             raise ValueError("at most %d stop ids" % N.JTK_DECODE_MAX_STOP_IDS)
         return ids
 
-    def decode_rows_device(self, rows, begin=None, end=None, pad_id=None, stop=(), keep_stop=False, cell_offsets=False):
+    def decode_rows_device(self, rows, begin=None, end=None, pad_id=None, stop=(), keep_stop=False, cell_offsets=False,
+                           stop_strings=None, search_from=None):
         """Encoding.decodeBytes for every row of a device-resident id matrix, as generate() or this library's padded rows hand
         it out (jtk_batch_decode_rows_device; the rule is in jtk_decode_rows_rules.h).  rows: 2-d CUDA torch.int32 / int64
         tensor on this encoding's device with stride(1) == 1 (a row-strided view is read in place); begin / end: CUDA int64
@@ -1530,7 +1569,12 @@ class HipEncoding:
         ids or special-token literals, the first of which ends its row (keep_stop: and is decoded too).  Returns a dict of CUDA
         tensors written on torch.cuda.current_stream(): bytes uint8, byte_off int64 [n_rows + 1], status int32 [n_rows] (0 or
         JTK_ERR_UNKNOWN_TOKEN; rows do not raise) and, with cell_offsets, cell_byte int64 [n_rows, width]: where in `bytes`
-        every cell's bytes start.  The call waits as decode does: once for the size of the output, once at the end."""
+        every cell's bytes start.  The call waits as decode does: once for the size of the output, once at the end.
+        stop_strings (a sequence of bytes / str, a str as its UTF-8 bytes; None: no search) runs jtk_batch_decode_find_stops over
+        the rows' bytes and adds stop_pos int64, stop_which int32, hold int32 and stop_col int64, each [n_rows] (the rule is
+        jtk_stop_rules.h; positions are bytes in `bytes`, UTF-16 positions of stops are not computed); search_from: CUDA int64
+        [n_rows] or None, where in every row's bytes the search starts.  cell_byte is then computed for stop_col even without
+        cell_offsets, but returned only with it."""
         import torch
         dev = N.lib().jtk_encoding_device(self._h)
         if (not isinstance(rows, torch.Tensor) or rows.device.type != "cuda" or rows.dim() != 2
@@ -1553,6 +1597,13 @@ class HipEncoding:
             if (not isinstance(t, torch.Tensor) or t.device != device or t.dtype != torch.int64 or t.dim() != 1 or t.numel() != nr
                     or not t.is_contiguous()):
                 raise ValueError("%s must be a contiguous CUDA int64 tensor of n_rows entries on %s" % (name, device))
+        if search_from is not None:
+            if stop_strings is None:
+                raise ValueError("search_from needs stop_strings")
+            t = search_from
+            if (not isinstance(t, torch.Tensor) or t.device != device or t.dtype != torch.int64 or t.dim() != 1 or t.numel() != nr
+                    or not t.is_contiguous()):
+                raise ValueError("search_from must be a contiguous CUDA int64 tensor of n_rows entries on %s" % device)
         stop_ids = self._stop_ids(stop)
         b = self._b()
         cur = torch.cuda.current_stream(device)
@@ -1562,11 +1613,12 @@ class HipEncoding:
             side = torch.cuda.ExternalStream(b.stream(), device=device)
             side.wait_stream(cur)
         stream = (side or cur).cuda_stream
-        cells = torch.empty((nr, width), dtype=torch.int64, device=device) if cell_offsets else None
+        want_cells = cell_offsets or stop_strings is not None
+        cells = torch.empty((nr, width), dtype=torch.int64, device=device) if want_cells else None
         nb = b.decode_rows_device(rows.data_ptr() if nr * width else None, rows.element_size(), nr, width, stride,
                                   None if begin is None else begin.data_ptr(), None if end is None else end.data_ptr(),
                                   0 if pad_id is None else int(pad_id), stop_ids, pad_id is not None, keep_stop,
-                                  cells.data_ptr() if cell_offsets and nr * width else None, stream)
+                                  cells.data_ptr() if want_cells and nr * width else None, stream)
         out = dict(bytes=torch.empty(nb, dtype=torch.uint8, device=device), byte_off=torch.empty(nr + 1, dtype=torch.int64, device=device),
                    status=torch.empty(nr, dtype=torch.int32, device=device))
         for key, src in zip(("bytes", "byte_off", "status"), b.decode_device_result()):
@@ -1575,13 +1627,43 @@ class HipEncoding:
                 _copy_d2d(t.data_ptr(), src, t.numel() * t.element_size(), stream)
         if cell_offsets:
             out["cell_byte"] = cells
+        if stop_strings is not None:
+            b.decode_find_stops(stop_strings, None if search_from is None else search_from.data_ptr(),
+                                cells.data_ptr() if nr * width else None, width, stream)
+            for key, dt, src in zip(("stop_pos", "stop_which", "hold", "stop_col"), (torch.int64, torch.int32, torch.int32, torch.int64),
+                                    b.decode_stops_device_result()):
+                t = out[key] = torch.empty(nr, dtype=dt, device=device)
+                if nr:
+                    _copy_d2d(t.data_ptr(), src, nr * t.element_size(), stream)
         if side is not None:
             cur.wait_stream(side)
         return out
 
-    def decode_rows(self, rows, begin=None, end=None, pad_id=None, stop=(), keep_stop=False, strict=True):
+    def _cut_at_stops(self, b, raw, byte_off, n, stop_strings, search_from, keep_stop_string):
+        """The sequences of the batch's last decode, cut at the first stop string (jtk_batch_decode_find_stops): search_from is
+        a host array of n byte offsets or None; keep_stop_string keeps the matched string at the end of its sequence."""
+        bs = _stop_blob(stop_strings)
+        lens = np.diff(bs[1].astype(np.int64))
+        d_from = None
+        if search_from is not None:
+            f = np.ascontiguousarray(search_from, dtype=np.int64)
+            if f.shape != (n,):
+                raise ValueError("search_from needs one entry per sequence")
+            d_from = _DeviceArray(f)
+        try:
+            b.decode_find_stops(stop_strings, None if d_from is None else d_from.ptr)
+            pos, which, _, _ = b.decode_stops_fetch()
+        finally:
+            if d_from is not None:
+                d_from.free()
+        return [raw[byte_off[q]:pos[q] + (int(lens[which[q]]) if keep_stop_string and which[q] >= 0 else 0)] for q in range(n)]
+
+    def decode_rows(self, rows, begin=None, end=None, pad_id=None, stop=(), keep_stop=False, strict=True, stop_strings=None,
+                    search_from=None, keep_stop_string=False):
         """The same for a numpy id matrix (2-d, int32 or int64) -> list of bytes, one per row.  strict: raise for a row with an
-        unknown id among its decoded cells, as decode_batch does."""
+        unknown id among its decoded cells, as decode_batch does.  stop_strings: every row is cut at its first stop string
+        (found on the device: jtk_batch_decode_find_stops), searched from byte search_from[r] of the row (a host array, None:
+        0); keep_stop_string: the matched string stays at the row's end."""
         b = self._b()
         rows = np.asarray(rows)
         b.decode_rows_host(rows, begin, end, 0 if pad_id is None else int(pad_id), self._stop_ids(stop), pad_id is not None, keep_stop)
@@ -1590,6 +1672,8 @@ class HipEncoding:
             q = int(np.argmin(status))
             raise EncodingError(int(status[q]), "Unknown token for decoding (row %d)" % q)
         raw = out.tobytes()
+        if stop_strings is not None:
+            return self._cut_at_stops(b, raw, byte_off, rows.shape[0], stop_strings, search_from, keep_stop_string)
         return [raw[byte_off[q]:byte_off[q + 1]] for q in range(rows.shape[0])]
 
     # ---- UTF-16 in and out: a Java String's char[] crosses as it is (the rules are jtk_utf16_rules.h) -------------
@@ -1696,12 +1780,14 @@ class HipEncoding:
         raw = units.tobytes()
         return [raw[2 * unit_off[q]:2 * unit_off[q + 1]].decode("utf-16-le", "surrogatepass") for q in range(len(token_lists))]
 
-    def decode_rows_utf16_device(self, rows, begin=None, end=None, pad_id=None, stop=(), keep_stop=False, cell_offsets=False):
+    def decode_rows_utf16_device(self, rows, begin=None, end=None, pad_id=None, stop=(), keep_stop=False, cell_offsets=False,
+                                 stop_strings=None, search_from=None):
         """decode_rows_device, then the rows' bytes as UTF-16 units (jtk_batch_decode_utf16).  Returns its dict with, added, units
         uint16 and unit_off int64 [n_rows + 1] (CUDA tensors written on torch.cuda.current_stream()): row r is
-        units[unit_off[r]:unit_off[r + 1]], new String(bytes of row r, UTF_8).  status is the decode's."""
+        units[unit_off[r]:unit_off[r + 1]], new String(bytes of row r, UTF_8).  status is the decode's.  stop_strings /
+        search_from: as for decode_rows_device; the stops are positions in `bytes`, not in `units`."""
         import torch
-        out = self.decode_rows_device(rows, begin, end, pad_id, stop, keep_stop, cell_offsets)
+        out = self.decode_rows_device(rows, begin, end, pad_id, stop, keep_stop, cell_offsets, stop_strings, search_from)
         device, nr = rows.device, rows.shape[0]
         b = self._b()
         cur, side, stream = self._torch_stream(b, device)
