@@ -1787,6 +1787,9 @@ template <int I> __device__ __forceinline__ uint32_t res_tok(const uint4& r) {
 
 constexpr int PACK_STAGE = JTK_PACK_STAGE;     // tokens of a tile assembled in LDS (ordinary text: a few hundred)
 constexpr int PQT = JTK_PACK_TINY;
+// s_waitcnt operand "vmcnt(0)" in the gfx9 encoding (gfx950 included): vmcnt = bits 3:0 and 15:14, expcnt (bits 6:4) and
+// lgkmcnt (bits 11:8) at their maxima, so only vector memory is waited for.  Other targets lay the fields out differently.
+constexpr int WAITCNT_VMCNT0_GFX9 = 0x0F70;
 
 __global__ void __launch_bounds__(64) k_pack_tokens(JtkWork w) {
     // ONE WAVE PER TILE, no workgroup barriers.  A wave keeps a whole tile in flight: 8 list entries per lane, the head
@@ -1796,7 +1799,7 @@ __global__ void __launch_bounds__(64) k_pack_tokens(JtkWork w) {
     // Results and assembly words are one array of 16-byte slots (jtk_stage_rules.h): the slots that the tile's tokens leave
     // free hold the results beyond the staged heads, so that a tile with many merged pieces finds them in LDS too.
     __shared__ uint4 s_qe[JTK_PACK_SLOTS + JTK_PACK_OUT_SLOTS];
-    __shared__ uint2 s_qt[PQT];                 // staged results of the tile's tiny pieces
+    __shared__ uint2 s_qt[PQT + 1];             // staged results of the tile's tiny pieces (+ 1: a step reads 16 bytes at a result)
     __shared__ uint64_t s_dm[TW];
     __shared__ uint32_t s_ext[8];               // per bin: jtk_stage_word of its extension (tiles with results beyond the heads)
     uint32_t* const s_out = reinterpret_cast<uint32_t*>(s_qe + JTK_PACK_SLOTS);
@@ -1830,6 +1833,9 @@ __global__ void __launch_bounds__(64) k_pack_tokens(JtkWork w) {
             }
         }
     } else tile_base = w.tile_off[tile];
+    // (as scalars: a step then forms its store address once, from this base and a 32-bit offset per lane)
+    tile_base = (int64_t)((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)tile_base) |
+                          (uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(uint32_t)((uint64_t)tile_base >> 32)) << 32);
     uint32_t* const dst = reinterpret_cast<uint32_t*>(w.tokens + tile_base);
     uint32_t e[8];
 #pragma unroll
@@ -1930,8 +1936,8 @@ __global__ void __launch_bounds__(64) k_pack_tokens(JtkWork w) {
     uint32_t run = 0;
     // a tiny piece's 8-byte result as a merge result word: the ids are where res_tok<0..2> looks, the count moves up
     auto tiny_word = [](uint2 r) { return make_uint4(r.x, r.y & 0x3FFFFFFFu, 0u, (r.y >> 30) << 24); };
+    const bool anydoc = __ballot(dmw != 0ull) != 0ull;                    // (wave-uniform) a document starts in this tile
     // one step: 64 consecutive pieces of the list, entry ej in lane order; out = s_out or dst
-#define STORE(x) do { if (store) { x; } } while (0)
     auto step = [&](uint32_t* out, uint32_t ej, int k) {
         const bool valid = k < np;
         const bool hard = (ej & JTK_PL_HARD) != 0;
@@ -1947,15 +1953,22 @@ __global__ void __launch_bounds__(64) k_pack_tokens(JtkWork w) {
             sidx = x ? (xw & 0xFFFFu) + qi : sidx;
             inlds = staged || x;
         }
-        uint4 qe = s_qe[sidx];
-        if (__ballot(queued && tinyp)) { if (staged && tinyp) qe = tiny_word(s_qt[qi]); }
-        uint32_t c = valid ? (hard ? (qe.w >> 24) + 1u : 1u) : 0u;
         const uint32_t off = hard ? (ej & 2047u) : ((ej >> JTK_PL_OFF_SHIFT) & 2047u);
-        const bool isdoc = valid && ((s_dm[off >> 6] >> (off & 63)) & 1ull);
+        // the step's LDS reads, requested together: one 16-byte read for either kind of result (a slot of s_qe, or a tiny
+        // piece's 8 bytes and the 8 behind them) and, in a tile with a document start, the half of the mask word with the
+        // piece's bit
+        const uint2* const rp = staged && tinyp ? s_qt + qi : reinterpret_cast<const uint2*>(s_qe + sidx);
+        const uint2 lo = rp[0], hi = rp[1];
+        uint32_t dm = 0u;
+        if (anydoc) dm = reinterpret_cast<const uint32_t*>(s_dm)[off >> 5];
+        uint4 qe = make_uint4(lo.x, lo.y, hi.x, hi.y);
+        if (staged && tinyp) qe = tiny_word(lo);
+        uint32_t c = valid ? (hard ? (qe.w >> 24) + 1u : 1u) : 0u;
         uint32_t pre;
         if (!__ballot(valid && hard && (!inlds || c > 7u))) {
-            // the common case, without divergent branches: exclusive scan of c (1 for most lanes, at most 7) by ballots of
-            // the bits of c - 1, first tokens in one full store, the few further ones in sparse stores
+            // the common case: ballots, v_mbcnt and stores, nothing to wait for.  Exclusive scan of c (1 for most lanes, at
+            // most 7) by ballots of the bits of c - 1, first tokens in one full store, the few further ones in sparse
+            // stores at constant offsets from one address, the levels under the wave-uniform tests of the ballots
             const uint32_t x = c ? c - 1u : 0u;
             const uint64_t bv = __ballot(valid);
             const uint64_t b0 = __ballot((x & 1u) != 0u), b1 = __ballot((x & 2u) != 0u), b2 = __ballot((x & 4u) != 0u);
@@ -1967,22 +1980,27 @@ __global__ void __launch_bounds__(64) k_pack_tokens(JtkWork w) {
                 pre += 2u * below(b1, 0u) + 4u * below(b2, 0u);
                 run += 2u * (uint32_t)__popcll(b1) + 4u * (uint32_t)__popcll(b2);
             }
-            if (valid) STORE(out[pre] = (hard ? qe.x : ej) & JTK_HT_ID_MASK);
-            if (b0 | b1 | b2) {
-                if (c > 1u) STORE(out[pre + 1] = res_tok<1>(qe));
-                if (c > 2u) STORE(out[pre + 2] = res_tok<2>(qe));
-                if (b1 | b2) {
-                    if (c > 3u) STORE(out[pre + 3] = res_tok<3>(qe));
-                    if (b2) {
-                        if (c > 4u) STORE(out[pre + 4] = res_tok<4>(qe));
-                        if (c > 5u) STORE(out[pre + 5] = res_tok<5>(qe));
-                        if (c > 6u) STORE(out[pre + 6] = res_tok<6>(qe));
+            if (store) {
+                char* const p = reinterpret_cast<char*>(out) + (size_t)(pre * 4u);    // (a tile's tokens: far below 2^30)
+                auto put = [&](int i, uint32_t v) { *reinterpret_cast<uint32_t*>(p + 4 * i) = v; };
+                if (valid) put(0, (hard ? qe.x : ej) & JTK_HT_ID_MASK);
+                if (b0 | b1 | b2) {
+                    if (c > 1u) put(1, res_tok<1>(qe));
+                    if (b1 | b2) {                                     // (c > 2: bit 1 or bit 2 of c - 1)
+                        if (c > 2u) put(2, res_tok<2>(qe));
+                        if (c > 3u) put(3, res_tok<3>(qe));
+                        if (b2) {
+                            if (c > 4u) put(4, res_tok<4>(qe));
+                            if (c > 5u) put(5, res_tok<5>(qe));
+                            if (c > 6u) put(6, res_tok<6>(qe));
+                        }
                     }
                 }
             }
         } else {
             // general case: results beyond what is staged, results of more than 7 tokens (tokens in htok), pieces merged
-            // by the wave / workgroup phases (count and tokens in htok)
+            // by the wave / workgroup phases (count and tokens in htok).  It consumes what it loads and stores all of its
+            // tokens before it rejoins: nothing loaded here is live in the common path, which so never waits for memory.
             const uint32_t qb = (uint32_t)__shfl((int)meta, (int)(bin < JTK_NBINS ? bin : 0u));   // (all lanes take part)
             if (valid && queued && !inlds) {
                 qe = tinyp ? tiny_word(res5[qi]) : (w.qd[bin] + shard * w.q_cap[bin] + qb)[qi];
@@ -1991,35 +2009,52 @@ __global__ void __launch_bounds__(64) k_pack_tokens(JtkWork w) {
             const uint32_t inc = jtk_wave_incl_scan(c);
             pre = run + inc - c;
             run += (uint32_t)__shfl((int)inc, 63);
-            if (valid) {
-                if (!hard) STORE(out[pre] = ej & JTK_HT_ID_MASK);
+            if (valid && store) {
+                if (!hard) out[pre] = ej & JTK_HT_ID_MASK;
                 else if (queued && c <= 7u) {
-                    STORE(out[pre] = qe.x & JTK_HT_ID_MASK);
-                    if (c > 1u) STORE(out[pre + 1] = res_tok<1>(qe));
-                    if (c > 2u) STORE(out[pre + 2] = res_tok<2>(qe));
-                    if (c > 3u) STORE(out[pre + 3] = res_tok<3>(qe));
-                    if (c > 4u) STORE(out[pre + 4] = res_tok<4>(qe));
-                    if (c > 5u) STORE(out[pre + 5] = res_tok<5>(qe));
-                    if (c > 6u) STORE(out[pre + 6] = res_tok<6>(qe));
-                } else if (store) pack_copy(out + pre, w.htok + B + off, c);
+                    out[pre] = qe.x & JTK_HT_ID_MASK;
+                    if (c > 1u) out[pre + 1] = res_tok<1>(qe);
+                    if (c > 2u) out[pre + 2] = res_tok<2>(qe);
+                    if (c > 3u) out[pre + 3] = res_tok<3>(qe);
+                    if (c > 4u) out[pre + 4] = res_tok<4>(qe);
+                    if (c > 5u) out[pre + 5] = res_tok<5>(qe);
+                    if (c > 6u) out[pre + 6] = res_tok<6>(qe);
+                } else pack_copy(out + pre, w.htok + B + off, c);
             }
+            __builtin_amdgcn_s_waitcnt(WAITCNT_VMCNT0_GFX9);             // vmcnt(0): this region's loads and stores end here
         }
         // document starts among these pieces: tokens of the tile before them
-        if (__ballot(isdoc)) { if (isdoc) w.docpre[B + off] = pre; }
+        if (anydoc) {
+            const bool isdoc = valid && ((dm >> (off & 31u)) & 1u);
+            if (__ballot(isdoc)) { if (isdoc) w.docpre[B + off] = pre; }
+        }
     };
-#undef STORE
-    for (int k0 = 0; k0 < np; k0 += 512) {
-        if (k0) {
+    // A round is 512 pieces, eight steps on list words that are in registers.  A tile of more pieces requests the next round's
+    // words before this round's last step and waits for them once, behind the round: a step waits for no load.  (The last
+    // step stands twice, so that no path leads from the request past the wait.)
+    auto rounds = [&](uint32_t* out) {
+        for (int k0 = 0;; k0 += 512) {
 #pragma unroll
-            for (int j = 0; j < 8; j++) { const int k = k0 + j * 64 + lane; e[j] = (k < np) ? plist[k] : 0u; }
-        }
+            for (int j = 0; j < 7; j++) {
+                if (k0 + j * 64 >= np) return;
+                step(out, e[j], k0 + j * 64 + lane);
+            }
+            if (k0 + 512 >= np) {                                         // (wave-uniform) the tile's last round
+                if (k0 + 448 < np) step(out, e[7], k0 + 448 + lane);
+                return;
+            }
+            const uint32_t* nl = plist + k0 + 512 + lane;                 // (inside the tile's list: k0 <= 1024)
+            const uint32_t e7 = e[7];
 #pragma unroll
-        for (int j = 0; j < 8; j++) {
-            if (k0 + j * 64 >= np) break;
-            if (stage) step(s_out, e[j], k0 + j * 64 + lane);
-            else step(dst, e[j], k0 + j * 64 + lane);
+            for (int i = 0; i < 8; i++) e[i] = nl[i * 64];
+            step(out, e7, k0 + 448 + lane);
+            __builtin_amdgcn_s_waitcnt(WAITCNT_VMCNT0_GFX9);             // vmcnt(0), here and not where a step first looks at a word
+#pragma unroll
+            for (int i = 0; i < 8; i++) e[i] = (k0 + 512 + i * 64 + lane < np) ? e[i] : 0u;
         }
-    }
+    };
+    if (stage) rounds(s_out);
+    else rounds(dst);
     if (stage && store) {
         wave_lds_fence();
         for (uint32_t i = lane; i < total; i += WAVE) dst[i] = s_out[i];

@@ -13,7 +13,9 @@ line per loop with the sums over its blocks.  Classes go by mnemonic prefix only
     smem    s_load*, s_buffer_load*              scalar memory reads
     lds     ds_*                                 LDS reads, writes and atomics
     vmem    global_*, buffer_*, flat_*, scratch_*  vector memory
-    wait    s_wait*, s_nop*, s_sle*, s_barr*     waits and barriers
+    wait    s_wait*, s_nop*, s_sle*, s_barr*     waits and barriers; of these, by the terms of an s_waitcnt:
+    w_vm    ... with a vmcnt term                vector-memory waits (loads and, on gfx9, stores)
+    w_lgkm  ... with an lgkmcnt term             LDS, scalar-memory and message waits (one s_waitcnt may count in both)
     branch  s_bra*, s_cbr*, s_setpc*, s_swap*, s_endp*
 
 A block starts at a label and after every branch.  Counts are static: a block under an exec-mask branch counts
@@ -24,6 +26,7 @@ import re
 import sys
 
 CLASSES = ("valu", "salu", "smem", "lds", "vmem", "wait", "branch")
+WAIT_KINDS = ("w_vm", "w_lgkm")
 PREFIXES = (
     ("branch", ("s_bra", "s_cbr", "s_setpc", "s_swap", "s_endp")),
     ("wait", ("s_wait", "s_nop", "s_sle", "s_barr")),
@@ -66,6 +69,7 @@ class Block:
     def __init__(self, name):
         self.name = name
         self.counts = dict.fromkeys(CLASSES, 0)
+        self.waits = dict.fromkeys(WAIT_KINDS, 0)
         self.targets = []         # labels branched to
         self.falls = True         # control can run into the next block
         self.succ = []
@@ -100,6 +104,9 @@ def blocks_of(lines):
             cut = False
         b = blocks[-1]
         b.counts[cls] += 1
+        if m.group(1) == "s_waitcnt":
+            b.waits["w_vm"] += "vmcnt" in m.group(2)
+            b.waits["w_lgkm"] += "lgkmcnt" in m.group(2)
         if cls == "branch":
             cut = True
             t = m.group(2).strip()
@@ -150,19 +157,21 @@ def main():
     for h in sorted(loops, key=lambda h: -len(loops[h])):     # the smallest loop that holds a block names it
         for x in loops[h]:
             in_loop[x] = h
-    head = "%-16s %5s " % ("block", "all") + " ".join("%6s" % c for c in CLASSES) + "  loop            to"
+    head = "%-16s %5s " % ("block", "all") + " ".join("%6s" % c for c in CLASSES + WAIT_KINDS) + "  loop            to"
     print(head)
     tot = Block("kernel")
     for i, b in enumerate(blocks):
         for c in CLASSES:
             tot.counts[c] += b.counts[c]
+        for c in WAIT_KINDS:
+            tot.waits[c] += b.waits[c]
         if a.loops_only and i not in in_loop:
             continue
         h = in_loop.get(i)
         mark = "" if h is None else ("%s%s" % ("*" if h in inner else " ", blocks[h].name))
-        print("%-16s %5d " % (b.name, b.total) + " ".join("%6d" % b.counts[c] for c in CLASSES) +
+        print("%-16s %5d " % (b.name, b.total) + " ".join("%6d" % b.counts[c] for c in CLASSES) + " " + " ".join("%6d" % b.waits[c] for c in WAIT_KINDS) +
               "  %-15s %s" % (mark, " ".join(blocks[s].name for s in b.succ)))
-    print("%-16s %5d " % ("kernel", tot.total) + " ".join("%6d" % tot.counts[c] for c in CLASSES))
+    print("%-16s %5d " % ("kernel", tot.total) + " ".join("%6d" % tot.counts[c] for c in CLASSES) + " " + " ".join("%6d" % tot.waits[c] for c in WAIT_KINDS))
     print()
     print("loops (* innermost): sums over the loop's blocks")
     for h in sorted(loops):
@@ -170,7 +179,10 @@ def main():
         for x in loops[h]:
             for c in CLASSES:
                 s.counts[c] += blocks[x].counts[c]
+            for c in WAIT_KINDS:
+                s.waits[c] += blocks[x].waits[c]
         print("%s%-15s %5d " % ("*" if h in inner else " ", blocks[h].name, s.total) + " ".join("%6d" % s.counts[c] for c in CLASSES) +
+              " " + " ".join("%6d" % s.waits[c] for c in WAIT_KINDS) +
               "  %d blocks, %s .. %s" % (len(loops[h]), blocks[min(loops[h])].name, blocks[max(loops[h])].name))
     return 0
 
