@@ -133,6 +133,13 @@ int jtk_encoding_id_bits(const jtk_encoding* enc);               /* 16 + hb of "
  * Output (after jtk_batch_fetch / in device memory): token ids of all documents back to back in
  * document order, document d occupying [tok_off[d], tok_off[d+1]); status[d] = JTK_OK or
  * JTK_ERR_UNSUPPORTED_SPECIAL / JTK_ERR_BAD_UTF8 / JTK_ERR_PIECE_TOO_LONG for that document.
+ *
+ * What a batch holds: the result of its last encode and what was derived from it (truncation, chunks, the byte scan, pack,
+ * the character index), and the result of its last decode and what was derived from that (UTF-16 units, stops).  Every
+ * encode entry point drops the first group, every decode entry point the second, at its point of no return: behind the checks
+ * that read only the arguments, before anything the old result lives in is touched.  So a call refused for its arguments
+ * leaves the batch as it was, and a call that fails past that point leaves no result: the calls that read one return
+ * JTK_ERR_INVALID_ARGUMENT until the next encode (decode) succeeds.
  */
 int jtk_batch_create(const jtk_encoding* enc, jtk_batch** out);
 void jtk_batch_destroy(jtk_batch* b);
@@ -284,7 +291,8 @@ int jtk_batch_device_truncated(jtk_batch* b, const int64_t** d_kept, const uint8
  * (8 per wanted token + 64, 4x more for the documents that turn out to need it) and a result is taken once it is certain to be the
  * head of the full token list.  Host buffers.  tokens: [n_docs * max_tokens], document d's ids at tokens + d * max_tokens;
  * kept[d] ids are valid; truncated[d] (may be NULL) = EncodingResult.isTruncated(); status[d] (may be NULL) is JTK_OK or
- * JTK_ERR_UNSUPPORTED_SPECIAL.  flags: JTK_ENCODE_ORDINARY or 0. */
+ * JTK_ERR_UNSUPPORTED_SPECIAL.  flags: JTK_ENCODE_ORDINARY or 0.  Afterwards the batch's encode result is that of the last
+ * group of leading bytes the call encoded (an internal job, of no use to the caller), or the earlier one if it encoded none. */
 int jtk_batch_encode_max_tokens(jtk_batch* b, const uint8_t* utf8, const int64_t* doc_off, int64_t n_docs, uint32_t flags,
                                 int64_t max_tokens, int32_t* tokens, int64_t* kept, uint8_t* truncated, int32_t* status);
 
@@ -302,7 +310,8 @@ int jtk_batch_encode_max_tokens(jtk_batch* b, const uint8_t* utf8, const int64_t
  *            jtk_batch_encode_device.  The call waits for the device once per round, to read a 16-byte word (open
  *            documents, gathered bytes), plus the chunk plan's wait when the leading bytes span more than one chunk
  *            (JTK_OPT_CHUNK_BYTES).  It returns when all rows are written.
- *   Batch:   afterwards the batch holds no encode result: jtk_batch_fetch / jtk_batch_truncate fail until the next encode. */
+ *   Batch:   afterwards the batch holds no encode result, whether the call succeeded or failed in any round: jtk_batch_fetch /
+ *            jtk_batch_truncate fail until the next encode. */
 int jtk_batch_encode_device_max_tokens(jtk_batch* b, const uint8_t* d_utf8, const int64_t* d_doc_off, int64_t n_docs,
                                        int64_t n_bytes, uint32_t flags, int64_t max_tokens, int32_t pad_id,
                                        int32_t* d_tokens, int64_t* d_kept, uint8_t* d_truncated, int32_t* d_status,

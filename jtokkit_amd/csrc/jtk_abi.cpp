@@ -50,6 +50,9 @@ struct DevBuf {
     }
     void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
 };
+struct TmpDevBuf : DevBuf {      // staging that lives for one call
+    ~TmpDevBuf() { release(); }
+};
 
 constexpr int N_STAGES = 8;
 const char* const STAGE_NAMES[N_STAGES] = {"mark_docs", "validate_utf8", "pretok_split", "piece_resolve", "bpe_merge",
@@ -208,6 +211,35 @@ struct jtk_batch {
     std::vector<hipEvent_t> prof_ev;     // [chunk][stage][start, end]
     int prof_chunks = 0;                 // chunks of the last job that recorded events
 };
+
+// What a batch holds exists relative to its last encode, or to its last decode.  These two are the only places that give it up
+// on behalf of another call (a pass that replaces its own result -- chunk, pack, the char index, UTF-16 out, stops -- clears
+// its own flag and no other).  Every encode / decode entry calls its one at the point of no return: behind the checks that
+// read only the arguments, before the first allocation, copy or launch that can touch memory the old result lives in.  A call
+// that fails past that point leaves no result.
+static void drop_encode_result(jtk_batch* b) {
+    b->have_result = b->have_host_result = b->have_trunc = b->have_chunk = b->have_tiles = b->have_pack = false;
+    b->cp_unit = -1;
+    b->ck_end_level = nullptr;
+    b->synced = false;
+}
+static void drop_decode_result(jtk_batch* b) {
+    b->have_decode = b->have_u16_dec = b->have_stops = false;
+    b->dec_rows_width = -1;
+}
+
+static hipStream_t pick_stream(const jtk_batch* b, void* stream_or_null) { return stream_or_null ? (hipStream_t)stream_or_null : b->stream; }
+
+// what a pass over the last encode needs of it, besides that there is one
+enum : unsigned { NEED_IDS = 1,         // token ids (the encode was not count-only)
+                  NEED_TEXT_POS = 2 };  // positions that are positions in the text (it did not take caller-supplied pieces)
+static int need_encode(const jtk_batch* b, unsigned what) {
+    if (!b || !b->have_result) return fail(JTK_ERR_INVALID_ARGUMENT, "no batch encode result on this batch (jtk_batch_encode_device_max_tokens leaves none)");
+    if ((what & NEED_IDS) && (b->job_flags & JTK_ENCODE_COUNT_ONLY)) return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode was count-only: there are no token ids");
+    if ((what & NEED_TEXT_POS) && b->job_pieces)
+        return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode took caller-supplied pieces: its positions are positions in the decoded stream, not in the text");
+    return JTK_OK;
+}
 
 #include "jtk_unicode_tables.h"
 #include "jtk_block_classify.h"
@@ -909,16 +941,10 @@ int run_job(jtk_batch* b, const uint8_t* d_text, const uint8_t* h_text, const in
     b->job_bytes = n_bytes;
     b->job_flags = flags;
     b->job_pieces = pieces != nullptr;
-    b->have_result = true;
-    b->have_host_result = to_host;
-    b->have_trunc = false;
-    b->have_chunk = false;
-    b->have_tiles = false;
-    b->have_pack = false;
-    b->cp_unit = -1;
-    b->synced = false;
     b->last_stream = s;
     b->prof_chunks = prof ? n_chunks : 0;
+    // (what the last encode left was dropped by the entry point, before any of the above)
+    b->have_result = true; b->have_host_result = to_host;
     return JTK_OK;
 }
 
@@ -945,6 +971,27 @@ int plan_device_chunks(jtk_batch* b, const int64_t* d_doc_off, int64_t n_docs, i
             if (o < b->chunk_off.back() || o > n_bytes) return fail(JTK_ERR_INVALID_ARGUMENT, "document offsets are not non-decreasing within [0, n_bytes]");
             b->chunk_doc.push_back(d);
             b->chunk_off.push_back(o);
+        }
+    }
+    b->chunk_doc.push_back(n_docs);
+    b->chunk_off.push_back(n_bytes);
+    return JTK_OK;
+}
+
+// Chunk plan of a batch whose offsets are in host memory, and the check of the offsets, in one pass; cb: the chunk size.
+// (A refusal leaves the plan vectors half written and the kept device plan forgotten: no result reads them, every encode
+// plans anew, and a second pass over the offsets only to spare them is not worth its time on the per-call path.)
+int plan_host_chunks(jtk_batch* b, const int64_t* doc_off, int64_t n_docs, int64_t n_bytes, int64_t cb) {
+    b->plan_doc_off = nullptr;
+    b->chunk_doc.assign(1, 0);
+    b->chunk_off.assign(1, 0);
+    int64_t next = cb;
+    for (int64_t d = 0; d < n_docs; d++) {
+        if (doc_off[d + 1] < doc_off[d]) return fail(JTK_ERR_INVALID_ARGUMENT, "doc_off must be non-decreasing");
+        if (doc_off[d] >= next && d > b->chunk_doc.back() && n_bytes - doc_off[d] > cb / 4) {
+            b->chunk_doc.push_back(d);
+            b->chunk_off.push_back(doc_off[d]);
+            next = doc_off[d] + cb;
         }
     }
     b->chunk_doc.push_back(n_docs);
@@ -1044,6 +1091,7 @@ int run_allow_special(jtk_batch* b, const uint8_t* d_text, const int64_t* d_doc_
     const uint32_t sub_flags = JTK_ENCODE_ORDINARY | (flags & (JTK_ENCODE_VALIDATE_UTF8 | JTK_ENCODE_COUNT_ONLY));
     flags &= ~(uint32_t)JTK_ENCODE_COMPACT_IDS;
     if ((rc = plan(w.sub_off, w.n_sub)) || (rc = run_job(b, d_text, nullptr, w.sub_off, w.n_sub, n_bytes, sub_flags, s, false))) return rc;
+    drop_encode_result(b);           // (the sub-documents' result is not the batch's: the stitched one is, once it is whole)
     // the stitched result: JtkResult | tok_off [n_docs + 1] | tokens (status: in the find scratch)
     const size_t o_tok_off = 64, o_tokens = align_up(o_tok_off + ((size_t)n_docs + 1) * 8, 256);
     if ((rc = b->sp_out.ensure(o_tokens + (count_only ? 0 : ((size_t)n_bytes + 64) * 4)))) return rc;
@@ -1060,8 +1108,6 @@ int run_allow_special(jtk_batch* b, const uint8_t* d_text, const int64_t* d_doc_
     b->job_doc_off = d_doc_off;
     b->job_docs = n_docs;
     b->job_flags = flags & ~(uint32_t)JTK_ENCODE_TO_HOST;
-    b->have_host_result = false;
-    b->host_compact = false;
     if (to_host) {
         // (the stitch comes after the last chunk: the ids go to the host in one copy behind it, not chunk by chunk)
         HIP_TRY(hipStreamSynchronize(s));
@@ -1087,9 +1133,9 @@ int run_allow_special(jtk_batch* b, const uint8_t* d_text, const int64_t* d_doc_
         } else if (nt > 0 && !count_only) HIP_TRY(hipMemcpyAsync(b->h_tokens, w.tokens, (size_t)nt * 4, hipMemcpyDeviceToHost, s));
         b->r_tokens = compact ? nullptr : b->h_tokens; b->r_tok_off = b->h_tok_off; b->r_status = b->h_status;
         b->r_lo = (const uint16_t*)b->h_tokens; b->r_hi = b->h_hi;
-        b->have_host_result = true;
-        b->host_compact = compact_req;
     }
+    b->host_compact = compact_req;
+    b->have_result = true; b->have_host_result = to_host;
     return JTK_OK;
 }
 
@@ -1106,30 +1152,24 @@ int jtk_batch_encode_device(jtk_batch* b, const uint8_t* d_utf8, const int64_t* 
     if (flags & JTK_ENCODE_TO_HOST) return fail(JTK_ERR_INVALID_ARGUMENT, "JTK_ENCODE_TO_HOST is for jtk_batch_encode (host buffers)");
     if (flags & JTK_ENCODE_COMPACT_IDS) return fail(JTK_ERR_INVALID_ARGUMENT, "JTK_ENCODE_COMPACT_IDS is for jtk_batch_encode with JTK_ENCODE_TO_HOST (on the device: jtk_batch_compact)");
     HIP_TRY(hipSetDevice(b->enc->device));
-    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    drop_encode_result(b);
+    hipStream_t s = pick_stream(b, stream_or_null);
     if ((flags & JTK_ENCODE_ALLOW_SPECIAL) && !sp_any_allowed(b)) flags &= ~(uint32_t)JTK_ENCODE_ALLOW_SPECIAL;   // empty set: today's call
+    int rc;
     if (flags & JTK_ENCODE_ALLOW_SPECIAL) {
         b->plan_doc_off = nullptr;                                  // (no JTK_OPT_REUSE_CHUNK_PLAN here)
-        const int rc = run_allow_special(b, d_utf8, d_doc_off, n_docs, n_bytes, flags, s, b->chunk_bytes);
-        if (rc != JTK_OK) return rc;
-        if (n_tokens) {
-            HIP_TRY(hipStreamSynchronize(s));
-            b->synced = true;
-            *n_tokens = b->host_result->n_tokens;
+        rc = run_allow_special(b, d_utf8, d_doc_off, n_docs, n_bytes, flags, s, b->chunk_bytes);
+    } else {
+        // chunk plan: a batch of up to one chunk needs none; a larger one reads the chunk boundaries from the offsets (the one
+        // place where this call waits for the work queued on `s` before it)
+        const bool same_plan = b->reuse_plan && b->plan_doc_off == d_doc_off && b->plan_docs == n_docs && b->plan_bytes == n_bytes && b->plan_chunk_bytes == b->chunk_bytes &&
+                               b->chunk_doc.size() >= 2 && b->chunk_doc.back() == n_docs && b->chunk_off.back() == n_bytes;
+        if (!same_plan) {
+            if ((rc = plan_device_chunks(b, d_doc_off, n_docs, n_bytes, s))) return rc;
+            b->plan_doc_off = d_doc_off; b->plan_docs = n_docs; b->plan_bytes = n_bytes; b->plan_chunk_bytes = b->chunk_bytes;
         }
-        return JTK_OK;
+        if ((rc = run_job(b, d_utf8, nullptr, d_doc_off, n_docs, n_bytes, flags, s, false))) b->plan_doc_off = nullptr;
     }
-    // chunk plan: a batch of up to one chunk needs none; a larger one reads the chunk boundaries from the offsets (the one
-    // place where this call waits for the work queued on `s` before it)
-    const bool same_plan = b->reuse_plan && b->plan_doc_off == d_doc_off && b->plan_docs == n_docs && b->plan_bytes == n_bytes && b->plan_chunk_bytes == b->chunk_bytes &&
-                           b->chunk_doc.size() >= 2 && b->chunk_doc.back() == n_docs && b->chunk_off.back() == n_bytes;
-    if (!same_plan) {
-        const int rc = plan_device_chunks(b, d_doc_off, n_docs, n_bytes, s);
-        if (rc != JTK_OK) return rc;
-        b->plan_doc_off = d_doc_off; b->plan_docs = n_docs; b->plan_bytes = n_bytes; b->plan_chunk_bytes = b->chunk_bytes;
-    }
-    int rc = run_job(b, d_utf8, nullptr, d_doc_off, n_docs, n_bytes, flags, s, false);
-    if (rc != JTK_OK) b->plan_doc_off = nullptr;
     if (rc != JTK_OK) return rc;
     if (n_tokens) {
         HIP_TRY(hipStreamSynchronize(s));
@@ -1148,26 +1188,11 @@ int jtk_batch_encode(jtk_batch* b, const uint8_t* utf8, const int64_t* doc_off, 
     const int64_t n_bytes = doc_off[n_docs];
     if (n_bytes > 0 && !utf8) return fail(JTK_ERR_INVALID_ARGUMENT, "utf8 is NULL");
     if (n_bytes >= (int64_t)1 << 37) return fail(JTK_ERR_INVALID_ARGUMENT, "batch too large (128 GiB of text per call at most)");
-    // chunk plan (and the check of the offsets) in one pass
     const int64_t cb = b->host_chunk_bytes < b->chunk_bytes ? b->host_chunk_bytes : b->chunk_bytes;
-    b->plan_doc_off = nullptr;
-    b->chunk_doc.assign(1, 0);
-    b->chunk_off.assign(1, 0);
-    {
-        int64_t next = cb;
-        for (int64_t d = 0; d < n_docs; d++) {
-            if (doc_off[d + 1] < doc_off[d]) return fail(JTK_ERR_INVALID_ARGUMENT, "doc_off must be non-decreasing");
-            if (doc_off[d] >= next && d > b->chunk_doc.back() && n_bytes - doc_off[d] > cb / 4) {
-                b->chunk_doc.push_back(d);
-                b->chunk_off.push_back(doc_off[d]);
-                next = doc_off[d] + cb;
-            }
-        }
-    }
-    b->chunk_doc.push_back(n_docs);
-    b->chunk_off.push_back(n_bytes);
-    HIP_TRY(hipSetDevice(b->enc->device));
     int rc;
+    if ((rc = plan_host_chunks(b, doc_off, n_docs, n_bytes, cb))) return rc;
+    HIP_TRY(hipSetDevice(b->enc->device));
+    drop_encode_result(b);
     if ((flags & JTK_ENCODE_ALLOW_SPECIAL) && !sp_any_allowed(b)) flags &= ~(uint32_t)JTK_ENCODE_ALLOW_SPECIAL;   // empty set: today's call
     if (flags & JTK_ENCODE_ALLOW_SPECIAL) {
         // the text goes down whole (the candidates are found before any chunk is encoded); then as device input
@@ -1175,13 +1200,7 @@ int jtk_batch_encode(jtk_batch* b, const uint8_t* utf8, const int64_t* doc_off, 
         HIP_TRY(hipMemcpyAsync(b->in_off.p, doc_off, ((size_t)n_docs + 1) * 8, hipMemcpyHostToDevice, b->stream));
         if (n_bytes > 0) HIP_TRY(hipMemcpyAsync(b->in_text.p, utf8, (size_t)n_bytes, hipMemcpyHostToDevice, b->stream));
         rc = run_allow_special(b, (const uint8_t*)b->in_text.p, (const int64_t*)b->in_off.p, n_docs, n_bytes, flags, b->stream, cb);
-        if (rc != JTK_OK) return rc;
-        HIP_TRY(hipStreamSynchronize(b->stream));
-        b->synced = true;
-        if (n_tokens) *n_tokens = b->host_result->n_tokens;
-        return JTK_OK;
-    }
-    if (b->chunk_doc.size() == 2 && n_bytes <= TINY_JOB_BYTES) {
+    } else if (b->chunk_doc.size() == 2 && n_bytes <= TINY_JOB_BYTES) {
         // a per-call device batch: offsets and text go down in ONE copy (staged side by side in pinned memory; copying a few KB on
         // the host costs less than a second DMA)
         const size_t off_text = align_up(((size_t)n_docs + 1) * 8, 256), total = off_text + (size_t)n_bytes;
@@ -1228,25 +1247,10 @@ int jtk_batch_encode_pieces(jtk_batch* b, const uint8_t* utf8, const int64_t* do
             prev_end = e;
         }
     }
-    const int64_t cb = b->host_chunk_bytes < b->chunk_bytes ? b->host_chunk_bytes : b->chunk_bytes;
-    b->plan_doc_off = nullptr;
-    b->chunk_doc.assign(1, 0);
-    b->chunk_off.assign(1, 0);
-    {
-        int64_t next = cb;
-        for (int64_t d = 0; d < n_docs; d++) {
-            if (doc_off[d + 1] < doc_off[d]) return fail(JTK_ERR_INVALID_ARGUMENT, "doc_off must be non-decreasing");
-            if (doc_off[d] >= next && d > b->chunk_doc.back() && n_bytes - doc_off[d] > cb / 4) {
-                b->chunk_doc.push_back(d);
-                b->chunk_off.push_back(doc_off[d]);
-                next = doc_off[d] + cb;
-            }
-        }
-    }
-    b->chunk_doc.push_back(n_docs);
-    b->chunk_off.push_back(n_bytes);
-    HIP_TRY(hipSetDevice(b->enc->device));
     int rc;
+    if ((rc = plan_host_chunks(b, doc_off, n_docs, n_bytes, b->host_chunk_bytes < b->chunk_bytes ? b->host_chunk_bytes : b->chunk_bytes))) return rc;
+    HIP_TRY(hipSetDevice(b->enc->device));
+    drop_encode_result(b);
     if ((rc = b->in_text.ensure((size_t)n_bytes + 64)) || (rc = b->in_off.ensure(((size_t)n_docs + 1) * 8)) ||
         (rc = b->in_pieces.ensure((size_t)(n_pieces > 0 ? n_pieces : 1) * 16)))
         return rc;
@@ -1422,7 +1426,8 @@ int jtk_batch_decode_device(jtk_batch* b, const int32_t* d_ids, const int64_t* d
     if (!b || n_seqs < 0 || n_ids < 0 || (n_ids > 0 && !d_ids) || !d_seq_off) return fail(JTK_ERR_INVALID_ARGUMENT, "bad arguments");
     const jtk_encoding* enc = b->enc;
     HIP_TRY(hipSetDevice(enc->device));
-    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    drop_decode_result(b);
+    hipStream_t s = pick_stream(b, stream_or_null);
     JtkDecodeWork& w = b->dwork;
     w.ids = d_ids; w.seq_off = d_seq_off; w.n_tok = n_ids; w.n_seqs = n_seqs;
     w.n_tiles = (n_ids + JTK_DEC_TILE - 1) / JTK_DEC_TILE;
@@ -1459,10 +1464,7 @@ int jtk_batch_decode_device(jtk_batch* b, const int32_t* d_ids, const int64_t* d
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s));
     b->dec_total = total;
-    b->dec_rows_width = -1;
     b->have_decode = true;
-    b->have_u16_dec = false;
-    b->have_stops = false;
     if (n_bytes) *n_bytes = total;
     return JTK_OK;
 }
@@ -1475,6 +1477,7 @@ int jtk_batch_decode(jtk_batch* b, const int32_t* ids, const int64_t* seq_off, i
     const int64_t n_ids = seq_off[n_seqs];
     if (n_ids > 0 && !ids) return fail(JTK_ERR_INVALID_ARGUMENT, "ids is NULL");
     HIP_TRY(hipSetDevice(b->enc->device));
+    drop_decode_result(b);
     int rc;
     if ((rc = b->dec_in_ids.ensure((size_t)n_ids * 4 + 64)) || (rc = b->dec_in_off.ensure(((size_t)n_seqs + 1) * 8))) return rc;
     if (n_ids > 0) HIP_TRY(hipMemcpyAsync(b->dec_in_ids.p, ids, (size_t)n_ids * 4, hipMemcpyHostToDevice, b->stream));
@@ -1532,7 +1535,8 @@ int jtk_batch_decode_rows_device(jtk_batch* b, const void* d_rows, int id_bytes,
     if ((rc = decode_rows_args(b, d_rows, id_bytes, n_rows, width, row_stride, stop_ids, n_stop, flags, &n_cells))) return rc;
     const jtk_encoding* enc = b->enc;
     HIP_TRY(hipSetDevice(enc->device));
-    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    drop_decode_result(b);           // (dec_zero, dec_tile and dec_byte_off below are the last decode's)
+    hipStream_t s = pick_stream(b, stream_or_null);
     JtkDecodeRowsWork w{};
     w.rows = d_rows; w.id_bytes = id_bytes; w.n_rows = n_rows; w.width = width; w.row_stride = row_stride; w.n_cells = n_cells;
     w.n_tiles = (n_cells + JTK_DEC_TILE - 1) / JTK_DEC_TILE;
@@ -1556,7 +1560,6 @@ int jtk_batch_decode_rows_device(jtk_batch* b, const void* d_rows, int id_bytes,
     w.cell_byte = d_cell_byte_or_null;
     w.first_stop = n_stop > 0 ? (unsigned long long*)b->dec_first.p : nullptr;
     // phase 1: sizes (the output is allocated once they are known)
-    b->have_decode = false;
     HIP_TRY(hipMemsetAsync(z, 0, zero_bytes, s));
     int64_t total = 0;
     if (n_cells > 0) {
@@ -1577,8 +1580,6 @@ int jtk_batch_decode_rows_device(jtk_batch* b, const void* d_rows, int id_bytes,
     b->dec_total = total;
     b->dec_rows_width = width;
     b->have_decode = true;
-    b->have_u16_dec = false;
-    b->have_stops = false;
     if (n_bytes) *n_bytes = total;
     return JTK_OK;
 }
@@ -1590,6 +1591,7 @@ int jtk_batch_decode_rows(jtk_batch* b, const void* rows, int id_bytes, int64_t 
     int rc;
     if ((rc = decode_rows_args(b, rows, id_bytes, n_rows, width, row_stride, stop_ids, n_stop, flags, &n_cells))) return rc;
     HIP_TRY(hipSetDevice(b->enc->device));
+    drop_decode_result(b);
     const size_t n_elem = n_cells > 0 ? (size_t)(n_rows - 1) * (size_t)row_stride + (size_t)width : 0;   // the last row's tail is not read
     const size_t row_bytes = (size_t)(n_rows > 0 ? n_rows : 1) * 8;
     if ((rc = b->dec_in_ids.ensure(n_elem * (size_t)id_bytes + 64)) || (rc = b->dec_in_win.ensure(2 * row_bytes)) ||
@@ -1832,16 +1834,15 @@ int jtk_batch_encode_device_max_tokens(jtk_batch* b, const uint8_t* d_utf8, cons
     if (n_bytes >= (int64_t)1 << 37) return fail(JTK_ERR_INVALID_ARGUMENT, "batch too large (128 GiB of text per call at most)");
     const jtk_encoding* enc = b->enc;
     HIP_TRY(hipSetDevice(enc->device));
-    // the batch's last encode result is given up (its chunk plan and scratch are reused below)
-    b->have_result = false;
-    b->have_trunc = false;
-    b->have_chunk = false;
-    b->have_tiles = false;
-    b->have_pack = false;
-    b->cp_unit = -1;
-    b->plan_doc_off = nullptr;
+    // the batch's last encode result is given up (its chunk plan and scratch are reused below), and the rounds' prefix jobs
+    // are not results of the batch: none is left on any return path
+    struct NoResult {
+        jtk_batch* b;
+        ~NoResult() { drop_encode_result(b); b->plan_doc_off = nullptr; }
+    } no_result{b};
+    drop_encode_result(b);
     if (n_docs == 0) return JTK_OK;
-    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    hipStream_t s = pick_stream(b, stream_or_null);
     const size_t nd = (size_t)n_docs;
     const int64_t n_blk = (n_docs + 1023) / 1024;
     // scratch: hdr (4 x i64: open documents, gathered bytes, bad flag) | act[2][nd] | goff[nd + 1] | blk_base[2 * n_blk] |
@@ -1917,8 +1918,6 @@ int jtk_batch_encode_device_max_tokens(jtk_batch* b, const uint8_t* d_utf8, cons
         }
         n_in = n_act;
     }
-    b->have_result = false;
-    b->plan_doc_off = nullptr;
     return JTK_OK;
 }
 
@@ -1968,16 +1967,44 @@ static int ck_tiles(jtk_batch* b, int64_t n_tok, hipStream_t s) {
     return JTK_OK;
 }
 
+// the byte scan of the last encode's tokens, ready on s: the one a chunk plan or an earlier position call left, or a new one
+// behind the encode
+static int ck_byte_scan(jtk_batch* b, hipStream_t s) {
+    if (b->have_tiles) return ck_order(b, b->ck_stream, s);
+    int64_t nt = 0;
+    int rc;
+    if ((rc = jtk_batch_result(b, &nt, nullptr, nullptr)) || (rc = ck_order(b, b->last_stream, s)) || (rc = ck_setup(b)) ||
+        (rc = ck_tiles(b, nt, s)))
+        return rc;
+    b->ck_stream = s;
+    return JTK_OK;
+}
+
+// the records of nc chunks in ck_rec: chunk_doc | tok_begin | byte_begin | byte_end (i64) | n_tok (i32) | split (u8), and
+// behind them, when end_level is asked for, end_level (u8)
+static int ck_records(jtk_batch* b, int64_t nc, uint8_t** end_level) {
+    const size_t n = (size_t)(nc > 0 ? nc : 1), o_i32 = 4 * n * 8, o_u8 = align_up(o_i32 + n * 4, 16);
+    int rc;
+    if ((rc = b->ck_rec.ensure(o_u8 + (end_level ? 2 : 1) * n))) return rc;
+    JtkChunkWork& w = b->ck;
+    int64_t* r64 = (int64_t*)b->ck_rec.p;
+    w.chunk_doc = r64; w.tok_begin = r64 + n; w.byte_begin = r64 + 2 * n; w.byte_end = r64 + 3 * n;
+    w.n_tok_out = (int32_t*)((uint8_t*)b->ck_rec.p + o_i32);
+    w.split = (uint8_t*)b->ck_rec.p + o_u8;
+    w.n_chunks = nc;
+    if (end_level) *end_level = w.split + n;
+    return JTK_OK;
+}
+
 int jtk_batch_chunk(jtk_batch* b, int64_t chunk_tokens, int64_t overlap, void* stream_or_null, int64_t* n_chunks) {
     if (!b || !n_chunks) return fail(JTK_ERR_INVALID_ARGUMENT, "bad arguments");
     *n_chunks = 0;
-    if (!b->have_result) return fail(JTK_ERR_INVALID_ARGUMENT, "no batch encode result on this batch (jtk_batch_encode_device_max_tokens leaves none)");
-    if (b->job_flags & JTK_ENCODE_COUNT_ONLY) return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode was count-only: there are no token ids");
+    int rc;
+    if ((rc = need_encode(b, NEED_IDS))) return rc;
     if (chunk_tokens < 1 || chunk_tokens > INT32_MAX) return fail(JTK_ERR_INVALID_ARGUMENT, "chunk_tokens must be in [1, 2^31 - 1]");
     if (overlap < 0 || overlap >= chunk_tokens) return fail(JTK_ERR_INVALID_ARGUMENT, "overlap must be in [0, chunk_tokens)");
     HIP_TRY(hipSetDevice(b->enc->device));
-    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
-    int rc;
+    hipStream_t s = pick_stream(b, stream_or_null);
     b->have_chunk = false;
     b->have_tiles = false;
     if ((rc = ck_order(b, b->last_stream, s)) || (rc = ck_setup(b)) || (rc = ensure_pinned((void**)&b->h_ck, &b->h_ck_cap, 32, 0))) return rc;
@@ -1990,15 +2017,7 @@ int jtk_batch_chunk(jtk_batch* b, int64_t chunk_tokens, int64_t overlap, void* s
     HIP_TRY(hipMemcpyAsync(b->h_ck, w.hdr, 16, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     const int64_t nc = b->h_ck[0], nt = b->h_ck[1];
-    if ((rc = ck_tiles(b, nt, s))) return rc;
-    // records: chunk_doc | tok_begin | byte_begin | byte_end (i64) | n_tok (i32) | split (u8)
-    const size_t n = (size_t)(nc > 0 ? nc : 1), o_i32 = 4 * n * 8, o_u8 = align_up(o_i32 + n * 4, 16);
-    if ((rc = b->ck_rec.ensure(o_u8 + n))) return rc;
-    int64_t* r64 = (int64_t*)b->ck_rec.p;
-    w.chunk_doc = r64; w.tok_begin = r64 + n; w.byte_begin = r64 + 2 * n; w.byte_end = r64 + 3 * n;
-    w.n_tok_out = (int32_t*)((uint8_t*)b->ck_rec.p + o_i32);
-    w.split = (uint8_t*)b->ck_rec.p + o_u8;
-    w.n_chunks = nc;
+    if ((rc = ck_tiles(b, nt, s)) || (rc = ck_records(b, nc, nullptr))) return rc;
     jtk_launch_chunk_write(w, s);
     HIP_TRY(hipGetLastError());
     b->have_chunk = true;
@@ -2046,7 +2065,7 @@ int jtk_batch_chunk_rows(jtk_batch* b, int32_t pad_id, int32_t* d_rows, void* st
     if (b->ck.n_chunks > 0 && !d_rows) return fail(JTK_ERR_INVALID_ARGUMENT, "d_rows is NULL");
     if (((uintptr_t)d_rows & 3u) != 0) return fail(JTK_ERR_INVALID_ARGUMENT, "d_rows must be 4-byte aligned");
     HIP_TRY(hipSetDevice(b->enc->device));
-    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    hipStream_t s = pick_stream(b, stream_or_null);
     int rc;
     if ((rc = ck_order(b, b->ck_stream, s))) return rc;
     jtk_launch_chunk_rows(b->ck, pad_id, d_rows, s);
@@ -2055,15 +2074,15 @@ int jtk_batch_chunk_rows(jtk_batch* b, int32_t pad_id, int32_t* d_rows, void* st
 }
 
 int jtk_batch_compact(jtk_batch* b, uint16_t* d_lo, uint32_t* d_hi, void* stream_or_null) {
-    if (!b || !b->have_result) return fail(JTK_ERR_INVALID_ARGUMENT, "no batch encode result on this batch (jtk_batch_encode_device_max_tokens leaves none)");
-    if (b->job_flags & JTK_ENCODE_COUNT_ONLY) return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode was count-only: there are no token ids");
-    if (((uintptr_t)d_lo & 1u) != 0 || ((uintptr_t)d_hi & 3u) != 0) return fail(JTK_ERR_INVALID_ARGUMENT, "d_lo must be 2-byte and d_hi 4-byte aligned");
-    int64_t nt = 0;
     int rc;
+    if ((rc = need_encode(b, NEED_IDS))) return rc;
+    if (((uintptr_t)d_lo & 1u) != 0 || ((uintptr_t)d_hi & 3u) != 0) return fail(JTK_ERR_INVALID_ARGUMENT, "d_lo must be 2-byte and d_hi 4-byte aligned");
+    HIP_TRY(hipSetDevice(b->enc->device));
+    int64_t nt = 0;
     if ((rc = jtk_batch_result(b, &nt, nullptr, nullptr))) return rc;
     const int hb = b->enc->hb;
     if (nt > 0 && (!d_lo || (hb && !d_hi))) return fail(JTK_ERR_INVALID_ARGUMENT, hb ? "d_lo or d_hi is NULL" : "d_lo is NULL");
-    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    hipStream_t s = pick_stream(b, stream_or_null);
     if ((rc = ck_order(b, b->last_stream, s))) return rc;
     jtk_launch_compact((const int32_t*)b->tokens.p, 0, nt, nullptr, d_lo, d_hi, 0, hb, s);
     HIP_TRY(hipGetLastError());
@@ -2071,35 +2090,26 @@ int jtk_batch_compact(jtk_batch* b, uint16_t* d_lo, uint32_t* d_hi, void* stream
 }
 
 int jtk_batch_token_offsets(jtk_batch* b, int64_t* d_byte_pos, void* stream_or_null) {
-    if (!b || !b->have_result) return fail(JTK_ERR_INVALID_ARGUMENT, "no batch encode result on this batch");
-    if (b->job_flags & JTK_ENCODE_COUNT_ONLY) return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode was count-only: there are no token ids");
-    HIP_TRY(hipSetDevice(b->enc->device));
-    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
     int rc;
-    if (!b->have_tiles) {                   // no chunk plan on this encode: the byte scan first
-        int64_t nt = 0;
-        if ((rc = jtk_batch_result(b, &nt, nullptr, nullptr)) || (rc = ck_order(b, b->last_stream, s)) || (rc = ck_setup(b))) return rc;
-        if ((rc = ck_tiles(b, nt, s))) return rc;
-        b->ck_stream = s;
-    } else if ((rc = ck_order(b, b->ck_stream, s))) {
-        return rc;
-    }
+    if ((rc = need_encode(b, NEED_IDS))) return rc;
+    HIP_TRY(hipSetDevice(b->enc->device));
+    hipStream_t s = pick_stream(b, stream_or_null);
+    if ((rc = ck_byte_scan(b, s))) return rc;
     if (b->ck.n_tok > 0 && !d_byte_pos) return fail(JTK_ERR_INVALID_ARGUMENT, "d_byte_pos is NULL");
     jtk_launch_token_offsets(b->ck, d_byte_pos, s);
     HIP_TRY(hipGetLastError());
     return JTK_OK;
 }
 
-
 int jtk_batch_token_cut_levels(jtk_batch* b, uint32_t prefer, uint8_t* d_level, void* stream_or_null) {
-    if (!b || !b->have_result) return fail(JTK_ERR_INVALID_ARGUMENT, "no batch encode result on this batch (jtk_batch_encode_device_max_tokens leaves none)");
-    if (b->job_flags & JTK_ENCODE_COUNT_ONLY) return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode was count-only: there are no token ids");
-    if (prefer & ~15u) return fail(JTK_ERR_INVALID_ARGUMENT, "prefer holds bits outside JTK_CUT_WORD | _SENTENCE | _LINE | _PARAGRAPH");
-    int64_t nt = 0;
     int rc;
+    if ((rc = need_encode(b, NEED_IDS))) return rc;
+    if (prefer & ~15u) return fail(JTK_ERR_INVALID_ARGUMENT, "prefer holds bits outside JTK_CUT_WORD | _SENTENCE | _LINE | _PARAGRAPH");
+    HIP_TRY(hipSetDevice(b->enc->device));
+    int64_t nt = 0;
     if ((rc = jtk_batch_result(b, &nt, nullptr, nullptr))) return rc;
     if (nt > 0 && !d_level) return fail(JTK_ERR_INVALID_ARGUMENT, "d_level is NULL");
-    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    hipStream_t s = pick_stream(b, stream_or_null);
     if ((rc = ck_order(b, b->last_stream, s))) return rc;
     // (a view of the last encode of its own: the batch's chunk result stays as it is)
     JtkChunkWork w{};
@@ -2114,14 +2124,14 @@ int jtk_batch_chunk_prefer(jtk_batch* b, int64_t chunk_tokens, int64_t overlap, 
                            void* stream_or_null, int64_t* n_chunks) {
     if (!b || !n_chunks) return fail(JTK_ERR_INVALID_ARGUMENT, "bad arguments");
     *n_chunks = 0;
-    if (!b->have_result) return fail(JTK_ERR_INVALID_ARGUMENT, "no batch encode result on this batch (jtk_batch_encode_device_max_tokens leaves none)");
-    if (b->job_flags & JTK_ENCODE_COUNT_ONLY) return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode was count-only: there are no token ids");
+    int rc;
+    if ((rc = need_encode(b, NEED_IDS))) return rc;
     if (chunk_tokens < 1 || chunk_tokens > INT32_MAX) return fail(JTK_ERR_INVALID_ARGUMENT, "chunk_tokens must be in [1, 2^31 - 1]");
     if (overlap < 0 || overlap >= chunk_tokens) return fail(JTK_ERR_INVALID_ARGUMENT, "overlap must be in [0, chunk_tokens)");
     if (min_tokens < 1 || min_tokens > chunk_tokens) return fail(JTK_ERR_INVALID_ARGUMENT, "min_tokens must be in [1, chunk_tokens]");
     if (prefer & ~15u) return fail(JTK_ERR_INVALID_ARGUMENT, "prefer holds bits outside JTK_CUT_WORD | _SENTENCE | _LINE | _PARAGRAPH");
-    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
-    int rc;
+    HIP_TRY(hipSetDevice(b->enc->device));
+    hipStream_t s = pick_stream(b, stream_or_null);
     int64_t nt = 0;
     if ((rc = jtk_batch_result(b, &nt, nullptr, nullptr))) return rc;      // (the plane is sized by the token count)
     b->have_chunk = false;
@@ -2141,16 +2151,7 @@ int jtk_batch_chunk_prefer(jtk_batch* b, int64_t chunk_tokens, int64_t overlap, 
     HIP_TRY(hipMemcpyAsync(b->h_ck, w.hdr, 16, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     const int64_t nc = b->h_ck[0];
-    if ((rc = ck_tiles(b, nt, s))) return rc;
-    // records: chunk_doc | tok_begin | byte_begin | byte_end (i64) | n_tok (i32) | split (u8) | end_level (u8)
-    const size_t n = (size_t)(nc > 0 ? nc : 1), o_i32 = 4 * n * 8, o_u8 = align_up(o_i32 + n * 4, 16);
-    if ((rc = b->ck_rec.ensure(o_u8 + 2 * n))) return rc;
-    int64_t* r64 = (int64_t*)b->ck_rec.p;
-    w.chunk_doc = r64; w.tok_begin = r64 + n; w.byte_begin = r64 + 2 * n; w.byte_end = r64 + 3 * n;
-    w.n_tok_out = (int32_t*)((uint8_t*)b->ck_rec.p + o_i32);
-    w.split = (uint8_t*)b->ck_rec.p + o_u8;
-    p.end_level = w.split + n;
-    w.n_chunks = nc;
+    if ((rc = ck_tiles(b, nt, s)) || (rc = ck_records(b, nc, &p.end_level))) return rc;
     p.w = w;
     jtk_launch_chunk_prefer_write(p, s);
     HIP_TRY(hipGetLastError());
@@ -2186,8 +2187,8 @@ int jtk_batch_pack(jtk_batch* b, int64_t seq_len, int32_t sep_id, uint32_t flags
                    int64_t* n_rows, int64_t* n_segments, int32_t* max_seqlen) {
     if (!b || !n_rows || !n_segments || !max_seqlen) return fail(JTK_ERR_INVALID_ARGUMENT, "bad arguments");
     *n_rows = 0; *n_segments = 0; *max_seqlen = 0;
-    if (!b->have_result) return fail(JTK_ERR_INVALID_ARGUMENT, "no batch encode result on this batch (jtk_batch_encode_device_max_tokens leaves none)");
-    if (b->job_flags & JTK_ENCODE_COUNT_ONLY) return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode was count-only: there are no token ids");
+    int rc;
+    if ((rc = need_encode(b, NEED_IDS))) return rc;
     if (seq_len < 1) return fail(JTK_ERR_INVALID_ARGUMENT, "seq_len must be at least 1");
     if (seq_len > INT32_MAX)
         return fail(JTK_ERR_INVALID_ARGUMENT, "seq_len must be below 2^31: cu_seqlens (int32) indexes the cells of the rows");
@@ -2201,14 +2202,13 @@ int jtk_batch_pack(jtk_batch* b, int64_t seq_len, int32_t sep_id, uint32_t flags
     const int64_t n = b->job_docs;
     if (n >= INT32_MAX) return fail(JTK_ERR_INVALID_ARGUMENT, "too many documents to pack in one call (2^31 - 1 at most)");
     HIP_TRY(hipSetDevice(b->enc->device));
-    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
-    b->have_pack = false;
+    hipStream_t s = pick_stream(b, stream_or_null);
+    b->have_pack = false;                                              // (this call replaces its own result)
     int K = 1;
     while (K < 62 && ((int64_t)1 << K) <= n) K++;                      // 2^K > n >= the number of groups
     // scratch: hdr[4] | P | SEG | RS [n + 1] | flag [n] | up [K][n + 1]
     const size_t m = (size_t)n + 1, o_flag = 32 + 3 * m * 8, o_up = align_up(o_flag + m, 16);
     const size_t bytes = whole ? o_up + (size_t)K * m * 4 : o_flag;
-    int rc;
     if ((rc = b->pk_scratch.ensure(bytes)) || (rc = ensure_pinned((void**)&b->h_pk, &b->h_pk_cap, 32, 0)) ||
         (rc = ck_order(b, b->last_stream, s)))
         return rc;
@@ -2263,7 +2263,7 @@ int jtk_batch_pack_write(jtk_batch* b, int32_t pad_id, int32_t* d_rows, int32_t*
     if (((uintptr_t)d_rows & 3u) || ((uintptr_t)d_positions & 3u) || ((uintptr_t)d_cu_seqlens & 3u) || ((uintptr_t)d_seg_doc & 7u))
         return fail(JTK_ERR_INVALID_ARGUMENT, "unaligned output (4-byte int32, 8-byte int64 arrays)");
     HIP_TRY(hipSetDevice(b->enc->device));
-    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    hipStream_t s = pick_stream(b, stream_or_null);
     int rc;
     if ((rc = ck_order(b, b->pk_stream, s))) return rc;
     jtk_launch_pack_write(b->pk, pad_id, d_rows, d_positions, d_cu_seqlens, d_seg_doc, s);
@@ -2277,20 +2277,18 @@ int jtk_batch_pack_fetch(jtk_batch* b, int32_t pad_id, int32_t* rows, int32_t* p
     // device staging: rows | positions | cu_seqlens | seg_doc
     const size_t o_pos = align_up(cells * 4, 16), o_cu = o_pos + align_up(cells * 4, 16), o_sd = align_up(o_cu + (ns + 1) * 4, 16);
     HIP_TRY(hipSetDevice(b->enc->device));
-    DevBuf tmp;
-    int rc = tmp.ensure(o_sd + ns * 8 + 16);
-    if (rc) return rc;
+    TmpDevBuf tmp;
+    int rc;
+    if ((rc = tmp.ensure(o_sd + ns * 8 + 16))) return rc;
     uint8_t* p = (uint8_t*)tmp.p;
-    rc = jtk_batch_pack_write(b, pad_id, (int32_t*)p, positions ? (int32_t*)(p + o_pos) : nullptr, (int32_t*)(p + o_cu),
-                              seg_doc ? (int64_t*)(p + o_sd) : nullptr, b->pk_stream);
-    hipError_t e = rc == JTK_OK ? hipStreamSynchronize(b->pk_stream) : hipSuccess;
-    if (rc == JTK_OK && e == hipSuccess && rows && cells) e = hipMemcpy(rows, p, cells * 4, hipMemcpyDeviceToHost);
-    if (rc == JTK_OK && e == hipSuccess && positions && cells) e = hipMemcpy(positions, p + o_pos, cells * 4, hipMemcpyDeviceToHost);
-    if (rc == JTK_OK && e == hipSuccess && cu_seqlens) e = hipMemcpy(cu_seqlens, p + o_cu, (ns + 1) * 4, hipMemcpyDeviceToHost);
-    if (rc == JTK_OK && e == hipSuccess && seg_doc && ns) e = hipMemcpy(seg_doc, p + o_sd, ns * 8, hipMemcpyDeviceToHost);
-    tmp.release();
-    if (rc != JTK_OK) return rc;
-    HIP_TRY(e);
+    if ((rc = jtk_batch_pack_write(b, pad_id, (int32_t*)p, positions ? (int32_t*)(p + o_pos) : nullptr, (int32_t*)(p + o_cu),
+                                   seg_doc ? (int64_t*)(p + o_sd) : nullptr, b->pk_stream)))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(b->pk_stream));
+    if (rows && cells) HIP_TRY(hipMemcpy(rows, p, cells * 4, hipMemcpyDeviceToHost));
+    if (positions && cells) HIP_TRY(hipMemcpy(positions, p + o_pos, cells * 4, hipMemcpyDeviceToHost));
+    if (cu_seqlens) HIP_TRY(hipMemcpy(cu_seqlens, p + o_cu, (ns + 1) * 4, hipMemcpyDeviceToHost));
+    if (seg_doc && ns) HIP_TRY(hipMemcpy(seg_doc, p + o_sd, ns * 8, hipMemcpyDeviceToHost));
     return JTK_OK;
 }
 
@@ -2298,10 +2296,8 @@ int jtk_batch_pack_fetch(jtk_batch* b, int32_t pad_id, int32_t* rows, int32_t* p
 // ---- labels of the packed rows from byte spans (jtk_label.hip) ---------------------------------------------------------
 int jtk_batch_token_spans(jtk_batch* b, const int64_t* d_span_begin, const int64_t* d_span_end, int64_t n_spans, int rule,
                           int32_t* d_tok_span, void* stream_or_null) {
-    if (!b || !b->have_result) return fail(JTK_ERR_INVALID_ARGUMENT, "no batch encode result on this batch (jtk_batch_encode_device_max_tokens leaves none)");
-    if (b->job_flags & JTK_ENCODE_COUNT_ONLY) return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode was count-only: there are no token ids");
-    if (b->job_pieces)
-        return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode took caller-supplied pieces: its token positions are not positions in the text");
+    int rc;
+    if ((rc = need_encode(b, NEED_IDS | NEED_TEXT_POS))) return rc;
     if (rule != JTK_SPAN_WHOLE && rule != JTK_SPAN_START && rule != JTK_SPAN_ANY)
         return fail(JTK_ERR_INVALID_ARGUMENT, "rule: JTK_SPAN_WHOLE, JTK_SPAN_START or JTK_SPAN_ANY");
     if (n_spans < 0 || n_spans > INT32_MAX) return fail(JTK_ERR_INVALID_ARGUMENT, "n_spans must be in [0, 2^31 - 1]");
@@ -2309,16 +2305,8 @@ int jtk_batch_token_spans(jtk_batch* b, const int64_t* d_span_begin, const int64
     if (((uintptr_t)d_span_begin & 7u) || ((uintptr_t)d_span_end & 7u) || ((uintptr_t)d_tok_span & 3u))
         return fail(JTK_ERR_INVALID_ARGUMENT, "unaligned array (8-byte int64 spans, 4-byte int32 tok_span)");
     HIP_TRY(hipSetDevice(b->enc->device));
-    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
-    int rc;
-    if (!b->have_tiles) {                   // no chunk plan or token offsets on this encode: the byte scan first
-        int64_t nt = 0;
-        if ((rc = jtk_batch_result(b, &nt, nullptr, nullptr)) || (rc = ck_order(b, b->last_stream, s)) || (rc = ck_setup(b))) return rc;
-        if ((rc = ck_tiles(b, nt, s))) return rc;
-        b->ck_stream = s;
-    } else if ((rc = ck_order(b, b->ck_stream, s))) {
-        return rc;
-    }
+    hipStream_t s = pick_stream(b, stream_or_null);
+    if ((rc = ck_byte_scan(b, s))) return rc;
     if (b->ck.n_tok > 0 && !d_tok_span) return fail(JTK_ERR_INVALID_ARGUMENT, "d_tok_span is NULL");
     jtk_launch_label_spans(b->ck, d_span_begin, d_span_end, n_spans, rule, d_tok_span, s);
     HIP_TRY(hipGetLastError());
@@ -2332,7 +2320,7 @@ int jtk_batch_pack_labels(jtk_batch* b, const int32_t* d_tok_span_or_null, int32
     if (b->pk.n_rows > 0 && !d_labels) return fail(JTK_ERR_INVALID_ARGUMENT, "d_labels is NULL");
     if (((uintptr_t)d_tok_span_or_null & 3u) || ((uintptr_t)d_labels & 3u)) return fail(JTK_ERR_INVALID_ARGUMENT, "unaligned array (4-byte int32)");
     HIP_TRY(hipSetDevice(b->enc->device));
-    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    hipStream_t s = pick_stream(b, stream_or_null);
     int rc;
     if ((rc = ck_order(b, b->pk_stream, s))) return rc;
     JtkLabelView lv;
@@ -2348,15 +2336,13 @@ int jtk_batch_pack_labels_fetch(jtk_batch* b, const int32_t* d_tok_span_or_null,
     const size_t cells = (size_t)(b->pk.n_rows * b->pk.v.L);
     if (cells && !labels) return fail(JTK_ERR_INVALID_ARGUMENT, "labels is NULL");
     HIP_TRY(hipSetDevice(b->enc->device));
-    DevBuf tmp;
-    int rc = tmp.ensure(cells * 4 + 16);
-    if (rc) return rc;
-    rc = jtk_batch_pack_labels(b, d_tok_span_or_null, ignore_index, flags, (int32_t*)tmp.p, b->pk_stream);
-    hipError_t e = rc == JTK_OK ? hipStreamSynchronize(b->pk_stream) : hipSuccess;
-    if (rc == JTK_OK && e == hipSuccess && cells) e = hipMemcpy(labels, tmp.p, cells * 4, hipMemcpyDeviceToHost);
-    tmp.release();
-    if (rc != JTK_OK) return rc;
-    HIP_TRY(e);
+    TmpDevBuf tmp;
+    int rc;
+    if ((rc = tmp.ensure(cells * 4 + 16)) ||
+        (rc = jtk_batch_pack_labels(b, d_tok_span_or_null, ignore_index, flags, (int32_t*)tmp.p, b->pk_stream)))
+        return rc;
+    HIP_TRY(hipStreamSynchronize(b->pk_stream));
+    if (cells) HIP_TRY(hipMemcpy(labels, tmp.p, cells * 4, hipMemcpyDeviceToHost));
     return JTK_OK;
 }
 
@@ -2364,10 +2350,9 @@ int jtk_batch_pack_labels_fetch(jtk_batch* b, const int32_t* d_tok_span_or_null,
 // ---- character positions of the last encode's text (jtk_charpos.hip; the rule is jtk_charpos_rules.h) -----------------------
 static_assert(JTK_UNIT_BYTE == JTK_CP_UNIT_BYTE && JTK_UNIT_UTF16 == JTK_CP_UNIT_UTF16 && JTK_UNIT_CODEPOINT == JTK_CP_UNIT_CODEPOINT &&
               JTK_CHAR_FLOOR == JTK_CP_FLOOR && JTK_CHAR_CEIL == JTK_CP_CEIL, "the rule header's values are the ABI's");
-static int cp_check(jtk_batch* b, int unit) {
-    if (!b || !b->have_result) return fail(JTK_ERR_INVALID_ARGUMENT, "no batch encode result on this batch (jtk_batch_encode_device_max_tokens leaves none)");
-    if (b->job_pieces)
-        return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode took caller-supplied pieces: its positions are positions in the decoded stream, not in the text");
+static int cp_check(jtk_batch* b, int unit, unsigned also = 0) {
+    int rc;
+    if ((rc = need_encode(b, NEED_TEXT_POS | also))) return rc;
     if (!jtk_cp_valid_unit(unit)) return fail(JTK_ERR_INVALID_ARGUMENT, "unit: JTK_UNIT_BYTE, JTK_UNIT_UTF16 or JTK_UNIT_CODEPOINT");
     return JTK_OK;
 }
@@ -2405,7 +2390,7 @@ int jtk_batch_char_index(jtk_batch* b, int unit, int64_t* d_doc_units_or_null, v
     if ((uintptr_t)d_doc_units_or_null & 7u) return fail(JTK_ERR_INVALID_ARGUMENT, "unaligned array (8-byte int64)");
     if (b->job_docs == 0) return JTK_OK;
     HIP_TRY(hipSetDevice(b->enc->device));
-    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    hipStream_t s = pick_stream(b, stream_or_null);
     if ((rc = cp_index(b, unit, s))) return rc;
     if (d_doc_units_or_null) {
         jtk_launch_charpos_doc_units(b->job_doc_off, b->cp_dunit, b->job_docs, d_doc_units_or_null, s);
@@ -2425,7 +2410,7 @@ int jtk_batch_char_positions(jtk_batch* b, int unit, int round, const int64_t* d
         return fail(JTK_ERR_INVALID_ARGUMENT, "unaligned array (8-byte int64)");
     if (n == 0) return JTK_OK;
     HIP_TRY(hipSetDevice(b->enc->device));
-    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    hipStream_t s = pick_stream(b, stream_or_null);
     if ((rc = cp_index(b, unit, s))) return rc;
     jtk_launch_charpos_rank(b->cp, b->job_doc_off, b->cp_dunit, b->job_docs, round, d_doc_or_null, d_byte_pos, n, d_char_pos, s);
     HIP_TRY(hipGetLastError());
@@ -2442,7 +2427,7 @@ int jtk_batch_byte_positions(jtk_batch* b, int unit, const int64_t* d_doc, const
         return fail(JTK_ERR_INVALID_ARGUMENT, "unaligned array (8-byte int64)");
     if (n == 0) return JTK_OK;
     HIP_TRY(hipSetDevice(b->enc->device));
-    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    hipStream_t s = pick_stream(b, stream_or_null);
     if ((rc = cp_index(b, unit, s))) return rc;
     jtk_launch_charpos_select(b->cp, b->job_doc_off, b->cp_dunit, b->job_docs, d_doc, d_char_pos, n, d_byte_pos, s);
     HIP_TRY(hipGetLastError());
@@ -2451,19 +2436,11 @@ int jtk_batch_byte_positions(jtk_batch* b, int unit, const int64_t* d_doc, const
 
 int jtk_batch_token_char_offsets(jtk_batch* b, int unit, int64_t* d_begin, int64_t* d_end_or_null, void* stream_or_null) {
     int rc;
-    if ((rc = cp_check(b, unit))) return rc;
-    if (b->job_flags & JTK_ENCODE_COUNT_ONLY) return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode was count-only: there are no token ids");
+    if ((rc = cp_check(b, unit, NEED_IDS))) return rc;
     if (((uintptr_t)d_begin & 7u) || ((uintptr_t)d_end_or_null & 7u)) return fail(JTK_ERR_INVALID_ARGUMENT, "unaligned array (8-byte int64)");
     HIP_TRY(hipSetDevice(b->enc->device));
-    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
-    if (!b->have_tiles) {                   // no chunk plan, token offsets or spans on this encode: the byte scan first
-        int64_t nt = 0;
-        if ((rc = jtk_batch_result(b, &nt, nullptr, nullptr)) || (rc = ck_order(b, b->last_stream, s)) || (rc = ck_setup(b))) return rc;
-        if ((rc = ck_tiles(b, nt, s))) return rc;
-        b->ck_stream = s;
-    } else if ((rc = ck_order(b, b->ck_stream, s))) {
-        return rc;
-    }
+    hipStream_t s = pick_stream(b, stream_or_null);
+    if ((rc = ck_byte_scan(b, s))) return rc;
     if (b->ck.n_tok == 0) return JTK_OK;
     if (!d_begin) return fail(JTK_ERR_INVALID_ARGUMENT, "d_begin is NULL");
     if ((rc = cp_index(b, unit, s))) return rc;
@@ -2473,14 +2450,19 @@ int jtk_batch_token_char_offsets(jtk_batch* b, int unit, int64_t* d_begin, int64
 }
 
 // ---- UTF-16 in and out (jtk_utf16.hip; the rules are jtk_utf16_rules.h) -------------------------------------------------------
-// E into (text, off) of the batch: count, the one wait (size of the output, offsets check), write
-static int u16_transcode(jtk_batch* b, DevBuf& text, DevBuf& off, const uint16_t* d_units, const int64_t* d_unit_off, int64_t n_docs,
-                         int64_t n_units, hipStream_t s, int64_t* n_bytes) {
+// E into u16_enc_* (for_encode: the text of a new encode, so the last encode's result goes before a byte of it is written) or
+// u16_tx_* of the batch: count, the one wait (size of the output, offsets check), write
+static int u16_transcode(jtk_batch* b, bool for_encode, const uint16_t* d_units, const int64_t* d_unit_off, int64_t n_docs,
+                         int64_t n_units, void* stream_or_null, int64_t* n_bytes) {
     if (!b || n_docs < 0 || n_units < 0 || (n_units > 0 && !d_units) || !d_unit_off) return fail(JTK_ERR_INVALID_ARGUMENT, "bad arguments");
     if ((uintptr_t)d_units & 1u) return fail(JTK_ERR_INVALID_ARGUMENT, "d_units must be 2-byte aligned");
     if ((uintptr_t)d_unit_off & 7u) return fail(JTK_ERR_INVALID_ARGUMENT, "unaligned array (8-byte int64)");
     if (n_units >= (int64_t)1 << 35) return fail(JTK_ERR_INVALID_ARGUMENT, "batch too large (32 Gi units per call at most)");
     HIP_TRY(hipSetDevice(b->enc->device));
+    if (for_encode) drop_encode_result(b);
+    DevBuf& text = for_encode ? b->u16_enc_text : b->u16_tx_text;
+    DevBuf& off = for_encode ? b->u16_enc_off : b->u16_tx_off;
+    hipStream_t s = pick_stream(b, stream_or_null);
     JtkU16EncWork w{};
     w.units = d_units; w.n_units = n_units; w.unit_off = d_unit_off; w.n_docs = n_docs;
     w.n_tiles = (n_units + JTK_U16_E_TILE - 1) / JTK_U16_E_TILE;
@@ -2514,9 +2496,7 @@ static int u16_transcode(jtk_batch* b, DevBuf& text, DevBuf& off, const uint16_t
 
 int jtk_batch_transcode_utf16_device(jtk_batch* b, const uint16_t* d_units, const int64_t* d_unit_off, int64_t n_docs, int64_t n_units,
                                      void* stream_or_null, int64_t* n_bytes) {
-    if (!b) return fail(JTK_ERR_INVALID_ARGUMENT, "batch is NULL");
-    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
-    return u16_transcode(b, b->u16_tx_text, b->u16_tx_off, d_units, d_unit_off, n_docs, n_units, s, n_bytes);
+    return u16_transcode(b, /*for_encode=*/false, d_units, d_unit_off, n_docs, n_units, stream_or_null, n_bytes);
 }
 
 int jtk_batch_utf8_device_result(jtk_batch* b, const uint8_t** d_utf8, const int64_t** d_doc_off, int64_t* n_bytes) {
@@ -2535,13 +2515,12 @@ static int u16_encode_flags(uint32_t flags) {
 
 int jtk_batch_encode_utf16_device(jtk_batch* b, const uint16_t* d_units, const int64_t* d_unit_off, int64_t n_docs, int64_t n_units,
                                   uint32_t flags, void* stream_or_null, int64_t* n_tokens) {
-    if (!b) return fail(JTK_ERR_INVALID_ARGUMENT, "batch is NULL");
     int rc;
     if ((rc = u16_encode_flags(flags))) return rc;
-    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
     int64_t n_bytes = 0;
-    if ((rc = u16_transcode(b, b->u16_enc_text, b->u16_enc_off, d_units, d_unit_off, n_docs, n_units, s, &n_bytes))) return rc;
-    return jtk_batch_encode_device(b, (const uint8_t*)b->u16_enc_text.p, (const int64_t*)b->u16_enc_off.p, n_docs, n_bytes, flags, (void*)s, n_tokens);
+    // (true: into u16_enc_*, and the last encode's result is dropped there, behind the argument checks, before the first write)
+    if ((rc = u16_transcode(b, /*for_encode=*/true, d_units, d_unit_off, n_docs, n_units, stream_or_null, &n_bytes))) return rc;
+    return jtk_batch_encode_device(b, (const uint8_t*)b->u16_enc_text.p, (const int64_t*)b->u16_enc_off.p, n_docs, n_bytes, flags, stream_or_null, n_tokens);
 }
 
 int jtk_batch_encode_utf16(jtk_batch* b, const uint16_t* units, const int64_t* unit_off, int64_t n_docs, uint32_t flags, int64_t* n_tokens) {
@@ -2555,6 +2534,7 @@ int jtk_batch_encode_utf16(jtk_batch* b, const uint16_t* units, const int64_t* u
     if (n_units > 0 && !units) return fail(JTK_ERR_INVALID_ARGUMENT, "units is NULL");
     if (n_units >= (int64_t)1 << 35) return fail(JTK_ERR_INVALID_ARGUMENT, "batch too large (32 Gi units per call at most)");
     HIP_TRY(hipSetDevice(b->enc->device));
+    drop_encode_result(b);
     // one upload: units | offsets, then the device call (not chunk-pipelined)
     const size_t o_off = align_up((size_t)n_units * 2 + 16, 256);
     if ((rc = b->u16_in.ensure(o_off + ((size_t)n_docs + 1) * 8))) return rc;
@@ -2570,7 +2550,7 @@ int jtk_batch_encode_utf16(jtk_batch* b, const uint16_t* units, const int64_t* u
 int jtk_batch_decode_utf16(jtk_batch* b, void* stream_or_null, int64_t* n_units) {
     if (!b || !b->have_decode) return fail(JTK_ERR_INVALID_ARGUMENT, "no decode has run on this batch");
     HIP_TRY(hipSetDevice(b->enc->device));
-    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    hipStream_t s = pick_stream(b, stream_or_null);
     JtkU16DecWork w{};
     w.text = b->dwork.out; w.n_bytes = b->dec_total; w.byte_off = b->dwork.byte_off; w.n_seqs = b->dwork.n_seqs;
     w.n_tiles = (w.n_bytes + JTK_U16_D_TILE - 1) / JTK_U16_D_TILE;
@@ -2581,7 +2561,7 @@ int jtk_batch_decode_utf16(jtk_batch* b, void* stream_or_null, int64_t* n_units)
     uint8_t* z = (uint8_t*)b->u16_dscratch.p;
     w.hdr = (int64_t*)z; w.tile_off = (int64_t*)(z + 16); w.tile_cnt = (uint32_t*)(z + o_cnt); w.sub = (uint16_t*)(z + o_sub);
     w.unit_off = (int64_t*)b->u16_unit_off.p;
-    b->have_u16_dec = false;
+    b->have_u16_dec = false;                                              // (this call replaces its own result)
     jtk_launch_u16_dec_count(w, s);
     HIP_TRY(hipGetLastError());
     int64_t total = 0;
@@ -2626,14 +2606,14 @@ int jtk_batch_decode_find_stops(jtk_batch* b, const uint8_t* strings, const uint
                                 void* stream_or_null) {
     if (!b || !b->have_decode) return fail(JTK_ERR_INVALID_ARGUMENT, "no decode has run on this batch");
     JtkStopWork& w = b->stop;
-    b->have_stops = false;
+    b->have_stops = false;                                                // (this call replaces its own result, b->stop, in place)
     if (!jtk_stop_set_init(&w.set, strings, str_off, n_strings))
         return fail(JTK_ERR_INVALID_ARGUMENT, "stop strings: 0..16 strings of 1..64 bytes, str_off increasing from 0");
     // cell_byte belongs to a rows decode: the last decode must be one, of this width (after a flat decode there are no cells)
     if (d_cell_byte_or_null && (width < 1 || width != b->dec_rows_width))
         return fail(JTK_ERR_INVALID_ARGUMENT, "cell_byte needs the width of the rows decode it came from");
     HIP_TRY(hipSetDevice(b->enc->device));
-    hipStream_t s = stream_or_null ? (hipStream_t)stream_or_null : b->stream;
+    hipStream_t s = pick_stream(b, stream_or_null);
     const int64_t n = b->dwork.n_seqs;
     w.out = b->dwork.out; w.n_bytes = b->dec_total; w.byte_off = b->dwork.byte_off; w.n_seqs = n;
     w.n_tiles = (w.n_bytes + JTK_STOP_TILE - 1) / JTK_STOP_TILE;
