@@ -768,7 +768,11 @@ struct LeanLds {
 // table entry.
 template <int NS, int STRIDE, bool SKIP_WHOLE, class M>
 __device__ __forceinline__ M lean_steps(uint32_t* id, uint32_t* rk, M alive, const uint8_t* bk, uint32_t nb) {
-    for (;;) {
+    const M one = 1;
+    uint32_t minr, mini, nxt, nn, pv;
+    bool act, want1, want2;
+    // the leftmost minimum of the lane's keys (:234-240), its neighbours, and which of the two new pairs the lane has to look up
+    auto scan = [&]() {
         uint32_t k[NS];
 #pragma unroll
         for (int j = 0; j < NS; j++) k[j] = rk[j * STRIDE];
@@ -778,15 +782,13 @@ __device__ __forceinline__ M lean_steps(uint32_t* id, uint32_t* rk, M alive, con
             for (int j = 0; j + d < NS; j += 2 * d) k[j] = min(k[j], k[j + d]);
         }
         const uint32_t m = k[0];
-        const bool act = m != KL_NONE;                                                       // :247,:261
-        if (!__ballot(act)) break;
-        const uint32_t minr = act ? (m >> 6) : 0u, mini = act ? (m & 63u) : 0u;
-        const M one = 1;
+        act = m != KL_NONE;                                                                  // :247,:261
+        minr = act ? (m >> 6) : 0u;
+        mini = act ? (m & 63u) : 0u;
         const M above = alive & ~(((one << mini) << 1) - one);
         const M above2 = above & (above - one);
         const M below = alive & ((one << mini) - one);
         const bool has_nn = act && above2 != 0, has_pv = act && below != 0;
-        uint32_t nxt, nn, pv;
         if (sizeof(M) == 8) {
             nxt = above ? (uint32_t)jtk_ctz64(above) : 0u;
             nn = above2 ? (uint32_t)jtk_ctz64(above2) : 0u;
@@ -798,11 +800,18 @@ __device__ __forceinline__ M lean_steps(uint32_t* id, uint32_t* rk, M alive, con
         }
         // (minr, id of the part after next) and (id of the previous part, minr); a pair that would be the whole piece is
         // known to be absent
-        bool want1 = has_nn, want2 = has_pv;
+        want1 = has_nn;
+        want2 = has_pv;
         if (SKIP_WHOLE) {
             want1 = want1 && !(mini == 0u && (above2 & (above2 - one)) == 0);
             want2 = want2 && !(pv == 0u && !has_nn);
         }
+    };
+    // The loop is bottom-tested, with the scan once ahead of it and once at the end of a step: its one exit is a scalar branch
+    // on the ballot, a step's loads stand in straight-line code behind it, and the next scan's LDS reads are requested right
+    // behind the update's stores.  A wave without a lane that merges takes the same exit: no `act`, no wants.
+    scan();
+    while (__ballot(want1 || want2)) {
         const uint32_t idnn = want1 ? id[nn * STRIDE] : 0u, idpv = want2 ? id[pv * STRIDE] : 0u;
         const uint32_t a1 = want1 ? minr : 0u, b2 = want2 ? minr : 0u;
         const uint32_t m1 = jtk_pair_mix(a1, idnn), m2 = jtk_pair_mix(idpv, b2);
@@ -836,6 +845,22 @@ __device__ __forceinline__ M lean_steps(uint32_t* id, uint32_t* rk, M alive, con
             id[mini * STRIDE] = minr;
             alive &= ~(one << nxt);                                                                          // :259
         }
+        scan();
+    }
+    // No lane wants a lookup: this is the wave's last step (or, with no lane `act`, none at all), and it is finished here with
+    // both new ranks absent: no gathers at the dummy key, no wait for them, and no further scan to learn that the wave is done.
+    // Why nothing is left: a lane that is `act` and wants neither side has, without SKIP_WHOLE, no part after next and none
+    // before -- it merges its last two parts into one.  With SKIP_WHOLE it may also have three parts, the chosen one first
+    // (want1 dropped: slot 0 never dies, so mini == 0 is the first part and above2 holds only the last) or second (want2
+    // dropped): two remain, and their pair is the whole piece, which is no entry.  Either way every key the lane keeps is
+    // KL_NONE after these stores -- the last part's always was, a removed slot's is set when it goes --, and a lane that is not
+    // `act` had only such keys before: the next scan would find nothing in any lane.
+    if (act) {
+        rk[pv * STRIDE] = KL_NONE;
+        rk[mini * STRIDE] = KL_NONE;
+        rk[nxt * STRIDE] = KL_NONE;
+        id[mini * STRIDE] = minr;
+        alive &= ~(one << nxt);
     }
     return alive;
 }
