@@ -55,7 +55,12 @@ enum {
                                      (GptBytePairEncoding.java:62-64 vs :47-59) */
     JTK_ENCODE_VALIDATE_UTF8 = 2u,/* also check every document is well-formed UTF-8 (what String.getBytes(UTF_8)
                                      produces); offenders get status JTK_ERR_BAD_UTF8.  Without the flag the
-                                     input is trusted: malformed bytes are encoded as the bytes they are. */
+                                     input is trusted: malformed bytes are encoded as the bytes they are.  The flag
+                                     changes nothing but the status: an offender's tokens and offsets are those of the
+                                     call without it (under JTK_ENCODE_ALLOW_SPECIAL an offender has no tokens).  An empty
+                                     document is never an offender.  When two codes apply to one document -- under
+                                     encode() it holds a special-token literal and a malformed byte -- its status is the
+                                     lower one, JTK_ERR_BAD_UTF8.  The rule: jtokkit_amd/csrc/jtk_validate_rules.h */
     JTK_ENCODE_COUNT_ONLY = 4u,   /* Encoding.countTokens() / countTokensOrdinary() (GptBytePairEncoding.java:122-129) for
                                      the whole batch: token offsets (tok_off[d + 1] - tok_off[d] = the count) and
                                      status, but no token ids -- fetch with tokens == NULL */
@@ -268,7 +273,11 @@ int jtk_batch_kernel_times(jtk_batch* b, const char** names, float* ms, int cap,
  * Encoding.encode(String[, maxTokens]) / encodeOrdinary(..) (GptBytePairEncoding.java:38-69):
  * max_tokens < 0 means "no limit"; otherwise the result is clipped to max_tokens and backed off to
  * a code-point boundary exactly as :90-100 does, and *truncated gets EncodingResult.isTruncated().
- * utf8 == NULL mirrors text == null (empty result, :48-50). */
+ * utf8 == NULL mirrors text == null (empty result, :48-50).
+ * Flags: JTK_ENCODE_ORDINARY; JTK_ENCODE_VALIDATE_UTF8 without a token limit (max_tokens < 0): a malformed document
+ * returns JTK_ERR_BAD_UTF8 with *n_tokens = 0 and no tokens written, a well-formed one is unaffected; with a token limit
+ * the flag is ignored (only the document's leading bytes are looked at).  JTK_ENCODE_COUNT_ONLY is ignored;
+ * JTK_ENCODE_ALLOW_SPECIAL and JTK_ENCODE_COMPACT_IDS are JTK_ERR_INVALID_ARGUMENT. */
 int jtk_encode(jtk_batch* b, const uint8_t* utf8, int64_t len, uint32_t flags, int64_t max_tokens,
                int32_t* tokens, int64_t tokens_cap, int64_t* n_tokens, int* truncated);
 
