@@ -57,7 +57,7 @@ enum {
                                      produces); offenders get status JTK_ERR_BAD_UTF8.  Without the flag the
                                      input is trusted: malformed bytes are encoded as the bytes they are.  The flag
                                      changes nothing but the status: an offender's tokens and offsets are those of the
-                                     call without it (under JTK_ENCODE_ALLOW_SPECIAL an offender has no tokens).  An empty
+                                     call without it (under JTK_ENCODE_ALLOW_SPECIAL and JTK_ENCODE_FIM an offender has no tokens).  An empty
                                      document is never an offender.  When two codes apply to one document -- under
                                      encode() it holds a special-token literal and a malformed byte -- its status is the
                                      lower one, JTK_ERR_BAD_UTF8.  The rule: jtokkit_amd/csrc/jtk_validate_rules.h */
@@ -70,10 +70,14 @@ enum {
     JTK_ENCODE_ALLOW_SPECIAL = 16u,/* jtk_batch_encode / jtk_batch_encode_device only: the batch's allowed special-token
                                      literals are encoded as their ids (jtk_batch_set_allowed_special has the rule);
                                      every other entry point that takes flags returns JTK_ERR_INVALID_ARGUMENT for it */
-    JTK_ENCODE_COMPACT_IDS = 32u  /* jtk_batch_encode / jtk_batch_encode_pieces, only together with JTK_ENCODE_TO_HOST: the ids
+    JTK_ENCODE_COMPACT_IDS = 32u, /* jtk_batch_encode / jtk_batch_encode_pieces, only together with JTK_ENCODE_TO_HOST: the ids
                                      reach pinned host memory as a 16-bit plane plus a plane of the bits above ("compact
                                      token ids" below) -- 2 to 2.125 bytes per token over the link instead of 4; read them
                                      with jtk_batch_host_result_compact().  Anywhere else: JTK_ERR_INVALID_ARGUMENT */
+    JTK_ENCODE_FIM = 64u          /* jtk_batch_encode / jtk_batch_encode_device only, together with JTK_ENCODE_ORDINARY and
+                                     without JTK_ENCODE_ALLOW_SPECIAL: the fill-in-the-middle transformation by the batch's
+                                     parameters (jtk_batch_set_fim has the rule); every other entry point that takes flags
+                                     returns JTK_ERR_INVALID_ARGUMENT for it */
 };
 
 /* Options of jtk_batch_set_option.  A batch larger than one chunk is cut into runs of whole documents ("chunks") that flow
@@ -248,6 +252,52 @@ int jtk_batch_encode_device(jtk_batch* b, const uint8_t* d_utf8, const int64_t* 
  *                JTK_ENCODE_TO_HOST the result goes to the pinned buffers in one copy behind the last chunk (one more wait,
  *                for its size) instead of chunk by chunk.  JTK_OPT_REUSE_CHUNK_PLAN does not apply to these calls. */
 int jtk_batch_set_allowed_special(jtk_batch* b, const int32_t* special_ids, int n);
+
+/* ---- fill-in-the-middle training data (JTK_ENCODE_FIM) ----------------------------------------------------------------------
+ * Bavarian et al., "Efficient Training of Language Models to Fill in the Middle": with probability fim_rate a document is cut
+ * at two random positions of its text into prefix, middle and suffix, the three parts are encoded separately as
+ * encodeOrdinary(part), and the document's tokens become
+ *   PSM:  prefix_id enc(prefix) suffix_id enc(suffix) middle_id enc(middle)
+ *   SPM:  prefix_id suffix_id enc(suffix) middle_id enc(prefix) enc(middle)       (with probability spm_rate among the cut ones)
+ * The rule (jtokkit_amd/csrc/jtk_fim_rules.h), per document d of len bytes, g = doc_index_base + d:
+ *   Draws:     mix = the splitmix64 finaliser; draw(g, k) = mix(mix(seed + 0x9E3779B97F4A7C15 * (g + 1)) + k) modulo 2^64.  They
+ *              are counter-based: a document's outcome depends on (seed, g, its bytes) only, so a shard of a corpus, encoded
+ *              with doc_index_base = the index of its first document, draws what the whole corpus would.
+ *   Kind:      0 (untouched: exactly the call without the flag) when len == 0, or when (draw(g, 0) >> 32) >= fim_rate and
+ *              fim_rate != 0xFFFFFFFF; else 2 (SPM) when (draw(g, 1) >> 32) < spm_rate or spm_rate == 0xFFFFFFFF; else 1 (PSM).
+ *   Cuts:      p_k = the high 64 bits of draw(g, 2 + k) * (len + 1), k = 0, 1, each uniform over [0, len], then moved back to
+ *              a character start: while 0 < p < len and the byte at p is 0x80..0xBF, at most 3 times, p -= 1.  a = the lower,
+ *              b = the higher; prefix [0, a), middle [a, b), suffix [b, len), any of them may be empty.
+ *   Status:    the lowest of the three parts' statuses (JTK_ENCODE_VALIDATE_UTF8 so judges the whole document: its parts are
+ *              well-formed exactly when it is); a document with a negative status has no tokens.
+ *   Flags:     JTK_ENCODE_ORDINARY is required (encode()'s special-token check would have to look across the cuts);
+ *              JTK_ENCODE_VALIDATE_UTF8, JTK_ENCODE_COUNT_ONLY, JTK_ENCODE_TO_HOST and JTK_ENCODE_COMPACT_IDS compose with it as
+ *              they do with JTK_ENCODE_ALLOW_SPECIAL (host input goes down whole, the host result in one copy behind the last
+ *              chunk); JTK_ENCODE_ALLOW_SPECIAL with it, the flag without parameters set, and the flag at any other entry
+ *              point are JTK_ERR_INVALID_ARGUMENT.  JTK_OPT_REUSE_CHUNK_PLAN does not apply.
+ *   Afterwards: token positions are no longer positions in the text: jtk_batch_chunk / _chunk_prefer, jtk_batch_token_offsets,
+ *              jtk_batch_token_spans, the jtk_batch_char_* calls and jtk_batch_truncate return JTK_ERR_INVALID_ARGUMENT;
+ *              fetch, device and host results, jtk_batch_compact and jtk_batch_pack (and its labels without spans) work on
+ *              the result as on any other.
+ *   Waits:     none of its own: the chunk plan's wait of a text larger than JTK_OPT_CHUNK_BYTES as without the flag, and with
+ *              JTK_ENCODE_TO_HOST one for the size of the copy.
+ * jtk_batch_set_fim: the parameters of later JTK_ENCODE_FIM encodes on this batch (copied); NULL clears them.  Each of the three
+ * ids must be a special id of the encoding (JTK_ERR_INVALID_ARGUMENT otherwise, the parameters are then unchanged).
+ * jtk_batch_fim_result: after a JTK_ENCODE_FIM encode (JTK_ERR_INVALID_ARGUMENT otherwise), device pointers valid until the next
+ * encode on this batch: kind [n_docs] (0 untouched, 1 PSM, 2 SPM), cut [n_docs][2] (a, b: byte positions relative to the
+ * document; len, len for kind 0), part_tok [n_docs][3] (tokens of prefix, middle, suffix; 0 for a document without tokens).
+ * The middle is the last part_tok[d][1] tokens of document d in both layouts.  _fetch copies them to host arrays (it waits
+ * for the encode).  Any pointer may be NULL. */
+typedef struct jtk_fim_params {
+    uint64_t seed;
+    int64_t doc_index_base;     /* the global index of the batch's document 0 */
+    uint32_t fim_rate;          /* in units of 2^-32; 0xFFFFFFFF: always */
+    uint32_t spm_rate;          /* in units of 2^-32; 0xFFFFFFFF: always */
+    int32_t prefix_id, middle_id, suffix_id;
+} jtk_fim_params;
+int jtk_batch_set_fim(jtk_batch* b, const jtk_fim_params* params_or_null);
+int jtk_batch_fim_result(jtk_batch* b, const uint8_t** d_kind, const int64_t** d_cut, const int64_t** d_part_tok);
+int jtk_batch_fim_result_fetch(jtk_batch* b, uint8_t* kind, int64_t* cut, int64_t* part_tok);
 
 /* The batch's own HIP stream (a hipStream_t), e.g. to order a caller's work after a non-synchronising encode. */
 void* jtk_batch_stream(jtk_batch* b);

@@ -31,6 +31,10 @@ JTK_ENCODE_COUNT_ONLY = 4
 JTK_ENCODE_TO_HOST = 8
 JTK_ENCODE_ALLOW_SPECIAL = 16
 JTK_ENCODE_COMPACT_IDS = 32
+JTK_ENCODE_FIM = 64
+JTK_FIM_NONE = 0
+JTK_FIM_PSM = 1
+JTK_FIM_SPM = 2
 JTK_PACK_WHOLE_DOCS = 1
 JTK_PACK_SEP_FIRST = 2
 JTK_PACK_DROP_LAST = 4
@@ -65,6 +69,14 @@ JTK_OPT_CHUNKS_IN_FLIGHT = 2
 JTK_OPT_HOST_CHUNK_BYTES = 3
 JTK_OPT_REUSE_CHUNK_PLAN = 4
 
+
+
+class FimParamsStruct(C.Structure):
+    """jtk_fim_params"""
+    _fields_ = [("seed", C.c_uint64), ("doc_index_base", C.c_int64), ("fim_rate", C.c_uint32), ("spm_rate", C.c_uint32),
+                ("prefix_id", C.c_int32), ("middle_id", C.c_int32), ("suffix_id", C.c_int32)]
+
+
 # every symbol include/jtokkit_amd.h declares: (restype, argtypes)
 _p = C.c_void_p
 _i64 = C.c_int64
@@ -93,6 +105,9 @@ SIGNATURES = {
     "jtk_batch_encode_pieces": (C.c_int, [_p, _p, _p, _i64, _p, _p, _i64, C.c_uint32, C.POINTER(_i64)]),
     "jtk_batch_encode_device": (C.c_int, [_p, _p, _p, _i64, _i64, C.c_uint32, _p, C.POINTER(_i64)]),
     "jtk_batch_set_allowed_special": (C.c_int, [_p, _p, C.c_int]),
+    "jtk_batch_set_fim": (C.c_int, [_p, C.POINTER(FimParamsStruct)]),
+    "jtk_batch_fim_result": (C.c_int, [_p, C.POINTER(_p), C.POINTER(_p), C.POINTER(_p)]),
+    "jtk_batch_fim_result_fetch": (C.c_int, [_p, _p, _p, _p]),
     "jtk_batch_stream": (_p, [_p]),
     "jtk_batch_result": (C.c_int, [_p, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(C.c_int32)]),
     "jtk_batch_fetch": (C.c_int, [_p, _p, _i64, _p, _p]),

@@ -189,6 +189,14 @@ struct jtk_batch {
     DevBuf sp_lits;                  // ids [n] (int32) | allowed [n]
     DevBuf sp_find, sp_cand, sp_out;
     int64_t* h_sp = nullptr; size_t h_sp_cap = 0;   // pinned: (candidates, bad offsets) read once per call
+    // JTK_ENCODE_FIM (jtk_fim.hip): the parameters (jtk_batch_set_fim) and, alive with the encode's result, hdr | the stitched
+    // status | sub_off | cut | part_tok | kind; the stitched tokens and offsets share sp_out with allow-special
+    jtk_fim_params fim{};
+    bool fim_set = false, have_fim = false;
+    DevBuf fim_buf;
+    const uint8_t* fim_kind = nullptr;
+    const int64_t* fim_cut = nullptr;
+    const int64_t* fim_part_tok = nullptr;
     JtkDecodeWork dwork{};
     bool have_decode = false;
     int64_t dec_total = 0;
@@ -218,7 +226,7 @@ struct jtk_batch {
 // read only the arguments, before the first allocation, copy or launch that can touch memory the old result lives in.  A call
 // that fails past that point leaves no result.
 static void drop_encode_result(jtk_batch* b) {
-    b->have_result = b->have_host_result = b->have_trunc = b->have_chunk = b->have_tiles = b->have_pack = false;
+    b->have_result = b->have_host_result = b->have_trunc = b->have_chunk = b->have_tiles = b->have_pack = b->have_fim = false;
     b->cp_unit = -1;
     b->ck_end_level = nullptr;
     b->synced = false;
@@ -232,12 +240,15 @@ static hipStream_t pick_stream(const jtk_batch* b, void* stream_or_null) { retur
 
 // what a pass over the last encode needs of it, besides that there is one
 enum : unsigned { NEED_IDS = 1,         // token ids (the encode was not count-only)
-                  NEED_TEXT_POS = 2 };  // positions that are positions in the text (it did not take caller-supplied pieces)
+                  NEED_TEXT_POS = 2,    // positions that are positions in the text (it did not take caller-supplied pieces)
+                  NEED_TEXT_ORDER = 4 };// tokens in the order of the text's bytes (it did not rearrange the documents: JTK_ENCODE_FIM)
 static int need_encode(const jtk_batch* b, unsigned what) {
     if (!b || !b->have_result) return fail(JTK_ERR_INVALID_ARGUMENT, "no batch encode result on this batch (jtk_batch_encode_device_max_tokens leaves none)");
     if ((what & NEED_IDS) && (b->job_flags & JTK_ENCODE_COUNT_ONLY)) return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode was count-only: there are no token ids");
     if ((what & NEED_TEXT_POS) && b->job_pieces)
         return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode took caller-supplied pieces: its positions are positions in the decoded stream, not in the text");
+    if ((what & (NEED_TEXT_POS | NEED_TEXT_ORDER)) && (b->job_flags & JTK_ENCODE_FIM))
+        return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode was a JTK_ENCODE_FIM encode: its tokens are rearranged around sentinel ids and have no positions in the text");
     return JTK_OK;
 }
 
@@ -507,7 +518,7 @@ void jtk_batch_destroy(jtk_batch* b) {
     DevBuf* bufs[] = {&b->in_text, &b->in_off, &b->in_pieces, &b->out, &b->plan, &b->dec_in_ids, &b->dec_in_off,
                       &b->dec_zero, &b->dec_tile, &b->dec_pre, &b->dec_out, &b->dec_byte_off, &b->dec_first, &b->dec_in_win, &b->dec_cell, &b->trunc_kept, &b->trunc_flag,
                       &b->mt_scratch, &b->mt_gather, &b->ck_scratch, &b->ck_tiles, &b->ck_rec, &b->ck_plane, &b->pk_scratch, &b->sp_lits, &b->sp_find,
-                      &b->sp_cand, &b->sp_out, &b->cp_buf, &b->u16_scratch, &b->u16_in, &b->u16_tx_text, &b->u16_tx_off, &b->u16_enc_text, &b->u16_enc_off,
+                      &b->sp_cand, &b->sp_out, &b->fim_buf, &b->cp_buf, &b->u16_scratch, &b->u16_in, &b->u16_tx_text, &b->u16_tx_off, &b->u16_enc_text, &b->u16_enc_off,
                       &b->u16_dscratch, &b->u16_units, &b->u16_unit_off, &b->stop_buf};
     for (DevBuf* d : bufs) d->release();
     if (b->h_sp) (void)hipHostFree(b->h_sp);
@@ -579,6 +590,41 @@ int jtk_batch_set_allowed_special(jtk_batch* b, const int32_t* special_ids, int 
     if (b->have_result && !b->synced) { HIP_TRY(hipStreamSynchronize(b->last_stream)); b->synced = true; }
     b->sp_allowed.swap(allowed);
     b->sp_dirty = true;
+    return JTK_OK;
+}
+
+int jtk_batch_set_fim(jtk_batch* b, const jtk_fim_params* params) {
+    if (!b) return fail(JTK_ERR_INVALID_ARGUMENT, "batch is NULL");
+    if (!params) { b->fim_set = false; return JTK_OK; }
+    const int32_t ids[3] = {params->prefix_id, params->middle_id, params->suffix_id};
+    const char* const names[3] = {"prefix_id", "middle_id", "suffix_id"};
+    for (int k = 0; k < 3; k++) {
+        bool known = false;
+        for (auto& sp : b->enc->host.specials) known = known || sp.second == ids[k];
+        if (!known) return fail(JTK_ERR_INVALID_ARGUMENT, std::string(names[k]) + " " + std::to_string(ids[k]) + " is not a special token of this encoding");
+    }
+    b->fim = *params;                // (read by the host when an encode is queued: the kernels take copies)
+    b->fim_set = true;
+    return JTK_OK;
+}
+
+int jtk_batch_fim_result(jtk_batch* b, const uint8_t** d_kind, const int64_t** d_cut, const int64_t** d_part_tok) {
+    if (!b || !b->have_result || !b->have_fim) return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode on this batch did not run with JTK_ENCODE_FIM");
+    if (d_kind) *d_kind = b->fim_kind;
+    if (d_cut) *d_cut = b->fim_cut;
+    if (d_part_tok) *d_part_tok = b->fim_part_tok;
+    return JTK_OK;
+}
+
+int jtk_batch_fim_result_fetch(jtk_batch* b, uint8_t* kind, int64_t* cut, int64_t* part_tok) {
+    if (!b || !b->have_result || !b->have_fim) return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode on this batch did not run with JTK_ENCODE_FIM");
+    HIP_TRY(hipSetDevice(b->enc->device));
+    if (!b->synced) { HIP_TRY(hipStreamSynchronize(b->last_stream)); b->synced = true; }
+    const size_t n = (size_t)b->job_docs;
+    if (n == 0) return JTK_OK;
+    if (kind) HIP_TRY(hipMemcpy(kind, b->fim_kind, n, hipMemcpyDeviceToHost));
+    if (cut) HIP_TRY(hipMemcpy(cut, b->fim_cut, n * 16, hipMemcpyDeviceToHost));
+    if (part_tok) HIP_TRY(hipMemcpy(part_tok, b->fim_part_tok, n * 24, hipMemcpyDeviceToHost));
     return JTK_OK;
 }
 
@@ -1004,6 +1050,52 @@ bool sp_any_allowed(const jtk_batch* b) {
     return false;
 }
 
+// A stitched result (allow-special's, fill-in-the-middle's: written by a stitch behind the pipeline's run on sub-documents)
+// becomes the batch's: result / status / tok_off / tokens are device memory that lives with it, flags the call's.  With
+// JTK_ENCODE_TO_HOST the stitch comes after the last chunk, so the ids go to the host in one copy behind it, not chunk by chunk
+// (one wait, for the token count); with JTK_ENCODE_COMPACT_IDS as the planes of the whole result.
+int install_stitched(jtk_batch* b, const JtkResult* result, int32_t* status, int64_t* tok_off, int32_t* tokens, const int64_t* d_doc_off,
+                     int64_t n_docs, uint32_t flags, hipStream_t s) {
+    const bool to_host = (flags & JTK_ENCODE_TO_HOST) != 0, count_only = (flags & JTK_ENCODE_COUNT_ONLY) != 0;
+    const bool compact_req = to_host && (flags & JTK_ENCODE_COMPACT_IDS) != 0, compact = compact_req && !count_only;
+    const int hb = b->enc->hb;
+    int rc;
+    b->job.p = (void*)result; b->status.p = status; b->tok_off.p = tok_off; b->tokens.p = tokens;
+    b->host_result = b->host_result_own;
+    HIP_TRY(hipMemcpyAsync(b->host_result, result, sizeof(JtkResult), hipMemcpyDeviceToHost, s));
+    b->job_doc_off = d_doc_off;
+    b->job_docs = n_docs;
+    b->job_flags = flags & ~(uint32_t)(JTK_ENCODE_TO_HOST | JTK_ENCODE_COMPACT_IDS);
+    if (to_host) {
+        HIP_TRY(hipStreamSynchronize(s));
+        const int64_t nt = b->host_result->n_tokens;
+        const size_t lo_bytes = align_up((size_t)jtk_compact_lo_bytes(nt), 256), hi_bytes = (size_t)jtk_compact_hi_words(nt, hb) * 4;
+        if ((rc = ensure_pinned((void**)&b->h_tok_off, &b->h_tok_off_cap, ((size_t)n_docs + 1) * 8, 0)) ||
+            (rc = ensure_pinned((void**)&b->h_status, &b->h_status_cap, (size_t)(n_docs > 0 ? n_docs : 1) * 4, 0)) ||
+            (rc = ensure_pinned((void**)&b->h_tokens, &b->h_tokens_cap, (size_t)nt * (compact ? 2 : 4) + 4096, 0)))
+            return rc;
+        HIP_TRY(hipMemcpyAsync(b->h_tok_off, tok_off, ((size_t)n_docs + 1) * 8, hipMemcpyDeviceToHost, s));
+        if (n_docs > 0) HIP_TRY(hipMemcpyAsync(b->h_status, status, (size_t)n_docs * 4, hipMemcpyDeviceToHost, s));
+        if (compact) {
+            // the planes of the whole stitched result, compacted behind the stitch, in one copy each
+            if ((hb && (rc = ensure_pinned((void**)&b->h_hi, &b->h_hi_cap, hi_bytes + 4096, 0))) || (rc = b->cp_stage.ensure(lo_bytes + hi_bytes + 16))) return rc;
+            uint16_t* d_lo = (uint16_t*)b->cp_stage.p;
+            uint32_t* d_hi = (uint32_t*)((uint8_t*)b->cp_stage.p + lo_bytes);
+            if (nt > 0) {
+                jtk_launch_compact(tokens, 0, nt, nullptr, d_lo, d_hi, 0, hb, s);
+                HIP_TRY(hipGetLastError());
+                HIP_TRY(hipMemcpyAsync(b->h_tokens, d_lo, (size_t)nt * 2, hipMemcpyDeviceToHost, s));
+                if (hb) HIP_TRY(hipMemcpyAsync(b->h_hi, d_hi, hi_bytes, hipMemcpyDeviceToHost, s));
+            }
+        } else if (nt > 0 && !count_only) HIP_TRY(hipMemcpyAsync(b->h_tokens, tokens, (size_t)nt * 4, hipMemcpyDeviceToHost, s));
+        b->r_tokens = compact ? nullptr : b->h_tokens; b->r_tok_off = b->h_tok_off; b->r_status = b->h_status;
+        b->r_lo = (const uint16_t*)b->h_tokens; b->r_hi = b->h_hi;
+    }
+    b->host_compact = compact_req;
+    b->have_result = true; b->have_host_result = to_host;
+    return JTK_OK;
+}
+
 // JTK_ENCODE_ALLOW_SPECIAL on a device-resident batch (host input is copied down whole first), jtk_special.hip: find the
 // candidates; with none in any document the pipeline runs on the documents as they are (today's call: its own special-token
 // check then sees only literals outside the allowed set), else on the sub-documents, and the stitch writes the result.  cb: the
@@ -1014,8 +1106,6 @@ int run_allow_special(jtk_batch* b, const uint8_t* d_text, const int64_t* d_doc_
     const jtk_encoding* enc = b->enc;
     const bool to_host = (flags & JTK_ENCODE_TO_HOST) != 0, count_only = (flags & JTK_ENCODE_COUNT_ONLY) != 0;
     const uint32_t base_flags = flags & ~(uint32_t)(JTK_ENCODE_ALLOW_SPECIAL | JTK_ENCODE_TO_HOST);       // (keeps JTK_ENCODE_COMPACT_IDS)
-    const bool compact_req = to_host && (flags & JTK_ENCODE_COMPACT_IDS) != 0, compact = compact_req && !count_only;
-    const int hb = enc->hb;
     const int n_lits = (int)enc->host.specials.size();
     int rc;
     if (b->sp_dirty) {
@@ -1089,7 +1179,6 @@ int run_allow_special(jtk_batch* b, const uint8_t* d_text, const int64_t* d_doc_
     HIP_TRY(hipGetLastError());
     // encodeOrdinary of every sub-document (the literals' tokens are not used: their ids are written instead)
     const uint32_t sub_flags = JTK_ENCODE_ORDINARY | (flags & (JTK_ENCODE_VALIDATE_UTF8 | JTK_ENCODE_COUNT_ONLY));
-    flags &= ~(uint32_t)JTK_ENCODE_COMPACT_IDS;
     if ((rc = plan(w.sub_off, w.n_sub)) || (rc = run_job(b, d_text, nullptr, w.sub_off, w.n_sub, n_bytes, sub_flags, s, false))) return rc;
     drop_encode_result(b);           // (the sub-documents' result is not the batch's: the stitched one is, once it is whole)
     // the stitched result: JtkResult | tok_off [n_docs + 1] | tokens (status: in the find scratch)
@@ -1102,42 +1191,67 @@ int run_allow_special(jtk_batch* b, const uint8_t* d_text, const int64_t* d_doc_
     HIP_TRY(hipMemsetAsync(out, 0, sizeof(JtkResult), s));
     jtk_launch_special_stitch(w, s);
     HIP_TRY(hipGetLastError());
-    b->job.p = out; b->status.p = w.status; b->tok_off.p = w.tok_off; b->tokens.p = w.tokens;
-    b->host_result = b->host_result_own;
-    HIP_TRY(hipMemcpyAsync(b->host_result, w.result, sizeof(JtkResult), hipMemcpyDeviceToHost, s));
-    b->job_doc_off = d_doc_off;
-    b->job_docs = n_docs;
-    b->job_flags = flags & ~(uint32_t)JTK_ENCODE_TO_HOST;
-    if (to_host) {
-        // (the stitch comes after the last chunk: the ids go to the host in one copy behind it, not chunk by chunk)
-        HIP_TRY(hipStreamSynchronize(s));
-        const int64_t nt = b->host_result->n_tokens;
-        const size_t lo_bytes = align_up((size_t)jtk_compact_lo_bytes(nt), 256), hi_bytes = (size_t)jtk_compact_hi_words(nt, hb) * 4;
-        if ((rc = ensure_pinned((void**)&b->h_tok_off, &b->h_tok_off_cap, ((size_t)n_docs + 1) * 8, 0)) ||
-            (rc = ensure_pinned((void**)&b->h_status, &b->h_status_cap, (size_t)(n_docs > 0 ? n_docs : 1) * 4, 0)) ||
-            (rc = ensure_pinned((void**)&b->h_tokens, &b->h_tokens_cap, (size_t)nt * (compact ? 2 : 4) + 4096, 0)))
-            return rc;
-        HIP_TRY(hipMemcpyAsync(b->h_tok_off, w.tok_off, ((size_t)n_docs + 1) * 8, hipMemcpyDeviceToHost, s));
-        if (n_docs > 0) HIP_TRY(hipMemcpyAsync(b->h_status, w.status, (size_t)n_docs * 4, hipMemcpyDeviceToHost, s));
-        if (compact) {
-            // the planes of the whole stitched result, compacted behind the stitch, in one copy each
-            if ((hb && (rc = ensure_pinned((void**)&b->h_hi, &b->h_hi_cap, hi_bytes + 4096, 0))) || (rc = b->cp_stage.ensure(lo_bytes + hi_bytes + 16))) return rc;
-            uint16_t* d_lo = (uint16_t*)b->cp_stage.p;
-            uint32_t* d_hi = (uint32_t*)((uint8_t*)b->cp_stage.p + lo_bytes);
-            if (nt > 0) {
-                jtk_launch_compact(w.tokens, 0, nt, nullptr, d_lo, d_hi, 0, hb, s);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipMemcpyAsync(b->h_tokens, d_lo, (size_t)nt * 2, hipMemcpyDeviceToHost, s));
-                if (hb) HIP_TRY(hipMemcpyAsync(b->h_hi, d_hi, hi_bytes, hipMemcpyDeviceToHost, s));
-            }
-        } else if (nt > 0 && !count_only) HIP_TRY(hipMemcpyAsync(b->h_tokens, w.tokens, (size_t)nt * 4, hipMemcpyDeviceToHost, s));
-        b->r_tokens = compact ? nullptr : b->h_tokens; b->r_tok_off = b->h_tok_off; b->r_status = b->h_status;
-        b->r_lo = (const uint16_t*)b->h_tokens; b->r_hi = b->h_hi;
-    }
-    b->host_compact = compact_req;
-    b->have_result = true; b->have_host_result = to_host;
+    return install_stitched(b, w.result, w.status, w.tok_off, w.tokens, d_doc_off, n_docs, flags, s);
+}
+
+// JTK_ENCODE_FIM on a device-resident batch (host input is copied down whole first), jtk_fim.hip: kind, cuts and the three
+// sub-documents of every document, the pipeline on the sub-documents, the stitch.  cb: the chunk size of the pipeline run.  No
+// wait of its own: the chunk plan's of a run longer than one chunk, and install_stitched's for a host copy.
+int run_fim(jtk_batch* b, const uint8_t* d_text, const int64_t* d_doc_off, int64_t n_docs, int64_t n_bytes, uint32_t flags, hipStream_t s,
+            int64_t cb) {
+    const bool count_only = (flags & JTK_ENCODE_COUNT_ONLY) != 0;
+    int rc;
+    // hdr [4] | status [n] | sub_off [3n + 1] | cut [2n] | part_tok [3n] | kind [n];  the stitched result: JtkResult | tok_off
+    // [n + 1] | tokens (at most a token per byte and three sentinels per document)
+    const size_t n = (size_t)n_docs, status_bytes = align_up((n > 0 ? n : 1) * 4, 16);
+    const size_t o_sub = 32 + status_bytes, o_cut = o_sub + (3 * n + 1) * 8, o_part = o_cut + 2 * n * 8, o_kind = o_part + 3 * n * 8;
+    const size_t o_tok_off = 64, o_tokens = align_up(o_tok_off + (n + 1) * 8, 256);
+    if ((rc = b->fim_buf.ensure(o_kind + n + 16)) ||
+        (rc = b->sp_out.ensure(o_tokens + (count_only ? 0 : ((size_t)n_bytes + 3 * n + 64) * 4))))
+        return rc;
+    uint8_t* z = (uint8_t*)b->fim_buf.p;
+    uint8_t* out = (uint8_t*)b->sp_out.p;
+    JtkFimWork w{};
+    w.text = d_text; w.doc_off = d_doc_off; w.n_docs = n_docs; w.n_bytes = n_bytes;
+    w.seed = b->fim.seed; w.doc_index_base = b->fim.doc_index_base; w.fim_rate = b->fim.fim_rate; w.spm_rate = b->fim.spm_rate;
+    w.hdr = (int64_t*)z; w.status = (int32_t*)(z + 32); w.sub_off = (int64_t*)(z + o_sub); w.cut = (int64_t*)(z + o_cut);
+    w.part_tok = (int64_t*)(z + o_part); w.kind = z + o_kind;
+    w.result = (JtkResult*)out; w.tok_off = (int64_t*)(out + o_tok_off); w.tokens = (int32_t*)(out + o_tokens);
+    w.count_only = count_only ? 1u : 0u;
+    HIP_TRY(hipMemsetAsync(z, 0, 32, s));
+    HIP_TRY(hipMemsetAsync(out, 0, sizeof(JtkResult), s));
+    jtk_launch_fim_cuts(w, s);
+    HIP_TRY(hipGetLastError());
+    // encodeOrdinary of every sub-document
+    const uint32_t sub_flags = JTK_ENCODE_ORDINARY | (flags & (JTK_ENCODE_VALIDATE_UTF8 | JTK_ENCODE_COUNT_ONLY));
+    const int64_t save_cb = b->chunk_bytes;
+    b->chunk_bytes = cb;
+    rc = plan_device_chunks(b, w.sub_off, 3 * n_docs, n_bytes, s);
+    b->chunk_bytes = save_cb;
+    if (rc || (rc = run_job(b, d_text, nullptr, w.sub_off, 3 * n_docs, n_bytes, sub_flags, s, false))) return rc;
+    drop_encode_result(b);           // (the sub-documents' result is not the batch's: the stitched one is, once it is whole)
+    w.sub_tok_off = (const int64_t*)b->tok_off.p; w.sub_status = (const int32_t*)b->status.p;
+    w.v.n_docs = n_docs; w.v.kind = w.kind; w.v.part_tok = w.part_tok; w.v.tok_off = w.tok_off;
+    w.v.sub_tok_off = w.sub_tok_off; w.v.sub_tokens = (const int32_t*)b->tokens.p;
+    w.v.prefix_id = b->fim.prefix_id; w.v.middle_id = b->fim.middle_id; w.v.suffix_id = b->fim.suffix_id;
+    jtk_launch_fim_stitch(w, s);
+    HIP_TRY(hipGetLastError());
+    if ((rc = install_stitched(b, w.result, w.status, w.tok_off, w.tokens, d_doc_off, n_docs, flags, s))) return rc;
+    b->fim_kind = w.kind; b->fim_cut = w.cut; b->fim_part_tok = w.part_tok;
+    b->have_fim = true;
     return JTK_OK;
 }
+
+// what JTK_ENCODE_FIM needs at the two entry points that take it
+int fim_flags(const jtk_batch* b, uint32_t flags) {
+    if (!(flags & JTK_ENCODE_FIM)) return JTK_OK;
+    if (!b->fim_set) return fail(JTK_ERR_INVALID_ARGUMENT, "JTK_ENCODE_FIM without parameters: jtk_batch_set_fim has not set any on this batch");
+    if (!(flags & JTK_ENCODE_ORDINARY))
+        return fail(JTK_ERR_INVALID_ARGUMENT, "JTK_ENCODE_FIM needs JTK_ENCODE_ORDINARY: encode()'s special-token check would have to look across the cuts");
+    if (flags & JTK_ENCODE_ALLOW_SPECIAL) return fail(JTK_ERR_INVALID_ARGUMENT, "JTK_ENCODE_FIM does not combine with JTK_ENCODE_ALLOW_SPECIAL");
+    return JTK_OK;
+}
+const char* const FIM_ELSEWHERE = "JTK_ENCODE_FIM is for jtk_batch_encode / jtk_batch_encode_device";
 
 }  // namespace
 
@@ -1151,12 +1265,16 @@ int jtk_batch_encode_device(jtk_batch* b, const uint8_t* d_utf8, const int64_t* 
     if (n_bytes >= (int64_t)1 << 37) return fail(JTK_ERR_INVALID_ARGUMENT, "batch too large (128 GiB of text per call at most)");
     if (flags & JTK_ENCODE_TO_HOST) return fail(JTK_ERR_INVALID_ARGUMENT, "JTK_ENCODE_TO_HOST is for jtk_batch_encode (host buffers)");
     if (flags & JTK_ENCODE_COMPACT_IDS) return fail(JTK_ERR_INVALID_ARGUMENT, "JTK_ENCODE_COMPACT_IDS is for jtk_batch_encode with JTK_ENCODE_TO_HOST (on the device: jtk_batch_compact)");
+    int rc;
+    if ((rc = fim_flags(b, flags))) return rc;
     HIP_TRY(hipSetDevice(b->enc->device));
     drop_encode_result(b);
     hipStream_t s = pick_stream(b, stream_or_null);
     if ((flags & JTK_ENCODE_ALLOW_SPECIAL) && !sp_any_allowed(b)) flags &= ~(uint32_t)JTK_ENCODE_ALLOW_SPECIAL;   // empty set: today's call
-    int rc;
-    if (flags & JTK_ENCODE_ALLOW_SPECIAL) {
+    if (flags & JTK_ENCODE_FIM) {
+        b->plan_doc_off = nullptr;                                  // (no JTK_OPT_REUSE_CHUNK_PLAN here)
+        rc = run_fim(b, d_utf8, d_doc_off, n_docs, n_bytes, flags, s, b->chunk_bytes);
+    } else if (flags & JTK_ENCODE_ALLOW_SPECIAL) {
         b->plan_doc_off = nullptr;                                  // (no JTK_OPT_REUSE_CHUNK_PLAN here)
         rc = run_allow_special(b, d_utf8, d_doc_off, n_docs, n_bytes, flags, s, b->chunk_bytes);
     } else {
@@ -1190,16 +1308,17 @@ int jtk_batch_encode(jtk_batch* b, const uint8_t* utf8, const int64_t* doc_off, 
     if (n_bytes >= (int64_t)1 << 37) return fail(JTK_ERR_INVALID_ARGUMENT, "batch too large (128 GiB of text per call at most)");
     const int64_t cb = b->host_chunk_bytes < b->chunk_bytes ? b->host_chunk_bytes : b->chunk_bytes;
     int rc;
-    if ((rc = plan_host_chunks(b, doc_off, n_docs, n_bytes, cb))) return rc;
+    if ((rc = fim_flags(b, flags)) || (rc = plan_host_chunks(b, doc_off, n_docs, n_bytes, cb))) return rc;
     HIP_TRY(hipSetDevice(b->enc->device));
     drop_encode_result(b);
     if ((flags & JTK_ENCODE_ALLOW_SPECIAL) && !sp_any_allowed(b)) flags &= ~(uint32_t)JTK_ENCODE_ALLOW_SPECIAL;   // empty set: today's call
-    if (flags & JTK_ENCODE_ALLOW_SPECIAL) {
-        // the text goes down whole (the candidates are found before any chunk is encoded); then as device input
+    if (flags & (JTK_ENCODE_ALLOW_SPECIAL | JTK_ENCODE_FIM)) {
+        // the text goes down whole (the candidates are found, the cuts are made, before any chunk is encoded); then as device input
         if ((rc = b->in_text.ensure((size_t)n_bytes + 64)) || (rc = b->in_off.ensure(((size_t)n_docs + 1) * 8))) return rc;
         HIP_TRY(hipMemcpyAsync(b->in_off.p, doc_off, ((size_t)n_docs + 1) * 8, hipMemcpyHostToDevice, b->stream));
         if (n_bytes > 0) HIP_TRY(hipMemcpyAsync(b->in_text.p, utf8, (size_t)n_bytes, hipMemcpyHostToDevice, b->stream));
-        rc = run_allow_special(b, (const uint8_t*)b->in_text.p, (const int64_t*)b->in_off.p, n_docs, n_bytes, flags, b->stream, cb);
+        rc = (flags & JTK_ENCODE_FIM) ? run_fim(b, (const uint8_t*)b->in_text.p, (const int64_t*)b->in_off.p, n_docs, n_bytes, flags, b->stream, cb)
+                                      : run_allow_special(b, (const uint8_t*)b->in_text.p, (const int64_t*)b->in_off.p, n_docs, n_bytes, flags, b->stream, cb);
     } else if (b->chunk_doc.size() == 2 && n_bytes <= TINY_JOB_BYTES) {
         // a per-call device batch: offsets and text go down in ONE copy (staged side by side in pinned memory; copying a few KB on
         // the host costs less than a second DMA)
@@ -1230,6 +1349,7 @@ int jtk_batch_encode_pieces(jtk_batch* b, const uint8_t* utf8, const int64_t* do
     if (!b || n_docs < 0 || !doc_off || n_pieces < 0 || (n_pieces > 0 && (!piece_begin || !piece_end)))
         return fail(JTK_ERR_INVALID_ARGUMENT, "bad arguments");
     if (flags & JTK_ENCODE_ALLOW_SPECIAL) return fail(JTK_ERR_INVALID_ARGUMENT, "JTK_ENCODE_ALLOW_SPECIAL is for jtk_batch_encode / jtk_batch_encode_device");
+    if (flags & JTK_ENCODE_FIM) return fail(JTK_ERR_INVALID_ARGUMENT, FIM_ELSEWHERE);
     if ((flags & JTK_ENCODE_COMPACT_IDS) && !(flags & JTK_ENCODE_TO_HOST))
         return fail(JTK_ERR_INVALID_ARGUMENT, "JTK_ENCODE_COMPACT_IDS needs JTK_ENCODE_TO_HOST (on the device: jtk_batch_compact)");
     if (doc_off[0] != 0) return fail(JTK_ERR_INVALID_ARGUMENT, "doc_off[0] must be 0");
@@ -1388,6 +1508,7 @@ int jtk_batch_kernel_times(jtk_batch* b, const char** names, float* ms, int cap,
 int jtk_batch_truncate(jtk_batch* b, int64_t max_tokens) {
     if (!b || !b->have_result || max_tokens < 0) return fail(JTK_ERR_INVALID_ARGUMENT, "bad arguments (an encode must have run on this batch)");
     if (b->job_flags & JTK_ENCODE_ALLOW_SPECIAL) return fail(JTK_ERR_INVALID_ARGUMENT, "maxTokens is not defined after a JTK_ENCODE_ALLOW_SPECIAL encode");
+    if (b->job_flags & JTK_ENCODE_FIM) return fail(JTK_ERR_INVALID_ARGUMENT, "maxTokens is not defined after a JTK_ENCODE_FIM encode");
     HIP_TRY(hipSetDevice(b->enc->device));
     if (!b->synced) { HIP_TRY(hipStreamSynchronize(b->last_stream)); b->synced = true; }
     const int64_t nd = b->job_docs;
@@ -1641,6 +1762,7 @@ int jtk_encode(jtk_batch* b, const uint8_t* utf8, int64_t len, uint32_t flags, i
                int32_t* tokens, int64_t tokens_cap, int64_t* n_tokens, int* truncated) {
     if (!b || len < 0) return fail(JTK_ERR_INVALID_ARGUMENT, "bad arguments");
     if (flags & JTK_ENCODE_ALLOW_SPECIAL) return fail(JTK_ERR_INVALID_ARGUMENT, "JTK_ENCODE_ALLOW_SPECIAL is for jtk_batch_encode / jtk_batch_encode_device");
+    if (flags & JTK_ENCODE_FIM) return fail(JTK_ERR_INVALID_ARGUMENT, FIM_ELSEWHERE);
     if (flags & JTK_ENCODE_COMPACT_IDS) return fail(JTK_ERR_INVALID_ARGUMENT, "JTK_ENCODE_COMPACT_IDS is for jtk_batch_encode with JTK_ENCODE_TO_HOST");
     if (truncated) *truncated = 0;
     if (n_tokens) *n_tokens = 0;
@@ -1693,6 +1815,7 @@ int jtk_batch_encode_max_tokens(jtk_batch* b, const uint8_t* utf8, const int64_t
     if (!b || n_docs < 0 || !doc_off || max_tokens < 0 || !kept || (max_tokens > 0 && n_docs > 0 && !tokens))
         return fail(JTK_ERR_INVALID_ARGUMENT, "bad arguments");
     if (flags & JTK_ENCODE_ALLOW_SPECIAL) return fail(JTK_ERR_INVALID_ARGUMENT, "JTK_ENCODE_ALLOW_SPECIAL is for jtk_batch_encode / jtk_batch_encode_device");
+    if (flags & JTK_ENCODE_FIM) return fail(JTK_ERR_INVALID_ARGUMENT, FIM_ELSEWHERE);
     if (doc_off[0] != 0) return fail(JTK_ERR_INVALID_ARGUMENT, "doc_off[0] must be 0");
     for (int64_t d = 0; d < n_docs; d++)
         if (doc_off[d + 1] < doc_off[d]) return fail(JTK_ERR_INVALID_ARGUMENT, "doc_off must be non-decreasing");
@@ -2000,7 +2123,7 @@ int jtk_batch_chunk(jtk_batch* b, int64_t chunk_tokens, int64_t overlap, void* s
     if (!b || !n_chunks) return fail(JTK_ERR_INVALID_ARGUMENT, "bad arguments");
     *n_chunks = 0;
     int rc;
-    if ((rc = need_encode(b, NEED_IDS))) return rc;
+    if ((rc = need_encode(b, NEED_IDS | NEED_TEXT_ORDER))) return rc;
     if (chunk_tokens < 1 || chunk_tokens > INT32_MAX) return fail(JTK_ERR_INVALID_ARGUMENT, "chunk_tokens must be in [1, 2^31 - 1]");
     if (overlap < 0 || overlap >= chunk_tokens) return fail(JTK_ERR_INVALID_ARGUMENT, "overlap must be in [0, chunk_tokens)");
     HIP_TRY(hipSetDevice(b->enc->device));
@@ -2091,7 +2214,7 @@ int jtk_batch_compact(jtk_batch* b, uint16_t* d_lo, uint32_t* d_hi, void* stream
 
 int jtk_batch_token_offsets(jtk_batch* b, int64_t* d_byte_pos, void* stream_or_null) {
     int rc;
-    if ((rc = need_encode(b, NEED_IDS))) return rc;
+    if ((rc = need_encode(b, NEED_IDS | NEED_TEXT_ORDER))) return rc;
     HIP_TRY(hipSetDevice(b->enc->device));
     hipStream_t s = pick_stream(b, stream_or_null);
     if ((rc = ck_byte_scan(b, s))) return rc;
@@ -2125,7 +2248,7 @@ int jtk_batch_chunk_prefer(jtk_batch* b, int64_t chunk_tokens, int64_t overlap, 
     if (!b || !n_chunks) return fail(JTK_ERR_INVALID_ARGUMENT, "bad arguments");
     *n_chunks = 0;
     int rc;
-    if ((rc = need_encode(b, NEED_IDS))) return rc;
+    if ((rc = need_encode(b, NEED_IDS | NEED_TEXT_ORDER))) return rc;
     if (chunk_tokens < 1 || chunk_tokens > INT32_MAX) return fail(JTK_ERR_INVALID_ARGUMENT, "chunk_tokens must be in [1, 2^31 - 1]");
     if (overlap < 0 || overlap >= chunk_tokens) return fail(JTK_ERR_INVALID_ARGUMENT, "overlap must be in [0, chunk_tokens)");
     if (min_tokens < 1 || min_tokens > chunk_tokens) return fail(JTK_ERR_INVALID_ARGUMENT, "min_tokens must be in [1, chunk_tokens]");
@@ -2508,6 +2631,7 @@ int jtk_batch_utf8_device_result(jtk_batch* b, const uint8_t** d_utf8, const int
 }
 
 static int u16_encode_flags(uint32_t flags) {
+    if (flags & JTK_ENCODE_FIM) return fail(JTK_ERR_INVALID_ARGUMENT, FIM_ELSEWHERE);
     if (flags & (JTK_ENCODE_TO_HOST | JTK_ENCODE_COMPACT_IDS))
         return fail(JTK_ERR_INVALID_ARGUMENT, "JTK_ENCODE_TO_HOST and JTK_ENCODE_COMPACT_IDS are not for the UTF-16 entry points (the result stays on the device: jtk_batch_fetch, jtk_batch_compact)");
     return JTK_OK;

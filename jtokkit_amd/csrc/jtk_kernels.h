@@ -13,6 +13,7 @@
 #include "jtk_charpos_rules.h"
 #include "jtk_utf16_rules.h"
 #include "jtk_stop_rules.h"
+#include "jtk_fim_rules.h"
 
 #define JTK_SPLIT_TILE 4096      // bytes per pretok_split workgroup
 #define JTK_SPLIT_HALO 64
@@ -460,6 +461,33 @@ struct JtkSpecialWork {
 void jtk_launch_special_find(const JtkSpecialWork& w, hipStream_t s);      // offsets check, candidates per block, scan -> hdr
 void jtk_launch_special_write(const JtkSpecialWork& w, hipStream_t s);     // candidates, resolve, sub-documents (needs n_cand)
 void jtk_launch_special_stitch(const JtkSpecialWork& w, hipStream_t s);    // status, counts, scan, offsets, ids (after the pipeline)
+// Device-side state of a fill-in-the-middle encode (jtk_fim.hip, JTK_ENCODE_FIM; the rule is jtk_fim_rules.h).  Every document
+// becomes three sub-documents in text order (prefix, middle, suffix; an untouched document: itself and two empty ones), known
+// before anything runs: no find pass and no wait.  The encode pipeline runs on the sub-documents (encodeOrdinary), and the
+// stitch writes each document's parts and sentinel ids into the final result in the order of its kind.
+struct JtkFimWork {
+    const uint8_t* text;        // the batch text
+    const int64_t* doc_off;     // [n_docs + 1]
+    int64_t n_docs, n_bytes;
+    uint64_t seed;
+    int64_t doc_index_base;
+    uint32_t fim_rate, spm_rate;
+    int64_t* hdr;               // [0] != 0: the offsets are bad (not non-decreasing within [0, n_bytes], from 0 to n_bytes)
+    uint8_t* kind;              // [n_docs]
+    int64_t* cut;               // [n_docs][2] relative to the document
+    int64_t* sub_off;           // [3 n_docs + 1]
+    const int64_t* sub_tok_off; // the pipeline's result on the sub-documents: [3 n_docs + 1]
+    const int32_t* sub_status;  // [3 n_docs]
+    int64_t* part_tok;          // [n_docs][3]
+    uint32_t count_only;
+    int32_t* status;            // final, [n_docs]
+    int64_t* tok_off;           // final, [n_docs + 1]: the counts, then their exclusive scan
+    int32_t* tokens;            // final
+    JtkResult* result;          // final (zeroed before the cuts, which report bad offsets in it)
+    JtkFimView v;               // what the gather reads (points at the arrays above and the sub-documents' ids)
+};
+void jtk_launch_fim_cuts(const JtkFimWork& w, hipStream_t s);      // offsets check, kind, cuts, sub-documents
+void jtk_launch_fim_stitch(const JtkFimWork& w, hipStream_t s);    // status, counts, scan, ids (after the pipeline)
 void jtk_launch_decode_count(const JtkDecodeWork& w, hipStream_t s);     // mark, count, scan
 void jtk_launch_decode_scatter(const JtkDecodeWork& w, hipStream_t s);   // scatter, offsets
 

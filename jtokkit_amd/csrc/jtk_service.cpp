@@ -251,6 +251,8 @@ int jtk_service_submit(jtk_service* s, const uint8_t* utf8, int64_t len, uint32_
     if (!s || !ticket || len < 0 || (len > 0 && !utf8)) return jtk_fail_msg(JTK_ERR_INVALID_ARGUMENT, "bad arguments");
     if (flags & JTK_ENCODE_ALLOW_SPECIAL)
         return jtk_fail_msg(JTK_ERR_INVALID_ARGUMENT, "JTK_ENCODE_ALLOW_SPECIAL is for jtk_batch_encode / jtk_batch_encode_device");
+    if (flags & JTK_ENCODE_FIM)
+        return jtk_fail_msg(JTK_ERR_INVALID_ARGUMENT, "JTK_ENCODE_FIM is for jtk_batch_encode / jtk_batch_encode_device");
     jtk_ticket* t = new (std::nothrow) jtk_ticket();
     if (!t) return jtk_fail_msg(JTK_ERR_OUT_OF_MEMORY, "out of host memory");
     t->utf8 = utf8; t->len = len; t->flags = flags & (JTK_ENCODE_ORDINARY | JTK_ENCODE_COUNT_ONLY); t->max_tokens = max_tokens;

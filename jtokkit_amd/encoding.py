@@ -130,6 +130,29 @@ def _stop_blob(stop_strings):
     return np.frombuffer(b"".join(bs), dtype=np.uint8), str_off
 
 
+def fim_rate_u32(rate):
+    """A probability as the ABI takes it: units of 2^-32, 0xFFFFFFFF = always."""
+    rate = float(rate)
+    if not 0.0 <= rate <= 1.0:
+        raise ValueError("a FIM rate must be in [0, 1]")
+    return min(int(rate * 2 ** 32), 2 ** 32 - 1)
+
+
+class FimParams:
+    """Fill-in-the-middle parameters (jtk_fim_params; the rule is in include/jtokkit_amd.h): rate = the probability that a
+    document is cut into prefix, middle and suffix, spm_rate = the probability that a cut document is emitted in SPM order
+    (else PSM), seed, and doc_index_base = the corpus index of the batch's first document (a shard then draws what the whole
+    corpus would).  prefix_id / middle_id / suffix_id: None = the encoding's <|fim_prefix|> / <|fim_middle|> / <|fim_suffix|>."""
+
+    def __init__(self, rate, spm_rate=0.5, seed=0, doc_index_base=0, prefix_id=None, middle_id=None, suffix_id=None):
+        self.rate, self.spm_rate, self.seed, self.doc_index_base = rate, spm_rate, seed, doc_index_base
+        self.prefix_id, self.middle_id, self.suffix_id = prefix_id, middle_id, suffix_id
+        fim_rate_u32(rate), fim_rate_u32(spm_rate)
+
+    def __repr__(self):
+        return "FimParams(rate=%r, spm_rate=%r, seed=%r, doc_index_base=%r)" % (self.rate, self.spm_rate, self.seed, self.doc_index_base)
+
+
 class _DeviceArray:
     """A numpy array's bytes in device memory of the HIP runtime the library is bound to, for host-input calls whose C entry
     point takes device arrays (no torch needed).  fetch() copies back."""
@@ -289,19 +312,46 @@ class Batch:
         arr = np.ascontiguousarray(list(ids), dtype=np.int32)
         _check(N.lib().jtk_batch_set_allowed_special(self._h, arr.ctypes.data if len(arr) else None, len(arr)))
 
+    def set_fim(self, fim, prefix_id=None, middle_id=None, suffix_id=None):
+        """jtk_batch_set_fim: the parameters of later encodes with fim=True.  fim: a FimParams (None clears them); the ids default
+        to fim's own, then to the encoding's <|fim_prefix|>, <|fim_middle|>, <|fim_suffix|>."""
+        if fim is None:
+            _check(N.lib().jtk_batch_set_fim(self._h, None))
+            return
+        ids = self.encoding.fim_ids(fim, prefix_id, middle_id, suffix_id)
+        p = N.FimParamsStruct(int(fim.seed) & (2 ** 64 - 1), int(fim.doc_index_base), fim_rate_u32(fim.rate), fim_rate_u32(fim.spm_rate), *ids)
+        _check(N.lib().jtk_batch_set_fim(self._h, C.byref(p)))
+
+    def fim_result(self):
+        """After an encode with fim=True: (kind uint8 [n_docs] -- 0 untouched, 1 PSM, 2 SPM --, cut int64 [n_docs, 2] -- byte
+        positions relative to the document --, part_tok int64 [n_docs, 3] -- tokens of prefix, middle, suffix)."""
+        _, nd, _ = self.result()
+        kind, cut = np.zeros(max(nd, 1), dtype=np.uint8), np.zeros((max(nd, 1), 2), dtype=np.int64)
+        part = np.zeros((max(nd, 1), 3), dtype=np.int64)
+        _check(N.lib().jtk_batch_fim_result_fetch(self._h, kind.ctypes.data, cut.ctypes.data, part.ctypes.data))
+        return kind[:nd], cut[:nd], part[:nd]
+
+    def fim_device_result(self):
+        """Device pointers (kind, cut, part_tok) of the last fim=True encode, valid until the next encode."""
+        a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
+        _check(N.lib().jtk_batch_fim_result(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return a.value, b.value, c.value
+
     def encode_host(self, text_u8, doc_off, ordinary=False, validate=False, count_only=False, to_host=False, allow_special=False,
-                    compact=False):
+                    compact=False, fim=False):
         """Host buffers in (numpy arrays, or anything with .ctypes.data such as a pinned HostBuffer view).  to_host: the result
         is streamed to the batch's pinned host memory while later chunks are encoded (read it with host_result()).
         allow_special: the batch's allowed special-token literals become their ids (JTK_ENCODE_ALLOW_SPECIAL).
         compact (with to_host): the ids go up as a 16-bit plane and a plane of the bits above (JTK_ENCODE_COMPACT_IDS; read
-        them with host_result_compact())."""
+        them with host_result_compact()).  fim: the fill-in-the-middle transformation by the parameters of set_fim()
+        (JTK_ENCODE_FIM; needs ordinary)."""
         text_u8 = np.ascontiguousarray(text_u8, dtype=np.uint8)
         doc_off = np.ascontiguousarray(doc_off, dtype=np.int64)
         nt = C.c_int64(0)
         flags = ((N.JTK_ENCODE_ORDINARY if ordinary else 0) | (N.JTK_ENCODE_VALIDATE_UTF8 if validate else 0)
                  | (N.JTK_ENCODE_COUNT_ONLY if count_only else 0) | (N.JTK_ENCODE_TO_HOST if to_host else 0)
-                 | (N.JTK_ENCODE_ALLOW_SPECIAL if allow_special else 0) | (N.JTK_ENCODE_COMPACT_IDS if compact else 0))
+                 | (N.JTK_ENCODE_ALLOW_SPECIAL if allow_special else 0) | (N.JTK_ENCODE_COMPACT_IDS if compact else 0)
+                 | (N.JTK_ENCODE_FIM if fim else 0))
         self._count_only = count_only
         _check(N.lib().jtk_batch_encode(self._h, text_u8.ctypes.data, doc_off.ctypes.data, len(doc_off) - 1,
                                         flags, C.byref(nt)))
@@ -360,10 +410,11 @@ class Batch:
         _check(N.lib().jtk_batch_compact(self._h, d_lo_ptr, d_hi_ptr, stream))
 
     def encode_device(self, d_text_ptr, d_doc_off_ptr, n_docs, n_bytes, ordinary=False, stream=None, sync=True,
-                      allow_special=False, validate=False, count_only=False):
+                      allow_special=False, validate=False, count_only=False, fim=False):
         nt = C.c_int64(0)
         flags = ((N.JTK_ENCODE_ORDINARY if ordinary else 0) | (N.JTK_ENCODE_ALLOW_SPECIAL if allow_special else 0)
-                 | (N.JTK_ENCODE_VALIDATE_UTF8 if validate else 0) | (N.JTK_ENCODE_COUNT_ONLY if count_only else 0))
+                 | (N.JTK_ENCODE_VALIDATE_UTF8 if validate else 0) | (N.JTK_ENCODE_COUNT_ONLY if count_only else 0)
+                 | (N.JTK_ENCODE_FIM if fim else 0))
         _check(N.lib().jtk_batch_encode_device(self._h, d_text_ptr, d_doc_off_ptr, n_docs, n_bytes, flags, stream,
                                                C.byref(nt) if sync else None))
         return nt.value if sync else None
@@ -881,22 +932,53 @@ class HipEncoding:
     getName = get_name
 
     # ---- batch -----------------------------------------------------------------------------------------
-    def encode_batch(self, texts, ordinary=False, validate=False, allowed_special=None):
+    def fim_ids(self, fim, prefix_id=None, middle_id=None, suffix_id=None):
+        """(prefix_id, middle_id, suffix_id) of a FimParams: the arguments, else its own, else the encoding's <|fim_*|> ids
+        (ValueError when the encoding has none and none is given)."""
+        out = []
+        for given, own, lit in ((prefix_id, fim.prefix_id, "<|fim_prefix|>"), (middle_id, fim.middle_id, "<|fim_middle|>"),
+                                (suffix_id, fim.suffix_id, "<|fim_suffix|>")):
+            v = given if given is not None else own
+            if v is None:
+                if lit not in self._specials:
+                    raise ValueError("%s has no %s: give FimParams the three sentinel ids" % (self._name, lit))
+                v = self._specials[lit]
+            out.append(int(v))
+        return tuple(out)
+
+    def _fim(self, b, fim, ordinary, allowed_special=None):
+        """Sets the batch's FIM parameters for fim (not None); returns whether the encode takes the flag."""
+        if fim is None:
+            return False
+        if not ordinary:
+            raise ValueError("fim= needs ordinary=True: encode()'s special-token check would have to look across the cuts")
+        if allowed_special is not None:
+            raise ValueError("fim= does not combine with allowed_special=")
+        if self._host_pattern is not None:
+            raise ValueError("fim=: the device cannot run this encoding's custom split pattern")
+        b.set_fim(fim)
+        return True
+
+    def encode_batch(self, texts, ordinary=False, validate=False, allowed_special=None, fim=None):
         """List of str/bytes -> BatchResult (one jtk_batch_encode call).  allowed_special: None (the literals are refused by
         encode() and ordinary text to encodeOrdinary()), "all", or an iterable of literals that are encoded as their ids
-        (JTK_ENCODE_ALLOW_SPECIAL; the rule is in include/jtokkit_amd.h)."""
+        (JTK_ENCODE_ALLOW_SPECIAL; the rule is in include/jtokkit_amd.h).  fim: a FimParams -- the fill-in-the-middle
+        transformation of every document it draws (JTK_ENCODE_FIM; with ordinary=True); the result then also has .fim_kind,
+        .fim_cut and .fim_part_tok (Batch.fim_result)."""
         bs = [t if isinstance(t, (bytes, bytearray)) else t.encode("utf-8") for t in texts]
         doc_off = np.zeros(len(bs) + 1, dtype=np.int64)
         if bs:
             np.cumsum([len(b) for b in bs], out=doc_off[1:])
         text = np.frombuffer(b"".join(bs), dtype=np.uint8) if doc_off[-1] else np.zeros(0, dtype=np.uint8)
-        return self.encode_batch_packed(text, doc_off, ordinary, validate, allowed_special)
+        return self.encode_batch_packed(text, doc_off, ordinary, validate, allowed_special, fim=fim)
 
-    def encode_batch_packed(self, text_u8, doc_off, ordinary=False, validate=False, allowed_special=None, compact=False):
+    def encode_batch_packed(self, text_u8, doc_off, ordinary=False, validate=False, allowed_special=None, compact=False, fim=None):
         """compact: the ids cross the link as two planes (JTK_ENCODE_COMPACT_IDS) and come back as a CompactBatchResult that
         owns copies of them."""
         b = self._b()
-        if self._allow(b, allowed_special):
+        if self._fim(b, fim, ordinary, allowed_special):
+            b.encode_host(text_u8, doc_off, ordinary, validate, to_host=compact, compact=compact, fim=True)
+        elif self._allow(b, allowed_special):
             b.encode_host(text_u8, doc_off, ordinary, validate, allow_special=True, to_host=compact, compact=compact)
         elif self._host_pattern is not None:
             pb, pe = self._match_on_host(text_u8, doc_off)
@@ -905,8 +987,12 @@ class HipEncoding:
             b.encode_host(text_u8, doc_off, ordinary, validate, to_host=compact, compact=compact)
         if compact:
             r = b.host_result_compact()
-            return CompactBatchResult(r.lo.copy(), None if r.hi is None else r.hi.copy(), r.id_bits, r.tok_off.copy(), r.status.copy())
-        return b.fetch()
+            res = CompactBatchResult(r.lo.copy(), None if r.hi is None else r.hi.copy(), r.id_bits, r.tok_off.copy(), r.status.copy())
+        else:
+            res = b.fetch()
+        if fim is not None:
+            res.fim_kind, res.fim_cut, res.fim_part_tok = b.fim_result()
+        return res
 
     def _char_unit(self, unit, what):
         """JTK_UNIT_* of `unit`; None for bytes.  A custom split pattern has no positions in the text to convert."""
@@ -1289,7 +1375,7 @@ class HipEncoding:
 
     def pack_batch(self, texts, seq_len, sep=None, sep_first=False, whole_docs=False, drop_last=False, pad_id=-1, ordinary=False,
                    allowed_special=None, train_spans=None, span_rule="whole", label_shift=False, label_sep=False,
-                   ignore_index=-100, span_unit="byte"):
+                   ignore_index=-100, span_unit="byte", fim=None):
         """Every text encoded, then packed into rows of seq_len tokens (jtk_batch_pack; the rule is in jtk_pack_rules.h): a dict
         of numpy arrays rows, positions int32 [n_rows, seq_len], cu_seqlens int32 [n_segments + 1], seg_doc int64
         [n_segments], status int32 [n_docs] and max_seqlen (int).  sep: None, a token id or a special-token literal such as
@@ -1303,7 +1389,11 @@ class HipEncoding:
         last token) and on pad; label_shift: next-token targets within each segment -- and tok_span int32 [n_tokens], each
         token's range (numbered over the batch) or -1.  The rule is in jtk_label_rules.h.
         span_unit: "byte" (default), or "char" / "utf16": train_spans are ranges of the Python str / of a Java String, checked
-        against the texts' lengths in that unit and converted on the device (jtk_batch_byte_positions)."""
+        against the texts' lengths in that unit and converted on the device (jtk_batch_byte_positions).
+        fim: a FimParams for the encode (with ordinary=True; see encode_batch); the dict then also holds fim_kind, fim_cut and
+        fim_part_tok.  Together with train_spans it raises ValueError: a rearranged document has no positions in the text."""
+        if fim is not None and train_spans is not None:
+            raise ValueError("fim= and train_spans= do not combine: after the transformation tokens have no positions in the text")
         su = self._char_unit(span_unit, "pack_batch") if train_spans is not None else None
         bs = [t if isinstance(t, (bytes, bytearray)) else t.encode("utf-8") for t in texts]
         doc_off = np.zeros(len(bs) + 1, dtype=np.int64)
@@ -1317,11 +1407,13 @@ class HipEncoding:
                 begin, end = self._batch_spans(train_spans, doc_off)
             elif len(train_spans) != len(bs):
                 self._batch_spans(train_spans, doc_off)                     # (raises: one list per text)
-        res = self.encode_batch_packed(text, doc_off, ordinary, False, allowed_special)
+        res = self.encode_batch_packed(text, doc_off, ordinary, False, allowed_special, fim=fim)
         b = self._b()
         _, _, mx = b.pack(seq_len, sep_id, whole_docs, sep_first, drop_last)
         f = b.pack_fetch(pad_id)
         f["status"] = res.status.copy()
+        if fim is not None:
+            f["fim_kind"], f["fim_cut"], f["fim_part_tok"] = res.fim_kind, res.fim_cut, res.fim_part_tok
         f["max_seqlen"] = mx
         if train_spans is not None:
             bufs = []
@@ -1364,7 +1456,7 @@ class HipEncoding:
 
     def pack_batch_device(self, text, doc_off, seq_len, sep=None, sep_first=False, whole_docs=False, drop_last=False, pad_id=-1,
                           ordinary=False, allowed_special=None, span_begin=None, span_end=None, span_rule="whole",
-                          label_shift=False, label_sep=False, ignore_index=-100):
+                          label_shift=False, label_sep=False, ignore_index=-100, fim=None):
         """pack_batch for a device-resident batch.  text: CUDA torch.uint8 tensor, doc_off: CUDA torch.int64 tensor [n_docs + 1],
         on this encoding's device.  Returns a dict of CUDA tensors written on torch.cuda.current_stream(): rows int32
         [n_rows, seq_len], positions int32 [n_rows, seq_len], cu_seqlens int32 [n_segments + 1], seg_doc int64 [n_segments],
@@ -1373,11 +1465,15 @@ class HipEncoding:
         span_begin / span_end: CUDA torch.int64 tensors of equal length, byte ranges [begin, end) in positions of `text`, sorted
         and disjoint (not checked: ranges out of order give unspecified labels).  The dict then also holds labels int32
         [n_rows, seq_len] and tok_span int32 [n_tokens], as pack_batch describes them, written on the same stream; the token
-        count costs one more wait."""
+        count costs one more wait.
+        fim: a FimParams for the encode (with ordinary=True; not with spans: ValueError); the dict then also holds fim_kind uint8
+        [n_docs], fim_cut int64 [n_docs, 2] and fim_part_tok int64 [n_docs, 3], written on the same stream."""
         import torch
         self._check_device_inputs("pack_batch_device", text, doc_off)
         if (span_begin is None) != (span_end is None):
             raise ValueError("span_begin and span_end go together")
+        if fim is not None and span_begin is not None:
+            raise ValueError("fim= and spans do not combine: after the transformation tokens have no positions in the text")
         if span_begin is not None:
             self._check_device_spans(text, span_begin, span_end)
             rule = _span_rule(span_rule)
@@ -1387,6 +1483,7 @@ class HipEncoding:
         if whole_docs and drop_last:
             raise ValueError("drop_last applies to the concatenated stream only")
         sep_id = self._sep_id(sep)
+        use_fim = self._fim(self._b(), fim, ordinary, allowed_special)
         allow = self._allow(self._b(), allowed_special)
         nd = doc_off.numel() - 1
         if nd < 0:
@@ -1407,7 +1504,7 @@ class HipEncoding:
             side = torch.cuda.ExternalStream(b.stream(), device=device)
             side.wait_stream(cur)
         stream = (side or cur).cuda_stream
-        b.encode_device(text.data_ptr(), doc_off.data_ptr(), nd, n, ordinary, stream=stream, sync=False, allow_special=allow)
+        b.encode_device(text.data_ptr(), doc_off.data_ptr(), nd, n, ordinary, stream=stream, sync=False, allow_special=allow, fim=use_fim)
         nr, ns, mx = b.pack(L, sep_id, whole_docs, sep_first, drop_last, stream)
         out = dict(rows=torch.empty((nr, L), dtype=torch.int32, device=device),
                    positions=torch.empty((nr, L), dtype=torch.int32, device=device),
@@ -1418,6 +1515,13 @@ class HipEncoding:
                      out["seg_doc"].data_ptr(), stream)
         if nd:
             _copy_d2d(out["status"].data_ptr(), b.device_result()[2], nd * 4, stream)
+        if use_fim:
+            out["fim_kind"] = torch.empty(nd, dtype=torch.uint8, device=device)
+            out["fim_cut"] = torch.empty((nd, 2), dtype=torch.int64, device=device)
+            out["fim_part_tok"] = torch.empty((nd, 3), dtype=torch.int64, device=device)
+            if nd:
+                for t, src in zip((out["fim_kind"], out["fim_cut"], out["fim_part_tok"]), b.fim_device_result()):
+                    _copy_d2d(t.data_ptr(), src, t.numel() * t.element_size(), stream)
         if span_begin is not None:
             nt = b.result()[0]
             out["tok_span"] = torch.empty(nt, dtype=torch.int32, device=device)
