@@ -35,6 +35,12 @@ int64_t sim_maxtok_decide(const uint8_t* text, int64_t len, int64_t p, const uin
     return r.keep;
 }
 
+// The last safe piece start of a prefix of p bytes whose bits begin at `base` of `mask` (the host passes a document's offset in
+// its group's gather buffer, the device its offset from the chunk's origin): t = the prefix.
+int64_t sim_maxtok_last_safe_start(const uint64_t* mask, int64_t base, const uint8_t* t, int64_t p) {
+    return jtk_maxtok_last_safe_start(mask, base, t, p);
+}
+
 // The prefix sizes of the rounds: out[r] for r < n_rounds (cb: the chunk size past which a document goes whole).
 void sim_maxtok_prefixes(int64_t len, int64_t max_tokens, int64_t cb, int n_rounds, int64_t* out) {
     int64_t P = jtk_maxtok_first_prefix(max_tokens);

@@ -2,7 +2,10 @@
 (device) share -- jtokkit_amd/csrc/jtk_maxtok_rules.h: the last safe piece start, the decision, the back-off -- run on the
 CPU through the shim tests/maxtok_sim, fed with piece starts from the split-rule shim (libjtk_hostsim.so, sim_split) and
 token lists from the oracle.  Whenever the rules decide on a prefix, the result equals the oracle's encode(text, max) of
-the whole text."""
+the whole text.  The case tier beside it, tests/test_maxtok_cases_cpu.py, runs the header's last safe start at a nonzero
+`base` with the neighbours' bits in the mask, against the plain model tests/maxtok_ref.py on the batches of
+tests/maxtok_cases.py, and asserts that those batches reach the kernels' edges; tests/test_maxtok_edges_gpu.py runs them
+on the device."""
 import ctypes as C
 import os
 import random
