@@ -247,7 +247,9 @@ int jtk_batch_encode_device(jtk_batch* b, const uint8_t* d_utf8, const int64_t* 
  *                is its literal, as the decode table holds it); jtk_batch_truncate returns JTK_ERR_INVALID_ARGUMENT after it.
  *   Waits:       once for the number of literal candidates in the batch, plus the chunk plan's wait of a text larger than
  *                JTK_OPT_CHUNK_BYTES (JTK_OPT_HOST_CHUNK_BYTES for host input) as without the flag -- at most two before the
- *                work is queued; a batch without a match then runs exactly the call without the flag.  Host input is
+ *                work is queued; a batch without a match then runs exactly the call without the flag (unless it holds a
+ *                literal outside the allowed set under encode(), or JTK_ENCODE_VALIDATE_UTF8 is set: offenders have no
+ *                tokens, so the whole path runs).  Host input is
  *                copied down whole before the candidates are found (no overlap of the copy with the kernels), and with
  *                JTK_ENCODE_TO_HOST the result goes to the pinned buffers in one copy behind the last chunk (one more wait,
  *                for its size) instead of chunk by chunk.  JTK_OPT_REUSE_CHUNK_PLAN does not apply to these calls. */

@@ -188,7 +188,7 @@ struct jtk_batch {
     bool sp_dirty = true;
     DevBuf sp_lits;                  // ids [n] (int32) | allowed [n]
     DevBuf sp_find, sp_cand, sp_out;
-    int64_t* h_sp = nullptr; size_t h_sp_cap = 0;   // pinned: (candidates, bad offsets) read once per call
+    int64_t* h_sp = nullptr; size_t h_sp_cap = 0;   // pinned: (candidates, bad offsets, refusals) read once per call
     // JTK_ENCODE_FIM (jtk_fim.hip): the parameters (jtk_batch_set_fim) and, alive with the encode's result, hdr | the stitched
     // status | sub_off | cut | part_tok | kind; the stitched tokens and offsets share sp_out with allow-special
     jtk_fim_params fim{};
@@ -1137,7 +1137,7 @@ int run_allow_special(jtk_batch* b, const uint8_t* d_text, const int64_t* d_doc_
     w.n_blk = (n_bytes + JTK_SPECIAL_BLOCK - 1) / JTK_SPECIAL_BLOCK;
     const size_t status_bytes = align_up((size_t)(n_docs > 0 ? n_docs : 1) * 4, 16);
     if ((rc = b->sp_find.ensure(32 + status_bytes + ((size_t)w.n_blk + 1) * 8)) ||
-        (rc = ensure_pinned((void**)&b->h_sp, &b->h_sp_cap, 16, 0)))
+        (rc = ensure_pinned((void**)&b->h_sp, &b->h_sp_cap, 32, 0)))
         return rc;
     uint8_t* z = (uint8_t*)b->sp_find.p;
     w.hdr = (int64_t*)z;
@@ -1146,7 +1146,7 @@ int run_allow_special(jtk_batch* b, const uint8_t* d_text, const int64_t* d_doc_
     HIP_TRY(hipMemsetAsync(z, 0, 32 + status_bytes, s));
     jtk_launch_special_find(w, s);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(b->h_sp, w.hdr, 16, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(b->h_sp, w.hdr, 24, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
     w.n_cand = b->h_sp[0];
     const int64_t save_cb = b->chunk_bytes;
@@ -1156,7 +1156,10 @@ int run_allow_special(jtk_batch* b, const uint8_t* d_text, const int64_t* d_doc_
         b->chunk_bytes = save_cb;
         return r;
     };
-    if (b->h_sp[1] != 0 || w.n_cand == 0) {
+    // a document that ends with a negative status has no tokens, which only the stitch sees to: without a candidate it still
+    // runs where the find pass has refused a document, and under validation, whose offenders are known only behind the pipeline
+    const bool may_refuse = (b->h_sp[2] != 0 || (flags & JTK_ENCODE_VALIDATE_UTF8)) && n_docs > 0 && n_bytes > 0;
+    if (b->h_sp[1] != 0 || (w.n_cand == 0 && !may_refuse)) {
         // no allowed literal in any document (or bad offsets, which today's call reports as it always does)
         if ((rc = plan(d_doc_off, n_docs)) || (rc = run_job(b, d_text, nullptr, d_doc_off, n_docs, n_bytes, base_flags, s, to_host))) return rc;
         b->job_flags |= JTK_ENCODE_ALLOW_SPECIAL;

@@ -433,7 +433,8 @@ struct JtkSpecialWork {
     int64_t maxlen;             // longest allowed literal
     uint32_t check_dis;         // encode(): a literal outside the allowed set anywhere in a document -> JTK_ERR_UNSUPPORTED_SPECIAL
     uint32_t first[8];          // bit b: a literal the find pass looks for starts with byte b
-    int64_t* hdr;               // [0] candidates, [1] offsets are bad (not non-decreasing within [0, n_bytes], doc_off[0] != 0)
+    int64_t* hdr;               // [0] candidates, [1] offsets are bad (not non-decreasing within [0, n_bytes], doc_off[0] != 0),
+                                // [2] the find pass has refused a document (a literal outside the allowed set, under encode())
     int64_t* blk;               // [n_blk + 1] candidates per block of JTK_SPECIAL_BLOCK text bytes, then their exclusive scan
     int64_t n_blk;
     int64_t n_cand;             // candidates, in position order:

@@ -90,7 +90,10 @@ __global__ void __launch_bounds__(FT) k_sp_find(JtkSpecialWork w) {
             int len, lit;
             int64_t d;
             const bool dis = sp_at(w, p0 + j, &len, &lit, &d);
-            if (!WRITE && dis) atomicMin(&w.status[d], -2 /* JTK_ERR_UNSUPPORTED_SPECIAL */);
+            if (!WRITE && dis) {
+                atomicMin(&w.status[d], -2 /* JTK_ERR_UNSUPPORTED_SPECIAL */);
+                atomicMax((unsigned long long*)&w.hdr[2], 1ull);
+            }
             if (len > 0) {
                 if (first_j < 0) { first_j = j; first_len = len; first_lit = lit; first_doc = d; }
                 found |= 1u << j;
