@@ -213,6 +213,41 @@ int jtk_batch_host_result_compact(jtk_batch* b, const uint16_t** lo, const uint3
 int jtk_batch_compact(jtk_batch* b, uint16_t* d_lo, uint32_t* d_hi, void* stream_or_null);
 int jtk_widen_ids(const uint16_t* lo, const uint32_t* hi, int id_bits, int64_t first, int64_t n, int32_t* out_int32);
 
+/* MinHash signatures and LSH band keys over the token n-grams of the last batch encode, for near-duplicate detection
+ * (jtk_minhash.hip; the rule, bit for bit, is csrc/jtk_minhash_rules.h -- integer arithmetic only, so every result is exact).
+ *   With G = 0x9E3779B97F4A7C15, mix = the splitmix64 finaliser (as for jtk_fim_params), key = mix(seed + G * (ngram + 1)) and
+ *   draw(j) = mix(key + j), all modulo 2^64: a document of l tokens (l = 0 when its status < 0) has the shingles t[i .. i + m),
+ *   m = min(ngram, l), 0 <= i <= l - m (none when l == 0; a document shorter than ngram is one shingle); H = H * G + id + 1
+ *   over a shingle's ids (as uint32: special ids, FIM sentinels and pseudo ids count), x = the low 32 bits of mix(H ^ key);
+ *   sig[d][k] = min over the shingles of ((a_k * x + b_k) mod 2^64) >> 32 with a_k = draw(2k + 1) | 1, b_k = draw(2k + 2), and
+ *   0xFFFFFFFF without shingles; band_key[d][j] = h after h = draw(2^32 + j) and h = mix(h ^ v) for the r = num_hashes / bands
+ *   words v of band j in order.  The number of k on which two rows agree, over num_hashes, estimates the Jaccard similarity
+ *   of the two shingle sets.
+ *   A signature depends on (seed, ngram, num_hashes, the document's ids) alone -- not on the batch, the document's index or
+ *   the device --, so the shards of a corpus agree by construction and their rows can be gathered into one array.
+ * jtk_batch_minhash: works on the LAST batch encode on `b` (host or device input, any flags but JTK_ENCODE_COUNT_ONLY:
+ *   JTK_ERR_INVALID_ARGUMENT then, and with no result).  ngram 1..32, num_hashes 1..256, bands 0 (no keys) or a divisor of
+ *   num_hashes, flags 0: anything else is JTK_ERR_INVALID_ARGUMENT.  Caller-owned device buffers: d_sig[n_docs * num_hashes]
+ *   uint32, d_n_shingles[n_docs] int32 (may be NULL), d_band_keys[n_docs * bands] uint64 (may be NULL, also with bands > 0:
+ *   keys are then not computed).  Waits once, for the token count (as jtk_batch_compact); the pass is then queued behind the
+ *   encode on stream_or_null, or on the batch's stream when it is NULL, and the call does not wait for it.  It reads the ids,
+ *   tok_off and status only and keeps no state in the batch: chunk, pack, truncate and FIM results are untouched.
+ * jtk_batch_minhash_agree: d_agree[p] = the number of k < num_hashes with d_sig[d_pair_a[p]][k] == d_sig[d_pair_b[p]][k] for
+ *   rows of d_sig[n_sig * num_hashes] -- which may hold signatures gathered from many batches; `b` gives the device and the
+ *   default stream only, no encode is needed --, or -1 where an index is outside [0, n_sig): no row is read for such a pair.
+ *   Queued, does not wait. */
+typedef struct jtk_minhash_params {
+    uint64_t seed;
+    int32_t ngram;          /* n: 1..32 */
+    int32_t num_hashes;     /* K: 1..256 */
+    int32_t bands;          /* 0 = no band keys; otherwise divides num_hashes */
+    uint32_t flags;         /* 0 */
+} jtk_minhash_params;
+int jtk_batch_minhash(jtk_batch* b, const jtk_minhash_params* params, uint32_t* d_sig, int32_t* d_n_shingles_or_null,
+                      uint64_t* d_band_keys_or_null, void* stream_or_null);
+int jtk_batch_minhash_agree(jtk_batch* b, const uint32_t* d_sig, int64_t n_sig, int32_t num_hashes, const int64_t* d_pair_a,
+                            const int64_t* d_pair_b, int64_t n_pairs, int32_t* d_agree, void* stream_or_null);
+
 /* Device buffers already resident in HBM (what bench.py times).  `stream_or_null` = a hipStream_t
  * to order against, or NULL for the batch's own stream: the whole encode is ordered like one operation on that stream
  * (inside, the chunks of a large batch run on the batch's own streams, forked from and joined into it).  With

@@ -77,6 +77,11 @@ class FimParamsStruct(C.Structure):
                 ("prefix_id", C.c_int32), ("middle_id", C.c_int32), ("suffix_id", C.c_int32)]
 
 
+class MinhashParamsStruct(C.Structure):
+    """jtk_minhash_params"""
+    _fields_ = [("seed", C.c_uint64), ("ngram", C.c_int32), ("num_hashes", C.c_int32), ("bands", C.c_int32), ("flags", C.c_uint32)]
+
+
 # every symbol include/jtokkit_amd.h declares: (restype, argtypes)
 _p = C.c_void_p
 _i64 = C.c_int64
@@ -100,6 +105,8 @@ SIGNATURES = {
     "jtk_batch_host_result": (C.c_int, [_p, C.POINTER(_p), C.POINTER(_p), C.POINTER(_p)]),
     "jtk_batch_host_result_compact": (C.c_int, [_p, C.POINTER(_p), C.POINTER(_p), C.POINTER(C.c_int), C.POINTER(_p), C.POINTER(_p)]),
     "jtk_batch_compact": (C.c_int, [_p, _p, _p, _p]),
+    "jtk_batch_minhash": (C.c_int, [_p, C.POINTER(MinhashParamsStruct), _p, _p, _p, _p]),
+    "jtk_batch_minhash_agree": (C.c_int, [_p, _p, _i64, C.c_int32, _p, _p, _i64, _p, _p]),
     "jtk_widen_ids": (C.c_int, [_p, _p, C.c_int, _i64, _i64, _p]),
     "jtk_batch_encode": (C.c_int, [_p, _p, _p, _i64, C.c_uint32, C.POINTER(_i64)]),
     "jtk_batch_encode_pieces": (C.c_int, [_p, _p, _p, _i64, _p, _p, _i64, C.c_uint32, C.POINTER(_i64)]),

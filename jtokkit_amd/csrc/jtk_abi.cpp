@@ -2215,6 +2215,45 @@ int jtk_batch_compact(jtk_batch* b, uint16_t* d_lo, uint32_t* d_hi, void* stream
     return JTK_OK;
 }
 
+// ---- MinHash signatures of the last encode (jtk_minhash.hip) -------------------------------------------------------------
+int jtk_batch_minhash(jtk_batch* b, const jtk_minhash_params* p, uint32_t* d_sig, int32_t* d_n_shingles, uint64_t* d_band_keys,
+                      void* stream_or_null) {
+    int rc;
+    if ((rc = need_encode(b, NEED_IDS))) return rc;
+    if (!p) return fail(JTK_ERR_INVALID_ARGUMENT, "params is NULL");
+    if (!jtk_mh_params_ok(p->ngram, p->num_hashes, p->bands, p->flags))
+        return fail(JTK_ERR_INVALID_ARGUMENT, "minhash: ngram 1..32, num_hashes 1..256, bands 0 or a divisor of num_hashes, flags 0");
+    if (((uintptr_t)d_sig & 3u) || ((uintptr_t)d_n_shingles & 3u) || ((uintptr_t)d_band_keys & 7u))
+        return fail(JTK_ERR_INVALID_ARGUMENT, "unaligned array (4-byte sig and n_shingles, 8-byte band keys)");
+    HIP_TRY(hipSetDevice(b->enc->device));
+    int64_t nt = 0;
+    if ((rc = jtk_batch_result(b, &nt, nullptr, nullptr))) return rc;
+    if (b->job_docs > 0 && !d_sig) return fail(JTK_ERR_INVALID_ARGUMENT, "d_sig is NULL");
+    hipStream_t s = pick_stream(b, stream_or_null);
+    if ((rc = ck_order(b, b->last_stream, s))) return rc;
+    JtkMhView v;
+    v.tokens = (const int32_t*)b->tokens.p; v.tok_off = (const int64_t*)b->tok_off.p; v.status = (const int32_t*)b->status.p;
+    v.n_docs = b->job_docs; v.total = nt; v.ngram = p->ngram;
+    jtk_launch_minhash(v, p->seed, p->num_hashes, p->bands, d_sig, d_n_shingles, d_band_keys, s);
+    HIP_TRY(hipGetLastError());
+    return JTK_OK;
+}
+
+int jtk_batch_minhash_agree(jtk_batch* b, const uint32_t* d_sig, int64_t n_sig, int32_t num_hashes, const int64_t* d_pair_a,
+                            const int64_t* d_pair_b, int64_t n_pairs, int32_t* d_agree, void* stream_or_null) {
+    if (!b) return fail(JTK_ERR_INVALID_ARGUMENT, "batch is NULL");
+    if (num_hashes < 1 || num_hashes > JTK_MH_MAX_HASHES) return fail(JTK_ERR_INVALID_ARGUMENT, "num_hashes must be in 1..256");
+    if (n_sig < 0 || n_pairs < 0) return fail(JTK_ERR_INVALID_ARGUMENT, "n_sig and n_pairs must not be negative");
+    if (n_pairs > 0 && (!d_pair_a || !d_pair_b || !d_agree || (n_sig > 0 && !d_sig)))
+        return fail(JTK_ERR_INVALID_ARGUMENT, "d_sig, d_pair_a, d_pair_b or d_agree is NULL");
+    if (((uintptr_t)d_sig & 3u) || ((uintptr_t)d_pair_a & 7u) || ((uintptr_t)d_pair_b & 7u) || ((uintptr_t)d_agree & 3u))
+        return fail(JTK_ERR_INVALID_ARGUMENT, "unaligned array (4-byte sig and agree, 8-byte int64 pairs)");
+    HIP_TRY(hipSetDevice(b->enc->device));
+    jtk_launch_minhash_agree(d_sig, n_sig, num_hashes, d_pair_a, d_pair_b, n_pairs, d_agree, pick_stream(b, stream_or_null));
+    HIP_TRY(hipGetLastError());
+    return JTK_OK;
+}
+
 int jtk_batch_token_offsets(jtk_batch* b, int64_t* d_byte_pos, void* stream_or_null) {
     int rc;
     if ((rc = need_encode(b, NEED_IDS | NEED_TEXT_ORDER))) return rc;

@@ -14,6 +14,7 @@
 #include "jtk_utf16_rules.h"
 #include "jtk_stop_rules.h"
 #include "jtk_fim_rules.h"
+#include "jtk_minhash_rules.h"
 
 #define JTK_SPLIT_TILE 4096      // bytes per pretok_split workgroup
 #define JTK_SPLIT_HALO 64
@@ -415,6 +416,13 @@ void jtk_launch_stop_find(const JtkStopWork& w, hipStream_t s);      // find (wi
 // at min(t1, *d_total).  hi may be NULL when hb == 0.
 void jtk_launch_compact(const int32_t* ids, int64_t t0, int64_t t1, const int64_t* d_total, uint16_t* lo, uint32_t* hi,
                         int64_t origin, int hb, hipStream_t s);
+// MinHash (jtk_minhash.hip; the rule is jtk_minhash_rules.h).  sig[n_docs * num_hashes], n_shingles[n_docs] (may be NULL) and
+// band_keys[n_docs * bands] (may be NULL: no keys) of the documents of v; three kernels at most, in order on s.
+void jtk_launch_minhash(const JtkMhView& v, uint64_t seed, int32_t num_hashes, int32_t bands, uint32_t* sig, int32_t* n_shingles,
+                        uint64_t* band_keys, hipStream_t s);
+// agree[p] = the words on which rows pair_a[p] and pair_b[p] of sig[n_sig * num_hashes] agree; -1 for an index outside [0, n_sig)
+void jtk_launch_minhash_agree(const uint32_t* sig, int64_t n_sig, int32_t num_hashes, const int64_t* pair_a, const int64_t* pair_b,
+                              int64_t n_pairs, int32_t* agree, hipStream_t s);
 // Device-side state of an allow-special encode (jtk_special.hip, JTK_ENCODE_ALLOW_SPECIAL; the rule is jtk_special_rules.h).
 // Candidates (per position, the longest allowed literal there) are found in position order, resolved to the kept matches, and
 // the batch is cut into sub-documents that partition the text: per document a segment, then per candidate i two slots

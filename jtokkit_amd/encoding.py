@@ -409,6 +409,20 @@ class Batch:
         at d_hi_ptr (None when id_bits == 16), device pointers; waits for the token count, not for the pass."""
         _check(N.lib().jtk_batch_compact(self._h, d_lo_ptr, d_hi_ptr, stream))
 
+    def minhash(self, d_sig_ptr, ngram=5, num_hashes=128, bands=0, seed=0, d_n_shingles_ptr=None, d_band_keys_ptr=None, stream=None):
+        """jtk_batch_minhash on the last encode: uint32 [n_docs * num_hashes] at d_sig_ptr, int32 [n_docs] at d_n_shingles_ptr
+        (or None), uint64 [n_docs * bands] at d_band_keys_ptr (or None: no keys), device pointers; waits for the token count, not
+        for the pass."""
+        p = N.MinhashParamsStruct(seed & 0xFFFFFFFFFFFFFFFF, ngram, num_hashes, bands, 0)
+        _check(N.lib().jtk_batch_minhash(self._h, C.byref(p), d_sig_ptr, d_n_shingles_ptr, d_band_keys_ptr, stream))
+
+    def minhash_agree(self, d_sig_ptr, n_sig, num_hashes, d_pair_a_ptr, d_pair_b_ptr, n_pairs, d_agree_ptr, stream=None):
+        """jtk_batch_minhash_agree: int32 [n_pairs] at d_agree_ptr, per pair (int64 indices at d_pair_a_ptr, d_pair_b_ptr) the
+        words on which the two rows of uint32 [n_sig * num_hashes] at d_sig_ptr agree, -1 for an index outside [0, n_sig).
+        Needs no encode on the batch; does not wait."""
+        _check(N.lib().jtk_batch_minhash_agree(self._h, d_sig_ptr, n_sig, num_hashes, d_pair_a_ptr, d_pair_b_ptr, n_pairs,
+                                               d_agree_ptr, stream))
+
     def encode_device(self, d_text_ptr, d_doc_off_ptr, n_docs, n_bytes, ordinary=False, stream=None, sync=True,
                       allow_special=False, validate=False, count_only=False, fim=False):
         nt = C.c_int64(0)
@@ -1088,6 +1102,142 @@ class HipEncoding:
         if side is not None:
             cur.wait_stream(side)
         return lo, hi, tok_off, status
+
+    def minhash_batch(self, texts, ngram=5, num_hashes=128, bands=0, seed=0, ordinary=True, allowed_special=None):
+        """MinHash signatures of a list of str/bytes over their token n-grams (jtk_batch_minhash; the rule is in
+        include/jtokkit_amd.h): (sig uint32 [n, num_hashes], n_shingles int32 [n], band_keys uint64 [n, bands] or None when
+        bands == 0).  The fraction of columns on which two rows agree estimates the Jaccard similarity of the two documents'
+        n-gram sets; a refused document (status < 0) has no shingles and a row of 0xFFFFFFFF."""
+        bs = [t if isinstance(t, (bytes, bytearray)) else t.encode("utf-8") for t in texts]
+        doc_off = np.zeros(len(bs) + 1, dtype=np.int64)
+        if bs:
+            np.cumsum([len(b) for b in bs], out=doc_off[1:])
+        text = np.frombuffer(b"".join(bs), dtype=np.uint8) if doc_off[-1] else np.zeros(0, dtype=np.uint8)
+        self.encode_batch_packed(text, doc_off, ordinary, False, allowed_special)
+        n = len(bs)
+        b = self._b()
+        bufs = []
+        try:
+            bufs.append(_DeviceArray(np.zeros((n, num_hashes), dtype=np.uint32)))
+            bufs.append(_DeviceArray(np.zeros(n, dtype=np.int32)))
+            if bands:
+                bufs.append(_DeviceArray(np.zeros((n, bands), dtype=np.uint64)))
+            b.minhash(bufs[0].ptr, ngram, num_hashes, bands, seed, bufs[1].ptr, bufs[2].ptr if bands else None)
+            _stream_sync(b.stream())
+            return bufs[0].fetch(), bufs[1].fetch(), bufs[2].fetch() if bands else None
+        finally:
+            for x in bufs:
+                x.free()
+
+    def minhash_batch_device(self, text, doc_off, ngram=5, num_hashes=128, bands=0, seed=0, ordinary=True, allowed_special=None):
+        """Encodes a device-resident batch (text CUDA torch.uint8, doc_off CUDA torch.int64 [n_docs + 1]) and returns its MinHash
+        signatures as CUDA tensors written on torch.cuda.current_stream(): (sig int32 [n_docs, num_hashes] -- the bit patterns of
+        the uint32 minima --, n_shingles int32 [n_docs], band_keys int64 [n_docs, bands] -- bit patterns of the uint64 keys -- or
+        None when bands == 0, tok_off int64 [n_docs + 1], status int32 [n_docs]).  The ids stay in the batch (device_result).
+        Waits once, for the token count (and, with allowed_special, once more for the encode's count of literal candidates)."""
+        import torch
+        self._check_device_inputs("minhash_batch_device", text, doc_off)
+        allow = self._allow(self._b(), allowed_special)
+        nd = doc_off.numel() - 1
+        if nd < 0:
+            raise ValueError("doc_off needs n_docs + 1 entries")
+        device = text.device
+        n = text.numel()
+        st = text.untyped_storage()
+        if text.data_ptr() % 16 or st.data_ptr() + st.nbytes() < text.data_ptr() + (n + 15) // 16 * 16:
+            # (the encode reads whole aligned 16-byte blocks)
+            buf = torch.zeros((n + 15) // 16 * 16 + 16, dtype=torch.uint8, device=device)
+            buf[:n].copy_(text)
+            text = buf
+        b = self._b()
+        cur = torch.cuda.current_stream(device)
+        side = None
+        if cur.cuda_stream == 0:
+            # (the legacy default stream: see chunk_batch_device)
+            side = torch.cuda.ExternalStream(b.stream(), device=device)
+            side.wait_stream(cur)
+        stream = (side or cur).cuda_stream
+        b.encode_device(text.data_ptr(), doc_off.data_ptr(), nd, n, ordinary, stream=stream, sync=False, allow_special=allow)
+        sig = torch.empty((nd, num_hashes), dtype=torch.int32, device=device)
+        n_shingles = torch.empty(nd, dtype=torch.int32, device=device)
+        band_keys = torch.empty((nd, bands), dtype=torch.int64, device=device) if bands else None
+        b.minhash(sig.data_ptr() if nd else None, ngram, num_hashes, bands, seed, n_shingles.data_ptr() if nd else None,
+                  band_keys.data_ptr() if bands and nd else None, stream)
+        tok_off = torch.empty(nd + 1, dtype=torch.int64, device=device)
+        status = torch.empty(nd, dtype=torch.int32, device=device)
+        _, p_off, p_status = b.device_result()
+        for t, src in ((tok_off, p_off), (status, p_status)):
+            if t.numel():
+                _copy_d2d(t.data_ptr(), src, t.numel() * t.element_size(), stream)
+        if side is not None:
+            cur.wait_stream(side)
+        return sig, n_shingles, band_keys, tok_off, status
+
+    def near_duplicates(self, texts, threshold=0.8, ngram=5, num_hashes=128, bands=16, seed=0, ordinary=True, allowed_special=None):
+        """Clusters of near-duplicate documents by MinHash and LSH: int64 [n] labels, the smallest document index of each
+        document's cluster.  Per band the documents that have shingles are stable-sorted by band key on the device and every
+        two consecutive ones with equal keys are a candidate pair; the pairs of all bands, made unique, are verified by
+        signature agreement (minhash_agree) and those with agree >= ceil(threshold * num_hashes) are joined (union-find on the
+        host).  A document without shingles (empty or refused) is its own cluster.  Deterministic: the same texts and
+        parameters give the same labels on every device."""
+        import math
+        import torch
+        if bands < 1:
+            raise ValueError("near_duplicates needs bands >= 1")
+        bs = [t if isinstance(t, (bytes, bytearray)) else t.encode("utf-8") for t in texts]
+        n = len(bs)
+        labels = np.arange(n, dtype=np.int64)
+        if n < 2:
+            return labels
+        device = torch.device("cuda", N.lib().jtk_encoding_device(self._h))
+        lens = np.array([len(x) for x in bs], dtype=np.int64)
+        doc_off = torch.from_numpy(np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)).to(device)
+        blob = b"".join(bs)
+        if not blob:
+            return labels
+        text = torch.from_numpy(np.frombuffer(blob, dtype=np.uint8).copy()).to(device)
+        sig, n_shingles, band_keys, _, _ = self.minhash_batch_device(text, doc_off, ngram, num_hashes, bands, seed, ordinary, allowed_special)
+        live = torch.nonzero(n_shingles > 0).flatten()
+        if live.numel() < 2:
+            return labels
+        codes = []
+        for j in range(bands):
+            keys, order = torch.sort(band_keys[live, j], stable=True)
+            docs = live[order]
+            eq = keys[1:] == keys[:-1]
+            codes.append(docs[:-1][eq] * n + docs[1:][eq])
+        codes = torch.unique(torch.cat(codes))
+        if codes.numel() == 0:
+            return labels
+        pa = torch.div(codes, n, rounding_mode="floor").contiguous()
+        pb = (codes - pa * n).contiguous()
+        agree = torch.empty(codes.numel(), dtype=torch.int32, device=device)
+        b = self._b()
+        cur = torch.cuda.current_stream(device)
+        side = None
+        if cur.cuda_stream == 0:
+            side = torch.cuda.ExternalStream(b.stream(), device=device)
+            side.wait_stream(cur)
+        b.minhash_agree(sig.data_ptr(), n, num_hashes, pa.data_ptr(), pb.data_ptr(), codes.numel(), agree.data_ptr(), (side or cur).cuda_stream)
+        if side is not None:
+            cur.wait_stream(side)
+        keep = agree >= int(math.ceil(threshold * num_hashes))
+        pa, pb = pa[keep].cpu().numpy(), pb[keep].cpu().numpy()
+        parent = list(range(n))
+
+        def find(x):
+            while parent[x] != x:
+                parent[x] = parent[parent[x]]
+                x = parent[x]
+            return x
+
+        for a, c in zip(pa.tolist(), pb.tolist()):
+            ra, rc = find(a), find(c)
+            if ra != rc:
+                parent[max(ra, rc)] = min(ra, rc)        # (the root is the component's smallest index)
+        for d in range(n):
+            labels[d] = find(d)
+        return labels
 
     def special_ids(self, allowed_special):
         """"all" or an iterable of special-token literals -> their ids (ValueError for a literal that is no special token)."""
