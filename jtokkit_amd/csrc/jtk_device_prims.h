@@ -65,6 +65,19 @@ __device__ __forceinline__ uint64_t jtk_wave_incl_scan(uint64_t v) {
     return v;
 }
 
+// ---- inclusive prefix sum over lanes 0..31 of the wave, for values that only those lanes hold (what lanes 32..63 return is
+// not a prefix of anything).  In registers: four shifts inside each row of 16 lanes (a lane without a source adds 0), then
+// lane 15's sum into row 1 -- no LDS round trip, where the 64-lane scan above makes six.  Called by all 64 lanes.
+__device__ __forceinline__ uint32_t jtk_wave_incl_scan32(uint32_t v) {
+    constexpr int ROW_SHR = 0x110, ROW_BCAST15 = 0x142;
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ROW_SHR + 1, 0xF, 0xF, true);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ROW_SHR + 2, 0xF, 0xF, true);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ROW_SHR + 4, 0xF, 0xF, true);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ROW_SHR + 8, 0xF, 0xF, true);
+    v += (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, ROW_BCAST15, 0xA, 0xF, false);   // rows 1 and 3 only
+    return v;
+}
+
 // ---- sum over the wave; every lane ends with it
 __device__ __forceinline__ uint32_t jtk_wave_sum(uint32_t v) {
 #pragma unroll

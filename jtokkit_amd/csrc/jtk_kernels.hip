@@ -380,7 +380,7 @@ __global__ void __launch_bounds__(SPLIT_THREADS) __attribute__((amdgpu_waves_per
 // ---------------------------------------------------------------------------------------------------
 constexpr int T = JTK_TILE;
 constexpr int TW = T / 64;                                          // mask words per tile
-static_assert(TW <= 64, "tile scans assume at most 64 mask words");
+static_assert(TW <= 32, "the word counts are scanned by jtk_wave_incl_scan32");
 static_assert((T & (T - 1)) == 0, "piece_resolve wraps positions into the tile with a mask");
 
 // this tile's queued pieces by bin, in LDS until its slices of the queues are claimed
@@ -398,12 +398,13 @@ constexpr int Q_TOTAL = q_off(JTK_BIN_TINY) + JTK_TINY_CAP;
 #endif
 constexpr int RES_WAVES = JTK_RES_WAVES, RES_THREADS = 64 * RES_WAVES;   // waves per tile
 static_assert(RES_THREADS >= (T + 16) / 16 && RES_THREADS > 64, "the prologue's lane roles");
+static_assert(TW % RES_WAVES == 0, "every wave takes TW / RES_WAVES mask words");
 
 __global__ void __launch_bounds__(RES_THREADS) __attribute__((amdgpu_waves_per_eu(8, 8))) k_piece_resolve(JtkWork w, JtkDeviceTables t) {
     __shared__ __attribute__((aligned(16))) uint8_t s_tx[T + 16];
     __shared__ uint16_t s_plist[T + 64];       // piece starts, then where the last piece ends, repeated to the end of the last chunk
-    __shared__ uint64_t s_pm[TW];
     __shared__ uint64_t s_gap[TW];
+    __shared__ uint32_t s_pre[TW + 1];         // piece starts in the tile's mask words before word wd; [TW]: in all of them
     __shared__ uint32_t s_q[Q_TOTAL];          // this tile's pieces for the merge kernels, by bin: offset | (len - 1) << 11 | index in this list << 19
     __shared__ uint32_t s_qn[JTK_NBINS + 1], s_qb[JTK_NBINS + 1], s_binc[JTK_NBINS + 1], s_nhard;
     __shared__ int64_t s_next_after;           // first piece start at or after B + T (global position)
@@ -425,16 +426,44 @@ __global__ void __launch_bounds__(RES_THREADS) __attribute__((amdgpu_waves_per_e
         }
         reinterpret_cast<uint4*>(s_tx)[tid] = v;
     }
+    // Which positions of the tile may start a piece, as a byte range [lo, hi) of the tile: from the chunk's lead -- a chunk of a
+    // larger batch starts at its first document, not at its first (tile-aligned) byte -- to the end of the text or of the mask.
+    // The end sentinel (bit n) starts no piece, and the padding words after it are not written by pretok_split for every n (they
+    // may hold bits of an earlier, longer batch).  Nearly every tile is whole: lo = 0, hi = T.
+    const int64_t mask_end = n < w.n_words * 64 ? n : w.n_words * 64;
+    const int lo = (int)(w.lead - B < 0 ? 0 : w.lead - B < T ? w.lead - B : T);
+    const int hi = (int)(mask_end - B < 0 ? 0 : mask_end - B < T ? mask_end - B : T);
+    const bool whole = lo == 0 && hi == T;                           // workgroup-uniform
+    const uint64_t* const pm = w.piecemask + (B >> 6);
+    auto mask_word = [&](int j) -> uint64_t {                        // word j of the tile; reads no word that has no valid bit
+        const int a = lo - 64 * j < 0 ? 0 : lo - 64 * j, b = hi - 64 * j < 64 ? hi - 64 * j : 64;   // its bits [a, b) are valid
+        if (b <= a) return 0ull;
+        return pm[j] & (~0ull >> (64 - b)) & (~0ull << a);           // (0 <= a < b <= 64: shifts of 0..63)
+    };
+    // Each wave's share of the mask words -- TW / RES_WAVES consecutive ones -- as scalars: the address is wave-uniform, so
+    // these are scalar loads, requested here and used behind the barrier, where a word is the execution mask of its list stores.
+    constexpr int WPW = TW / RES_WAVES;
+    uint64_t mw[WPW];
+    if (whole) {
+#pragma unroll
+        for (int j = 0; j < WPW; j++) mw[j] = pm[wv * WPW + j];
+    } else {
+#pragma unroll
+        for (int j = 0; j < WPW; j++) mw[j] = mask_word(wv * WPW + j);
+    }
+    uint32_t wcnt = 0;                                               // lane l of wave 0: piece starts in mask word l
     if (tid < TW) {
         const int64_t wd = (B >> 6) + tid;
-        uint64_t m = (wd < w.n_words) ? w.piecemask[wd] : 0ull;
-        // only positions before n start pieces: the end sentinel (bit n) does not, and the padding words after it are
-        // not written by pretok_split for every n (they may hold bits of an earlier, longer batch)
-        if (wd * 64 + 63 >= n) m &= (wd * 64 >= n) ? 0ull : ((1ull << (n - wd * 64)) - 1ull);
-        // a chunk of a larger batch starts at its first document, not at its first (tile-aligned) byte
-        if (wd * 64 < w.lead) m &= (wd * 64 + 64 <= w.lead) ? 0ull : ~((1ull << (w.lead - wd * 64)) - 1ull);
-        s_pm[tid] = m;
+        const uint64_t m = whole ? pm[tid] : mask_word(tid);
         s_gap[tid] = (w.gapmask && wd < w.n_words) ? w.gapmask[wd] : 0ull;
+        wcnt = (uint32_t)__popcll(m);
+    }
+    if (wv == 0) {
+        // where each word's pieces start in the list, once per tile: the word counts are in wave 0's registers, and their
+        // prefix rides on the barrier below.  (All 64 lanes of the wave take part; lanes TW.. hold 0.)
+        const uint32_t inc = jtk_wave_incl_scan32(wcnt);
+        if (lane < TW) s_pre[lane + 1] = inc;
+        if (lane == 0) s_pre[0] = 0;
     }
     if (tid < JTK_NBINS + 1) {
         s_qn[tid] = 0;
@@ -452,18 +481,19 @@ __global__ void __launch_bounds__(RES_THREADS) __attribute__((amdgpu_waves_per_e
         s_next_after = (pos < 0) ? n : pos;
     }
     __syncthreads();
-    // piece list: every wave scans the 32 word counts itself (lane l: word l), then compacts its share of the words
+    // piece list: every wave compacts its share of the mask words, each word from where the prefix says its pieces start
     int np;
     {
-        const uint32_t c = lane < TW ? (uint32_t)__popcll(s_pm[lane]) : 0u;
-        const uint32_t inc = jtk_wave_incl_scan(c);
-        np = __builtin_amdgcn_readlane((int)inc, 63);                 // a scalar: the chunk loop's bounds and branches are too
-        const uint32_t pre = inc - c;
-        for (int wd = wv; wd < TW; wd += RES_WAVES) {
-            const uint64_t m = s_pm[wd];
-            const uint32_t base = (uint32_t)__shfl((int)pre, wd);
-            if ((m >> lane) & 1ull)
-                s_plist[base + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = (uint16_t)(wd * 64 + lane);
+        np = __builtin_amdgcn_readfirstlane((int)s_pre[TW]);          // a scalar: the chunk loop's bounds and branches are too
+        uint32_t base[WPW];                                          // (read ahead of the stores, not one per word and wait)
+#pragma unroll
+        for (int j = 0; j < WPW; j++) base[j] = s_pre[wv * WPW + j];
+#pragma unroll
+        for (int j = 0; j < WPW; j++) {
+            const int wd = wv * WPW + j;
+            const uint64_t m = mw[j];
+            if (__builtin_amdgcn_inverse_ballot_w64(m))
+                s_plist[base[j] + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u))] = (uint16_t)(wd * 64 + lane);
         }
         if (wv == 0) {
             // where the last piece ends: the sentinel (bit n) or the next tile's first piece; a piece of more than 64 KB only
