@@ -248,6 +248,58 @@ int jtk_batch_minhash(jtk_batch* b, const jtk_minhash_params* params, uint32_t* 
 int jtk_batch_minhash_agree(jtk_batch* b, const uint32_t* d_sig, int64_t n_sig, int32_t num_hashes, const int64_t* d_pair_a,
                             const int64_t* d_pair_b, int64_t n_pairs, int32_t* d_agree, void* stream_or_null);
 
+/* Token n-gram sets and overlap, for benchmark decontamination: a corpus document is flagged, and the exact token ranges are
+ * marked, where it shares a token n-gram with a set of held-out texts encoded by the same encoder (jtk_ngram.hip; the rule, bit
+ * for bit, is csrc/jtk_ngram_rules.h -- integer arithmetic only, so every result is exact).
+ *   With G and mix as for jtk_minhash_params and key = mix(seed + G * (ngram + 33)), all modulo 2^64: a document of l tokens has
+ *   the n-grams t[i .. i + ngram), 0 <= i <= l - ngram -- none when l < ngram (not MinHash's short-document rule) and none when
+ *   its status < 0 --; H = H * G + id + 1 over an n-gram's ids (as uint32: special ids, FIM sentinels and pseudo ids count) and
+ *   k = mix(H ^ key), G where that is 0.  The set is the distinct k inserted so far (a 64-bit collision is part of the rule),
+ *   kept on the device in a table of `capacity` 64-bit slots, a power of two: home slot k & (capacity - 1), linear probing with
+ *   wrap-around, 0 = empty.  Before an insert of at most m new keys into c keys the capacity grows to the smallest power of two
+ *   >= max(64, 2 (c + m)) when that is larger (the table is rehashed on the device; it never shrinks); m = n for add_keys, the
+ *   number of n-grams of the batch's documents for add_batch.  A new set has 64 slots.
+ *   Per token p of a document: JTK_NG_START when an n-gram starts at p and its k is in the set, JTK_NG_COVERED when a
+ *   start-flagged i of the same document has p - ngram < i <= p.  Per document: n_hit = the start flags, n_covered = the
+ *   covered tokens, first_hit = the document-relative index of the first start, or -1.
+ * jtk_ngram_set_create: an empty set on enc's device.  ngram 1..32, flags 0: anything else is JTK_ERR_INVALID_ARGUMENT.  A set
+ *   belongs to `enc` (which must outlive it) and takes batches of that encoding object only; it holds no reference to any batch:
+ *   destroying a batch, or encoding on it again, leaves the set as it is.  Calls on one set are not thread-safe.
+ * jtk_ngram_set_destroy: waits for the set's queued work; NULL is allowed.
+ * jtk_ngram_set_add_batch: inserts every n-gram of the LAST batch encode on `b` (host or device input, any flags but
+ *   JTK_ENCODE_COUNT_ONLY).  Waits for the token count (as jtk_batch_minhash) and once more for the set's key count and the
+ *   batch's n-gram count, which decide the capacity; the insert is then queued on stream_or_null (the batch's stream when NULL),
+ *   behind the encode and behind the set's earlier work, and the call does not wait for it.
+ * jtk_ngram_set_add_keys: inserts n keys from host memory -- the jtk_ngram_set_keys of a saved set or of another shard's --; a key
+ *   that is already in the set is not counted again.  n < 0, keys == NULL with n > 0, and a key of 0 are
+ *   JTK_ERR_INVALID_ARGUMENT (the set is then unchanged).  Waits until the keys are in.
+ * jtk_ngram_set_size: the number of distinct keys and the capacity (either may be NULL); waits for the set's queued work.
+ * jtk_ngram_set_keys: the n_keys keys into keys[cap], in no particular order; cap < n_keys is JTK_ERR_INVALID_ARGUMENT.  Waits.
+ * jtk_batch_ngram_overlap: the last batch encode on `b` against `s`, with the set's seed and ngram.  Caller-owned device buffers,
+ *   each may be NULL and is then not written: d_tok_flags[n_tokens] uint8 (any alignment; 8-byte aligned takes the fast path),
+ *   d_n_hit[n_docs] and d_n_covered[n_docs] int32 (4-byte aligned), d_first_hit[n_docs] int64 (8-byte aligned).  An empty set
+ *   is valid: all flags 0, all counts 0, first_hit -1.  Waits once, for the token count; the pass is then queued on
+ *   stream_or_null (the batch's stream when NULL) behind the encode and the set's earlier work, and the call does not wait for
+ *   it.  It reads the ids, tok_off and status only and keeps no state in the batch: chunk, pack, truncate and FIM results are
+ *   untouched.  A later jtk_ngram_set_add_* is ordered behind it.  A NULL set and a batch of another encoding object than the
+ *   set's are JTK_ERR_INVALID_ARGUMENT.  jtk_batch_token_offsets turns the covered token runs into byte spans. */
+#define JTK_NG_START 1
+#define JTK_NG_COVERED 2
+typedef struct jtk_ngram_params {
+    uint64_t seed;
+    int32_t ngram;          /* n: 1..32 */
+    uint32_t flags;         /* 0 */
+} jtk_ngram_params;
+typedef struct jtk_ngram_set jtk_ngram_set;
+int jtk_ngram_set_create(const jtk_encoding* enc, const jtk_ngram_params* params, jtk_ngram_set** out);
+void jtk_ngram_set_destroy(jtk_ngram_set* s);
+int jtk_ngram_set_add_batch(jtk_ngram_set* s, jtk_batch* b, void* stream_or_null);
+int jtk_ngram_set_add_keys(jtk_ngram_set* s, const uint64_t* keys, int64_t n);
+int jtk_ngram_set_size(const jtk_ngram_set* s, int64_t* n_keys, int64_t* capacity);
+int jtk_ngram_set_keys(const jtk_ngram_set* s, uint64_t* keys, int64_t cap);
+int jtk_batch_ngram_overlap(jtk_batch* b, const jtk_ngram_set* s, uint8_t* d_tok_flags_or_null, int32_t* d_n_hit_or_null,
+                            int32_t* d_n_covered_or_null, int64_t* d_first_hit_or_null, void* stream_or_null);
+
 /* Device buffers already resident in HBM (what bench.py times).  `stream_or_null` = a hipStream_t
  * to order against, or NULL for the batch's own stream: the whole encode is ordered like one operation on that stream
  * (inside, the chunks of a large batch run on the batch's own streams, forked from and joined into it).  With

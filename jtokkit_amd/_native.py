@@ -64,6 +64,8 @@ JTK_DECODE_SKIP_PAD = 1
 JTK_DECODE_KEEP_STOP = 2
 JTK_STOP_MAX_STRINGS = 16
 JTK_STOP_MAX_BYTES = 64
+JTK_NG_START = 1
+JTK_NG_COVERED = 2
 JTK_OPT_CHUNK_BYTES = 1
 JTK_OPT_CHUNKS_IN_FLIGHT = 2
 JTK_OPT_HOST_CHUNK_BYTES = 3
@@ -80,6 +82,11 @@ class FimParamsStruct(C.Structure):
 class MinhashParamsStruct(C.Structure):
     """jtk_minhash_params"""
     _fields_ = [("seed", C.c_uint64), ("ngram", C.c_int32), ("num_hashes", C.c_int32), ("bands", C.c_int32), ("flags", C.c_uint32)]
+
+
+class NgramParamsStruct(C.Structure):
+    """jtk_ngram_params"""
+    _fields_ = [("seed", C.c_uint64), ("ngram", C.c_int32), ("flags", C.c_uint32)]
 
 
 # every symbol include/jtokkit_amd.h declares: (restype, argtypes)
@@ -107,6 +114,13 @@ SIGNATURES = {
     "jtk_batch_compact": (C.c_int, [_p, _p, _p, _p]),
     "jtk_batch_minhash": (C.c_int, [_p, C.POINTER(MinhashParamsStruct), _p, _p, _p, _p]),
     "jtk_batch_minhash_agree": (C.c_int, [_p, _p, _i64, C.c_int32, _p, _p, _i64, _p, _p]),
+    "jtk_ngram_set_create": (C.c_int, [_p, C.POINTER(NgramParamsStruct), C.POINTER(_p)]),
+    "jtk_ngram_set_destroy": (None, [_p]),
+    "jtk_ngram_set_add_batch": (C.c_int, [_p, _p, _p]),
+    "jtk_ngram_set_add_keys": (C.c_int, [_p, _p, _i64]),
+    "jtk_ngram_set_size": (C.c_int, [_p, C.POINTER(_i64), C.POINTER(_i64)]),
+    "jtk_ngram_set_keys": (C.c_int, [_p, _p, _i64]),
+    "jtk_batch_ngram_overlap": (C.c_int, [_p, _p, _p, _p, _p, _p, _p]),
     "jtk_widen_ids": (C.c_int, [_p, _p, C.c_int, _i64, _i64, _p]),
     "jtk_batch_encode": (C.c_int, [_p, _p, _p, _i64, C.c_uint32, C.POINTER(_i64)]),
     "jtk_batch_encode_pieces": (C.c_int, [_p, _p, _p, _i64, _p, _p, _i64, C.c_uint32, C.POINTER(_i64)]),

@@ -20,6 +20,7 @@
 #include "jtk_decode_rows_rules.h"
 #include "jtk_kernels.h"
 #include "jtk_maxtok_rules.h"
+#include "jtk_ngram_rules.h"
 #include "jtk_tables.h"
 
 namespace {
@@ -2252,6 +2253,182 @@ int jtk_batch_minhash_agree(jtk_batch* b, const uint32_t* d_sig, int64_t n_sig, 
     jtk_launch_minhash_agree(d_sig, n_sig, num_hashes, d_pair_a, d_pair_b, n_pairs, d_agree, pick_stream(b, stream_or_null));
     HIP_TRY(hipGetLastError());
     return JTK_OK;
+}
+
+// ---- token n-gram sets and overlap (jtk_ngram.hip) ----------------------------------------------------------------------
+// A set lives on its encoding's device and outlives batches.  Its calls may come on different streams: each call that queues work
+// first makes its stream wait for `ev` (ng_wait) and records `ev` behind what it queued (ng_done), so the calls take effect in
+// the order they were made, and no stream handle is kept.
+struct jtk_ngram_set {
+    const jtk_encoding* enc = nullptr;
+    jtk_ngram_params p{};
+    uint64_t* table = nullptr;       // [capacity], 0 = empty
+    int64_t capacity = 0;
+    uint64_t* d_hdr = nullptr;       // [0] the key count, [1] the n-grams of the batch that is being added
+    hipStream_t own = nullptr;       // add_keys and the reads
+    hipEvent_t ev = nullptr;
+};
+
+static int ng_wait(const jtk_ngram_set* s, hipStream_t st) { HIP_TRY(hipStreamWaitEvent(st, s->ev, 0)); return JTK_OK; }
+static int ng_done(const jtk_ngram_set* s, hipStream_t st) { HIP_TRY(hipEventRecord(s->ev, st)); return JTK_OK; }
+
+static void ng_free(jtk_ngram_set* s) {
+    if (s->ev) { (void)hipEventSynchronize(s->ev); (void)hipEventDestroy(s->ev); }
+    if (s->own) (void)hipStreamDestroy(s->own);
+    if (s->table) (void)hipFree(s->table);
+    if (s->d_hdr) (void)hipFree(s->d_hdr);
+    delete s;
+}
+
+// room for m more keys beside c, by the capacity rule; a larger table is filled from the old one on `st`, which is waited for
+static int ng_reserve(jtk_ngram_set* s, int64_t c, int64_t m, hipStream_t st) {
+    const int64_t cap = jtk_ng_capacity(c, m);
+    if (cap <= s->capacity) return JTK_OK;
+    uint64_t* grown = nullptr;
+    hipError_t e = hipMalloc((void**)&grown, (size_t)cap * 8);
+    if (e != hipSuccess) return fail(JTK_ERR_OUT_OF_MEMORY, std::string("hipMalloc (n-gram table): ") + hipGetErrorString(e));
+    e = hipMemsetAsync(grown, 0, (size_t)cap * 8, st);
+    if (e == hipSuccess) {
+        jtk_launch_ngram_insert_keys(s->table, s->capacity, grown, cap, nullptr, st);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) { (void)hipFree(grown); return fail(JTK_ERR_HIP, std::string("n-gram table growth: ") + hipGetErrorString(e)); }
+    (void)hipFree(s->table);
+    s->table = grown;
+    s->capacity = cap;
+    return JTK_OK;
+}
+
+static JtkMhView ng_view(const jtk_batch* b, int64_t nt, int32_t ngram) {
+    JtkMhView v;
+    v.tokens = (const int32_t*)b->tokens.p; v.tok_off = (const int64_t*)b->tok_off.p; v.status = (const int32_t*)b->status.p;
+    v.n_docs = b->job_docs; v.total = nt; v.ngram = ngram;
+    return v;
+}
+
+int jtk_ngram_set_create(const jtk_encoding* enc, const jtk_ngram_params* p, jtk_ngram_set** out) {
+    if (!enc || !p || !out) return fail(JTK_ERR_INVALID_ARGUMENT, "enc, params or out is NULL");
+    if (!jtk_ng_params_ok(p->ngram, p->flags)) return fail(JTK_ERR_INVALID_ARGUMENT, "n-gram set: ngram 1..32, flags 0");
+    HIP_TRY(hipSetDevice(enc->device));
+    jtk_ngram_set* s = new (std::nothrow) jtk_ngram_set();
+    if (!s) return fail(JTK_ERR_OUT_OF_MEMORY, "out of host memory");
+    s->enc = enc;
+    s->p = *p;
+    s->capacity = jtk_ng_capacity(0, 0);
+    hipError_t e = hipStreamCreateWithFlags(&s->own, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipMalloc((void**)&s->table, (size_t)s->capacity * 8);
+    if (e == hipSuccess) e = hipMalloc((void**)&s->d_hdr, 16);
+    if (e == hipSuccess) e = hipMemsetAsync(s->table, 0, (size_t)s->capacity * 8, s->own);
+    if (e == hipSuccess) e = hipMemsetAsync(s->d_hdr, 0, 16, s->own);
+    if (e == hipSuccess) e = hipEventRecord(s->ev, s->own);
+    if (e != hipSuccess) {
+        ng_free(s);
+        return fail(e == hipErrorOutOfMemory ? JTK_ERR_OUT_OF_MEMORY : JTK_ERR_HIP, std::string("jtk_ngram_set_create: ") + hipGetErrorString(e));
+    }
+    *out = s;
+    return JTK_OK;
+}
+
+void jtk_ngram_set_destroy(jtk_ngram_set* s) {
+    if (!s) return;
+    (void)hipSetDevice(s->enc->device);
+    ng_free(s);
+}
+
+int jtk_ngram_set_add_batch(jtk_ngram_set* s, jtk_batch* b, void* stream_or_null) {
+    if (!s) return fail(JTK_ERR_INVALID_ARGUMENT, "the n-gram set is NULL");
+    int rc;
+    if ((rc = need_encode(b, NEED_IDS))) return rc;
+    if (b->enc != s->enc) return fail(JTK_ERR_INVALID_ARGUMENT, "the batch belongs to another encoding object than the n-gram set");
+    HIP_TRY(hipSetDevice(b->enc->device));
+    int64_t nt = 0;
+    if ((rc = jtk_batch_result(b, &nt, nullptr, nullptr))) return rc;
+    hipStream_t st = pick_stream(b, stream_or_null);
+    if ((rc = ck_order(b, b->last_stream, st)) || (rc = ng_wait(s, st))) return rc;
+    const JtkMhView v = ng_view(b, nt, s->p.ngram);
+    HIP_TRY(hipMemsetAsync(s->d_hdr + 1, 0, 8, st));
+    jtk_launch_ngram_count(v, s->d_hdr + 1, st);
+    HIP_TRY(hipGetLastError());
+    int64_t h[2] = {0, 0};                                   // keys in the set, n-grams in the batch
+    HIP_TRY(hipMemcpyAsync(h, s->d_hdr, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if ((rc = ng_reserve(s, h[0], h[1], st))) return rc;
+    jtk_launch_ngram_insert(v, s->p.seed, s->table, s->capacity, s->d_hdr, st);
+    HIP_TRY(hipGetLastError());
+    return ng_done(s, st);
+}
+
+int jtk_ngram_set_add_keys(jtk_ngram_set* s, const uint64_t* keys, int64_t n) {
+    if (!s) return fail(JTK_ERR_INVALID_ARGUMENT, "the n-gram set is NULL");
+    if (n < 0) return fail(JTK_ERR_INVALID_ARGUMENT, "n must not be negative");
+    if (n > 0 && !keys) return fail(JTK_ERR_INVALID_ARGUMENT, "keys is NULL");
+    for (int64_t i = 0; i < n; i++)
+        if (keys[i] == 0) return fail(JTK_ERR_INVALID_ARGUMENT, "a key of 0 cannot be in an n-gram set (0 is the empty slot)");
+    if (n == 0) return JTK_OK;
+    HIP_TRY(hipSetDevice(s->enc->device));
+    int rc;
+    if ((rc = ng_wait(s, s->own))) return rc;
+    TmpDevBuf tmp;
+    if ((rc = tmp.ensure((size_t)n * 8))) return rc;
+    HIP_TRY(hipMemcpyAsync(tmp.p, keys, (size_t)n * 8, hipMemcpyHostToDevice, s->own));
+    int64_t c = 0;
+    HIP_TRY(hipMemcpyAsync(&c, s->d_hdr, 8, hipMemcpyDeviceToHost, s->own));
+    HIP_TRY(hipStreamSynchronize(s->own));
+    if ((rc = ng_reserve(s, c, n, s->own))) return rc;
+    jtk_launch_ngram_insert_keys((const uint64_t*)tmp.p, n, s->table, s->capacity, s->d_hdr, s->own);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s->own));
+    return ng_done(s, s->own);
+}
+
+int jtk_ngram_set_size(const jtk_ngram_set* s, int64_t* n_keys, int64_t* capacity) {
+    if (!s) return fail(JTK_ERR_INVALID_ARGUMENT, "the n-gram set is NULL");
+    HIP_TRY(hipSetDevice(s->enc->device));
+    if (n_keys) {
+        int rc;
+        if ((rc = ng_wait(s, s->own))) return rc;
+        HIP_TRY(hipMemcpyAsync(n_keys, s->d_hdr, 8, hipMemcpyDeviceToHost, s->own));
+        HIP_TRY(hipStreamSynchronize(s->own));
+    }
+    if (capacity) *capacity = s->capacity;
+    return JTK_OK;
+}
+
+int jtk_ngram_set_keys(const jtk_ngram_set* s, uint64_t* keys, int64_t cap) {
+    int64_t c = 0;
+    int rc;
+    if ((rc = jtk_ngram_set_size(s, &c, nullptr))) return rc;
+    if (cap < c) return fail(JTK_ERR_INVALID_ARGUMENT, "keys has room for fewer than n_keys keys");
+    if (c == 0) return JTK_OK;
+    if (!keys) return fail(JTK_ERR_INVALID_ARGUMENT, "keys is NULL");
+    std::vector<uint64_t> slots((size_t)s->capacity);
+    HIP_TRY(hipMemcpyAsync(slots.data(), s->table, slots.size() * 8, hipMemcpyDeviceToHost, s->own));
+    HIP_TRY(hipStreamSynchronize(s->own));
+    int64_t n = 0;
+    for (uint64_t k : slots)
+        if (k && n < c) keys[n++] = k;
+    if (n != c) return fail(JTK_ERR_HIP, "the n-gram table does not hold the number of keys it counts");
+    return JTK_OK;
+}
+
+int jtk_batch_ngram_overlap(jtk_batch* b, const jtk_ngram_set* s, uint8_t* d_tok_flags, int32_t* d_n_hit, int32_t* d_n_covered,
+                            int64_t* d_first_hit, void* stream_or_null) {
+    if (!s) return fail(JTK_ERR_INVALID_ARGUMENT, "the n-gram set is NULL");
+    int rc;
+    if ((rc = need_encode(b, NEED_IDS))) return rc;
+    if (b->enc != s->enc) return fail(JTK_ERR_INVALID_ARGUMENT, "the batch belongs to another encoding object than the n-gram set");
+    if (((uintptr_t)d_n_hit & 3u) || ((uintptr_t)d_n_covered & 3u) || ((uintptr_t)d_first_hit & 7u))
+        return fail(JTK_ERR_INVALID_ARGUMENT, "unaligned array (4-byte n_hit and n_covered, 8-byte first_hit)");
+    HIP_TRY(hipSetDevice(b->enc->device));
+    int64_t nt = 0;
+    if ((rc = jtk_batch_result(b, &nt, nullptr, nullptr))) return rc;
+    hipStream_t st = pick_stream(b, stream_or_null);
+    if ((rc = ck_order(b, b->last_stream, st)) || (rc = ng_wait(s, st))) return rc;
+    jtk_launch_ngram_overlap(ng_view(b, nt, s->p.ngram), s->p.seed, s->table, s->capacity, d_tok_flags, d_n_hit, d_n_covered, d_first_hit, st);
+    HIP_TRY(hipGetLastError());
+    return ng_done(s, st);
 }
 
 int jtk_batch_token_offsets(jtk_batch* b, int64_t* d_byte_pos, void* stream_or_null) {

@@ -123,6 +123,32 @@ public:
         check(jtk_batch_token_char_offsets(batch_, unit, dBegin, dEnd, stream));
     }
 
+    // token n-gram sets for decontamination (the rule is in jtokkit_amd.h): a set of this encoding, owned by the caller and freed
+    // with ngramSetDestroy before the Encoding; the n-grams of the last encodeBatch or host keys into it; its size and keys; and
+    // the overlap of the last encodeBatch with it into device arrays (each may be NULL)
+    jtk_ngram_set* ngramSetCreate(int32_t ngram, uint64_t seed = 0) {
+        const jtk_ngram_params p{seed, ngram, 0u};
+        jtk_ngram_set* s = nullptr;
+        check(jtk_ngram_set_create(enc_, &p, &s));
+        return s;
+    }
+    static void ngramSetDestroy(jtk_ngram_set* s) { jtk_ngram_set_destroy(s); }
+    void ngramSetAddLastEncode(jtk_ngram_set* s, void* stream = nullptr) { check(jtk_ngram_set_add_batch(s, batch_, stream)); }
+    static void ngramSetAddKeys(jtk_ngram_set* s, const std::vector<uint64_t>& keys) {
+        check(jtk_ngram_set_add_keys(s, keys.data(), (int64_t)keys.size()));
+    }
+    static std::vector<uint64_t> ngramSetKeys(const jtk_ngram_set* s, int64_t* capacity = nullptr) {
+        int64_t n = 0;
+        check(jtk_ngram_set_size(s, &n, capacity));
+        std::vector<uint64_t> keys((size_t)n);
+        check(jtk_ngram_set_keys(s, keys.data(), n));
+        return keys;
+    }
+    void ngramOverlap(const jtk_ngram_set* s, uint8_t* dTokFlags, int32_t* dNHit = nullptr, int32_t* dNCovered = nullptr,
+                      int64_t* dFirstHit = nullptr, void* stream = nullptr) {
+        check(jtk_batch_ngram_overlap(batch_, s, dTokFlags, dNHit, dNCovered, dFirstHit, stream));
+    }
+
     // batch decodeBytes: token lists back to back in `ids`, n+1 offsets -> bytes back to back + n+1 byte offsets + status
     void decodeBatch(const int32_t* ids, const std::vector<int64_t>& seqOff, std::string& bytes,
                      std::vector<int64_t>& byteOff, std::vector<int32_t>& status) {

@@ -423,6 +423,17 @@ void jtk_launch_minhash(const JtkMhView& v, uint64_t seed, int32_t num_hashes, i
 // agree[p] = the words on which rows pair_a[p] and pair_b[p] of sig[n_sig * num_hashes] agree; -1 for an index outside [0, n_sig)
 void jtk_launch_minhash_agree(const uint32_t* sig, int64_t n_sig, int32_t num_hashes, const int64_t* pair_a, const int64_t* pair_b,
                               int64_t n_pairs, int32_t* agree, hipStream_t s);
+// Token n-gram sets and overlap (jtk_ngram.hip; the rule is jtk_ngram_rules.h).  A set is a table of `capacity` (a power of two)
+// 64-bit slots, 0 = empty, and a device word that counts its keys.
+//   count         *sum += the n-grams of the documents of v (what an insert of them adds at most)
+//   insert        every n-gram of v; *count += the keys that were new
+//   insert_keys   keys[n], zeros skipped (so an old table can be given: the rehash); count may be NULL
+//   overlap       flags[total], n_hit / n_covered / first_hit [n_docs], each may be NULL and is then not written; two kernels at most
+void jtk_launch_ngram_count(const JtkMhView& v, uint64_t* sum, hipStream_t s);
+void jtk_launch_ngram_insert(const JtkMhView& v, uint64_t seed, uint64_t* table, int64_t capacity, uint64_t* count, hipStream_t s);
+void jtk_launch_ngram_insert_keys(const uint64_t* keys, int64_t n, uint64_t* table, int64_t capacity, uint64_t* count_or_null, hipStream_t s);
+void jtk_launch_ngram_overlap(const JtkMhView& v, uint64_t seed, const uint64_t* table, int64_t capacity, uint8_t* flags, int32_t* n_hit,
+                              int32_t* n_covered, int64_t* first_hit, hipStream_t s);
 // Device-side state of an allow-special encode (jtk_special.hip, JTK_ENCODE_ALLOW_SPECIAL; the rule is jtk_special_rules.h).
 // Candidates (per position, the longest allowed literal there) are found in position order, resolved to the kept matches, and
 // the batch is cut into sub-documents that partition the text: per document a segment, then per candidate i two slots

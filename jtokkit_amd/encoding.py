@@ -423,6 +423,12 @@ class Batch:
         _check(N.lib().jtk_batch_minhash_agree(self._h, d_sig_ptr, n_sig, num_hashes, d_pair_a_ptr, d_pair_b_ptr, n_pairs,
                                                d_agree_ptr, stream))
 
+    def ngram_overlap(self, ngram_set, d_tok_flags_ptr=None, d_n_hit_ptr=None, d_n_covered_ptr=None, d_first_hit_ptr=None, stream=None):
+        """jtk_batch_ngram_overlap of the last encode against an NgramSet: uint8 [n_tokens] at d_tok_flags_ptr, int32 [n_docs] at
+        d_n_hit_ptr and d_n_covered_ptr, int64 [n_docs] at d_first_hit_ptr, device pointers, each may be None and is then not
+        written; waits for the token count, not for the pass."""
+        _check(N.lib().jtk_batch_ngram_overlap(self._h, ngram_set._h, d_tok_flags_ptr, d_n_hit_ptr, d_n_covered_ptr, d_first_hit_ptr, stream))
+
     def encode_device(self, d_text_ptr, d_doc_off_ptr, n_docs, n_bytes, ordinary=False, stream=None, sync=True,
                       allow_special=False, validate=False, count_only=False, fim=False):
         nt = C.c_int64(0)
@@ -819,6 +825,67 @@ class Batch:
         return out[:nt.value].tolist(), bool(tr.value)
 
 
+class NgramSet:
+    """A device-resident set of token n-grams of held-out texts (jtk_ngram_set; the rule is in include/jtokkit_amd.h), for
+    decontamination: HipEncoding.ngram_overlap_batch marks where corpus documents share an n-gram with it.  It belongs to its
+    encoding, which must stay open while the set is used, and keeps no reference to any batch."""
+
+    def __init__(self, encoding, ngram, seed=0):
+        self.encoding = encoding
+        self.ngram = int(ngram)
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        p = N.NgramParamsStruct(self.seed, self.ngram, 0)
+        h = C.c_void_p()
+        _check(N.lib().jtk_ngram_set_create(encoding._h, C.byref(p), C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            N.lib().jtk_ngram_set_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:          # (interpreter shutdown: the module's globals may be gone)
+            pass
+
+    def add_last_encode(self, batch, stream=None):
+        """jtk_ngram_set_add_batch: every n-gram of the last encode on `batch` (a Batch of the same encoding)."""
+        _check(N.lib().jtk_ngram_set_add_batch(self._h, batch._h, stream))
+
+    def add_texts(self, texts, ordinary=True, **encode_kwargs):
+        """Encodes a list of str/bytes (encode_batch's keywords: ordinary, validate, allowed_special, fim) and inserts every
+        n-gram of the result; a refused document (status < 0) adds nothing.  Returns the encode's BatchResult."""
+        res = self.encoding.encode_batch(texts, ordinary=ordinary, **encode_kwargs)
+        self.add_last_encode(self.encoding._b())
+        return res
+
+    def add_keys(self, keys):
+        """jtk_ngram_set_add_keys: the keys() of a saved set, or of another shard's (uint64; a 0 is refused)."""
+        keys = np.ascontiguousarray(keys, dtype=np.uint64)
+        _check(N.lib().jtk_ngram_set_add_keys(self._h, keys.ctypes.data if keys.size else None, keys.size))
+
+    def _size(self):
+        n, cap = C.c_int64(0), C.c_int64(0)
+        _check(N.lib().jtk_ngram_set_size(self._h, C.byref(n), C.byref(cap)))
+        return n.value, cap.value
+
+    def __len__(self):
+        return self._size()[0]
+
+    @property
+    def capacity(self):
+        """Slots of the device table: the smallest power of two >= max(64, 2 (keys + what the largest insert could add))."""
+        return self._size()[1]
+
+    def keys(self):
+        """The distinct keys, uint64 [len(self)], in no particular order."""
+        out = np.zeros(len(self), dtype=np.uint64)
+        _check(N.lib().jtk_ngram_set_keys(self._h, out.ctypes.data if out.size else None, out.size))
+        return out
+
+
 class HipEncoding:
     """GPU-backed `Encoding` (reference GptBytePairEncoding.java:18 is the class this replaces)."""
 
@@ -1172,6 +1239,82 @@ class HipEncoding:
         if side is not None:
             cur.wait_stream(side)
         return sig, n_shingles, band_keys, tok_off, status
+
+    def ngram_set(self, ngram, seed=0):
+        """An empty NgramSet of this encoding: token n-grams of held-out texts, for ngram_overlap_batch (decontamination)."""
+        return NgramSet(self, ngram, seed)
+
+    def ngram_overlap_batch(self, texts, ngram_set, ordinary=True, allowed_special=None):
+        """Where a list of str/bytes shares a token n-gram with `ngram_set` (jtk_batch_ngram_overlap; the rule is in
+        include/jtokkit_amd.h): (flags uint8 [n_tokens] -- JTK_NG_START | JTK_NG_COVERED per token --, n_hit int32 [n],
+        n_covered int32 [n], first_hit int64 [n] -- the document-relative index of the first start, or -1 --, tok_off int64
+        [n + 1]).  The covered tokens of document d are the set bits of flags[tok_off[d]:tok_off[d + 1]] & JTK_NG_COVERED."""
+        bs = [t if isinstance(t, (bytes, bytearray)) else t.encode("utf-8") for t in texts]
+        doc_off = np.zeros(len(bs) + 1, dtype=np.int64)
+        if bs:
+            np.cumsum([len(b) for b in bs], out=doc_off[1:])
+        text = np.frombuffer(b"".join(bs), dtype=np.uint8) if doc_off[-1] else np.zeros(0, dtype=np.uint8)
+        res = self.encode_batch_packed(text, doc_off, ordinary, False, allowed_special)
+        n = len(bs)
+        b = self._b()
+        bufs = []
+        try:
+            bufs.append(_DeviceArray(np.zeros(len(res.tokens), dtype=np.uint8)))
+            bufs.append(_DeviceArray(np.zeros(n, dtype=np.int32)))
+            bufs.append(_DeviceArray(np.zeros(n, dtype=np.int32)))
+            bufs.append(_DeviceArray(np.zeros(n, dtype=np.int64)))
+            b.ngram_overlap(ngram_set, *[x.ptr for x in bufs])
+            _stream_sync(b.stream())
+            return tuple(x.fetch() for x in bufs) + (res.tok_off.copy(),)
+        finally:
+            for x in bufs:
+                x.free()
+
+    def ngram_overlap_batch_device(self, text, doc_off, ngram_set, ordinary=True, allowed_special=None):
+        """Encodes a device-resident batch (text CUDA torch.uint8, doc_off CUDA torch.int64 [n_docs + 1]) and returns its
+        overlap with `ngram_set` as CUDA tensors written on torch.cuda.current_stream(): (flags uint8 [n_tokens], n_hit int32
+        [n_docs], n_covered int32 [n_docs], first_hit int64 [n_docs], tok_off int64 [n_docs + 1], status int32 [n_docs]).  The
+        ids stay in the batch (device_result).  Waits once, for the token count (and, with allowed_special, once more for the
+        encode's count of literal candidates)."""
+        import torch
+        self._check_device_inputs("ngram_overlap_batch_device", text, doc_off)
+        allow = self._allow(self._b(), allowed_special)
+        nd = doc_off.numel() - 1
+        if nd < 0:
+            raise ValueError("doc_off needs n_docs + 1 entries")
+        device = text.device
+        n = text.numel()
+        st = text.untyped_storage()
+        if text.data_ptr() % 16 or st.data_ptr() + st.nbytes() < text.data_ptr() + (n + 15) // 16 * 16:
+            # (the encode reads whole aligned 16-byte blocks)
+            buf = torch.zeros((n + 15) // 16 * 16 + 16, dtype=torch.uint8, device=device)
+            buf[:n].copy_(text)
+            text = buf
+        b = self._b()
+        cur = torch.cuda.current_stream(device)
+        side = None
+        if cur.cuda_stream == 0:
+            # (the legacy default stream: see chunk_batch_device)
+            side = torch.cuda.ExternalStream(b.stream(), device=device)
+            side.wait_stream(cur)
+        stream = (side or cur).cuda_stream
+        b.encode_device(text.data_ptr(), doc_off.data_ptr(), nd, n, ordinary, stream=stream, sync=False, allow_special=allow)
+        nt = b.result()[0]
+        flags = torch.empty(nt, dtype=torch.uint8, device=device)
+        n_hit = torch.empty(nd, dtype=torch.int32, device=device)
+        n_covered = torch.empty(nd, dtype=torch.int32, device=device)
+        first_hit = torch.empty(nd, dtype=torch.int64, device=device)
+        b.ngram_overlap(ngram_set, flags.data_ptr() if nt else None, n_hit.data_ptr() if nd else None, n_covered.data_ptr() if nd else None,
+                        first_hit.data_ptr() if nd else None, stream)
+        tok_off = torch.empty(nd + 1, dtype=torch.int64, device=device)
+        status = torch.empty(nd, dtype=torch.int32, device=device)
+        _, p_off, p_status = b.device_result()
+        for t, src in ((tok_off, p_off), (status, p_status)):
+            if t.numel():
+                _copy_d2d(t.data_ptr(), src, t.numel() * t.element_size(), stream)
+        if side is not None:
+            cur.wait_stream(side)
+        return flags, n_hit, n_covered, first_hit, tok_off, status
 
     def near_duplicates(self, texts, threshold=0.8, ngram=5, num_hashes=128, bands=16, seed=0, ordinary=True, allowed_special=None):
         """Clusters of near-duplicate documents by MinHash and LSH: int64 [n] labels, the smallest document index of each
