@@ -6,6 +6,7 @@ batch entry points that are the reason this library exists.  The JVM is absent f
 so this Python class (and the C++ header jtokkit_amd/csrc/jtk_encoding.hpp) stand where the Java
 `HipEncoding implements Encoding` of INTEGRATION.md would.
 """
+import contextlib
 import ctypes as C
 import threading
 
@@ -53,6 +54,48 @@ def _copy_d2d(dst, src, n_bytes, stream):
     rc = _hip_memcpy_async(dst, src, n_bytes, 3, stream)
     if rc != 0:
         raise EncodingError(N.JTK_ERR_HIP, "hipMemcpyAsync failed (%d)" % rc)
+
+
+def _device_copy(src_ptr, shape, dtype, device, stream):
+    """A new CUDA tensor of the elements at device pointer src_ptr, copied on `stream`; an empty one reads nothing."""
+    import torch
+    t = torch.empty(shape, dtype=dtype, device=device)
+    if t.numel():
+        _copy_d2d(t.data_ptr(), src_ptr, t.numel() * t.element_size(), stream)
+    return t
+
+
+def _join_texts(texts):
+    """List of str/bytes -> (the documents' bytes, text uint8, doc_off int64 [n + 1]): the documents back to back."""
+    bs = [t if isinstance(t, (bytes, bytearray)) else t.encode("utf-8") for t in texts]
+    doc_off = np.zeros(len(bs) + 1, dtype=np.int64)
+    if bs:
+        np.cumsum([len(b) for b in bs], out=doc_off[1:])
+    text = np.frombuffer(b"".join(bs), dtype=np.uint8) if doc_off[-1] else np.zeros(0, dtype=np.uint8)
+    return bs, text, doc_off
+
+
+def _join_ids(token_lists):
+    """List of token-id lists -> (ids int32, seq_off int64 [n + 1]): the lists back to back."""
+    seq_off = np.zeros(len(token_lists) + 1, dtype=np.int64)
+    if token_lists:
+        np.cumsum([len(t) for t in token_lists], out=seq_off[1:])
+    return np.fromiter((i for t in token_lists for i in t), dtype=np.int32, count=int(seq_off[-1])), seq_off
+
+
+def _view(ptr, n, ctype, dtype):
+    """Zero-copy numpy view of n elements at a host pointer (an empty array for none)."""
+    if not ptr or n == 0:
+        return np.zeros(0, dtype=dtype)
+    return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), shape=(n,))
+
+
+def _encode_flags(ordinary=False, validate=False, count_only=False, to_host=False, allow_special=False, compact=False, fim=False):
+    """The JTK_ENCODE_* flag word of an encode call."""
+    return ((N.JTK_ENCODE_ORDINARY if ordinary else 0) | (N.JTK_ENCODE_VALIDATE_UTF8 if validate else 0)
+            | (N.JTK_ENCODE_COUNT_ONLY if count_only else 0) | (N.JTK_ENCODE_TO_HOST if to_host else 0)
+            | (N.JTK_ENCODE_ALLOW_SPECIAL if allow_special else 0) | (N.JTK_ENCODE_COMPACT_IDS if compact else 0)
+            | (N.JTK_ENCODE_FIM if fim else 0))
 
 
 _SPAN_RULES = {"whole": N.JTK_SPAN_WHOLE, "start": N.JTK_SPAN_START, "any": N.JTK_SPAN_ANY}
@@ -183,6 +226,21 @@ class _DeviceArray:
         if self.ptr:
             N.lib().hipFree(self.ptr)
             self.ptr = C.c_void_p()
+
+
+@contextlib.contextmanager
+def _device_arrays():
+    """Scratch of a host-input method: yields put(arr) -> _DeviceArray; every array put is freed on exit."""
+    held = []
+
+    def put(arr):
+        held.append(_DeviceArray(arr))
+        return held[-1]
+    try:
+        yield put
+    finally:
+        for x in held:
+            x.free()
 
 
 class EncodingResult:
@@ -348,10 +406,7 @@ class Batch:
         text_u8 = np.ascontiguousarray(text_u8, dtype=np.uint8)
         doc_off = np.ascontiguousarray(doc_off, dtype=np.int64)
         nt = C.c_int64(0)
-        flags = ((N.JTK_ENCODE_ORDINARY if ordinary else 0) | (N.JTK_ENCODE_VALIDATE_UTF8 if validate else 0)
-                 | (N.JTK_ENCODE_COUNT_ONLY if count_only else 0) | (N.JTK_ENCODE_TO_HOST if to_host else 0)
-                 | (N.JTK_ENCODE_ALLOW_SPECIAL if allow_special else 0) | (N.JTK_ENCODE_COMPACT_IDS if compact else 0)
-                 | (N.JTK_ENCODE_FIM if fim else 0))
+        flags = _encode_flags(ordinary, validate, count_only, to_host, allow_special, compact, fim)
         self._count_only = count_only
         _check(N.lib().jtk_batch_encode(self._h, text_u8.ctypes.data, doc_off.ctypes.data, len(doc_off) - 1,
                                         flags, C.byref(nt)))
@@ -365,8 +420,7 @@ class Batch:
         pb = np.ascontiguousarray(piece_begin, dtype=np.int64)
         pe = np.ascontiguousarray(piece_end, dtype=np.int64)
         nt = C.c_int64(0)
-        flags = ((N.JTK_ENCODE_ORDINARY if ordinary else 0) | (N.JTK_ENCODE_TO_HOST if to_host else 0)
-                 | (N.JTK_ENCODE_COMPACT_IDS if compact else 0))
+        flags = _encode_flags(ordinary, to_host=to_host, compact=compact)
         self._count_only = False
         _check(N.lib().jtk_batch_encode_pieces(self._h, text_u8.ctypes.data, doc_off.ctypes.data, len(doc_off) - 1,
                                                pb.ctypes.data, pe.ctypes.data, len(pb), flags, C.byref(nt)))
@@ -378,13 +432,8 @@ class Batch:
         nt, nd, _ = self.result()
         a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
         _check(N.lib().jtk_batch_host_result(self._h, C.byref(a), C.byref(b), C.byref(c)))
-
-        def view(ptr, n, ctype, dtype):
-            if not ptr or n == 0:
-                return np.zeros(0, dtype=dtype)
-            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), shape=(n,))
-        tokens = view(a.value, nt, C.c_int32, np.int32)
-        return BatchResult(tokens, view(b.value, nd + 1, C.c_int64, np.int64), view(c.value, nd, C.c_int32, np.int32))
+        return BatchResult(_view(a.value, nt, C.c_int32, np.int32), _view(b.value, nd + 1, C.c_int64, np.int64),
+                           _view(c.value, nd, C.c_int32, np.int32))
 
     def host_result_compact(self):
         """After encode_host(to_host=True, compact=True): zero-copy numpy views of the pinned planes as a CompactBatchResult
@@ -393,16 +442,11 @@ class Batch:
         lo, hi, t, s = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
         bits = C.c_int(0)
         _check(N.lib().jtk_batch_host_result_compact(self._h, C.byref(lo), C.byref(hi), C.byref(bits), C.byref(t), C.byref(s)))
-
-        def view(ptr, n, ctype, dtype):
-            if not ptr or n == 0:
-                return np.zeros(0, dtype=dtype)
-            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), shape=(n,))
         hb = bits.value - 16
         n_lo = nt if lo.value else 0
-        return CompactBatchResult(view(lo.value, n_lo, C.c_uint16, np.uint16),
-                                  view(hi.value, (n_lo * hb + 31) // 32, C.c_uint32, np.uint32) if hb else None, bits.value,
-                                  view(t.value, nd + 1, C.c_int64, np.int64), view(s.value, nd, C.c_int32, np.int32))
+        return CompactBatchResult(_view(lo.value, n_lo, C.c_uint16, np.uint16),
+                                  _view(hi.value, (n_lo * hb + 31) // 32, C.c_uint32, np.uint32) if hb else None, bits.value,
+                                  _view(t.value, nd + 1, C.c_int64, np.int64), _view(s.value, nd, C.c_int32, np.int32))
 
     def compact(self, d_lo_ptr, d_hi_ptr, stream=None):
         """jtk_batch_compact on the last encode: uint16 [n_tokens] at d_lo_ptr and uint32 [ceil(n_tokens * (id_bits - 16) / 32)]
@@ -432,9 +476,7 @@ class Batch:
     def encode_device(self, d_text_ptr, d_doc_off_ptr, n_docs, n_bytes, ordinary=False, stream=None, sync=True,
                       allow_special=False, validate=False, count_only=False, fim=False):
         nt = C.c_int64(0)
-        flags = ((N.JTK_ENCODE_ORDINARY if ordinary else 0) | (N.JTK_ENCODE_ALLOW_SPECIAL if allow_special else 0)
-                 | (N.JTK_ENCODE_VALIDATE_UTF8 if validate else 0) | (N.JTK_ENCODE_COUNT_ONLY if count_only else 0)
-                 | (N.JTK_ENCODE_FIM if fim else 0))
+        flags = _encode_flags(ordinary, validate, count_only, allow_special=allow_special, fim=fim)
         _check(N.lib().jtk_batch_encode_device(self._h, d_text_ptr, d_doc_off_ptr, n_docs, n_bytes, flags, stream,
                                                C.byref(nt) if sync else None))
         return nt.value if sync else None
@@ -727,17 +769,11 @@ class Batch:
         _check(N.lib().jtk_batch_utf8_device_result(self._h, C.byref(a), C.byref(o), C.byref(nb)))
         return a.value, o.value, nb.value
 
-    @staticmethod
-    def _utf16_flags(ordinary, allow_special, validate, count_only, to_host):
-        return ((N.JTK_ENCODE_ORDINARY if ordinary else 0) | (N.JTK_ENCODE_ALLOW_SPECIAL if allow_special else 0)
-                | (N.JTK_ENCODE_VALIDATE_UTF8 if validate else 0) | (N.JTK_ENCODE_COUNT_ONLY if count_only else 0)
-                | (N.JTK_ENCODE_TO_HOST if to_host else 0))
-
     def encode_utf16_device(self, d_units_ptr, d_unit_off_ptr, n_docs, n_units, ordinary=False, stream=None, sync=True,
                             allow_special=False, validate=False, count_only=False, to_host=False):
         """jtk_batch_encode_utf16_device: the transcode, then the encode of the owned text (to_host: the library refuses it)."""
         nt = C.c_int64(0)
-        flags = self._utf16_flags(ordinary, allow_special, validate, count_only, to_host)
+        flags = _encode_flags(ordinary, validate, count_only, to_host, allow_special)
         self._count_only = count_only
         _check(N.lib().jtk_batch_encode_utf16_device(self._h, d_units_ptr, d_unit_off_ptr, n_docs, n_units, flags, stream,
                                                      C.byref(nt) if sync else None))
@@ -751,7 +787,7 @@ class Batch:
             # (the C entry takes n_units = unit_off[n_docs]: only here is the length of the array known)
             raise ValueError("unit_off needs n_docs + 1 entries and must end at or below len(units)")
         nt = C.c_int64(0)
-        flags = self._utf16_flags(ordinary, allow_special, validate, count_only, to_host)
+        flags = _encode_flags(ordinary, validate, count_only, to_host, allow_special)
         self._count_only = count_only
         _check(N.lib().jtk_batch_encode_utf16(self._h, units.ctypes.data if len(units) else None, unit_off.ctypes.data, len(unit_off) - 1,
                                               flags, C.byref(nt)))
@@ -1046,11 +1082,7 @@ class HipEncoding:
         (JTK_ENCODE_ALLOW_SPECIAL; the rule is in include/jtokkit_amd.h).  fim: a FimParams -- the fill-in-the-middle
         transformation of every document it draws (JTK_ENCODE_FIM; with ordinary=True); the result then also has .fim_kind,
         .fim_cut and .fim_part_tok (Batch.fim_result)."""
-        bs = [t if isinstance(t, (bytes, bytearray)) else t.encode("utf-8") for t in texts]
-        doc_off = np.zeros(len(bs) + 1, dtype=np.int64)
-        if bs:
-            np.cumsum([len(b) for b in bs], out=doc_off[1:])
-        text = np.frombuffer(b"".join(bs), dtype=np.uint8) if doc_off[-1] else np.zeros(0, dtype=np.uint8)
+        _, text, doc_off = _join_texts(texts)
         return self.encode_batch_packed(text, doc_off, ordinary, validate, allowed_special, fim=fim)
 
     def encode_batch_packed(self, text_u8, doc_off, ordinary=False, validate=False, allowed_special=None, compact=False, fim=None):
@@ -1089,23 +1121,17 @@ class HipEncoding:
         unit "char": indices into the Python str (text[begin:end] holds the token's characters; a token that starts inside a
         character begins at that character, one that ends inside a character ends after it -- tiktoken's decode_with_offsets
         convention for begin); "utf16": indices into a Java String; "byte": the token's own bytes, unrounded."""
-        bs = [t if isinstance(t, (bytes, bytearray)) else t.encode("utf-8") for t in texts]
-        doc_off = np.zeros(len(bs) + 1, dtype=np.int64)
-        if bs:
-            np.cumsum([len(b) for b in bs], out=doc_off[1:])
-        text = np.frombuffer(b"".join(bs), dtype=np.uint8) if doc_off[-1] else np.zeros(0, dtype=np.uint8)
+        bs, text, doc_off = _join_texts(texts)
         u = self._char_unit(unit, "encode_batch_with_offsets")
         res = self.encode_batch_packed(text, doc_off, ordinary, False, allowed_special)
         nt = len(res.tokens)
         b = self._b()
-        bufs = []
-        try:
-            for _ in range(2):
-                bufs.append(_DeviceArray(np.zeros(nt, dtype=np.int64)))
+        with _device_arrays() as put:
+            d_begin, d_end = put(np.zeros(nt, dtype=np.int64)), put(np.zeros(nt, dtype=np.int64))
             if u is None:
-                b.token_offsets(bufs[0].ptr)
+                b.token_offsets(d_begin.ptr)
                 _stream_sync(b.stream())
-                pos = bufs[0].fetch()
+                pos = d_begin.fetch()
                 counts = np.diff(res.tok_off)
                 doc = np.repeat(np.arange(len(bs)), counts)
                 begin = pos - doc_off[doc]
@@ -1114,17 +1140,81 @@ class HipEncoding:
                 last = res.tok_off[1:][counts > 0] - 1
                 end[last] = (doc_off[1:] - doc_off[:-1])[doc[last]]             # ... a document's last token at its end
                 return res, begin, end
-            b.token_char_offsets(u, bufs[0].ptr, bufs[1].ptr)
+            b.token_char_offsets(u, d_begin.ptr, d_end.ptr)
             _stream_sync(b.stream())
-            return res, bufs[0].fetch(), bufs[1].fetch()
-        finally:
-            for x in bufs:
-                x.free()
+            return res, d_begin.fetch(), d_end.fetch()
 
     @property
     def id_bits(self):
         """Bits per id of the compact format: 16 + the high bits per token (jtk_encoding_id_bits)."""
         return N.lib().jtk_encoding_id_bits(self._h)
+
+    # ---- what the *_device methods share ---------------------------------------------------------------
+    def _check_device_inputs(self, what, *inputs):
+        """Every (name, tensor, dtype) of `inputs` is a contiguous 1-d CUDA tensor of that dtype on this encoding's device."""
+        import torch
+        if self._host_pattern is not None:
+            raise ValueError("%s: the device cannot run this encoding's custom split pattern" % what)
+        dev = N.lib().jtk_encoding_device(self._h)
+        for name, t, dt in inputs:
+            if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != dt or t.dim() != 1:
+                raise ValueError("%s must be a 1-d CUDA tensor of %s" % (name, dt))
+            if t.device.index != dev:
+                raise ValueError("%s is on cuda:%s, the encoding on cuda:%d" % (name, t.device.index, dev))
+            if not t.is_contiguous():
+                raise ValueError("%s must be contiguous" % name)
+
+    @staticmethod
+    def _n_docs(doc_off):
+        nd = doc_off.numel() - 1
+        if nd < 0:
+            raise ValueError("doc_off needs n_docs + 1 entries")
+        return nd
+
+    @contextlib.contextmanager
+    def _on_current_stream(self, b, device):
+        """Yields the raw handle of the stream a *_device method queues its work on: torch's current stream.  When that is the
+        legacy default stream, whose NULL handle means "the batch's own stream" to the library -- a non-blocking stream that
+        does not order against it --, the work goes to the batch's own stream explicitly, forked from the current stream on
+        entry and joined into it on exit, also when the body raises: what it has queued by then still orders before the
+        caller's next work."""
+        import torch
+        cur = torch.cuda.current_stream(device)
+        if cur.cuda_stream != 0:
+            yield cur.cuda_stream
+            return
+        side = torch.cuda.ExternalStream(b.stream(), device=device)
+        side.wait_stream(cur)
+        try:
+            yield side.cuda_stream
+        finally:
+            cur.wait_stream(side)
+
+    @contextlib.contextmanager
+    def _encode_device_batch(self, text, doc_off, ordinary, allow, fim=False):
+        """The encode of a checked device-resident batch, queued without a wait for its token count; yields (batch, n_docs,
+        device, stream) with _on_current_stream held for the method's post-passes and copies.  The staged text lives until the
+        block is left."""
+        import torch
+        nd = self._n_docs(doc_off)
+        device, n = text.device, text.numel()
+        st = text.untyped_storage()
+        if text.data_ptr() % 16 or st.data_ptr() + st.nbytes() < text.data_ptr() + (n + 15) // 16 * 16:
+            # (the encode reads whole aligned 16-byte blocks; the copy runs on the current stream, so before the fork below)
+            buf = torch.zeros((n + 15) // 16 * 16 + 16, dtype=torch.uint8, device=device)
+            buf[:n].copy_(text)
+            text = buf
+        b = self._b()
+        with self._on_current_stream(b, device) as stream:
+            b.encode_device(text.data_ptr(), doc_off.data_ptr(), nd, n, ordinary, stream=stream, sync=False, allow_special=allow, fim=fim)
+            yield b, nd, device, stream
+
+    @staticmethod
+    def _tok_off_and_status(b, nd, device, stream):
+        """(tok_off int64 [n_docs + 1], status int32 [n_docs]) of the batch's last encode as new CUDA tensors."""
+        import torch
+        _, p_off, p_status = b.device_result()
+        return _device_copy(p_off, nd + 1, torch.int64, device, stream), _device_copy(p_status, nd, torch.int32, device, stream)
 
     def compact_batch_device(self, text, doc_off, ordinary=False, allowed_special=None):
         """Encodes a device-resident batch and returns its ids compact, as CUDA tensors written on torch.cuda.current_stream():
@@ -1133,41 +1223,15 @@ class HipEncoding:
         CUDA torch.int64 tensor [n_docs + 1], on this encoding's device.  Waits once, for the token count (and, with
         allowed_special -- as for encode_batch --, once more for the encode's count of literal candidates)."""
         import torch
-        self._check_device_inputs("compact_batch_device", text, doc_off)
+        self._check_device_inputs("compact_batch_device", ("text", text, torch.uint8), ("doc_off", doc_off, torch.int64))
         allow = self._allow(self._b(), allowed_special)
-        nd = doc_off.numel() - 1
-        if nd < 0:
-            raise ValueError("doc_off needs n_docs + 1 entries")
-        device = text.device
-        n = text.numel()
-        st = text.untyped_storage()
-        if text.data_ptr() % 16 or st.data_ptr() + st.nbytes() < text.data_ptr() + (n + 15) // 16 * 16:
-            # (the encode reads whole aligned 16-byte blocks)
-            buf = torch.zeros((n + 15) // 16 * 16 + 16, dtype=torch.uint8, device=device)
-            buf[:n].copy_(text)
-            text = buf
-        b = self._b()
-        cur = torch.cuda.current_stream(device)
-        side = None
-        if cur.cuda_stream == 0:
-            # (the legacy default stream: see chunk_batch_device)
-            side = torch.cuda.ExternalStream(b.stream(), device=device)
-            side.wait_stream(cur)
-        stream = (side or cur).cuda_stream
-        b.encode_device(text.data_ptr(), doc_off.data_ptr(), nd, n, ordinary, stream=stream, sync=False, allow_special=allow)
-        nt = b.result()[0]
-        hb = self.id_bits - 16
-        lo = torch.empty(nt, dtype=torch.uint16, device=device)
-        hi = torch.empty((nt * hb + 31) // 32, dtype=torch.int32, device=device) if hb else None
-        b.compact(lo.data_ptr() if nt else None, hi.data_ptr() if hb and nt else None, stream)
-        tok_off = torch.empty(nd + 1, dtype=torch.int64, device=device)
-        status = torch.empty(nd, dtype=torch.int32, device=device)
-        _, p_off, p_status = b.device_result()
-        for t, src in ((tok_off, p_off), (status, p_status)):
-            if t.numel():
-                _copy_d2d(t.data_ptr(), src, t.numel() * t.element_size(), stream)
-        if side is not None:
-            cur.wait_stream(side)
+        with self._encode_device_batch(text, doc_off, ordinary, allow) as (b, nd, device, stream):
+            nt = b.result()[0]
+            hb = self.id_bits - 16
+            lo = torch.empty(nt, dtype=torch.uint16, device=device)
+            hi = torch.empty((nt * hb + 31) // 32, dtype=torch.int32, device=device) if hb else None
+            b.compact(lo.data_ptr() if nt else None, hi.data_ptr() if hb and nt else None, stream)
+            tok_off, status = self._tok_off_and_status(b, nd, device, stream)
         return lo, hi, tok_off, status
 
     def minhash_batch(self, texts, ngram=5, num_hashes=128, bands=0, seed=0, ordinary=True, allowed_special=None):
@@ -1175,26 +1239,16 @@ class HipEncoding:
         include/jtokkit_amd.h): (sig uint32 [n, num_hashes], n_shingles int32 [n], band_keys uint64 [n, bands] or None when
         bands == 0).  The fraction of columns on which two rows agree estimates the Jaccard similarity of the two documents'
         n-gram sets; a refused document (status < 0) has no shingles and a row of 0xFFFFFFFF."""
-        bs = [t if isinstance(t, (bytes, bytearray)) else t.encode("utf-8") for t in texts]
-        doc_off = np.zeros(len(bs) + 1, dtype=np.int64)
-        if bs:
-            np.cumsum([len(b) for b in bs], out=doc_off[1:])
-        text = np.frombuffer(b"".join(bs), dtype=np.uint8) if doc_off[-1] else np.zeros(0, dtype=np.uint8)
+        bs, text, doc_off = _join_texts(texts)
         self.encode_batch_packed(text, doc_off, ordinary, False, allowed_special)
         n = len(bs)
         b = self._b()
-        bufs = []
-        try:
-            bufs.append(_DeviceArray(np.zeros((n, num_hashes), dtype=np.uint32)))
-            bufs.append(_DeviceArray(np.zeros(n, dtype=np.int32)))
-            if bands:
-                bufs.append(_DeviceArray(np.zeros((n, bands), dtype=np.uint64)))
-            b.minhash(bufs[0].ptr, ngram, num_hashes, bands, seed, bufs[1].ptr, bufs[2].ptr if bands else None)
+        with _device_arrays() as put:
+            sig, n_shingles = put(np.zeros((n, num_hashes), dtype=np.uint32)), put(np.zeros(n, dtype=np.int32))
+            keys = put(np.zeros((n, bands), dtype=np.uint64)) if bands else None
+            b.minhash(sig.ptr, ngram, num_hashes, bands, seed, n_shingles.ptr, keys.ptr if bands else None)
             _stream_sync(b.stream())
-            return bufs[0].fetch(), bufs[1].fetch(), bufs[2].fetch() if bands else None
-        finally:
-            for x in bufs:
-                x.free()
+            return sig.fetch(), n_shingles.fetch(), keys.fetch() if bands else None
 
     def minhash_batch_device(self, text, doc_off, ngram=5, num_hashes=128, bands=0, seed=0, ordinary=True, allowed_special=None):
         """Encodes a device-resident batch (text CUDA torch.uint8, doc_off CUDA torch.int64 [n_docs + 1]) and returns its MinHash
@@ -1203,41 +1257,15 @@ class HipEncoding:
         None when bands == 0, tok_off int64 [n_docs + 1], status int32 [n_docs]).  The ids stay in the batch (device_result).
         Waits once, for the token count (and, with allowed_special, once more for the encode's count of literal candidates)."""
         import torch
-        self._check_device_inputs("minhash_batch_device", text, doc_off)
+        self._check_device_inputs("minhash_batch_device", ("text", text, torch.uint8), ("doc_off", doc_off, torch.int64))
         allow = self._allow(self._b(), allowed_special)
-        nd = doc_off.numel() - 1
-        if nd < 0:
-            raise ValueError("doc_off needs n_docs + 1 entries")
-        device = text.device
-        n = text.numel()
-        st = text.untyped_storage()
-        if text.data_ptr() % 16 or st.data_ptr() + st.nbytes() < text.data_ptr() + (n + 15) // 16 * 16:
-            # (the encode reads whole aligned 16-byte blocks)
-            buf = torch.zeros((n + 15) // 16 * 16 + 16, dtype=torch.uint8, device=device)
-            buf[:n].copy_(text)
-            text = buf
-        b = self._b()
-        cur = torch.cuda.current_stream(device)
-        side = None
-        if cur.cuda_stream == 0:
-            # (the legacy default stream: see chunk_batch_device)
-            side = torch.cuda.ExternalStream(b.stream(), device=device)
-            side.wait_stream(cur)
-        stream = (side or cur).cuda_stream
-        b.encode_device(text.data_ptr(), doc_off.data_ptr(), nd, n, ordinary, stream=stream, sync=False, allow_special=allow)
-        sig = torch.empty((nd, num_hashes), dtype=torch.int32, device=device)
-        n_shingles = torch.empty(nd, dtype=torch.int32, device=device)
-        band_keys = torch.empty((nd, bands), dtype=torch.int64, device=device) if bands else None
-        b.minhash(sig.data_ptr() if nd else None, ngram, num_hashes, bands, seed, n_shingles.data_ptr() if nd else None,
-                  band_keys.data_ptr() if bands and nd else None, stream)
-        tok_off = torch.empty(nd + 1, dtype=torch.int64, device=device)
-        status = torch.empty(nd, dtype=torch.int32, device=device)
-        _, p_off, p_status = b.device_result()
-        for t, src in ((tok_off, p_off), (status, p_status)):
-            if t.numel():
-                _copy_d2d(t.data_ptr(), src, t.numel() * t.element_size(), stream)
-        if side is not None:
-            cur.wait_stream(side)
+        with self._encode_device_batch(text, doc_off, ordinary, allow) as (b, nd, device, stream):
+            sig = torch.empty((nd, num_hashes), dtype=torch.int32, device=device)
+            n_shingles = torch.empty(nd, dtype=torch.int32, device=device)
+            band_keys = torch.empty((nd, bands), dtype=torch.int64, device=device) if bands else None
+            b.minhash(sig.data_ptr() if nd else None, ngram, num_hashes, bands, seed, n_shingles.data_ptr() if nd else None,
+                      band_keys.data_ptr() if bands and nd else None, stream)
+            tok_off, status = self._tok_off_and_status(b, nd, device, stream)
         return sig, n_shingles, band_keys, tok_off, status
 
     def ngram_set(self, ngram, seed=0):
@@ -1249,26 +1277,16 @@ class HipEncoding:
         include/jtokkit_amd.h): (flags uint8 [n_tokens] -- JTK_NG_START | JTK_NG_COVERED per token --, n_hit int32 [n],
         n_covered int32 [n], first_hit int64 [n] -- the document-relative index of the first start, or -1 --, tok_off int64
         [n + 1]).  The covered tokens of document d are the set bits of flags[tok_off[d]:tok_off[d + 1]] & JTK_NG_COVERED."""
-        bs = [t if isinstance(t, (bytes, bytearray)) else t.encode("utf-8") for t in texts]
-        doc_off = np.zeros(len(bs) + 1, dtype=np.int64)
-        if bs:
-            np.cumsum([len(b) for b in bs], out=doc_off[1:])
-        text = np.frombuffer(b"".join(bs), dtype=np.uint8) if doc_off[-1] else np.zeros(0, dtype=np.uint8)
+        bs, text, doc_off = _join_texts(texts)
         res = self.encode_batch_packed(text, doc_off, ordinary, False, allowed_special)
         n = len(bs)
         b = self._b()
-        bufs = []
-        try:
-            bufs.append(_DeviceArray(np.zeros(len(res.tokens), dtype=np.uint8)))
-            bufs.append(_DeviceArray(np.zeros(n, dtype=np.int32)))
-            bufs.append(_DeviceArray(np.zeros(n, dtype=np.int32)))
-            bufs.append(_DeviceArray(np.zeros(n, dtype=np.int64)))
-            b.ngram_overlap(ngram_set, *[x.ptr for x in bufs])
+        with _device_arrays() as put:
+            outs = [put(np.zeros(len(res.tokens), dtype=np.uint8)), put(np.zeros(n, dtype=np.int32)), put(np.zeros(n, dtype=np.int32)),
+                    put(np.zeros(n, dtype=np.int64))]
+            b.ngram_overlap(ngram_set, *[x.ptr for x in outs])
             _stream_sync(b.stream())
-            return tuple(x.fetch() for x in bufs) + (res.tok_off.copy(),)
-        finally:
-            for x in bufs:
-                x.free()
+            return tuple(x.fetch() for x in outs) + (res.tok_off.copy(),)
 
     def ngram_overlap_batch_device(self, text, doc_off, ngram_set, ordinary=True, allowed_special=None):
         """Encodes a device-resident batch (text CUDA torch.uint8, doc_off CUDA torch.int64 [n_docs + 1]) and returns its
@@ -1277,43 +1295,17 @@ class HipEncoding:
         ids stay in the batch (device_result).  Waits once, for the token count (and, with allowed_special, once more for the
         encode's count of literal candidates)."""
         import torch
-        self._check_device_inputs("ngram_overlap_batch_device", text, doc_off)
+        self._check_device_inputs("ngram_overlap_batch_device", ("text", text, torch.uint8), ("doc_off", doc_off, torch.int64))
         allow = self._allow(self._b(), allowed_special)
-        nd = doc_off.numel() - 1
-        if nd < 0:
-            raise ValueError("doc_off needs n_docs + 1 entries")
-        device = text.device
-        n = text.numel()
-        st = text.untyped_storage()
-        if text.data_ptr() % 16 or st.data_ptr() + st.nbytes() < text.data_ptr() + (n + 15) // 16 * 16:
-            # (the encode reads whole aligned 16-byte blocks)
-            buf = torch.zeros((n + 15) // 16 * 16 + 16, dtype=torch.uint8, device=device)
-            buf[:n].copy_(text)
-            text = buf
-        b = self._b()
-        cur = torch.cuda.current_stream(device)
-        side = None
-        if cur.cuda_stream == 0:
-            # (the legacy default stream: see chunk_batch_device)
-            side = torch.cuda.ExternalStream(b.stream(), device=device)
-            side.wait_stream(cur)
-        stream = (side or cur).cuda_stream
-        b.encode_device(text.data_ptr(), doc_off.data_ptr(), nd, n, ordinary, stream=stream, sync=False, allow_special=allow)
-        nt = b.result()[0]
-        flags = torch.empty(nt, dtype=torch.uint8, device=device)
-        n_hit = torch.empty(nd, dtype=torch.int32, device=device)
-        n_covered = torch.empty(nd, dtype=torch.int32, device=device)
-        first_hit = torch.empty(nd, dtype=torch.int64, device=device)
-        b.ngram_overlap(ngram_set, flags.data_ptr() if nt else None, n_hit.data_ptr() if nd else None, n_covered.data_ptr() if nd else None,
-                        first_hit.data_ptr() if nd else None, stream)
-        tok_off = torch.empty(nd + 1, dtype=torch.int64, device=device)
-        status = torch.empty(nd, dtype=torch.int32, device=device)
-        _, p_off, p_status = b.device_result()
-        for t, src in ((tok_off, p_off), (status, p_status)):
-            if t.numel():
-                _copy_d2d(t.data_ptr(), src, t.numel() * t.element_size(), stream)
-        if side is not None:
-            cur.wait_stream(side)
+        with self._encode_device_batch(text, doc_off, ordinary, allow) as (b, nd, device, stream):
+            nt = b.result()[0]
+            flags = torch.empty(nt, dtype=torch.uint8, device=device)
+            n_hit = torch.empty(nd, dtype=torch.int32, device=device)
+            n_covered = torch.empty(nd, dtype=torch.int32, device=device)
+            first_hit = torch.empty(nd, dtype=torch.int64, device=device)
+            b.ngram_overlap(ngram_set, flags.data_ptr() if nt else None, n_hit.data_ptr() if nd else None,
+                            n_covered.data_ptr() if nd else None, first_hit.data_ptr() if nd else None, stream)
+            tok_off, status = self._tok_off_and_status(b, nd, device, stream)
         return flags, n_hit, n_covered, first_hit, tok_off, status
 
     def near_duplicates(self, texts, threshold=0.8, ngram=5, num_hashes=128, bands=16, seed=0, ordinary=True, allowed_special=None):
@@ -1327,18 +1319,16 @@ class HipEncoding:
         import torch
         if bands < 1:
             raise ValueError("near_duplicates needs bands >= 1")
-        bs = [t if isinstance(t, (bytes, bytearray)) else t.encode("utf-8") for t in texts]
+        bs, text, doc_off = _join_texts(texts)
         n = len(bs)
         labels = np.arange(n, dtype=np.int64)
         if n < 2:
             return labels
         device = torch.device("cuda", N.lib().jtk_encoding_device(self._h))
-        lens = np.array([len(x) for x in bs], dtype=np.int64)
-        doc_off = torch.from_numpy(np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)).to(device)
-        blob = b"".join(bs)
-        if not blob:
+        if not len(text):
             return labels
-        text = torch.from_numpy(np.frombuffer(blob, dtype=np.uint8).copy()).to(device)
+        doc_off = torch.from_numpy(doc_off).to(device)
+        text = torch.from_numpy(text.copy()).to(device)                          # (a copy: frombuffer views are read-only)
         sig, n_shingles, band_keys, _, _ = self.minhash_batch_device(text, doc_off, ngram, num_hashes, bands, seed, ordinary, allowed_special)
         live = torch.nonzero(n_shingles > 0).flatten()
         if live.numel() < 2:
@@ -1356,14 +1346,8 @@ class HipEncoding:
         pb = (codes - pa * n).contiguous()
         agree = torch.empty(codes.numel(), dtype=torch.int32, device=device)
         b = self._b()
-        cur = torch.cuda.current_stream(device)
-        side = None
-        if cur.cuda_stream == 0:
-            side = torch.cuda.ExternalStream(b.stream(), device=device)
-            side.wait_stream(cur)
-        b.minhash_agree(sig.data_ptr(), n, num_hashes, pa.data_ptr(), pb.data_ptr(), codes.numel(), agree.data_ptr(), (side or cur).cuda_stream)
-        if side is not None:
-            cur.wait_stream(side)
+        with self._on_current_stream(b, device) as stream:
+            b.minhash_agree(sig.data_ptr(), n, num_hashes, pa.data_ptr(), pb.data_ptr(), codes.numel(), agree.data_ptr(), stream)
         keep = agree >= int(math.ceil(threshold * num_hashes))
         pa, pb = pa[keep].cpu().numpy(), pb[keep].cpu().numpy()
         parent = list(range(n))
@@ -1411,9 +1395,8 @@ class HipEncoding:
         allowed set raises UnsupportedOperationError, as encode() does; with it, such literals are ordinary text."""
         if text is None:
             return []
-        b = text if isinstance(text, (bytes, bytearray)) else text.encode("utf-8")
-        res = self.encode_batch_packed(np.frombuffer(bytes(b), dtype=np.uint8), np.array([0, len(b)], dtype=np.int64), ordinary,
-                                       False, allowed_special)
+        _, text_u8, doc_off = _join_texts([text])
+        res = self.encode_batch_packed(text_u8, doc_off, ordinary, False, allowed_special)
         if res.status[0] < 0:
             _check(int(res.status[0]))
         return res.tokens.tolist()
@@ -1443,11 +1426,7 @@ class HipEncoding:
     def encode_batch_max_tokens(self, texts, max_tokens, ordinary=False):
         """List of str/bytes -> list of EncodingResult, as Encoding.encode(text, maxTokens) gives for each.  Only the leading
         bytes of each document are encoded (jtk_batch_encode_max_tokens), as the reference stops matching at maxTokens."""
-        bs = [t if isinstance(t, (bytes, bytearray)) else t.encode("utf-8") for t in texts]
-        doc_off = np.zeros(len(bs) + 1, dtype=np.int64)
-        if bs:
-            np.cumsum([len(x) for x in bs], out=doc_off[1:])
-        text = np.frombuffer(b"".join(bs), dtype=np.uint8) if doc_off[-1] else np.zeros(0, dtype=np.uint8)
+        bs, text, doc_off = _join_texts(texts)
         if self._host_pattern is not None or len(bs) * max(0, int(max_tokens)) > (1 << 28):
             # a custom pattern (matched on the host), or a limit so large that n_docs x max_tokens ids are no sensible array:
             # encode whole, cut on the device
@@ -1468,13 +1447,11 @@ class HipEncoding:
         tensors (tokens int32 [n_docs, max_tokens] -- `out` if given --, kept int64, truncated bool, status int32), written on
         torch.cuda.current_stream().  Per-document statuses come back in `status`; they do not raise."""
         import torch
-        self._check_device_inputs("encode_batch_max_tokens_device", text, doc_off)
+        self._check_device_inputs("encode_batch_max_tokens_device", ("text", text, torch.uint8), ("doc_off", doc_off, torch.int64))
         mt = int(max_tokens)
         if mt < 0:
             raise ValueError("max_tokens must be >= 0")
-        nd = doc_off.numel() - 1
-        if nd < 0:
-            raise ValueError("doc_off needs n_docs + 1 entries")
+        nd = self._n_docs(doc_off)
         device = text.device
         if out is None:
             out = torch.empty((nd, mt), dtype=torch.int32, device=device)
@@ -1489,19 +1466,6 @@ class HipEncoding:
             self._b().encode_device_max_tokens(text.data_ptr(), doc_off.data_ptr(), nd, text.numel(), mt, out.data_ptr(),
                                                kept.data_ptr(), truncated.data_ptr(), status.data_ptr(), ordinary, pad_id, stream)
         return out, kept, truncated, status
-
-    def _check_device_inputs(self, what, text, doc_off):
-        import torch
-        if self._host_pattern is not None:
-            raise ValueError("%s: the device cannot run this encoding's custom split pattern" % what)
-        dev = N.lib().jtk_encoding_device(self._h)
-        for name, t, dt in (("text", text, torch.uint8), ("doc_off", doc_off, torch.int64)):
-            if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != dt or t.dim() != 1:
-                raise ValueError("%s must be a 1-d CUDA tensor of %s" % (name, dt))
-            if t.device.index != dev:
-                raise ValueError("%s is on cuda:%s, the encoding on cuda:%d" % (name, t.device.index, dev))
-            if not t.is_contiguous():
-                raise ValueError("%s must be contiguous" % name)
 
     def chunk_batch(self, texts, chunk_tokens, overlap=0, ordinary=False, allowed_special=None, unit="byte", prefer=None,
                     min_tokens=None):
@@ -1518,11 +1482,7 @@ class HipEncoding:
         gain a fifth field, the JTK_LEVEL_* of the chunk's end (6: the document's end)."""
         u = self._char_unit(unit, "chunk_batch")
         leveled = prefer is not None or min_tokens is not None
-        bs = [t if isinstance(t, (bytes, bytearray)) else t.encode("utf-8") for t in texts]
-        doc_off = np.zeros(len(bs) + 1, dtype=np.int64)
-        if bs:
-            np.cumsum([len(x) for x in bs], out=doc_off[1:])
-        text = np.frombuffer(b"".join(bs), dtype=np.uint8) if doc_off[-1] else np.zeros(0, dtype=np.uint8)
+        bs, text, doc_off = _join_texts(texts)
         res = self.encode_batch_packed(text, doc_off, ordinary, False, allowed_special)
         if len(res.status) and res.status.min() < 0:
             _check(int(res.status.min()))
@@ -1537,17 +1497,12 @@ class HipEncoding:
         start, end = f["byte_begin"] - doc_off[f["doc"]], f["byte_end"] - doc_off[f["doc"]]
         if u is not None and nc:
             p_doc, p_bb, p_be = (b.chunk_device_result()[i] for i in (1, 4, 5))
-            bufs = []
-            try:
-                for _ in range(2):
-                    bufs.append(_DeviceArray(np.zeros(nc, dtype=np.int64)))
-                b.char_positions(u, p_bb, nc, bufs[0].ptr, "floor", p_doc)
-                b.char_positions(u, p_be, nc, bufs[1].ptr, "ceil", p_doc)
+            with _device_arrays() as put:
+                d_start, d_end = put(np.zeros(nc, dtype=np.int64)), put(np.zeros(nc, dtype=np.int64))
+                b.char_positions(u, p_bb, nc, d_start.ptr, "floor", p_doc)
+                b.char_positions(u, p_be, nc, d_end.ptr, "ceil", p_doc)
                 _stream_sync(b.stream())
-                start, end = bufs[0].fetch(), bufs[1].fetch()
-            finally:
-                for x in bufs:
-                    x.free()
+                start, end = d_start.fetch(), d_end.fetch()
         out = [[] for _ in bs]
         for c in range(nc):
             d, tb, n = int(f["doc"][c]), int(f["tok_begin"][c]), int(f["n_tok"][c])
@@ -1568,7 +1523,7 @@ class HipEncoding:
         prefer / min_tokens: as for chunk_batch (jtk_batch_chunk_prefer); the dict then also holds level uint8 [n_chunks], the
         JTK_LEVEL_* of every chunk's end, and the call waits for the encode before it waits for the chunk count."""
         import torch
-        self._check_device_inputs("chunk_batch_device", text, doc_off)
+        self._check_device_inputs("chunk_batch_device", ("text", text, torch.uint8), ("doc_off", doc_off, torch.int64))
         leveled = prefer is not None or min_tokens is not None
         mask = prefer_mask(0 if prefer is None else prefer)
         u = None if unit is None else _unit(unit)
@@ -1576,54 +1531,26 @@ class HipEncoding:
         N_, ov = int(chunk_tokens), int(overlap)
         if N_ < 1 or not 0 <= ov < N_:
             raise ValueError("need chunk_tokens >= 1 and 0 <= overlap < chunk_tokens")
-        nd = doc_off.numel() - 1
-        if nd < 0:
-            raise ValueError("doc_off needs n_docs + 1 entries")
-        device = text.device
-        n = text.numel()
-        st = text.untyped_storage()
-        if text.data_ptr() % 16 or st.data_ptr() + st.nbytes() < text.data_ptr() + (n + 15) // 16 * 16:
-            # (the encode reads whole aligned 16-byte blocks)
-            buf = torch.zeros((n + 15) // 16 * 16 + 16, dtype=torch.uint8, device=device)
-            buf[:n].copy_(text)
-            text = buf
-        b = self._b()
-        cur = torch.cuda.current_stream(device)
-        side = None
-        if cur.cuda_stream == 0:
-            # (the legacy default stream: a NULL handle means "the batch's own stream" to the library, a non-blocking stream
-            # that does not order against it -- so the work goes there explicitly, forked from and joined into `cur`)
-            side = torch.cuda.ExternalStream(b.stream(), device=device)
-            side.wait_stream(cur)
-        stream = (side or cur).cuda_stream
-        b.encode_device(text.data_ptr(), doc_off.data_ptr(), nd, n, ordinary, stream=stream, sync=False, allow_special=allow)
-        nc = b.chunk_prefer(N_, ov, min_tokens, mask, stream) if leveled else b.chunk(N_, ov, stream)
-        out = dict(rows=torch.empty((nc, N_), dtype=torch.int32, device=device),
-                   n_tok=torch.empty(nc, dtype=torch.int32, device=device), doc=torch.empty(nc, dtype=torch.int64, device=device),
-                   byte_begin=torch.empty(nc, dtype=torch.int64, device=device),
-                   byte_end=torch.empty(nc, dtype=torch.int64, device=device), split=torch.empty(nc, dtype=torch.bool, device=device),
-                   chunk_off=torch.empty(nd + 1, dtype=torch.int64, device=device),
-                   status=torch.empty(nd, dtype=torch.int32, device=device))
-        b.chunk_rows(pad_id, out["rows"].data_ptr(), stream)
-        p_off, p_doc, _, p_ntok, p_bb, p_be, p_split = b.chunk_device_result()
-        p_status = b.device_result()[2]
-        for key, src in (("chunk_off", p_off), ("doc", p_doc), ("n_tok", p_ntok), ("byte_begin", p_bb), ("byte_end", p_be),
-                         ("split", p_split), ("status", p_status)):
-            t = out[key]
-            if t.numel():
-                _copy_d2d(t.data_ptr(), src, t.numel() * t.element_size(), stream)
-        if leveled:
-            out["level"] = torch.empty(nc, dtype=torch.uint8, device=device)
-            if nc:
-                _copy_d2d(out["level"].data_ptr(), b.chunk_levels_device(), nc, stream)
-        if u is not None:
-            out["char_begin"] = torch.empty(nc, dtype=torch.int64, device=device)
-            out["char_end"] = torch.empty(nc, dtype=torch.int64, device=device)
-            if nc:
-                b.char_positions(u, p_bb, nc, out["char_begin"].data_ptr(), "floor", p_doc, stream)
-                b.char_positions(u, p_be, nc, out["char_end"].data_ptr(), "ceil", p_doc, stream)
-        if side is not None:
-            cur.wait_stream(side)
+        with self._encode_device_batch(text, doc_off, ordinary, allow) as (b, nd, device, stream):
+            nc = b.chunk_prefer(N_, ov, min_tokens, mask, stream) if leveled else b.chunk(N_, ov, stream)
+            out = dict.fromkeys(("rows", "n_tok", "doc", "byte_begin", "byte_end", "split", "chunk_off", "status"))   # (their order)
+            out["rows"] = torch.empty((nc, N_), dtype=torch.int32, device=device)
+            b.chunk_rows(pad_id, out["rows"].data_ptr(), stream)
+            p_off, p_doc, _, p_ntok, p_bb, p_be, p_split = b.chunk_device_result()
+            p_status = b.device_result()[2]
+            for key, src, n, dt in (("chunk_off", p_off, nd + 1, torch.int64), ("doc", p_doc, nc, torch.int64),
+                                    ("n_tok", p_ntok, nc, torch.int32), ("byte_begin", p_bb, nc, torch.int64),
+                                    ("byte_end", p_be, nc, torch.int64), ("split", p_split, nc, torch.bool),
+                                    ("status", p_status, nd, torch.int32)):
+                out[key] = _device_copy(src, n, dt, device, stream)
+            if leveled:
+                out["level"] = _device_copy(b.chunk_levels_device() if nc else None, nc, torch.uint8, device, stream)
+            if u is not None:
+                out["char_begin"] = torch.empty(nc, dtype=torch.int64, device=device)
+                out["char_end"] = torch.empty(nc, dtype=torch.int64, device=device)
+                if nc:
+                    b.char_positions(u, p_bb, nc, out["char_begin"].data_ptr(), "floor", p_doc, stream)
+                    b.char_positions(u, p_be, nc, out["char_end"].data_ptr(), "ceil", p_doc, stream)
         return out
 
     def _sep_id(self, sep):
@@ -1688,11 +1615,7 @@ class HipEncoding:
         if fim is not None and train_spans is not None:
             raise ValueError("fim= and train_spans= do not combine: after the transformation tokens have no positions in the text")
         su = self._char_unit(span_unit, "pack_batch") if train_spans is not None else None
-        bs = [t if isinstance(t, (bytes, bytearray)) else t.encode("utf-8") for t in texts]
-        doc_off = np.zeros(len(bs) + 1, dtype=np.int64)
-        if bs:
-            np.cumsum([len(x) for x in bs], out=doc_off[1:])
-        text = np.frombuffer(b"".join(bs), dtype=np.uint8) if doc_off[-1] else np.zeros(0, dtype=np.uint8)
+        bs, text, doc_off = _join_texts(texts)
         sep_id = self._sep_id(sep)
         if train_spans is not None:
             rule = _span_rule(span_rule)
@@ -1709,30 +1632,22 @@ class HipEncoding:
             f["fim_kind"], f["fim_cut"], f["fim_part_tok"] = res.fim_kind, res.fim_cut, res.fim_part_tok
         f["max_seqlen"] = mx
         if train_spans is not None:
-            bufs = []
-            try:
+            with _device_arrays() as put:
                 if su is not None:
                     # the ranges are checked against the documents' lengths in the unit, then become byte positions on the device
-                    units = _DeviceArray(np.zeros(max(len(bs), 1), dtype=np.int64))
-                    bufs.append(units)
+                    units = put(np.zeros(max(len(bs), 1), dtype=np.int64))
                     b.char_index(su, units.ptr)
                     _stream_sync(b.stream())
                     doc, begin, end = self._batch_spans(train_spans, doc_off, units.fetch()[:len(bs)])
-                    d_doc, d_begin, d_end = _DeviceArray(doc), _DeviceArray(begin), _DeviceArray(end)
-                    bufs += [d_doc, d_begin, d_end]
+                    d_doc, d_begin, d_end = put(doc), put(begin), put(end)
                     b.byte_positions(su, d_doc.ptr, d_begin.ptr, len(doc), d_begin.ptr)     # (in place: one lane per entry)
                     b.byte_positions(su, d_doc.ptr, d_end.ptr, len(doc), d_end.ptr)
                 else:
-                    d_begin, d_end = _DeviceArray(begin), _DeviceArray(end)
-                    bufs += [d_begin, d_end]
-                d_span = _DeviceArray(np.zeros(len(res.tokens), dtype=np.int32))
-                bufs.append(d_span)
+                    d_begin, d_end = put(begin), put(end)
+                d_span = put(np.zeros(len(res.tokens), dtype=np.int32))
                 b.token_spans(d_begin.ptr, d_end.ptr, len(begin), rule, d_span.ptr)
                 f["labels"] = b.pack_labels_fetch(d_span.ptr, ignore_index, label_shift, label_sep)   # (synchronises)
                 f["tok_span"] = d_span.fetch()
-            finally:
-                for x in bufs:
-                    x.free()
         return f
 
     def _check_device_spans(self, text, span_begin, span_end):
@@ -1762,7 +1677,7 @@ class HipEncoding:
         fim: a FimParams for the encode (with ordinary=True; not with spans: ValueError); the dict then also holds fim_kind uint8
         [n_docs], fim_cut int64 [n_docs, 2] and fim_part_tok int64 [n_docs, 3], written on the same stream."""
         import torch
-        self._check_device_inputs("pack_batch_device", text, doc_off)
+        self._check_device_inputs("pack_batch_device", ("text", text, torch.uint8), ("doc_off", doc_off, torch.int64))
         if (span_begin is None) != (span_end is None):
             raise ValueError("span_begin and span_end go together")
         if fim is not None and span_begin is not None:
@@ -1778,51 +1693,27 @@ class HipEncoding:
         sep_id = self._sep_id(sep)
         use_fim = self._fim(self._b(), fim, ordinary, allowed_special)
         allow = self._allow(self._b(), allowed_special)
-        nd = doc_off.numel() - 1
-        if nd < 0:
-            raise ValueError("doc_off needs n_docs + 1 entries")
-        device = text.device
-        n = text.numel()
-        st = text.untyped_storage()
-        if text.data_ptr() % 16 or st.data_ptr() + st.nbytes() < text.data_ptr() + (n + 15) // 16 * 16:
-            # (the encode reads whole aligned 16-byte blocks)
-            buf = torch.zeros((n + 15) // 16 * 16 + 16, dtype=torch.uint8, device=device)
-            buf[:n].copy_(text)
-            text = buf
-        b = self._b()
-        cur = torch.cuda.current_stream(device)
-        side = None
-        if cur.cuda_stream == 0:
-            # (the legacy default stream: as in chunk_batch_device, the work goes to the batch's own stream explicitly)
-            side = torch.cuda.ExternalStream(b.stream(), device=device)
-            side.wait_stream(cur)
-        stream = (side or cur).cuda_stream
-        b.encode_device(text.data_ptr(), doc_off.data_ptr(), nd, n, ordinary, stream=stream, sync=False, allow_special=allow, fim=use_fim)
-        nr, ns, mx = b.pack(L, sep_id, whole_docs, sep_first, drop_last, stream)
-        out = dict(rows=torch.empty((nr, L), dtype=torch.int32, device=device),
-                   positions=torch.empty((nr, L), dtype=torch.int32, device=device),
-                   cu_seqlens=torch.empty(ns + 1, dtype=torch.int32, device=device),
-                   seg_doc=torch.empty(ns, dtype=torch.int64, device=device),
-                   status=torch.empty(nd, dtype=torch.int32, device=device))
-        b.pack_write(pad_id, out["rows"].data_ptr(), out["positions"].data_ptr(), out["cu_seqlens"].data_ptr(),
-                     out["seg_doc"].data_ptr(), stream)
-        if nd:
-            _copy_d2d(out["status"].data_ptr(), b.device_result()[2], nd * 4, stream)
-        if use_fim:
-            out["fim_kind"] = torch.empty(nd, dtype=torch.uint8, device=device)
-            out["fim_cut"] = torch.empty((nd, 2), dtype=torch.int64, device=device)
-            out["fim_part_tok"] = torch.empty((nd, 3), dtype=torch.int64, device=device)
-            if nd:
-                for t, src in zip((out["fim_kind"], out["fim_cut"], out["fim_part_tok"]), b.fim_device_result()):
-                    _copy_d2d(t.data_ptr(), src, t.numel() * t.element_size(), stream)
-        if span_begin is not None:
-            nt = b.result()[0]
-            out["tok_span"] = torch.empty(nt, dtype=torch.int32, device=device)
-            out["labels"] = torch.empty((nr, L), dtype=torch.int32, device=device)
-            b.token_spans(span_begin.data_ptr(), span_end.data_ptr(), span_begin.numel(), rule, out["tok_span"].data_ptr(), stream)
-            b.pack_labels(out["tok_span"].data_ptr(), ignore_index, out["labels"].data_ptr(), label_shift, label_sep, stream)
-        if side is not None:
-            cur.wait_stream(side)
+        with self._encode_device_batch(text, doc_off, ordinary, allow, fim=use_fim) as (b, nd, device, stream):
+            nr, ns, mx = b.pack(L, sep_id, whole_docs, sep_first, drop_last, stream)
+            out = dict(rows=torch.empty((nr, L), dtype=torch.int32, device=device),
+                       positions=torch.empty((nr, L), dtype=torch.int32, device=device),
+                       cu_seqlens=torch.empty(ns + 1, dtype=torch.int32, device=device),
+                       seg_doc=torch.empty(ns, dtype=torch.int64, device=device))
+            b.pack_write(pad_id, out["rows"].data_ptr(), out["positions"].data_ptr(), out["cu_seqlens"].data_ptr(),
+                         out["seg_doc"].data_ptr(), stream)
+            # (the results are asked for only when there are documents to copy them for)
+            out["status"] = _device_copy(b.device_result()[2] if nd else None, nd, torch.int32, device, stream)
+            if use_fim:
+                srcs = b.fim_device_result() if nd else (None, None, None)
+                for key, shape, dt, src in zip(("fim_kind", "fim_cut", "fim_part_tok"), (nd, (nd, 2), (nd, 3)),
+                                               (torch.uint8, torch.int64, torch.int64), srcs):
+                    out[key] = _device_copy(src, shape, dt, device, stream)
+            if span_begin is not None:
+                nt = b.result()[0]
+                out["tok_span"] = torch.empty(nt, dtype=torch.int32, device=device)
+                out["labels"] = torch.empty((nr, L), dtype=torch.int32, device=device)
+                b.token_spans(span_begin.data_ptr(), span_end.data_ptr(), span_begin.numel(), rule, out["tok_span"].data_ptr(), stream)
+                b.pack_labels(out["tok_span"].data_ptr(), ignore_index, out["labels"].data_ptr(), label_shift, label_sep, stream)
         out["max_seqlen"] = mx
         return out
 
@@ -1833,41 +1724,15 @@ class HipEncoding:
         torch.int64, positions in `text`, sorted and disjoint) that holds it by `rule`, or -1 (jtk_label_rules.h).  The ids
         stay in the batch (device_result).  Waits once, for the token count."""
         import torch
-        self._check_device_inputs("token_spans_device", text, doc_off)
+        self._check_device_inputs("token_spans_device", ("text", text, torch.uint8), ("doc_off", doc_off, torch.int64))
         self._check_device_spans(text, span_begin, span_end)
         rule = _span_rule(rule)
         allow = self._allow(self._b(), allowed_special)
-        nd = doc_off.numel() - 1
-        if nd < 0:
-            raise ValueError("doc_off needs n_docs + 1 entries")
-        device = text.device
-        n = text.numel()
-        st = text.untyped_storage()
-        if text.data_ptr() % 16 or st.data_ptr() + st.nbytes() < text.data_ptr() + (n + 15) // 16 * 16:
-            # (the encode reads whole aligned 16-byte blocks)
-            buf = torch.zeros((n + 15) // 16 * 16 + 16, dtype=torch.uint8, device=device)
-            buf[:n].copy_(text)
-            text = buf
-        b = self._b()
-        cur = torch.cuda.current_stream(device)
-        side = None
-        if cur.cuda_stream == 0:
-            # (the legacy default stream: as in chunk_batch_device, the work goes to the batch's own stream explicitly)
-            side = torch.cuda.ExternalStream(b.stream(), device=device)
-            side.wait_stream(cur)
-        stream = (side or cur).cuda_stream
-        b.encode_device(text.data_ptr(), doc_off.data_ptr(), nd, n, ordinary, stream=stream, sync=False, allow_special=allow)
-        nt = b.result()[0]
-        tok_span = torch.empty(nt, dtype=torch.int32, device=device)
-        tok_off = torch.empty(nd + 1, dtype=torch.int64, device=device)
-        status = torch.empty(nd, dtype=torch.int32, device=device)
-        b.token_spans(span_begin.data_ptr(), span_end.data_ptr(), span_begin.numel(), rule, tok_span.data_ptr(), stream)
-        _, p_off, p_status = b.device_result()
-        _copy_d2d(tok_off.data_ptr(), p_off, (nd + 1) * 8, stream)
-        if nd:
-            _copy_d2d(status.data_ptr(), p_status, nd * 4, stream)
-        if side is not None:
-            cur.wait_stream(side)
+        with self._encode_device_batch(text, doc_off, ordinary, allow) as (b, nd, device, stream):
+            nt = b.result()[0]
+            tok_span = torch.empty(nt, dtype=torch.int32, device=device)
+            b.token_spans(span_begin.data_ptr(), span_end.data_ptr(), span_begin.numel(), rule, tok_span.data_ptr(), stream)
+            tok_off, status = self._tok_off_and_status(b, nd, device, stream)
         return tok_span, tok_off, status
 
     def token_offsets_device(self, text, doc_off, unit="char", ordinary=False, allowed_special=None):
@@ -1877,51 +1742,21 @@ class HipEncoding:
         value), begin rounded down and end up to a character (jtk_batch_token_char_offsets).  The ids stay in the batch
         (device_result).  Waits once, for the token count."""
         import torch
-        self._check_device_inputs("token_offsets_device", text, doc_off)
+        self._check_device_inputs("token_offsets_device", ("text", text, torch.uint8), ("doc_off", doc_off, torch.int64))
         u = _unit(unit)
         allow = self._allow(self._b(), allowed_special)
-        nd = doc_off.numel() - 1
-        if nd < 0:
-            raise ValueError("doc_off needs n_docs + 1 entries")
-        device = text.device
-        n = text.numel()
-        st = text.untyped_storage()
-        if text.data_ptr() % 16 or st.data_ptr() + st.nbytes() < text.data_ptr() + (n + 15) // 16 * 16:
-            # (the encode reads whole aligned 16-byte blocks)
-            buf = torch.zeros((n + 15) // 16 * 16 + 16, dtype=torch.uint8, device=device)
-            buf[:n].copy_(text)
-            text = buf
-        b = self._b()
-        cur = torch.cuda.current_stream(device)
-        side = None
-        if cur.cuda_stream == 0:
-            # (the legacy default stream: as in chunk_batch_device, the work goes to the batch's own stream explicitly)
-            side = torch.cuda.ExternalStream(b.stream(), device=device)
-            side.wait_stream(cur)
-        stream = (side or cur).cuda_stream
-        b.encode_device(text.data_ptr(), doc_off.data_ptr(), nd, n, ordinary, stream=stream, sync=False, allow_special=allow)
-        nt = b.result()[0]
-        begin = torch.empty(nt, dtype=torch.int64, device=device)
-        end = torch.empty(nt, dtype=torch.int64, device=device)
-        tok_off = torch.empty(nd + 1, dtype=torch.int64, device=device)
-        status = torch.empty(nd, dtype=torch.int32, device=device)
-        b.token_char_offsets(u, begin.data_ptr() if nt else None, end.data_ptr() if nt else None, stream)
-        _, p_off, p_status = b.device_result()
-        _copy_d2d(tok_off.data_ptr(), p_off, (nd + 1) * 8, stream)
-        if nd:
-            _copy_d2d(status.data_ptr(), p_status, nd * 4, stream)
-        if side is not None:
-            cur.wait_stream(side)
+        with self._encode_device_batch(text, doc_off, ordinary, allow) as (b, nd, device, stream):
+            nt = b.result()[0]
+            begin = torch.empty(nt, dtype=torch.int64, device=device)
+            end = torch.empty(nt, dtype=torch.int64, device=device)
+            b.token_char_offsets(u, begin.data_ptr() if nt else None, end.data_ptr() if nt else None, stream)
+            tok_off, status = self._tok_off_and_status(b, nd, device, stream)
         return begin, end, tok_off, status
 
     def count_tokens_batch(self, texts, ordinary=False, allowed_special=None):
         """Encoding.countTokens / countTokensOrdinary for every text, one device call, no token ids written.  allowed_special:
         as for encode_batch."""
-        bs = [t if isinstance(t, (bytes, bytearray)) else t.encode("utf-8") for t in texts]
-        doc_off = np.zeros(len(bs) + 1, dtype=np.int64)
-        if bs:
-            np.cumsum([len(x) for x in bs], out=doc_off[1:])
-        text = np.frombuffer(b"".join(bs), dtype=np.uint8) if doc_off[-1] else np.zeros(0, dtype=np.uint8)
+        _, text, doc_off = _join_texts(texts)
         b = self._b()
         b.encode_host(text, doc_off, ordinary, count_only=True, allow_special=self._allow(b, allowed_special))
         counts, status = b.fetch_counts()
@@ -1933,10 +1768,7 @@ class HipEncoding:
         """List of token-id lists -> list of bytes (Encoding.decodeBytes for each), one device call.
         strict: raise for a list with an unknown id, as the reference does (GptBytePairEncoding.java:313).
         stop_strings, search_from, keep_stop_string: as for decode_rows."""
-        seq_off = np.zeros(len(token_lists) + 1, dtype=np.int64)
-        if token_lists:
-            np.cumsum([len(t) for t in token_lists], out=seq_off[1:])
-        ids = np.fromiter((i for t in token_lists for i in t), dtype=np.int32, count=int(seq_off[-1]))
+        ids, seq_off = _join_ids(token_lists)
         b = self._b()
         b.decode_host(ids, seq_off)
         out, byte_off, status = b.decode_fetch()
@@ -1988,52 +1820,38 @@ class HipEncoding:
         elif width > 1 and rows.stride(1) != 1:
             raise ValueError("rows must have stride(1) == 1 and stride(0) >= width")
         device = rows.device
-        for name, t in (("begin", begin), ("end", end)):
-            if t is None:
-                continue
+        def check_per_row(name, t):
             if (not isinstance(t, torch.Tensor) or t.device != device or t.dtype != torch.int64 or t.dim() != 1 or t.numel() != nr
                     or not t.is_contiguous()):
                 raise ValueError("%s must be a contiguous CUDA int64 tensor of n_rows entries on %s" % (name, device))
+        for name, t in (("begin", begin), ("end", end)):
+            if t is not None:
+                check_per_row(name, t)
         if search_from is not None:
             if stop_strings is None:
                 raise ValueError("search_from needs stop_strings")
-            t = search_from
-            if (not isinstance(t, torch.Tensor) or t.device != device or t.dtype != torch.int64 or t.dim() != 1 or t.numel() != nr
-                    or not t.is_contiguous()):
-                raise ValueError("search_from must be a contiguous CUDA int64 tensor of n_rows entries on %s" % device)
+            check_per_row("search_from", search_from)
         stop_ids = self._stop_ids(stop)
         b = self._b()
-        cur = torch.cuda.current_stream(device)
-        side = None
-        if cur.cuda_stream == 0:
-            # (the legacy default stream: see chunk_batch_device)
-            side = torch.cuda.ExternalStream(b.stream(), device=device)
-            side.wait_stream(cur)
-        stream = (side or cur).cuda_stream
-        want_cells = cell_offsets or stop_strings is not None
-        cells = torch.empty((nr, width), dtype=torch.int64, device=device) if want_cells else None
-        nb = b.decode_rows_device(rows.data_ptr() if nr * width else None, rows.element_size(), nr, width, stride,
-                                  None if begin is None else begin.data_ptr(), None if end is None else end.data_ptr(),
-                                  0 if pad_id is None else int(pad_id), stop_ids, pad_id is not None, keep_stop,
-                                  cells.data_ptr() if want_cells and nr * width else None, stream)
-        out = dict(bytes=torch.empty(nb, dtype=torch.uint8, device=device), byte_off=torch.empty(nr + 1, dtype=torch.int64, device=device),
-                   status=torch.empty(nr, dtype=torch.int32, device=device))
-        for key, src in zip(("bytes", "byte_off", "status"), b.decode_device_result()):
-            t = out[key]
-            if t.numel():
-                _copy_d2d(t.data_ptr(), src, t.numel() * t.element_size(), stream)
-        if cell_offsets:
-            out["cell_byte"] = cells
-        if stop_strings is not None:
-            b.decode_find_stops(stop_strings, None if search_from is None else search_from.data_ptr(),
-                                cells.data_ptr() if nr * width else None, width, stream)
-            for key, dt, src in zip(("stop_pos", "stop_which", "hold", "stop_col"), (torch.int64, torch.int32, torch.int32, torch.int64),
-                                    b.decode_stops_device_result()):
-                t = out[key] = torch.empty(nr, dtype=dt, device=device)
-                if nr:
-                    _copy_d2d(t.data_ptr(), src, nr * t.element_size(), stream)
-        if side is not None:
-            cur.wait_stream(side)
+        with self._on_current_stream(b, device) as stream:
+            want_cells = cell_offsets or stop_strings is not None
+            cells = torch.empty((nr, width), dtype=torch.int64, device=device) if want_cells else None
+            nb = b.decode_rows_device(rows.data_ptr() if nr * width else None, rows.element_size(), nr, width, stride,
+                                      None if begin is None else begin.data_ptr(), None if end is None else end.data_ptr(),
+                                      0 if pad_id is None else int(pad_id), stop_ids, pad_id is not None, keep_stop,
+                                      cells.data_ptr() if want_cells and nr * width else None, stream)
+            out = {}
+            for key, n, dt, src in zip(("bytes", "byte_off", "status"), (nb, nr + 1, nr), (torch.uint8, torch.int64, torch.int32),
+                                       b.decode_device_result()):
+                out[key] = _device_copy(src, n, dt, device, stream)
+            if cell_offsets:
+                out["cell_byte"] = cells
+            if stop_strings is not None:
+                b.decode_find_stops(stop_strings, None if search_from is None else search_from.data_ptr(),
+                                    cells.data_ptr() if nr * width else None, width, stream)
+                for key, dt, src in zip(("stop_pos", "stop_which", "hold", "stop_col"), (torch.int64, torch.int32, torch.int32, torch.int64),
+                                        b.decode_stops_device_result()):
+                    out[key] = _device_copy(src, nr, dt, device, stream)
         return out
 
     def _cut_at_stops(self, b, raw, byte_off, n, stop_strings, search_from, keep_stop_string):
@@ -2041,18 +1859,15 @@ class HipEncoding:
         a host array of n byte offsets or None; keep_stop_string keeps the matched string at the end of its sequence."""
         bs = _stop_blob(stop_strings)
         lens = np.diff(bs[1].astype(np.int64))
-        d_from = None
-        if search_from is not None:
-            f = np.ascontiguousarray(search_from, dtype=np.int64)
-            if f.shape != (n,):
-                raise ValueError("search_from needs one entry per sequence")
-            d_from = _DeviceArray(f)
-        try:
-            b.decode_find_stops(stop_strings, None if d_from is None else d_from.ptr)
+        with _device_arrays() as put:
+            d_from = None
+            if search_from is not None:
+                f = np.ascontiguousarray(search_from, dtype=np.int64)
+                if f.shape != (n,):
+                    raise ValueError("search_from needs one entry per sequence")
+                d_from = put(f).ptr
+            b.decode_find_stops(stop_strings, d_from)
             pos, which, _, _ = b.decode_stops_fetch()
-        finally:
-            if d_from is not None:
-                d_from.free()
         return [raw[byte_off[q]:pos[q] + (int(lens[which[q]]) if keep_stop_string and which[q] >= 0 else 0)] for q in range(n)]
 
     def decode_rows(self, rows, begin=None, end=None, pad_id=None, stop=(), keep_stop=False, strict=True, stop_strings=None,
@@ -2086,29 +1901,9 @@ class HipEncoding:
 
     def _check_utf16_inputs(self, what, units, unit_off):
         import torch
-        if self._host_pattern is not None:
-            raise ValueError("%s: the device cannot run this encoding's custom split pattern" % what)
-        dev = N.lib().jtk_encoding_device(self._h)
-        for name, t, dt in (("units", units, torch.uint16), ("unit_off", unit_off, torch.int64)):
-            if not isinstance(t, torch.Tensor) or t.device.type != "cuda" or t.dtype != dt or t.dim() != 1:
-                raise ValueError("%s must be a 1-d CUDA tensor of %s" % (name, dt))
-            if t.device.index != dev:
-                raise ValueError("%s is on cuda:%s, the encoding on cuda:%d" % (name, t.device.index, dev))
-            if not t.is_contiguous():
-                raise ValueError("%s must be contiguous" % name)
+        self._check_device_inputs(what, ("units", units, torch.uint16), ("unit_off", unit_off, torch.int64))
         if unit_off.numel() < 1:
             raise ValueError("unit_off needs n_docs + 1 entries")
-
-    def _torch_stream(self, b, device):
-        """(current stream, side stream or None, raw handle): the work goes to torch's current stream, or, when that is the legacy
-        default stream, to the batch's own stream explicitly (as in chunk_batch_device)."""
-        import torch
-        cur = torch.cuda.current_stream(device)
-        side = None
-        if cur.cuda_stream == 0:
-            side = torch.cuda.ExternalStream(b.stream(), device=device)
-            side.wait_stream(cur)
-        return cur, side, (side or cur).cuda_stream
 
     def transcode_utf16_device(self, units, unit_off):
         """Device-resident UTF-16 (units CUDA torch.uint16, any 2-byte alignment; unit_off CUDA torch.int64 [n_docs + 1]) ->
@@ -2119,16 +1914,11 @@ class HipEncoding:
         self._check_utf16_inputs("transcode_utf16_device", units, unit_off)
         device, nd = units.device, unit_off.numel() - 1
         b = self._b()
-        cur, side, stream = self._torch_stream(b, device)
-        nb = b.transcode_utf16_device(units.data_ptr() if units.numel() else None, unit_off.data_ptr(), nd, units.numel(), stream)
-        utf8 = torch.empty(nb, dtype=torch.uint8, device=device)
-        doc_off = torch.empty(nd + 1, dtype=torch.int64, device=device)
-        p_text, p_off, _ = b.utf8_device_result()
-        if nb:
-            _copy_d2d(utf8.data_ptr(), p_text, nb, stream)
-        _copy_d2d(doc_off.data_ptr(), p_off, (nd + 1) * 8, stream)
-        if side is not None:
-            cur.wait_stream(side)
+        with self._on_current_stream(b, device) as stream:
+            nb = b.transcode_utf16_device(units.data_ptr() if units.numel() else None, unit_off.data_ptr(), nd, units.numel(), stream)
+            p_text, p_off, _ = b.utf8_device_result()
+            utf8 = _device_copy(p_text, nb, torch.uint8, device, stream)
+            doc_off = _device_copy(p_off, nd + 1, torch.int64, device, stream)
         return utf8, doc_off
 
     def encode_batch_utf16_device(self, units, unit_off, ordinary=False, allowed_special=None):
@@ -2142,31 +1932,20 @@ class HipEncoding:
         b = self._b()
         allow = self._allow(b, allowed_special)
         device, nd = units.device, unit_off.numel() - 1
-        cur, side, stream = self._torch_stream(b, device)
-        nt = b.encode_utf16_device(units.data_ptr() if units.numel() else None, unit_off.data_ptr(), nd, units.numel(), ordinary,
-                                   stream=stream, allow_special=allow)
-        tokens = torch.empty(nt, dtype=torch.int32, device=device)
-        tok_off = torch.empty(nd + 1, dtype=torch.int64, device=device)
-        status = torch.empty(nd, dtype=torch.int32, device=device)
-        doc_off = torch.empty(nd + 1, dtype=torch.int64, device=device)
-        p_tok, p_off, p_status = b.device_result()
-        if nt:
-            _copy_d2d(tokens.data_ptr(), p_tok, nt * 4, stream)
-        _copy_d2d(tok_off.data_ptr(), p_off, (nd + 1) * 8, stream)
-        if nd:
-            _copy_d2d(status.data_ptr(), p_status, nd * 4, stream)
-        _copy_d2d(doc_off.data_ptr(), b.utf8_device_result()[1], (nd + 1) * 8, stream)
-        if side is not None:
-            cur.wait_stream(side)
+        with self._on_current_stream(b, device) as stream:
+            nt = b.encode_utf16_device(units.data_ptr() if units.numel() else None, unit_off.data_ptr(), nd, units.numel(), ordinary,
+                                       stream=stream, allow_special=allow)
+            p_tok, p_off, p_status = b.device_result()
+            tokens = _device_copy(p_tok, nt, torch.int32, device, stream)
+            tok_off = _device_copy(p_off, nd + 1, torch.int64, device, stream)
+            status = _device_copy(p_status, nd, torch.int32, device, stream)
+            doc_off = _device_copy(b.utf8_device_result()[1], nd + 1, torch.int64, device, stream)
         return tokens, tok_off, status, doc_off
 
     def decode_batch_utf16(self, token_lists, strict=True):
         """List of token-id lists -> list of str: new String(decodeBytes(tokens), UTF_8) for each, decoded and transcoded to
         UTF-16 units on the device (jtk_batch_decode_utf16: one U+FFFD per maximal ill-formed subpart).  strict: as decode_batch."""
-        seq_off = np.zeros(len(token_lists) + 1, dtype=np.int64)
-        if token_lists:
-            np.cumsum([len(t) for t in token_lists], out=seq_off[1:])
-        ids = np.fromiter((i for t in token_lists for i in t), dtype=np.int32, count=int(seq_off[-1]))
+        ids, seq_off = _join_ids(token_lists)
         b = self._b()
         b.decode_host(ids, seq_off)
         b.decode_utf16()
@@ -2187,16 +1966,11 @@ class HipEncoding:
         out = self.decode_rows_device(rows, begin, end, pad_id, stop, keep_stop, cell_offsets, stop_strings, search_from)
         device, nr = rows.device, rows.shape[0]
         b = self._b()
-        cur, side, stream = self._torch_stream(b, device)
-        nu = b.decode_utf16(stream)
-        out["units"] = torch.empty(nu, dtype=torch.uint16, device=device)
-        out["unit_off"] = torch.empty(nr + 1, dtype=torch.int64, device=device)
-        p_units, p_off, _ = b.decode_utf16_device_result()
-        if nu:
-            _copy_d2d(out["units"].data_ptr(), p_units, nu * 2, stream)
-        _copy_d2d(out["unit_off"].data_ptr(), p_off, (nr + 1) * 8, stream)
-        if side is not None:
-            cur.wait_stream(side)
+        with self._on_current_stream(b, device) as stream:
+            nu = b.decode_utf16(stream)
+            p_units, p_off, _ = b.decode_utf16_device_result()
+            out["units"] = _device_copy(p_units, nu, torch.uint16, device, stream)
+            out["unit_off"] = _device_copy(p_off, nr + 1, torch.int64, device, stream)
         return out
 
     def vocab_size(self):
