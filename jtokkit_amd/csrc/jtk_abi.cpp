@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
 #include <vector>
@@ -21,6 +22,7 @@
 #include "jtk_kernels.h"
 #include "jtk_maxtok_rules.h"
 #include "jtk_ngram_rules.h"
+#include "jtk_owned.h"
 #include "jtk_tables.h"
 
 namespace {
@@ -36,24 +38,6 @@ int fail(int code, const std::string& msg) { g_err = msg; return code; }
             return fail(e_ == hipErrorOutOfMemory ? JTK_ERR_OUT_OF_MEMORY : JTK_ERR_HIP,           \
                         std::string(#expr) + ": " + hipGetErrorString(e_));                        \
     } while (0)
-
-struct DevBuf {
-    void* p = nullptr;
-    size_t cap = 0;
-    int ensure(size_t bytes) {
-        if (bytes <= cap) return JTK_OK;
-        if (p) { (void)hipFree(p); p = nullptr; cap = 0; }
-        size_t want = bytes + bytes / 8 + 256;
-        hipError_t e = hipMalloc(&p, want);
-        if (e != hipSuccess) { p = nullptr; return fail(JTK_ERR_OUT_OF_MEMORY, std::string("hipMalloc: ") + hipGetErrorString(e)); }
-        cap = want;
-        return JTK_OK;
-    }
-    void release() { if (p) (void)hipFree(p); p = nullptr; cap = 0; }
-};
-struct TmpDevBuf : DevBuf {      // staging that lives for one call
-    ~TmpDevBuf() { release(); }
-};
 
 constexpr int N_STAGES = 8;
 const char* const STAGE_NAMES[N_STAGES] = {"mark_docs", "validate_utf8", "pretok_split", "piece_resolve", "bpe_merge",
@@ -81,10 +65,10 @@ int64_t jtk_max_tokens_backoff(const jtk_encoding* enc, const uint8_t* utf8, int
                                int64_t max_tokens, int* truncated);
 
 // One chunk in flight: a stream and the scratch of the kernels (sized for the largest chunk it has seen).
-struct ChunkSet {
-    hipStream_t stream = nullptr;
-    hipEvent_t ev_scan = nullptr;    // this set's tile_scan has run (the next chunk's scan waits for it: token order)
-    hipEvent_t ev_done = nullptr;    // this set's last kernel has run
+struct __attribute__((visibility("hidden"))) ChunkSet {      // (internal: no weak symbol of this name leaves the library)
+    Stream stream;
+    Event ev_scan;                   // this set's tile_scan has run (the next chunk's scan waits for it: token order)
+    Event ev_done;                   // this set's last kernel has run
     DevBuf zeroed;                   // docmask | list counters | queue counters
     DevBuf piecemask, gapmask, plist, htok, docpre, tile_np, tile_off, queues, q_meta, mid_list, long_list, giant_list;
     JtkWork work{};
@@ -97,12 +81,11 @@ constexpr int64_t TINY_JOB_BYTES = 128 << 10;     // host jobs this small are st
 
 struct jtk_batch {
     const jtk_encoding* enc = nullptr;
-    hipStream_t stream = nullptr;        // the batch's own main stream
+    Stream stream;                       // the batch's own main stream
     hipStream_t last_stream = nullptr;   // main stream of the last job (the caller's, or `stream`)
-    hipStream_t copy_stream = nullptr;   // tokens of finished chunks to pinned host memory (JTK_ENCODE_TO_HOST)
-    hipEvent_t ev_fork = nullptr, ev_copy = nullptr;
-    int64_t* h_info = nullptr;           // pinned, device-visible: per chunk, its first token and the end of its last
-    size_t h_info_cap = 0;
+    Stream copy_stream;                  // tokens of finished chunks to pinned host memory (JTK_ENCODE_TO_HOST)
+    Event ev_fork, ev_copy;
+    Pinned<int64_t> h_info;              // device-visible: per chunk, its first token and the end of its last
     ChunkSet set[MAX_SETS];
     int n_sets = 2;                      // chunks in flight (JTK_OPT_CHUNKS_IN_FLIGHT)
     bool n_sets_chosen = false;          // by the caller or the environment (else a job that streams ids to the host takes 3)
@@ -117,8 +100,7 @@ struct jtk_batch {
     struct View { void* p = nullptr; };
     View job, status, tok_off, tokens;   // where those parts are in `out` for the last job
     DevBuf plan;                     // chunk plan of a device-resident batch
-    int64_t* host_plan = nullptr;    // pinned
-    size_t host_plan_cap = 0;
+    Pinned<int64_t> host_plan;
     std::vector<int64_t> chunk_doc, chunk_off;
     // JTK_OPT_REUSE_CHUNK_PLAN: the plan of the last device-resident batch is kept while the same offsets array (same pointer, counts)
     // is encoded again -- a step loop --, which saves the plan kernel and the call's only synchronisation.  The caller promises
@@ -128,12 +110,12 @@ struct jtk_batch {
     int64_t plan_docs = -1, plan_bytes = -1, plan_chunk_bytes = -1;
     bool reuse_plan = false;             // JTK_OPT_REUSE_CHUNK_PLAN
     // results streamed to pinned host memory (JTK_ENCODE_TO_HOST)
-    int32_t* h_tokens = nullptr; size_t h_tokens_cap = 0;
-    int64_t* h_tok_off = nullptr; size_t h_tok_off_cap = 0;
-    int32_t* h_status = nullptr; size_t h_status_cap = 0;
-    uint8_t* h_small = nullptr; size_t h_small_cap = 0;   // a small job's whole `out` block (pinned)
-    uint8_t* h_in = nullptr; size_t h_in_cap = 0;         // a tiny host job's offsets and text, side by side (pinned)
-    uint8_t* h_gather = nullptr; size_t h_gather_cap = 0; // jtk_batch_encode_max_tokens: the documents' leading bytes, gathered (pinned)
+    Pinned<int32_t> h_tokens;
+    Pinned<int64_t> h_tok_off;
+    Pinned<int32_t> h_status;
+    Pinned<uint8_t> h_small;         // a small job's whole `out` block
+    Pinned<uint8_t> h_in;            // a tiny host job's offsets and text, side by side
+    Pinned<uint8_t> h_gather;        // jtk_batch_encode_max_tokens: the documents' leading bytes, gathered
     // where the host copy of the last job's result is: the buffers above, or inside h_small
     const int32_t* r_tokens = nullptr; const int64_t* r_tok_off = nullptr; int32_t* r_status = nullptr;
     bool have_host_result = false;
@@ -141,7 +123,7 @@ struct jtk_batch {
     // there are no int32 ids in host memory; cp_stage: one chunk's planes on the device (lo | hi), compacted and copied on
     // copy_stream (in order: the next chunk's pass follows this chunk's copies)
     bool host_compact = false;
-    uint32_t* h_hi = nullptr; size_t h_hi_cap = 0;
+    Pinned<uint32_t> h_hi;
     const uint16_t* r_lo = nullptr; const uint32_t* r_hi = nullptr;
     DevBuf cp_stage;
     // batch decode (jtk_batch_decode*)
@@ -149,20 +131,20 @@ struct jtk_batch {
     DevBuf dec_first, dec_in_win, dec_cell;   // jtk_batch_decode_rows*: first stop column per row | host begin, end | cell_byte for the host
     DevBuf trunc_kept, trunc_flag;   // jtk_batch_truncate
     DevBuf mt_scratch, mt_gather;    // jtk_batch_encode_device_max_tokens: per-document state of the rounds | the gathered prefixes
-    int64_t* h_mt = nullptr; size_t h_mt_cap = 0;   // pinned: the round's (open documents, gathered bytes)
+    Pinned<int64_t> h_mt;            // the round's (open documents, gathered bytes)
     bool have_trunc = false;
     // jtk_batch_chunk: hdr | per-document scan, long list, bases | tiles of the byte scan | records
     DevBuf ck_scratch, ck_tiles, ck_rec;
     DevBuf ck_plane;                     // jtk_batch_chunk_prefer: the level of the cut before every token
     const uint8_t* ck_end_level = nullptr;   // end_level[n_chunks] in ck_rec when the chunk result is jtk_batch_chunk_prefer's
-    int64_t* h_ck = nullptr; size_t h_ck_cap = 0;   // pinned: (chunks, tokens) read once per call
+    Pinned<int64_t> h_ck;                // (chunks, tokens) read once per call
     JtkChunkWork ck{};
     bool have_chunk = false, have_tiles = false;
     hipStream_t ck_stream = nullptr;     // stream of the last chunk plan
-    hipEvent_t ev_ck = nullptr;          // orders a chunk call's stream after the encode / the plan
+    Event ev_ck;                         // orders a chunk call's stream after the encode / the plan
     // jtk_batch_pack: hdr | P | SEG | RS | flag | lifting table (its own scratch: pack and chunk results outlive each other)
     DevBuf pk_scratch;
-    int64_t* h_pk = nullptr; size_t h_pk_cap = 0;   // pinned: the plan's hdr, read once per call
+    Pinned<int64_t> h_pk;            // the plan's hdr, read once per call
     JtkPackWork pk{};
     bool have_pack = false;
     hipStream_t pk_stream = nullptr;     // stream of the last pack plan
@@ -189,7 +171,7 @@ struct jtk_batch {
     bool sp_dirty = true;
     DevBuf sp_lits;                  // ids [n] (int32) | allowed [n]
     DevBuf sp_find, sp_cand, sp_out;
-    int64_t* h_sp = nullptr; size_t h_sp_cap = 0;   // pinned: (candidates, bad offsets, refusals) read once per call
+    Pinned<int64_t> h_sp;            // (candidates, bad offsets, refusals) read once per call
     // JTK_ENCODE_FIM (jtk_fim.hip): the parameters (jtk_batch_set_fim) and, alive with the encode's result, hdr | the stitched
     // status | sub_off | cut | part_tok | kind; the stitched tokens and offsets share sp_out with allow-special
     jtk_fim_params fim{};
@@ -207,8 +189,8 @@ struct jtk_batch {
     JtkStopWork stop{};
     bool have_stops = false;
     hipStream_t stop_stream = nullptr;   // stream of the last find_stops: the fetch waits for it
-    JtkResult* host_result = nullptr;   // pinned: host_result_own, or the head of h_small after a small job
-    JtkResult* host_result_own = nullptr;
+    JtkResult* host_result = nullptr;   // host_result_own, or the head of h_small after a small job
+    Pinned<JtkResult> host_result_own;
     // the last job
     const uint8_t* job_text = nullptr;
     const int64_t* job_doc_off = nullptr;
@@ -217,7 +199,7 @@ struct jtk_batch {
     bool have_result = false, synced = false;
     bool job_pieces = false;             // the last encode took caller-supplied pieces (jtk_batch_encode_pieces)
     bool profiling = false;
-    std::vector<hipEvent_t> prof_ev;     // [chunk][stage][start, end]
+    std::vector<Event> prof_ev;          // [chunk][stage][start, end]
     int prof_chunks = 0;                 // chunks of the last job that recorded events
 };
 
@@ -237,7 +219,7 @@ static void drop_decode_result(jtk_batch* b) {
     b->dec_rows_width = -1;
 }
 
-static hipStream_t pick_stream(const jtk_batch* b, void* stream_or_null) { return stream_or_null ? (hipStream_t)stream_or_null : b->stream; }
+static hipStream_t pick_stream(const jtk_batch* b, void* stream_or_null) { return stream_or_null ? (hipStream_t)stream_or_null : b->stream.h; }
 
 // what a pass over the last encode needs of it, besides that there is one
 enum : unsigned { NEED_IDS = 1,         // token ids (the encode was not count-only)
@@ -250,6 +232,11 @@ static int need_encode(const jtk_batch* b, unsigned what) {
         return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode took caller-supplied pieces: its positions are positions in the decoded stream, not in the text");
     if ((what & (NEED_TEXT_POS | NEED_TEXT_ORDER)) && (b->job_flags & JTK_ENCODE_FIM))
         return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode was a JTK_ENCODE_FIM encode: its tokens are rearranged around sentinel ids and have no positions in the text");
+    return JTK_OK;
+}
+
+static int sync_last(jtk_batch* b) {     // the host waits for the last encode, once (to read its header, or to rewrite its inputs)
+    if (!b->synced) { HIP_TRY(hipStreamSynchronize(b->last_stream)); b->synced = true; }
     return JTK_OK;
 }
 
@@ -331,12 +318,12 @@ int jtk_encoding_create(const char* name, int pattern_kind, const uint8_t* tikto
         if (special_ids[i] < 0 || special_ids[i] > JTK_MAX_SPECIAL_ID)
             return fail(JTK_ERR_INVALID_ARGUMENT, "special-token id out of range");
     }
-    jtk_encoding* enc = new (std::nothrow) jtk_encoding();
+    std::unique_ptr<jtk_encoding> enc(new (std::nothrow) jtk_encoding());      // (its members free themselves on every return)
     if (!enc) return fail(JTK_ERR_OUT_OF_MEMORY, "out of host memory");
     std::string err;
     int rc = jtk_build_tables(name, pattern_kind, tiktoken, tiktoken_len, special_literals, special_ids, n_specials,
                               enc->host, err);
-    if (rc != JTK_OK) { delete enc; return fail(rc, err); }
+    if (rc != JTK_OK) return fail(rc, err);
     enc->tok_len.assign((size_t)enc->host.max_id + 1 + (size_t)enc->host.n_missing, 1);     // (pseudo ids: one byte each)
     {   // the largest id a result can hold: table ids, the pseudo ids above them, every special id
         int64_t top = (int64_t)enc->host.max_id + (int64_t)enc->host.n_missing;
@@ -346,15 +333,10 @@ int jtk_encoding_create(const char* name, int pattern_kind, const uint8_t* tikto
     for (size_t i = 0; i <= (size_t)enc->host.max_id; i++) enc->tok_len[i] = (uint32_t)enc->host.id_to_bytes[i].size();
 
     int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) {
-        delete enc;
-        return fail(JTK_ERR_NO_DEVICE, "no HIP device: jtokkit_amd has no CPU path");
-    }
-    if (device < 0 || device >= ndev) { delete enc; return fail(JTK_ERR_INVALID_ARGUMENT, "device index out of range"); }
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return fail(JTK_ERR_NO_DEVICE, "no HIP device: jtokkit_amd has no CPU path");
+    if (device < 0 || device >= ndev) return fail(JTK_ERR_INVALID_ARGUMENT, "device index out of range");
     enc->device = device;
-    auto cleanup = [&]() { enc->uc1.release(); enc->uc2.release(); enc->uclds.release(); enc->splittab.release(); enc->brank.release(); enc->pairs.release(); enc->tok8.release(); enc->tok16.release(); enc->bprank.release(); enc->bpbits.release(); enc->bpcum.release(); enc->bpranks.release(); enc->pairin.release(); enc->dec_off.release(); enc->dec_blob.release(); enc->longtok.release(); enc->longblob.release(); enc->specials.release(); enc->bnd.release(); delete enc; };
-#define ENC_TRY(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { cleanup(); return fail(JTK_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(e_)); } } while (0)
-    ENC_TRY(hipSetDevice(device));
+    HIP_TRY(hipSetDevice(device));
     const size_t tok8_bytes = (enc->host.tok8.size() * sizeof(JtkTok8Slot) + 31) & ~(size_t)31;
     // the Unicode class table as pretok_split stages it in LDS (JtkDeviceTables::uc_lds_image)
     std::vector<uint8_t> uc_image;
@@ -370,19 +352,19 @@ int jtk_encoding_create(const char* name, int pattern_kind, const uint8_t* tikto
         // one base and a 32-bit offset; + 32: a 9..16-byte probe of the last slot may read 16 bytes past a 16-byte slot
         enc->tok8.ensure(tok8_bytes + enc->host.tok16.size() * sizeof(JtkTok16Slot) + 32) ||
         enc->bprank.ensure(65536 * 4) ||
-        enc->bpbits.ensure(1024 * 8) || enc->bpcum.ensure(1024 * 2) || enc->bpranks.ensure(JTK_BP_MAX * 4) || enc->pairin.ensure(2048 * 4)) { cleanup(); return JTK_ERR_OUT_OF_MEMORY; }
-    ENC_TRY(hipMemcpy(enc->uc1.p, jtk_uc_stage1_init, sizeof(jtk_uc_stage1_init), hipMemcpyHostToDevice));
-    ENC_TRY(hipMemcpy(enc->uc2.p, jtk_uc_stage2_init, sizeof(jtk_uc_stage2_init), hipMemcpyHostToDevice));
-    if (!uc_image.empty()) ENC_TRY(hipMemcpy(enc->uclds.p, uc_image.data(), uc_image.size(), hipMemcpyHostToDevice));
-    ENC_TRY(hipMemcpy(enc->brank.p, enc->host.byte_rank, 256 * 4, hipMemcpyHostToDevice));
-    ENC_TRY(hipMemcpy(enc->pairs.p, enc->host.pair_buckets.data(), enc->host.pair_buckets.size() * sizeof(JtkPairBucket), hipMemcpyHostToDevice));
-    ENC_TRY(hipMemcpy(enc->tok8.p, enc->host.tok8.data(), enc->host.tok8.size() * sizeof(JtkTok8Slot), hipMemcpyHostToDevice));
-    ENC_TRY(hipMemcpy((uint8_t*)enc->tok8.p + tok8_bytes, enc->host.tok16.data(), enc->host.tok16.size() * sizeof(JtkTok16Slot), hipMemcpyHostToDevice));
-    ENC_TRY(hipMemcpy(enc->bprank.p, enc->host.bp_rank.data(), 65536 * 4, hipMemcpyHostToDevice));
-    ENC_TRY(hipMemcpy(enc->bpbits.p, enc->host.bp_bits.data(), 1024 * 8, hipMemcpyHostToDevice));
-    ENC_TRY(hipMemcpy(enc->bpcum.p, enc->host.bp_cum.data(), 1024 * 2, hipMemcpyHostToDevice));
-    ENC_TRY(hipMemcpy(enc->bpranks.p, enc->host.bp_ranks.data(), JTK_BP_MAX * 4, hipMemcpyHostToDevice));
-    ENC_TRY(hipMemcpy(enc->pairin.p, enc->host.pair_in_token.data(), 2048 * 4, hipMemcpyHostToDevice));
+        enc->bpbits.ensure(1024 * 8) || enc->bpcum.ensure(1024 * 2) || enc->bpranks.ensure(JTK_BP_MAX * 4) || enc->pairin.ensure(2048 * 4)) return JTK_ERR_OUT_OF_MEMORY;
+    HIP_TRY(hipMemcpy(enc->uc1.p, jtk_uc_stage1_init, sizeof(jtk_uc_stage1_init), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(enc->uc2.p, jtk_uc_stage2_init, sizeof(jtk_uc_stage2_init), hipMemcpyHostToDevice));
+    if (!uc_image.empty()) HIP_TRY(hipMemcpy(enc->uclds.p, uc_image.data(), uc_image.size(), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(enc->brank.p, enc->host.byte_rank, 256 * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(enc->pairs.p, enc->host.pair_buckets.data(), enc->host.pair_buckets.size() * sizeof(JtkPairBucket), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(enc->tok8.p, enc->host.tok8.data(), enc->host.tok8.size() * sizeof(JtkTok8Slot), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy((uint8_t*)enc->tok8.p + tok8_bytes, enc->host.tok16.data(), enc->host.tok16.size() * sizeof(JtkTok16Slot), hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(enc->bprank.p, enc->host.bp_rank.data(), 65536 * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(enc->bpbits.p, enc->host.bp_bits.data(), 1024 * 8, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(enc->bpcum.p, enc->host.bp_cum.data(), 1024 * 2, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(enc->bpranks.p, enc->host.bp_ranks.data(), JTK_BP_MAX * 4, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(enc->pairin.p, enc->host.pair_in_token.data(), 2048 * 4, hipMemcpyHostToDevice));
     {   // decode table: byte strings of all ids (rank table + special tokens, GptBytePairEncoding.java:302-314) back to back
         uint32_t n_ids = enc->host.max_id + 1;
         for (auto& sp : enc->host.specials) if (sp.second >= 0 && (uint32_t)sp.second + 1 > n_ids) n_ids = (uint32_t)sp.second + 1;
@@ -394,20 +376,20 @@ int jtk_encoding_create(const char* name, int pattern_kind, const uint8_t* tikto
         for (uint32_t i = 0; i < n_ids; i++) { off[i] = (uint32_t)blob.size(); if (str[i]) blob += *str[i]; }
         off[n_ids] = (uint32_t)blob.size();
         blob.append(16, '\0');
-        if (enc->dec_off.ensure(off.size() * 4) || enc->dec_blob.ensure(blob.size())) { cleanup(); return JTK_ERR_OUT_OF_MEMORY; }
-        ENC_TRY(hipMemcpy(enc->dec_off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice));
-        ENC_TRY(hipMemcpy(enc->dec_blob.p, blob.data(), blob.size(), hipMemcpyHostToDevice));
+        if (enc->dec_off.ensure(off.size() * 4) || enc->dec_blob.ensure(blob.size())) return JTK_ERR_OUT_OF_MEMORY;
+        HIP_TRY(hipMemcpy(enc->dec_off.p, off.data(), off.size() * 4, hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(enc->dec_blob.p, blob.data(), blob.size(), hipMemcpyHostToDevice));
         enc->n_ids_table = n_ids;
         std::vector<uint32_t> bits((n_ids + 31) / 32 + 1, 0);
         for (uint32_t i = 0; i < n_ids; i++)
             if (!str[i] || str[i]->empty() || ((uint8_t)(*str[i])[0] & 0xC0) != 0x80) bits[i >> 5] |= 1u << (i & 31);
-        if (enc->bnd.ensure(bits.size() * 4)) { cleanup(); return JTK_ERR_OUT_OF_MEMORY; }
-        ENC_TRY(hipMemcpy(enc->bnd.p, bits.data(), bits.size() * 4, hipMemcpyHostToDevice));
+        if (enc->bnd.ensure(bits.size() * 4)) return JTK_ERR_OUT_OF_MEMORY;
+        HIP_TRY(hipMemcpy(enc->bnd.p, bits.data(), bits.size() * 4, hipMemcpyHostToDevice));
     }
     if (!enc->host.long_tok.empty()) {
-        if (enc->longtok.ensure(enc->host.long_tok.size() * sizeof(JtkLongTokSlot)) || enc->longblob.ensure(enc->host.long_blob.size())) { cleanup(); return JTK_ERR_OUT_OF_MEMORY; }
-        ENC_TRY(hipMemcpy(enc->longtok.p, enc->host.long_tok.data(), enc->host.long_tok.size() * sizeof(JtkLongTokSlot), hipMemcpyHostToDevice));
-        ENC_TRY(hipMemcpy(enc->longblob.p, enc->host.long_blob.data(), enc->host.long_blob.size(), hipMemcpyHostToDevice));
+        if (enc->longtok.ensure(enc->host.long_tok.size() * sizeof(JtkLongTokSlot)) || enc->longblob.ensure(enc->host.long_blob.size())) return JTK_ERR_OUT_OF_MEMORY;
+        HIP_TRY(hipMemcpy(enc->longtok.p, enc->host.long_tok.data(), enc->host.long_tok.size() * sizeof(JtkLongTokSlot), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(enc->longblob.p, enc->host.long_blob.data(), enc->host.long_blob.size(), hipMemcpyHostToDevice));
     }
     JtkDeviceTables& dt = enc->dt;
     memset(&dt, 0, sizeof(dt));
@@ -445,9 +427,9 @@ int jtk_encoding_create(const char* name, int pattern_kind, const uint8_t* tikto
             dt.special_first[f >> 5] |= 1u << (f & 31);
         }
         const size_t off_bytes = align_up(off.size() * 4, 16);
-        if (enc->specials.ensure(off_bytes + blob.size() + 16)) { cleanup(); return JTK_ERR_OUT_OF_MEMORY; }
-        ENC_TRY(hipMemcpy(enc->specials.p, off.data(), off.size() * 4, hipMemcpyHostToDevice));
-        if (!blob.empty()) ENC_TRY(hipMemcpy((uint8_t*)enc->specials.p + off_bytes, blob.data(), blob.size(), hipMemcpyHostToDevice));
+        if (enc->specials.ensure(off_bytes + blob.size() + 16)) return JTK_ERR_OUT_OF_MEMORY;
+        HIP_TRY(hipMemcpy(enc->specials.p, off.data(), off.size() * 4, hipMemcpyHostToDevice));
+        if (!blob.empty()) HIP_TRY(hipMemcpy((uint8_t*)enc->specials.p + off_bytes, blob.data(), blob.size(), hipMemcpyHostToDevice));
         dt.special_off = (const uint32_t*)enc->specials.p;
         dt.special_blob = (const uint8_t*)enc->specials.p + off_bytes;
     }
@@ -457,20 +439,15 @@ int jtk_encoding_create(const char* name, int pattern_kind, const uint8_t* tikto
         for (uint32_t b = 0; b < 256; b++) if (jtk_lead_all_letters(host_uc, b)) lead_letters[b >> 5] |= 1u << (b & 31);
         JtkCode4 tab[256];
         jtk_build_code4_table(pattern_kind == JTK_PAT_CL100K, dt.special_first, lead_letters, tab);
-        ENC_TRY(hipMemcpy(enc->splittab.p, tab, sizeof(tab), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(enc->splittab.p, tab, sizeof(tab), hipMemcpyHostToDevice));
     }
-#undef ENC_TRY
-    *out = enc;
+    *out = enc.release();
     return JTK_OK;
 }
 
 void jtk_encoding_destroy(jtk_encoding* enc) {
     if (!enc) return;
     (void)hipSetDevice(enc->device);
-    enc->uc1.release(); enc->uc2.release(); enc->uclds.release(); enc->splittab.release(); enc->brank.release(); enc->pairs.release();
-    enc->tok8.release(); enc->tok16.release(); enc->bprank.release(); enc->bpbits.release(); enc->bpcum.release(); enc->bpranks.release(); enc->pairin.release();
-    enc->dec_off.release(); enc->dec_blob.release(); enc->longtok.release(); enc->longblob.release(); enc->specials.release();
-    enc->bnd.release();
     delete enc;
 }
 const char* jtk_encoding_name(const jtk_encoding* enc) { return enc ? enc->host.name.c_str() : ""; }
@@ -490,9 +467,9 @@ int jtk_batch_create(const jtk_encoding* enc, jtk_batch** out) {
     if (const char* e = getenv("JTK_CHUNK_BYTES")) { const long long v = atoll(e); if (v >= (1 << 20)) b->chunk_bytes = v; }
     if (const char* e = getenv("JTK_HOST_CHUNK_BYTES")) { const long long v = atoll(e); if (v >= (1 << 16)) b->host_chunk_bytes = v; }
     if (const char* e = getenv("JTK_CHUNKS_IN_FLIGHT")) { const int v = atoi(e); if (v >= 1 && v <= MAX_SETS) { b->n_sets = v; b->n_sets_chosen = true; } }
-    hipError_t e = hipStreamCreateWithFlags(&b->stream, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&b->host_result_own, sizeof(JtkResult), hipHostMallocDefault);
-    b->host_result = b->host_result_own;
+    hipError_t e = b->stream.create();
+    if (e == hipSuccess) e = b->host_result_own.alloc(sizeof(JtkResult));
+    b->host_result = b->host_result_own.p;
     // (the streams and events of the chunk pipeline are created by the first job that forks: a batch that only ever sees
     // small single-chunk jobs -- one per caller thread in the per-call shape -- owns one stream, not six)
     if (e != hipSuccess) {
@@ -507,42 +484,10 @@ void jtk_batch_destroy(jtk_batch* b) {
     if (!b) return;
     (void)hipSetDevice(b->enc->device);
     if (b->stream) (void)hipStreamSynchronize(b->stream);
-    for (ChunkSet& cs : b->set) {
+    for (ChunkSet& cs : b->set)
         if (cs.stream) (void)hipStreamSynchronize(cs.stream);
-        DevBuf* bufs[] = {&cs.zeroed, &cs.piecemask, &cs.gapmask, &cs.plist, &cs.htok, &cs.docpre, &cs.tile_np, &cs.tile_off, &cs.queues, &cs.q_meta,
-                          &cs.mid_list, &cs.long_list, &cs.giant_list};
-        for (DevBuf* d : bufs) d->release();
-        if (cs.ev_scan) (void)hipEventDestroy(cs.ev_scan);
-        if (cs.ev_done) (void)hipEventDestroy(cs.ev_done);
-        if (cs.stream) (void)hipStreamDestroy(cs.stream);
-    }
-    DevBuf* bufs[] = {&b->in_text, &b->in_off, &b->in_pieces, &b->out, &b->plan, &b->dec_in_ids, &b->dec_in_off,
-                      &b->dec_zero, &b->dec_tile, &b->dec_pre, &b->dec_out, &b->dec_byte_off, &b->dec_first, &b->dec_in_win, &b->dec_cell, &b->trunc_kept, &b->trunc_flag,
-                      &b->mt_scratch, &b->mt_gather, &b->ck_scratch, &b->ck_tiles, &b->ck_rec, &b->ck_plane, &b->pk_scratch, &b->sp_lits, &b->sp_find,
-                      &b->sp_cand, &b->sp_out, &b->fim_buf, &b->cp_buf, &b->u16_scratch, &b->u16_in, &b->u16_tx_text, &b->u16_tx_off, &b->u16_enc_text, &b->u16_enc_off,
-                      &b->u16_dscratch, &b->u16_units, &b->u16_unit_off, &b->stop_buf};
-    for (DevBuf* d : bufs) d->release();
-    if (b->h_sp) (void)hipHostFree(b->h_sp);
-    for (hipEvent_t ev : b->prof_ev) (void)hipEventDestroy(ev);
-    if (b->ev_fork) (void)hipEventDestroy(b->ev_fork);
-    if (b->ev_copy) (void)hipEventDestroy(b->ev_copy);
-    if (b->copy_stream) { (void)hipStreamSynchronize(b->copy_stream); (void)hipStreamDestroy(b->copy_stream); }
-    if (b->h_info) (void)hipHostFree(b->h_info);
-    if (b->host_result_own) (void)hipHostFree(b->host_result_own);
-    if (b->h_small) (void)hipHostFree(b->h_small);
-    if (b->h_in) (void)hipHostFree(b->h_in);
-    if (b->h_gather) (void)hipHostFree(b->h_gather);
-    if (b->h_mt) (void)hipHostFree(b->h_mt);
-    if (b->h_ck) (void)hipHostFree(b->h_ck);
-    if (b->h_pk) (void)hipHostFree(b->h_pk);
-    if (b->ev_ck) (void)hipEventDestroy(b->ev_ck);
-    if (b->host_plan) (void)hipHostFree(b->host_plan);
-    if (b->h_tokens) (void)hipHostFree(b->h_tokens);
-    if (b->h_hi) (void)hipHostFree(b->h_hi);
-    if (b->h_tok_off) (void)hipHostFree(b->h_tok_off);
-    if (b->h_status) (void)hipHostFree(b->h_status);
-    if (b->stream) (void)hipStreamDestroy(b->stream);
-    delete b;
+    if (b->copy_stream) (void)hipStreamSynchronize(b->copy_stream);
+    delete b;                        // (every wait above comes before the first free: the members free themselves here)
 }
 
 int jtk_batch_set_option(jtk_batch* b, int option, int64_t value) {
@@ -588,7 +533,8 @@ int jtk_batch_set_allowed_special(jtk_batch* b, const int32_t* special_ids, int 
     }
     // (the device copy is rewritten by the next allow-special encode: the last one's kernels must be done reading it)
     HIP_TRY(hipSetDevice(b->enc->device));
-    if (b->have_result && !b->synced) { HIP_TRY(hipStreamSynchronize(b->last_stream)); b->synced = true; }
+    int rc;
+    if (b->have_result && (rc = sync_last(b))) return rc;
     b->sp_allowed.swap(allowed);
     b->sp_dirty = true;
     return JTK_OK;
@@ -620,7 +566,7 @@ int jtk_batch_fim_result(jtk_batch* b, const uint8_t** d_kind, const int64_t** d
 int jtk_batch_fim_result_fetch(jtk_batch* b, uint8_t* kind, int64_t* cut, int64_t* part_tok) {
     if (!b || !b->have_result || !b->have_fim) return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode on this batch did not run with JTK_ENCODE_FIM");
     HIP_TRY(hipSetDevice(b->enc->device));
-    if (!b->synced) { HIP_TRY(hipStreamSynchronize(b->last_stream)); b->synced = true; }
+    if (int rc = sync_last(b)) return rc;
     const size_t n = (size_t)b->job_docs;
     if (n == 0) return JTK_OK;
     if (kind) HIP_TRY(hipMemcpy(kind, b->fim_kind, n, hipMemcpyDeviceToHost));
@@ -641,17 +587,6 @@ void jtk_host_free(void* p) { if (p) (void)hipHostFree(p); }
 }  // extern "C"
 
 namespace {
-
-int ensure_pinned(void** p, size_t* cap, size_t bytes, size_t keep_bytes) {
-    if (bytes <= *cap) return JTK_OK;
-    void* q = nullptr;
-    const size_t want = bytes + bytes / 4 + 4096;
-    hipError_t e = hipHostMalloc(&q, want, hipHostMallocDefault);
-    if (e != hipSuccess) return fail(JTK_ERR_OUT_OF_MEMORY, std::string("hipHostMalloc: ") + hipGetErrorString(e));
-    if (*p) { if (keep_bytes) memcpy(q, *p, keep_bytes); (void)hipHostFree(*p); }
-    *p = q; *cap = want;
-    return JTK_OK;
-}
 
 // scratch of one chunk of `n_bytes` (from its tile-aligned origin) and `n_docs` documents; fills cs.work
 int prepare_set(ChunkSet& cs, int64_t n_bytes, int64_t n_docs, size_t* bytes_to_clear) {
@@ -768,8 +703,8 @@ int run_job(jtk_batch* b, const uint8_t* d_text, const uint8_t* h_text, const in
     }
     uint8_t* out_base;
     if (zero_copy_out) {
-        if ((rc = ensure_pinned((void**)&b->h_small, &b->h_small_cap, off_tokens + ((size_t)n_bytes + 64) * 4 + 4096, 0))) return rc;
-        out_base = b->h_small;
+        if ((rc = b->h_small.ensure(off_tokens + ((size_t)n_bytes + 64) * 4 + 4096))) return rc;
+        out_base = b->h_small.p;
     } else {
         if ((rc = b->out.ensure(off_tokens + ((size_t)n_bytes + 64) * 4))) return rc;
         out_base = (uint8_t*)b->out.p;
@@ -782,9 +717,9 @@ int run_job(jtk_batch* b, const uint8_t* d_text, const uint8_t* h_text, const in
     int64_t* d_totals = (int64_t*)((uint8_t*)b->job.p + 64);       // [c]: tokens of the chunks before c
     HIP_TRY(hipMemsetAsync(out_base, 0, off_tok_off, s));          // JtkResult, totals and status
     if (to_host && !small_to_host) {
-        if ((rc = ensure_pinned((void**)&b->h_tok_off, &b->h_tok_off_cap, ((size_t)n_docs + 1) * 8, 0)) ||
-            (rc = ensure_pinned((void**)&b->h_status, &b->h_status_cap, (size_t)(n_docs > 0 ? n_docs : 1) * 4, 0)) ||
-            (rc = ensure_pinned((void**)&b->h_tokens, &b->h_tokens_cap, (size_t)n_bytes * (n_bytes <= SMALL_JOB_BYTES ? 4 : 2) / (compact ? 2 : 1) + 4096, 0)))     // grown as the chunks report
+        if ((rc = b->h_tok_off.ensure(((size_t)n_docs + 1) * 8)) ||
+            (rc = b->h_status.ensure((size_t)(n_docs > 0 ? n_docs : 1) * 4)) ||
+            (rc = b->h_tokens.ensure((size_t)n_bytes * (n_bytes <= SMALL_JOB_BYTES ? 4 : 2) / (compact ? 2 : 1) + 4096)))     // grown as the chunks report
             return rc;
     }
     uint16_t* stage_lo = nullptr; uint32_t* stage_hi = nullptr;
@@ -795,7 +730,7 @@ int run_job(jtk_batch* b, const uint8_t* d_text, const uint8_t* h_text, const in
         for (int c = 0; c < n_chunks; c++) max_chunk = std::max(max_chunk, b->chunk_off[c + 1] - b->chunk_off[c]);
         const int64_t cap_tok = max_chunk + 64 + JTK_CP_RANGE_ALIGN;
         const size_t stage_lo_bytes = align_up((size_t)jtk_compact_lo_bytes(cap_tok), 256);
-        if ((hb && (rc = ensure_pinned((void**)&b->h_hi, &b->h_hi_cap, (size_t)jtk_compact_hi_words(n_bytes <= SMALL_JOB_BYTES ? n_bytes : n_bytes / 2, hb) * 4 + 4096, 0))) ||
+        if ((hb && (rc = b->h_hi.ensure((size_t)jtk_compact_hi_words(n_bytes <= SMALL_JOB_BYTES ? n_bytes : n_bytes / 2, hb) * 4 + 4096))) ||
             (rc = b->cp_stage.ensure(stage_lo_bytes + (size_t)jtk_compact_hi_words(cap_tok, hb) * 4 + 16)))
             return rc;
         stage_lo = (uint16_t*)b->cp_stage.p;
@@ -804,67 +739,64 @@ int run_job(jtk_batch* b, const uint8_t* d_text, const uint8_t* h_text, const in
     const bool prof = b->profiling;
     if (prof) {
         const size_t need = (size_t)n_chunks * N_STAGES * 2;
-        while (b->prof_ev.size() < need) { hipEvent_t ev; HIP_TRY(hipEventCreate(&ev)); b->prof_ev.push_back(ev); }
+        while (b->prof_ev.size() < need) { Event ev; HIP_TRY(ev.create_timed()); b->prof_ev.push_back(std::move(ev)); }
     }
     const bool fork = n_chunks > 1 || (h_text != nullptr && !(n_chunks == 1 && n_bytes <= SMALL_JOB_BYTES));
     if (fork) {
-        if (!b->ev_fork) {
-            HIP_TRY(hipEventCreateWithFlags(&b->ev_fork, hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&b->ev_copy, hipEventDisableTiming));
-            HIP_TRY(hipStreamCreateWithFlags(&b->copy_stream, hipStreamNonBlocking));
-        }
+        HIP_TRY(b->ev_fork.create());                              // (each made by the first job that needs it)
+        HIP_TRY(b->ev_copy.create());
+        HIP_TRY(b->copy_stream.create());
         for (int k = 0; k < n_sets; k++) {
             ChunkSet& cs = b->set[k];
-            if (cs.stream) continue;
-            HIP_TRY(hipStreamCreateWithFlags(&cs.stream, hipStreamNonBlocking));
-            HIP_TRY(hipEventCreateWithFlags(&cs.ev_scan, hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&cs.ev_done, hipEventDisableTiming));
+            HIP_TRY(cs.stream.create());
+            HIP_TRY(cs.ev_scan.create());
+            HIP_TRY(cs.ev_done.create());
         }
         HIP_TRY(hipEventRecord(b->ev_fork, s));
     }
     for (ChunkSet& cs : b->set) cs.used = false;
 
-    if ((rc = ensure_pinned((void**)&b->h_info, &b->h_info_cap, ((size_t)n_chunks + 1) * 16, 0))) return rc;
+    if ((rc = b->h_info.ensure(((size_t)n_chunks + 1) * 16))) return rc;
     // tokens of chunk c to the host: on the copy stream, after the chunk's last kernel; the host needs the chunk's token
     // range for that (written to pinned memory by its scan), so this is called one chunk behind the enqueueing
     auto send_chunk_to_host = [&](int c) -> int {
         ChunkSet& cs = b->set[c % n_sets];
         HIP_TRY(hipEventSynchronize(cs.ev_scan));
-        const int64_t t0 = b->h_info[2 * c], t1 = b->h_info[2 * c + 1];
+        const int64_t t0 = b->h_info.p[2 * c], t1 = b->h_info.p[2 * c + 1];
         if (t1 > t0 && compact) {
             // the range's planes: compacted into the staging planes from its start tb (a multiple of 32 tokens at or below t0:
             // the words shared with the chunk before are rewritten whole, here and in pinned memory), then the two copies
             const int64_t tb = jtk_compact_range_start(t0);
             const int64_t w0 = jtk_compact_hi_word(tb, hb), w1 = jtk_compact_hi_words(t1, hb);
-            if ((size_t)t1 * 2 > b->h_tokens_cap || (size_t)w1 * 4 > b->h_hi_cap) {
+            if ((size_t)t1 * 2 > b->h_tokens.cap || (size_t)w1 * 4 > b->h_hi.cap) {
                 // grow: earlier chunks' copies may still be in flight into the old buffers
                 HIP_TRY(hipStreamSynchronize(b->copy_stream));
                 const size_t rest = ((size_t)n_bytes - (size_t)b->chunk_off[c + 1]) / 2;        // tokens still expected
-                int rc2 = ensure_pinned((void**)&b->h_tokens, &b->h_tokens_cap, ((size_t)t1 + rest) * 2, (size_t)t0 * 2);
-                if (!rc2 && hb) rc2 = ensure_pinned((void**)&b->h_hi, &b->h_hi_cap, (size_t)jtk_compact_hi_words(t1 + (int64_t)rest, hb) * 4, (size_t)jtk_compact_hi_words(t0, hb) * 4);
+                int rc2 = b->h_tokens.ensure(((size_t)t1 + rest) * 2, (size_t)t0 * 2);
+                if (!rc2 && hb) rc2 = b->h_hi.ensure((size_t)jtk_compact_hi_words(t1 + (int64_t)rest, hb) * 4, (size_t)jtk_compact_hi_words(t0, hb) * 4);
                 if (rc2) return rc2;
             }
             HIP_TRY(hipStreamWaitEvent(b->copy_stream, cs.ev_done, 0));
             jtk_launch_compact((const int32_t*)b->tokens.p, t0, t1, nullptr, stage_lo, stage_hi, tb, hb, b->copy_stream);
             HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync((uint16_t*)b->h_tokens + t0, stage_lo + (t0 - tb), (size_t)(t1 - t0) * 2, hipMemcpyDeviceToHost, b->copy_stream));
-            if (hb) HIP_TRY(hipMemcpyAsync(b->h_hi + w0, stage_hi, (size_t)(w1 - w0) * 4, hipMemcpyDeviceToHost, b->copy_stream));
+            HIP_TRY(hipMemcpyAsync((uint16_t*)b->h_tokens.p + t0, stage_lo + (t0 - tb), (size_t)(t1 - t0) * 2, hipMemcpyDeviceToHost, b->copy_stream));
+            if (hb) HIP_TRY(hipMemcpyAsync(b->h_hi.p + w0, stage_hi, (size_t)(w1 - w0) * 4, hipMemcpyDeviceToHost, b->copy_stream));
         } else if (t1 > t0 && !(flags & JTK_ENCODE_COUNT_ONLY)) {
-            if ((size_t)t1 * 4 > b->h_tokens_cap) {
+            if ((size_t)t1 * 4 > b->h_tokens.cap) {
                 // grow: earlier chunks' copies may still be in flight into the old buffer
                 HIP_TRY(hipStreamSynchronize(b->copy_stream));
-                int rc2 = ensure_pinned((void**)&b->h_tokens, &b->h_tokens_cap, (size_t)t1 * 4 + ((size_t)n_bytes - (size_t)b->chunk_off[c + 1]) * 2, (size_t)t0 * 4);
+                int rc2 = b->h_tokens.ensure((size_t)t1 * 4 + ((size_t)n_bytes - (size_t)b->chunk_off[c + 1]) * 2, (size_t)t0 * 4);
                 if (rc2) return rc2;
             }
             HIP_TRY(hipStreamWaitEvent(b->copy_stream, cs.ev_done, 0));
-            HIP_TRY(hipMemcpyAsync(b->h_tokens + t0, (const int32_t*)b->tokens.p + t0, (size_t)(t1 - t0) * 4, hipMemcpyDeviceToHost, b->copy_stream));
+            HIP_TRY(hipMemcpyAsync(b->h_tokens.p + t0, (const int32_t*)b->tokens.p + t0, (size_t)(t1 - t0) * 4, hipMemcpyDeviceToHost, b->copy_stream));
         }
         return JTK_OK;
     };
 
     for (int c = 0; c < n_chunks; c++) {
         ChunkSet& cs = b->set[c % n_sets];
-        hipStream_t cst = fork ? cs.stream : s;
+        hipStream_t cst = fork ? cs.stream.h : s;
         const int64_t d0 = b->chunk_doc[c], d1 = b->chunk_doc[c + 1];
         const int64_t b0 = b->chunk_off[c], b1 = b->chunk_off[c + 1];
         const int64_t origin = b0 & ~(int64_t)(JTK_TILE - 1);
@@ -872,7 +804,7 @@ int run_job(jtk_batch* b, const uint8_t* d_text, const uint8_t* h_text, const in
         size_t zero_bytes = 0;
         if ((rc = prepare_set(cs, b1 - origin, d1 - d0, &zero_bytes)) != JTK_OK) return rc;
         JtkWork& w = cs.work;
-        w.set_info = b->h_info + 2 * c;
+        w.set_info = b->h_info.p + 2 * c;
         w.text = d_text + origin;
         w.text_base = origin;
         w.lead = b0 - origin;
@@ -894,7 +826,7 @@ int run_job(jtk_batch* b, const uint8_t* d_text, const uint8_t* h_text, const in
             HIP_TRY(hipMemcpyAsync((uint8_t*)b->in_text.p + b0, h_text + b0, (size_t)(b1 - b0), hipMemcpyHostToDevice, cst));
         }
         int stage = 0;
-        hipEvent_t* pe = prof ? &b->prof_ev[(size_t)c * N_STAGES * 2] : nullptr;
+        const Event* pe = prof ? &b->prof_ev[(size_t)c * N_STAGES * 2] : nullptr;
         auto begin = [&]() { if (prof) (void)hipEventRecord(pe[2 * stage], cst); };
         auto end = [&]() { if (prof) (void)hipEventRecord(pe[2 * stage + 1], cst); stage++; };
 
@@ -950,8 +882,8 @@ int run_job(jtk_batch* b, const uint8_t* d_text, const uint8_t* h_text, const in
                 HIP_TRY(hipGetLastError());
             }
             const size_t total = ((flags & JTK_ENCODE_COUNT_ONLY) || compact) ? off_tokens : off_tokens + (size_t)n_bytes * 4;
-            if ((rc = ensure_pinned((void**)&b->h_small, &b->h_small_cap, total + 4096, 0))) return rc;
-            HIP_TRY(hipMemcpyAsync(b->h_small, b->out.p, total, hipMemcpyDeviceToHost, cst));
+            if ((rc = b->h_small.ensure(total + 4096))) return rc;
+            HIP_TRY(hipMemcpyAsync(b->h_small.p, b->out.p, total, hipMemcpyDeviceToHost, cst));
         }
         if (fork) HIP_TRY(hipEventRecord(cs.ev_done, cst));
         if (to_host && !small_to_host && c > 0) { if ((rc = send_chunk_to_host(c - 1)) != JTK_OK) return rc; }
@@ -966,20 +898,20 @@ int run_job(jtk_batch* b, const uint8_t* d_text, const uint8_t* h_text, const in
         }
     }
     if (small_to_host) {
-        b->host_result = (JtkResult*)b->h_small;
-        b->r_status = (int32_t*)(b->h_small + off_status);
-        b->r_tok_off = (const int64_t*)(b->h_small + off_tok_off);
-        b->r_tokens = compact ? nullptr : (const int32_t*)(b->h_small + off_tokens);
-        b->r_lo = (const uint16_t*)(b->h_small + off_lo); b->r_hi = (const uint32_t*)(b->h_small + off_hi);
+        b->host_result = (JtkResult*)b->h_small.p;
+        b->r_status = (int32_t*)(b->h_small.p + off_status);
+        b->r_tok_off = (const int64_t*)(b->h_small.p + off_tok_off);
+        b->r_tokens = compact ? nullptr : (const int32_t*)(b->h_small.p + off_tokens);
+        b->r_lo = (const uint16_t*)(b->h_small.p + off_lo); b->r_hi = (const uint32_t*)(b->h_small.p + off_hi);
     } else {
         if (to_host) {
-            HIP_TRY(hipMemcpyAsync(b->h_tok_off, b->tok_off.p, ((size_t)n_docs + 1) * 8, hipMemcpyDeviceToHost, s));
-            if (n_docs > 0) HIP_TRY(hipMemcpyAsync(b->h_status, b->status.p, (size_t)n_docs * 4, hipMemcpyDeviceToHost, s));
+            HIP_TRY(hipMemcpyAsync(b->h_tok_off.p, b->tok_off.p, ((size_t)n_docs + 1) * 8, hipMemcpyDeviceToHost, s));
+            if (n_docs > 0) HIP_TRY(hipMemcpyAsync(b->h_status.p, b->status.p, (size_t)n_docs * 4, hipMemcpyDeviceToHost, s));
         }
-        b->host_result = b->host_result_own;
+        b->host_result = b->host_result_own.p;
         HIP_TRY(hipMemcpyAsync(b->host_result, d_result, sizeof(JtkResult), hipMemcpyDeviceToHost, s));
-        b->r_status = b->h_status; b->r_tok_off = b->h_tok_off; b->r_tokens = compact ? nullptr : b->h_tokens;
-        b->r_lo = (const uint16_t*)b->h_tokens; b->r_hi = b->h_hi;
+        b->r_status = b->h_status.p; b->r_tok_off = b->h_tok_off.p; b->r_tokens = compact ? nullptr : b->h_tokens.p;
+        b->r_lo = (const uint16_t*)b->h_tokens.p; b->r_hi = b->h_hi.p;
     }
     b->host_compact = compact_req;
     b->job_text = d_text;
@@ -1004,14 +936,14 @@ int plan_device_chunks(jtk_batch* b, const int64_t* d_doc_off, int64_t n_docs, i
         const int nc = (int)((n_bytes + b->chunk_bytes - 1) / b->chunk_bytes);
         int rc;
         if ((rc = b->plan.ensure(((size_t)nc + 1) * 16))) return rc;
-        if ((rc = ensure_pinned((void**)&b->host_plan, &b->host_plan_cap, ((size_t)nc + 1) * 16, 0))) return rc;
+        if ((rc = b->host_plan.ensure(((size_t)nc + 1) * 16))) return rc;
         int64_t* d_doc = (int64_t*)b->plan.p;
         int64_t* d_off = d_doc + nc + 1;
         jtk_launch_plan_chunks(d_doc_off, n_docs, b->chunk_bytes, nc, d_doc, d_off, s);
-        HIP_TRY(hipMemcpyAsync(b->host_plan, b->plan.p, ((size_t)nc + 1) * 16, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(b->host_plan.p, b->plan.p, ((size_t)nc + 1) * 16, hipMemcpyDeviceToHost, s));
         HIP_TRY(hipStreamSynchronize(s));
-        const int64_t* h_doc = b->host_plan;
-        const int64_t* h_off = b->host_plan + nc + 1;
+        const int64_t* h_doc = b->host_plan.p;
+        const int64_t* h_off = b->host_plan.p + nc + 1;
         for (int c = 1; c < nc; c++) {
             const int64_t d = h_doc[c], o = h_off[c];
             if (d <= b->chunk_doc.back() || d >= n_docs) continue;                 // no new document since the last boundary
@@ -1062,7 +994,7 @@ int install_stitched(jtk_batch* b, const JtkResult* result, int32_t* status, int
     const int hb = b->enc->hb;
     int rc;
     b->job.p = (void*)result; b->status.p = status; b->tok_off.p = tok_off; b->tokens.p = tokens;
-    b->host_result = b->host_result_own;
+    b->host_result = b->host_result_own.p;
     HIP_TRY(hipMemcpyAsync(b->host_result, result, sizeof(JtkResult), hipMemcpyDeviceToHost, s));
     b->job_doc_off = d_doc_off;
     b->job_docs = n_docs;
@@ -1071,26 +1003,26 @@ int install_stitched(jtk_batch* b, const JtkResult* result, int32_t* status, int
         HIP_TRY(hipStreamSynchronize(s));
         const int64_t nt = b->host_result->n_tokens;
         const size_t lo_bytes = align_up((size_t)jtk_compact_lo_bytes(nt), 256), hi_bytes = (size_t)jtk_compact_hi_words(nt, hb) * 4;
-        if ((rc = ensure_pinned((void**)&b->h_tok_off, &b->h_tok_off_cap, ((size_t)n_docs + 1) * 8, 0)) ||
-            (rc = ensure_pinned((void**)&b->h_status, &b->h_status_cap, (size_t)(n_docs > 0 ? n_docs : 1) * 4, 0)) ||
-            (rc = ensure_pinned((void**)&b->h_tokens, &b->h_tokens_cap, (size_t)nt * (compact ? 2 : 4) + 4096, 0)))
+        if ((rc = b->h_tok_off.ensure(((size_t)n_docs + 1) * 8)) ||
+            (rc = b->h_status.ensure((size_t)(n_docs > 0 ? n_docs : 1) * 4)) ||
+            (rc = b->h_tokens.ensure((size_t)nt * (compact ? 2 : 4) + 4096)))
             return rc;
-        HIP_TRY(hipMemcpyAsync(b->h_tok_off, tok_off, ((size_t)n_docs + 1) * 8, hipMemcpyDeviceToHost, s));
-        if (n_docs > 0) HIP_TRY(hipMemcpyAsync(b->h_status, status, (size_t)n_docs * 4, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(b->h_tok_off.p, tok_off, ((size_t)n_docs + 1) * 8, hipMemcpyDeviceToHost, s));
+        if (n_docs > 0) HIP_TRY(hipMemcpyAsync(b->h_status.p, status, (size_t)n_docs * 4, hipMemcpyDeviceToHost, s));
         if (compact) {
             // the planes of the whole stitched result, compacted behind the stitch, in one copy each
-            if ((hb && (rc = ensure_pinned((void**)&b->h_hi, &b->h_hi_cap, hi_bytes + 4096, 0))) || (rc = b->cp_stage.ensure(lo_bytes + hi_bytes + 16))) return rc;
+            if ((hb && (rc = b->h_hi.ensure(hi_bytes + 4096))) || (rc = b->cp_stage.ensure(lo_bytes + hi_bytes + 16))) return rc;
             uint16_t* d_lo = (uint16_t*)b->cp_stage.p;
             uint32_t* d_hi = (uint32_t*)((uint8_t*)b->cp_stage.p + lo_bytes);
             if (nt > 0) {
                 jtk_launch_compact(tokens, 0, nt, nullptr, d_lo, d_hi, 0, hb, s);
                 HIP_TRY(hipGetLastError());
-                HIP_TRY(hipMemcpyAsync(b->h_tokens, d_lo, (size_t)nt * 2, hipMemcpyDeviceToHost, s));
-                if (hb) HIP_TRY(hipMemcpyAsync(b->h_hi, d_hi, hi_bytes, hipMemcpyDeviceToHost, s));
+                HIP_TRY(hipMemcpyAsync(b->h_tokens.p, d_lo, (size_t)nt * 2, hipMemcpyDeviceToHost, s));
+                if (hb) HIP_TRY(hipMemcpyAsync(b->h_hi.p, d_hi, hi_bytes, hipMemcpyDeviceToHost, s));
             }
-        } else if (nt > 0 && !count_only) HIP_TRY(hipMemcpyAsync(b->h_tokens, tokens, (size_t)nt * 4, hipMemcpyDeviceToHost, s));
-        b->r_tokens = compact ? nullptr : b->h_tokens; b->r_tok_off = b->h_tok_off; b->r_status = b->h_status;
-        b->r_lo = (const uint16_t*)b->h_tokens; b->r_hi = b->h_hi;
+        } else if (nt > 0 && !count_only) HIP_TRY(hipMemcpyAsync(b->h_tokens.p, tokens, (size_t)nt * 4, hipMemcpyDeviceToHost, s));
+        b->r_tokens = compact ? nullptr : b->h_tokens.p; b->r_tok_off = b->h_tok_off.p; b->r_status = b->h_status.p;
+        b->r_lo = (const uint16_t*)b->h_tokens.p; b->r_hi = b->h_hi.p;
     }
     b->host_compact = compact_req;
     b->have_result = true; b->have_host_result = to_host;
@@ -1138,7 +1070,7 @@ int run_allow_special(jtk_batch* b, const uint8_t* d_text, const int64_t* d_doc_
     w.n_blk = (n_bytes + JTK_SPECIAL_BLOCK - 1) / JTK_SPECIAL_BLOCK;
     const size_t status_bytes = align_up((size_t)(n_docs > 0 ? n_docs : 1) * 4, 16);
     if ((rc = b->sp_find.ensure(32 + status_bytes + ((size_t)w.n_blk + 1) * 8)) ||
-        (rc = ensure_pinned((void**)&b->h_sp, &b->h_sp_cap, 32, 0)))
+        (rc = b->h_sp.ensure(32)))
         return rc;
     uint8_t* z = (uint8_t*)b->sp_find.p;
     w.hdr = (int64_t*)z;
@@ -1147,9 +1079,9 @@ int run_allow_special(jtk_batch* b, const uint8_t* d_text, const int64_t* d_doc_
     HIP_TRY(hipMemsetAsync(z, 0, 32 + status_bytes, s));
     jtk_launch_special_find(w, s);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(b->h_sp, w.hdr, 24, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(b->h_sp.p, w.hdr, 24, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    w.n_cand = b->h_sp[0];
+    w.n_cand = b->h_sp.p[0];
     const int64_t save_cb = b->chunk_bytes;
     auto plan = [&](const int64_t* off, int64_t nd) {
         b->chunk_bytes = cb;
@@ -1159,8 +1091,8 @@ int run_allow_special(jtk_batch* b, const uint8_t* d_text, const int64_t* d_doc_
     };
     // a document that ends with a negative status has no tokens, which only the stitch sees to: without a candidate it still
     // runs where the find pass has refused a document, and under validation, whose offenders are known only behind the pipeline
-    const bool may_refuse = (b->h_sp[2] != 0 || (flags & JTK_ENCODE_VALIDATE_UTF8)) && n_docs > 0 && n_bytes > 0;
-    if (b->h_sp[1] != 0 || (w.n_cand == 0 && !may_refuse)) {
+    const bool may_refuse = (b->h_sp.p[2] != 0 || (flags & JTK_ENCODE_VALIDATE_UTF8)) && n_docs > 0 && n_bytes > 0;
+    if (b->h_sp.p[1] != 0 || (w.n_cand == 0 && !may_refuse)) {
         // no allowed literal in any document (or bad offsets, which today's call reports as it always does)
         if ((rc = plan(d_doc_off, n_docs)) || (rc = run_job(b, d_text, nullptr, d_doc_off, n_docs, n_bytes, base_flags, s, to_host))) return rc;
         b->job_flags |= JTK_ENCODE_ALLOW_SPECIAL;
@@ -1327,12 +1259,12 @@ int jtk_batch_encode(jtk_batch* b, const uint8_t* utf8, const int64_t* doc_off, 
         // a per-call device batch: offsets and text go down in ONE copy (staged side by side in pinned memory; copying a few KB on
         // the host costs less than a second DMA)
         const size_t off_text = align_up(((size_t)n_docs + 1) * 8, 256), total = off_text + (size_t)n_bytes;
-        if ((rc = ensure_pinned((void**)&b->h_in, &b->h_in_cap, total + 64, 0)) || (rc = b->in_text.ensure(total + 64))) return rc;
-        memcpy(b->h_in, doc_off, ((size_t)n_docs + 1) * 8);
-        if (n_bytes > 0) memcpy(b->h_in + off_text, utf8, (size_t)n_bytes);
+        if ((rc = b->h_in.ensure(total + 64)) || (rc = b->in_text.ensure(total + 64))) return rc;
+        memcpy(b->h_in.p, doc_off, ((size_t)n_docs + 1) * 8);
+        if (n_bytes > 0) memcpy(b->h_in.p + off_text, utf8, (size_t)n_bytes);
         // (the other way round -- the kernels reading text and offsets from the pinned block over the link -- was 5 us slower:
         // four kernels read the text)
-        HIP_TRY(hipMemcpyAsync(b->in_text.p, b->h_in, total, hipMemcpyHostToDevice, b->stream));
+        HIP_TRY(hipMemcpyAsync(b->in_text.p, b->h_in.p, total, hipMemcpyHostToDevice, b->stream));
         rc = run_job(b, (const uint8_t*)b->in_text.p + off_text, nullptr, (const int64_t*)b->in_text.p, n_docs, n_bytes,
                      flags & ~(uint32_t)JTK_ENCODE_TO_HOST, b->stream, (flags & JTK_ENCODE_TO_HOST) != 0);
     } else {
@@ -1411,12 +1343,12 @@ int jtk_batch_encode_pieces(jtk_batch* b, const uint8_t* utf8, const int64_t* do
     return JTK_OK;
 }
 
-void* jtk_batch_stream(jtk_batch* b) { return b ? (void*)b->stream : nullptr; }
+void* jtk_batch_stream(jtk_batch* b) { return b ? (void*)b->stream.h : nullptr; }
 
 int jtk_batch_result(jtk_batch* b, int64_t* n_tokens, int64_t* n_docs, int32_t* worst_status) {
     if (!b || !b->have_result) return fail(JTK_ERR_INVALID_ARGUMENT, "no encode has run on this batch");
     HIP_TRY(hipSetDevice(b->enc->device));
-    if (!b->synced) { HIP_TRY(hipStreamSynchronize(b->last_stream)); b->synced = true; }
+    if (int rc = sync_last(b)) return rc;
     if (n_tokens) *n_tokens = b->host_result->n_tokens;
     if (n_docs) *n_docs = b->job_docs;
     if (worst_status) *worst_status = b->host_result->worst_status;
@@ -1448,7 +1380,7 @@ int jtk_batch_host_result(jtk_batch* b, const int32_t** tokens, const int64_t** 
     if (b->host_compact)
         return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode ran with JTK_ENCODE_COMPACT_IDS: host memory holds no int32 ids, read the planes with jtk_batch_host_result_compact()");
     HIP_TRY(hipSetDevice(b->enc->device));
-    if (!b->synced) { HIP_TRY(hipStreamSynchronize(b->last_stream)); b->synced = true; }
+    if (int rc = sync_last(b)) return rc;
     if (tokens) *tokens = (b->job_flags & JTK_ENCODE_COUNT_ONLY) ? nullptr : b->r_tokens;
     if (tok_off) *tok_off = b->r_tok_off;
     if (status) *status = b->r_status;
@@ -1460,7 +1392,7 @@ int jtk_batch_host_result_compact(jtk_batch* b, const uint16_t** lo, const uint3
     if (!b || !b->have_result || !b->have_host_result || !b->host_compact)
         return fail(JTK_ERR_INVALID_ARGUMENT, "the last encode on this batch did not run with JTK_ENCODE_TO_HOST | JTK_ENCODE_COMPACT_IDS");
     HIP_TRY(hipSetDevice(b->enc->device));
-    if (!b->synced) { HIP_TRY(hipStreamSynchronize(b->last_stream)); b->synced = true; }
+    if (int rc = sync_last(b)) return rc;
     const bool count_only = (b->job_flags & JTK_ENCODE_COUNT_ONLY) != 0;
     if (lo) *lo = count_only ? nullptr : b->r_lo;
     if (hi) *hi = (count_only || !b->enc->hb) ? nullptr : b->r_hi;
@@ -1514,7 +1446,7 @@ int jtk_batch_truncate(jtk_batch* b, int64_t max_tokens) {
     if (b->job_flags & JTK_ENCODE_ALLOW_SPECIAL) return fail(JTK_ERR_INVALID_ARGUMENT, "maxTokens is not defined after a JTK_ENCODE_ALLOW_SPECIAL encode");
     if (b->job_flags & JTK_ENCODE_FIM) return fail(JTK_ERR_INVALID_ARGUMENT, "maxTokens is not defined after a JTK_ENCODE_FIM encode");
     HIP_TRY(hipSetDevice(b->enc->device));
-    if (!b->synced) { HIP_TRY(hipStreamSynchronize(b->last_stream)); b->synced = true; }
+    if (int rc = sync_last(b)) return rc;
     const int64_t nd = b->job_docs;
     int rc;
     if ((rc = b->trunc_kept.ensure((size_t)(nd > 0 ? nd : 1) * 8)) || (rc = b->trunc_flag.ensure((size_t)(nd > 0 ? nd : 1)))) return rc;
@@ -1870,8 +1802,8 @@ int jtk_batch_encode_max_tokens(jtk_batch* b, const uint8_t* utf8, const int64_t
                 a1++;
             }
             double t0 = now();
-            { const int prc = ensure_pinned((void**)&b->h_gather, &b->h_gather_cap, (size_t)gbytes + 64, 0); if (prc) return prc; }
-            gtext = b->h_gather;
+            { const int prc = b->h_gather.ensure((size_t)gbytes + 64); if (prc) return prc; }
+            gtext = b->h_gather.p;
             host_slices(a1 - a0, [&](int, size_t lo, size_t hi) {
                 for (size_t i = lo; i < hi; i++)
                     memcpy(gtext + goff[i], utf8 + doc_off[active[a0 + i]], (size_t)(goff[i + 1] - goff[i]));
@@ -1978,7 +1910,7 @@ int jtk_batch_encode_device_max_tokens(jtk_batch* b, const uint8_t* d_utf8, cons
                  o_bc = o_bb + (size_t)n_blk * 8, o_sp = align_up(o_bc + (size_t)n_blk * 4, 16), o_ag = o_sp + align_up(nd, 16),
                  total = o_ag + 2 * align_up(nd, 16);
     int rc;
-    if ((rc = b->mt_scratch.ensure(total)) || (rc = ensure_pinned((void**)&b->h_mt, &b->h_mt_cap, 16, 0))) return rc;
+    if ((rc = b->mt_scratch.ensure(total)) || (rc = b->h_mt.ensure(16))) return rc;
     uint8_t* z = (uint8_t*)b->mt_scratch.p;
     JtkMaxTokWork m{};
     m.text = d_utf8; m.doc_off = d_doc_off; m.n_docs = n_docs; m.n_bytes = n_bytes;
@@ -2011,17 +1943,17 @@ int jtk_batch_encode_device_max_tokens(jtk_batch* b, const uint8_t* d_utf8, cons
         m.n_blk = (n_in + 1023) / 1024;
         m.act_in = act[cur ^ 1]; m.again_in = again[cur ^ 1];
         m.act = act[cur]; m.again = again[cur];
-        hipEvent_t ev[5] = {};
-        if (trace) for (auto& e : ev) HIP_TRY(hipEventCreate(&e));
+        Event ev[5];
+        if (trace) for (auto& e : ev) HIP_TRY(e.create_timed());
         if (trace) HIP_TRY(hipEventRecord(ev[0], s));
         jtk_launch_maxtok_plan(m, s);
         HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(b->h_mt, m.hdr, 16, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipMemcpyAsync(b->h_mt.p, m.hdr, 16, hipMemcpyDeviceToHost, s));
         if (trace) HIP_TRY(hipEventRecord(ev[1], s));
         HIP_TRY(hipStreamSynchronize(s));
-        const int64_t n_act = b->h_mt[0], gbytes = b->h_mt[1];
+        const int64_t n_act = b->h_mt.p[0], gbytes = b->h_mt.p[1];
         if (n_act < 0) return fail(JTK_ERR_INVALID_ARGUMENT, "document offsets are not non-decreasing within [0, n_bytes]");
-        if (n_act == 0) { if (trace) for (auto& e : ev) (void)hipEventDestroy(e); break; }
+        if (n_act == 0) break;
         if ((rc = b->mt_gather.ensure((size_t)gbytes + 64))) return rc;
         m.gather = (uint8_t*)b->mt_gather.p;
         m.gbytes = gbytes;
@@ -2041,7 +1973,6 @@ int jtk_batch_encode_device_max_tokens(jtk_batch* b, const uint8_t* d_utf8, cons
             (void)hipEventElapsedTime(&t_encode, ev[3], ev[4]);
             fprintf(stderr, "[device max_tokens] round %d P=%lld docs=%lld bytes=%lld chunks=%zu: plan %.3f gather %.3f encode+decide %.3f ms\n",
                     round, (long long)m.P, (long long)n_act, (long long)gbytes, b->chunk_doc.size() - 1, t_plan, t_gather, t_encode);
-            for (auto& e : ev) (void)hipEventDestroy(e);
         }
         n_in = n_act;
     }
@@ -2053,7 +1984,7 @@ int jtk_batch_encode_device_max_tokens(jtk_batch* b, const uint8_t* d_utf8, cons
 // `to` waits for the work queued on `from` so far (nothing when they are the same stream).
 static int ck_order(jtk_batch* b, hipStream_t from, hipStream_t to) {
     if (from == to) return JTK_OK;
-    if (!b->ev_ck) HIP_TRY(hipEventCreateWithFlags(&b->ev_ck, hipEventDisableTiming));
+    HIP_TRY(b->ev_ck.create());
     HIP_TRY(hipEventRecord(b->ev_ck, from));
     HIP_TRY(hipStreamWaitEvent(to, b->ev_ck, 0));
     return JTK_OK;
@@ -2134,16 +2065,16 @@ int jtk_batch_chunk(jtk_batch* b, int64_t chunk_tokens, int64_t overlap, void* s
     hipStream_t s = pick_stream(b, stream_or_null);
     b->have_chunk = false;
     b->have_tiles = false;
-    if ((rc = ck_order(b, b->last_stream, s)) || (rc = ck_setup(b)) || (rc = ensure_pinned((void**)&b->h_ck, &b->h_ck_cap, 32, 0))) return rc;
+    if ((rc = ck_order(b, b->last_stream, s)) || (rc = ck_setup(b)) || (rc = b->h_ck.ensure(32))) return rc;
     JtkChunkWork& w = b->ck;
     w.N = chunk_tokens; w.overlap = overlap;
     // count per document, scan; the one wait: (chunks, tokens)
     HIP_TRY(hipMemsetAsync(w.hdr, 0, 32, s));
     jtk_launch_chunk_count(w, s);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(b->h_ck, w.hdr, 16, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(b->h_ck.p, w.hdr, 16, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    const int64_t nc = b->h_ck[0], nt = b->h_ck[1];
+    const int64_t nc = b->h_ck.p[0], nt = b->h_ck.p[1];
     if ((rc = ck_tiles(b, nt, s)) || (rc = ck_records(b, nc, nullptr))) return rc;
     jtk_launch_chunk_write(w, s);
     HIP_TRY(hipGetLastError());
@@ -2262,21 +2193,20 @@ int jtk_batch_minhash_agree(jtk_batch* b, const uint32_t* d_sig, int64_t n_sig, 
 struct jtk_ngram_set {
     const jtk_encoding* enc = nullptr;
     jtk_ngram_params p{};
-    uint64_t* table = nullptr;       // [capacity], 0 = empty
+    DevBuf table;                    // uint64 [capacity], 0 = empty
     int64_t capacity = 0;
-    uint64_t* d_hdr = nullptr;       // [0] the key count, [1] the n-grams of the batch that is being added
-    hipStream_t own = nullptr;       // add_keys and the reads
-    hipEvent_t ev = nullptr;
+    DevBuf d_hdr;                    // uint64: [0] the key count, [1] the n-grams of the batch that is being added
+    Stream own;                      // add_keys and the reads
+    Event ev;
+    uint64_t* slots() const { return (uint64_t*)table.p; }
+    uint64_t* hdr() const { return (uint64_t*)d_hdr.p; }
 };
 
 static int ng_wait(const jtk_ngram_set* s, hipStream_t st) { HIP_TRY(hipStreamWaitEvent(st, s->ev, 0)); return JTK_OK; }
 static int ng_done(const jtk_ngram_set* s, hipStream_t st) { HIP_TRY(hipEventRecord(s->ev, st)); return JTK_OK; }
 
 static void ng_free(jtk_ngram_set* s) {
-    if (s->ev) { (void)hipEventSynchronize(s->ev); (void)hipEventDestroy(s->ev); }
-    if (s->own) (void)hipStreamDestroy(s->own);
-    if (s->table) (void)hipFree(s->table);
-    if (s->d_hdr) (void)hipFree(s->d_hdr);
+    if (s->ev) (void)hipEventSynchronize(s->ev);                // (the last call that queued work on the table)
     delete s;
 }
 
@@ -2284,18 +2214,17 @@ static void ng_free(jtk_ngram_set* s) {
 static int ng_reserve(jtk_ngram_set* s, int64_t c, int64_t m, hipStream_t st) {
     const int64_t cap = jtk_ng_capacity(c, m);
     if (cap <= s->capacity) return JTK_OK;
-    uint64_t* grown = nullptr;
-    hipError_t e = hipMalloc((void**)&grown, (size_t)cap * 8);
+    DevBuf grown;
+    hipError_t e = grown.alloc((size_t)cap * 8);
     if (e != hipSuccess) return fail(JTK_ERR_OUT_OF_MEMORY, std::string("hipMalloc (n-gram table): ") + hipGetErrorString(e));
-    e = hipMemsetAsync(grown, 0, (size_t)cap * 8, st);
+    e = hipMemsetAsync(grown.p, 0, (size_t)cap * 8, st);
     if (e == hipSuccess) {
-        jtk_launch_ngram_insert_keys(s->table, s->capacity, grown, cap, nullptr, st);
+        jtk_launch_ngram_insert_keys(s->slots(), s->capacity, (uint64_t*)grown.p, cap, nullptr, st);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) { (void)hipFree(grown); return fail(JTK_ERR_HIP, std::string("n-gram table growth: ") + hipGetErrorString(e)); }
-    (void)hipFree(s->table);
-    s->table = grown;
+    if (e != hipSuccess) return fail(JTK_ERR_HIP, std::string("n-gram table growth: ") + hipGetErrorString(e));
+    s->table = std::move(grown);     // (frees the old table: the insert that read it is done)
     s->capacity = cap;
     return JTK_OK;
 }
@@ -2316,12 +2245,12 @@ int jtk_ngram_set_create(const jtk_encoding* enc, const jtk_ngram_params* p, jtk
     s->enc = enc;
     s->p = *p;
     s->capacity = jtk_ng_capacity(0, 0);
-    hipError_t e = hipStreamCreateWithFlags(&s->own, hipStreamNonBlocking);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipMalloc((void**)&s->table, (size_t)s->capacity * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&s->d_hdr, 16);
-    if (e == hipSuccess) e = hipMemsetAsync(s->table, 0, (size_t)s->capacity * 8, s->own);
-    if (e == hipSuccess) e = hipMemsetAsync(s->d_hdr, 0, 16, s->own);
+    hipError_t e = s->own.create();
+    if (e == hipSuccess) e = s->ev.create();
+    if (e == hipSuccess) e = s->table.alloc((size_t)s->capacity * 8);
+    if (e == hipSuccess) e = s->d_hdr.alloc(16);
+    if (e == hipSuccess) e = hipMemsetAsync(s->table.p, 0, (size_t)s->capacity * 8, s->own);
+    if (e == hipSuccess) e = hipMemsetAsync(s->d_hdr.p, 0, 16, s->own);
     if (e == hipSuccess) e = hipEventRecord(s->ev, s->own);
     if (e != hipSuccess) {
         ng_free(s);
@@ -2348,14 +2277,14 @@ int jtk_ngram_set_add_batch(jtk_ngram_set* s, jtk_batch* b, void* stream_or_null
     hipStream_t st = pick_stream(b, stream_or_null);
     if ((rc = ck_order(b, b->last_stream, st)) || (rc = ng_wait(s, st))) return rc;
     const JtkMhView v = ng_view(b, nt, s->p.ngram);
-    HIP_TRY(hipMemsetAsync(s->d_hdr + 1, 0, 8, st));
-    jtk_launch_ngram_count(v, s->d_hdr + 1, st);
+    HIP_TRY(hipMemsetAsync(s->hdr() + 1, 0, 8, st));
+    jtk_launch_ngram_count(v, s->hdr() + 1, st);
     HIP_TRY(hipGetLastError());
     int64_t h[2] = {0, 0};                                   // keys in the set, n-grams in the batch
-    HIP_TRY(hipMemcpyAsync(h, s->d_hdr, 16, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h, s->hdr(), 16, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
     if ((rc = ng_reserve(s, h[0], h[1], st))) return rc;
-    jtk_launch_ngram_insert(v, s->p.seed, s->table, s->capacity, s->d_hdr, st);
+    jtk_launch_ngram_insert(v, s->p.seed, s->slots(), s->capacity, s->hdr(), st);
     HIP_TRY(hipGetLastError());
     return ng_done(s, st);
 }
@@ -2370,14 +2299,14 @@ int jtk_ngram_set_add_keys(jtk_ngram_set* s, const uint64_t* keys, int64_t n) {
     HIP_TRY(hipSetDevice(s->enc->device));
     int rc;
     if ((rc = ng_wait(s, s->own))) return rc;
-    TmpDevBuf tmp;
+    DevBuf tmp;                                                  // (staging that lives for this call)
     if ((rc = tmp.ensure((size_t)n * 8))) return rc;
     HIP_TRY(hipMemcpyAsync(tmp.p, keys, (size_t)n * 8, hipMemcpyHostToDevice, s->own));
     int64_t c = 0;
-    HIP_TRY(hipMemcpyAsync(&c, s->d_hdr, 8, hipMemcpyDeviceToHost, s->own));
+    HIP_TRY(hipMemcpyAsync(&c, s->hdr(), 8, hipMemcpyDeviceToHost, s->own));
     HIP_TRY(hipStreamSynchronize(s->own));
     if ((rc = ng_reserve(s, c, n, s->own))) return rc;
-    jtk_launch_ngram_insert_keys((const uint64_t*)tmp.p, n, s->table, s->capacity, s->d_hdr, s->own);
+    jtk_launch_ngram_insert_keys((const uint64_t*)tmp.p, n, s->slots(), s->capacity, s->hdr(), s->own);
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipStreamSynchronize(s->own));
     return ng_done(s, s->own);
@@ -2389,7 +2318,7 @@ int jtk_ngram_set_size(const jtk_ngram_set* s, int64_t* n_keys, int64_t* capacit
     if (n_keys) {
         int rc;
         if ((rc = ng_wait(s, s->own))) return rc;
-        HIP_TRY(hipMemcpyAsync(n_keys, s->d_hdr, 8, hipMemcpyDeviceToHost, s->own));
+        HIP_TRY(hipMemcpyAsync(n_keys, s->hdr(), 8, hipMemcpyDeviceToHost, s->own));
         HIP_TRY(hipStreamSynchronize(s->own));
     }
     if (capacity) *capacity = s->capacity;
@@ -2404,7 +2333,7 @@ int jtk_ngram_set_keys(const jtk_ngram_set* s, uint64_t* keys, int64_t cap) {
     if (c == 0) return JTK_OK;
     if (!keys) return fail(JTK_ERR_INVALID_ARGUMENT, "keys is NULL");
     std::vector<uint64_t> slots((size_t)s->capacity);
-    HIP_TRY(hipMemcpyAsync(slots.data(), s->table, slots.size() * 8, hipMemcpyDeviceToHost, s->own));
+    HIP_TRY(hipMemcpyAsync(slots.data(), s->slots(), slots.size() * 8, hipMemcpyDeviceToHost, s->own));
     HIP_TRY(hipStreamSynchronize(s->own));
     int64_t n = 0;
     for (uint64_t k : slots)
@@ -2426,7 +2355,7 @@ int jtk_batch_ngram_overlap(jtk_batch* b, const jtk_ngram_set* s, uint8_t* d_tok
     if ((rc = jtk_batch_result(b, &nt, nullptr, nullptr))) return rc;
     hipStream_t st = pick_stream(b, stream_or_null);
     if ((rc = ck_order(b, b->last_stream, st)) || (rc = ng_wait(s, st))) return rc;
-    jtk_launch_ngram_overlap(ng_view(b, nt, s->p.ngram), s->p.seed, s->table, s->capacity, d_tok_flags, d_n_hit, d_n_covered, d_first_hit, st);
+    jtk_launch_ngram_overlap(ng_view(b, nt, s->p.ngram), s->p.seed, s->slots(), s->capacity, d_tok_flags, d_n_hit, d_n_covered, d_first_hit, st);
     HIP_TRY(hipGetLastError());
     return ng_done(s, st);
 }
@@ -2478,7 +2407,7 @@ int jtk_batch_chunk_prefer(jtk_batch* b, int64_t chunk_tokens, int64_t overlap, 
     if ((rc = jtk_batch_result(b, &nt, nullptr, nullptr))) return rc;      // (the plane is sized by the token count)
     b->have_chunk = false;
     b->have_tiles = false;
-    if ((rc = ck_order(b, b->last_stream, s)) || (rc = ck_setup(b)) || (rc = ensure_pinned((void**)&b->h_ck, &b->h_ck_cap, 32, 0)) ||
+    if ((rc = ck_order(b, b->last_stream, s)) || (rc = ck_setup(b)) || (rc = b->h_ck.ensure(32)) ||
         (rc = b->ck_plane.ensure((size_t)nt + 16))) return rc;
     JtkChunkPreferWork p{};
     JtkChunkWork& w = b->ck;
@@ -2490,9 +2419,9 @@ int jtk_batch_chunk_prefer(jtk_batch* b, int64_t chunk_tokens, int64_t overlap, 
     p.w = w;
     jtk_launch_chunk_prefer_count(p, s);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(b->h_ck, w.hdr, 16, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(b->h_ck.p, w.hdr, 16, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    const int64_t nc = b->h_ck[0];
+    const int64_t nc = b->h_ck.p[0];
     if ((rc = ck_tiles(b, nt, s)) || (rc = ck_records(b, nc, &p.end_level))) return rc;
     p.w = w;
     jtk_launch_chunk_prefer_write(p, s);
@@ -2551,7 +2480,7 @@ int jtk_batch_pack(jtk_batch* b, int64_t seq_len, int32_t sep_id, uint32_t flags
     // scratch: hdr[4] | P | SEG | RS [n + 1] | flag [n] | up [K][n + 1]
     const size_t m = (size_t)n + 1, o_flag = 32 + 3 * m * 8, o_up = align_up(o_flag + m, 16);
     const size_t bytes = whole ? o_up + (size_t)K * m * 4 : o_flag;
-    if ((rc = b->pk_scratch.ensure(bytes)) || (rc = ensure_pinned((void**)&b->h_pk, &b->h_pk_cap, 32, 0)) ||
+    if ((rc = b->pk_scratch.ensure(bytes)) || (rc = b->h_pk.ensure(32)) ||
         (rc = ck_order(b, b->last_stream, s)))
         return rc;
     JtkPackWork& w = b->pk;
@@ -2574,17 +2503,17 @@ int jtk_batch_pack(jtk_batch* b, int64_t seq_len, int32_t sep_id, uint32_t flags
     HIP_TRY(hipMemsetAsync(w.hdr, 0, 32, s));
     jtk_launch_pack_plan(w, s);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(b->h_pk, w.hdr, 32, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipMemcpyAsync(b->h_pk.p, w.hdr, 32, hipMemcpyDeviceToHost, s));
     HIP_TRY(hipStreamSynchronize(s));
-    const int64_t S = b->h_pk[0];
-    int64_t rows, segs, longest = b->h_pk[3];
+    const int64_t S = b->h_pk.p[0];
+    int64_t rows, segs, longest = b->h_pk.p[3];
     if (whole) {
-        rows = b->h_pk[2];
-        segs = b->h_pk[1];
+        rows = b->h_pk.p[2];
+        segs = b->h_pk.p[1];
     } else {
         rows = jtk_pack_concat_rows(S, seq_len, drop);
         const int64_t pad = rows > 0 ? rows * seq_len - S : 0;        // (the last row's pad; never with DROP_LAST)
-        segs = b->h_pk[1] + (pad > 0 ? 1 : 0);
+        segs = b->h_pk.p[1] + (pad > 0 ? 1 : 0);
         if (pad > longest) longest = pad;
     }
     if (rows > INT32_MAX / seq_len)
@@ -2619,7 +2548,7 @@ int jtk_batch_pack_fetch(jtk_batch* b, int32_t pad_id, int32_t* rows, int32_t* p
     // device staging: rows | positions | cu_seqlens | seg_doc
     const size_t o_pos = align_up(cells * 4, 16), o_cu = o_pos + align_up(cells * 4, 16), o_sd = align_up(o_cu + (ns + 1) * 4, 16);
     HIP_TRY(hipSetDevice(b->enc->device));
-    TmpDevBuf tmp;
+    DevBuf tmp;                                                  // (staging that lives for this call)
     int rc;
     if ((rc = tmp.ensure(o_sd + ns * 8 + 16))) return rc;
     uint8_t* p = (uint8_t*)tmp.p;
@@ -2678,7 +2607,7 @@ int jtk_batch_pack_labels_fetch(jtk_batch* b, const int32_t* d_tok_span_or_null,
     const size_t cells = (size_t)(b->pk.n_rows * b->pk.v.L);
     if (cells && !labels) return fail(JTK_ERR_INVALID_ARGUMENT, "labels is NULL");
     HIP_TRY(hipSetDevice(b->enc->device));
-    TmpDevBuf tmp;
+    DevBuf tmp;                                                  // (staging that lives for this call)
     int rc;
     if ((rc = tmp.ensure(cells * 4 + 16)) ||
         (rc = jtk_batch_pack_labels(b, d_tok_span_or_null, ignore_index, flags, (int32_t*)tmp.p, b->pk_stream)))

@@ -13,8 +13,7 @@
 
 #include "../../include/jtokkit_amd.h"
 #include "jtk_kernels.h"
-
-int jtk_fail_msg(int code, const std::string& msg);          // jtk_abi.cpp: sets jtk_last_error()
+#include "jtk_owned.h"
 
 namespace {
 
@@ -77,10 +76,12 @@ int rccl_fail(const char* what, int rc) {
 struct jtk_comm {
     RcclComm comm = nullptr;
     int world = 1, rank = 0, device = 0;
-    int64_t* d_mine = nullptr;       // [1] this rank's token total
-    int64_t* d_totals = nullptr;     // [world] every rank's
-    int64_t* d_base = nullptr;       // [1] exclusive prefix: this shard's first global token
-    int64_t* h_out = nullptr;        // pinned [world + 1]: totals, base
+    DevBuf d_mine;                   // int64 [1] this rank's token total
+    DevBuf d_totals;                 // int64 [world] every rank's
+    DevBuf d_base;                   // int64 [1] exclusive prefix: this shard's first global token
+    Pinned<int64_t> h_out;           // [world + 1]: totals, base
+    int64_t* totals() const { return (int64_t*)d_totals.p; }
+    int64_t* base() const { return (int64_t*)d_base.p; }
 };
 
 extern "C" {
@@ -127,10 +128,10 @@ int jtk_comm_create(const uint8_t* id128, int world, int rank, int device, jtk_c
     memcpy(id.internal, id128, 128);
     const int r = g_rccl.comm_init_rank(&c->comm, world, id, rank);
     if (r != 0) { delete c; return rccl_fail("ncclCommInitRank", r); }
-    hipError_t e = hipMalloc((void**)&c->d_mine, 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&c->d_totals, (size_t)world * 8);
-    if (e == hipSuccess) e = hipMalloc((void**)&c->d_base, 8);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&c->h_out, ((size_t)world + 1) * 8, hipHostMallocDefault);
+    hipError_t e = c->d_mine.alloc(8);
+    if (e == hipSuccess) e = c->d_totals.alloc((size_t)world * 8);
+    if (e == hipSuccess) e = c->d_base.alloc(8);
+    if (e == hipSuccess) e = c->h_out.alloc(((size_t)world + 1) * 8);
     if (e != hipSuccess) { jtk_comm_destroy(c); return jtk_fail_msg(JTK_ERR_OUT_OF_MEMORY, std::string("comm buffers: ") + hipGetErrorString(e)); }
     *out = c;
     return JTK_OK;
@@ -140,11 +141,7 @@ void jtk_comm_destroy(jtk_comm* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     if (c->comm && g_rccl.comm_destroy) (void)g_rccl.comm_destroy(c->comm);
-    if (c->d_mine) (void)hipFree(c->d_mine);
-    if (c->d_totals) (void)hipFree(c->d_totals);
-    if (c->d_base) (void)hipFree(c->d_base);
-    if (c->h_out) (void)hipHostFree(c->h_out);
-    delete c;
+    delete c;                        // (the communicator first: its buffers free themselves here)
 }
 
 int jtk_comm_world(const jtk_comm* c) { return c ? c->world : 0; }
@@ -156,15 +153,15 @@ int jtk_comm_stitch(jtk_comm* c, const int64_t* d_tok_off, int64_t n_docs, int64
     if (hipSetDevice(c->device) != hipSuccess) return jtk_fail_msg(JTK_ERR_NO_DEVICE, "hipSetDevice failed");
     hipStream_t s = (hipStream_t)stream;
     // this shard's token total is the last entry of its token offsets: device to device, no host round trip
-    hipError_t e = hipMemcpyAsync(c->d_mine, d_tok_off + n_docs, 8, hipMemcpyDeviceToDevice, s);
+    hipError_t e = hipMemcpyAsync(c->d_mine.p, d_tok_off + n_docs, 8, hipMemcpyDeviceToDevice, s);
     if (e != hipSuccess) return jtk_fail_msg(JTK_ERR_HIP, std::string("hipMemcpyAsync: ") + hipGetErrorString(e));
-    const int r = g_rccl.all_gather(c->d_mine, c->d_totals, 1, RCCL_INT64, c->comm, s);
+    const int r = g_rccl.all_gather(c->d_mine.p, c->d_totals.p, 1, RCCL_INT64, c->comm, s);
     if (r != 0) return rccl_fail("ncclAllGather", r);
-    jtk_launch_stitch(c->d_totals, c->rank, c->d_base, d_tok_off, n_docs, d_global_off, s);
+    jtk_launch_stitch(c->totals(), c->rank, c->base(), d_tok_off, n_docs, d_global_off, s);
     e = hipGetLastError();
     if (e != hipSuccess) return jtk_fail_msg(JTK_ERR_HIP, std::string("stitch: ") + hipGetErrorString(e));
-    if (d_totals) *d_totals = c->d_totals;
-    if (d_base) *d_base = c->d_base;
+    if (d_totals) *d_totals = c->totals();
+    if (d_base) *d_base = c->base();
     return JTK_OK;
 }
 
@@ -172,12 +169,12 @@ int jtk_comm_fetch(jtk_comm* c, void* stream, int64_t* totals, int64_t* base) {
     if (!c) return jtk_fail_msg(JTK_ERR_INVALID_ARGUMENT, "comm is NULL");
     if (hipSetDevice(c->device) != hipSuccess) return jtk_fail_msg(JTK_ERR_NO_DEVICE, "hipSetDevice failed");
     hipStream_t s = (hipStream_t)stream;
-    hipError_t e = hipMemcpyAsync(c->h_out, c->d_totals, (size_t)c->world * 8, hipMemcpyDeviceToHost, s);
-    if (e == hipSuccess) e = hipMemcpyAsync(c->h_out + c->world, c->d_base, 8, hipMemcpyDeviceToHost, s);
+    hipError_t e = hipMemcpyAsync(c->h_out.p, c->d_totals.p, (size_t)c->world * 8, hipMemcpyDeviceToHost, s);
+    if (e == hipSuccess) e = hipMemcpyAsync(c->h_out.p + c->world, c->d_base.p, 8, hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return jtk_fail_msg(JTK_ERR_HIP, std::string("comm fetch: ") + hipGetErrorString(e));
-    if (totals) memcpy(totals, c->h_out, (size_t)c->world * 8);
-    if (base) *base = c->h_out[c->world];
+    if (totals) memcpy(totals, c->h_out.p, (size_t)c->world * 8);
+    if (base) *base = c->h_out.p[c->world];
     return JTK_OK;
 }
 

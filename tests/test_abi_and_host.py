@@ -349,6 +349,20 @@ def test_service_host_logic_under_sanitizers(tmp_path, sanitizer):
     assert "WARNING: ThreadSanitizer" not in p.stderr and "ERROR: AddressSanitizer" not in p.stderr and "runtime error" not in p.stderr, p.stderr[-2000:]
 
 
+def test_owning_types_under_sanitizers(tmp_path):
+    """jtokkit_amd/csrc/jtk_owned.h (device buffer, pinned buffer, stream, event) compiled for the CPU with AddressSanitizer and
+    UBSan against counting HIP stubs (tests/cpp/owned_main.cpp): no stub call on the ensure hit path or from an empty owner's
+    destructor, the two growth rules at 1, 255, 256 and 4097 bytes, a pinned grow keeps exactly keep_bytes, a move-assign frees
+    the old allocation once, a failed grow leaves a usable owner, and with any one creating call failing nothing outlives a
+    struct that holds one of each."""
+    exe = os.path.join(str(tmp_path), "owned_san")
+    subprocess.check_call(["g++", "-O1", "-g", "-std=c++17", "-fsanitize=address,undefined", "-D__HIP_PLATFORM_AMD__",
+                           "-I/opt/rocm/include", "-o", exe, os.path.join(ROOT, "tests", "cpp", "owned_main.cpp")])
+    p = subprocess.run([exe], capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0 and "owned ok" in p.stdout, (p.returncode, p.stdout[-300:], p.stderr[-2000:])
+    assert "ERROR: AddressSanitizer" not in p.stderr and "LeakSanitizer" not in p.stderr and "runtime error" not in p.stderr, p.stderr[-2000:]
+
+
 def _build_mirror_smoke(tmp_path):
     exe = os.path.join(str(tmp_path), "mirror_smoke")
     subprocess.check_call(["g++", "-O1", "-std=c++17", "-o", exe, os.path.join(ROOT, "tests", "cpp", "mirror_smoke.cpp"),

@@ -304,3 +304,77 @@ def test_a_call_refused_for_its_arguments_keeps_the_batch(N, enc, first):
     assert len(before[3]) == len(after[3]) == 10 and all(np.array_equal(x, y) for x, y in zip(before[3], after[3]))
     _same_as_oracle(b, first)
     b.close()
+
+
+@pytest.fixture(scope="module")
+def prompts(o):
+    """About 300 KB of text: the golden prompts of the encoding, one document each, over and over; the oracle's ids, once."""
+    import golden_util
+    rows = [r[0].encode("utf-8") for r in golden_util.load_rows(TABLE) if r[0]]
+    docs, total = [], 0
+    while total < 300_000:
+        docs.append(rows[len(docs) % len(rows)])
+        total += len(docs[-1])
+    doc_off = np.zeros(len(docs) + 1, dtype=np.int64)
+    np.cumsum([len(x) for x in docs], out=doc_off[1:])
+    text = np.frombuffer(b"".join(docs), dtype=np.uint8)
+    tokens, tok_off = o.encode_batch(text, doc_off, ordinary=True)
+    for a in (text, doc_off, tokens, tok_off):
+        a.setflags(write=False)
+    return text, doc_off, tokens, tok_off
+
+
+def test_three_lives_of_everything_a_batch_owns(jt, N, enc, first, prompts):
+    """Create, run, close, three times over, with one call of every family that makes the batch (or an n-gram set) own
+    something: a host encode streamed to pinned memory in 64 KiB chunks (the scratch sets, their streams and events, the copy
+    stream, the pinned planes), a device encode with chunk, pack, character index and truncation, UTF-16 in and out, a rows
+    decode with stops, the device maxTokens rounds, an n-gram set that takes the batch.  Every round's ids are the oracle's:
+    nothing a close() gave back is still in use, nothing the next batch allocates is stale."""
+    import torch
+    text, doc_off, tokens, tok_off = prompts
+    assert len(text) > 4 * (1 << 16)
+    nd, nb, mt, pad = len(DOCS), len(first.text), 4, 0
+    d_text, d_off = _dev(np.concatenate([first.text, np.zeros(16, dtype=np.uint8)])), _dev(first.doc_off)
+    seqs = [first.tokens[first.tok_off[d]:first.tok_off[d + 1]].tolist() for d in range(nd)]
+    n_keys = set()
+    for _ in range(3):
+        b = enc.new_batch()
+        b.set_option(N.JTK_OPT_HOST_CHUNK_BYTES, 1 << 16)
+        assert b.encode_host(text, doc_off, ordinary=True, to_host=True) == len(tokens)
+        r = b.host_result()
+        assert np.array_equal(r.tokens, tokens) and np.array_equal(r.tok_off, tok_off) and not r.status.any()
+
+        b.encode_device(d_text.data_ptr(), d_off.data_ptr(), nd, nb, ordinary=True)
+        _same_as_oracle(b, first)
+        _derive(b)
+        s = enc.ngram_set(3)
+        s.add_last_encode(b)
+        n_keys.add(len(s))
+        s.close()
+
+        b.encode_utf16_host(first.units, first.unit_off, ordinary=True)
+        _same_as_oracle(b, first)
+        b.decode_host(first.tokens, first.tok_off)
+        b.decode_utf16()
+        units, unit_off, status = b.decode_utf16_fetch()
+        assert units.tolist() == first.units.tolist() and unit_off.tolist() == first.unit_off.tolist() and not status.any()
+
+        b.decode_rows_host(_rows_of(first.tokens, first.tok_off, pad), pad_id=pad, skip_pad=True)
+        b.decode_find_stops([b"x"])
+        out, byte_off, status = b.decode_fetch()
+        assert out.tobytes() == first.text.tobytes() and byte_off.tolist() == first.doc_off.tolist() and not status.any()
+        assert len(b.decode_stops_fetch()[0]) == nd
+
+        rows = torch.zeros((nd, mt), dtype=torch.int32, device="cuda")
+        kept = torch.zeros(nd, dtype=torch.int64, device="cuda")
+        trunc = torch.zeros(nd, dtype=torch.uint8, device="cuda")
+        st = torch.zeros(nd, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()
+        b.encode_device_max_tokens(d_text.data_ptr(), d_off.data_ptr(), nd, nb, mt, rows.data_ptr(), kept.data_ptr(), trunc.data_ptr(),
+                                   st.data_ptr(), ordinary=True)
+        torch.cuda.synchronize()
+        rows, kept = rows.cpu().numpy(), kept.cpu().numpy()
+        assert not st.cpu().numpy().any() and (kept <= mt).all() and kept.sum() > 0
+        assert all(rows[d, :kept[d]].tolist() == seqs[d][:kept[d]] for d in range(nd))
+        b.close()
+    assert len(n_keys) == 1 and min(n_keys) > 0
