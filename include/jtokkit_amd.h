@@ -91,11 +91,15 @@ enum {
                                      here or by env JTK_CHUNKS_IN_FLIGHT: the host waits once per chunk there, two sets stall) */
     JTK_OPT_HOST_CHUNK_BYTES = 3, /* ... host input (default 32 MiB: the copy of one chunk overlaps the kernels of another;
                                      env JTK_HOST_CHUNK_BYTES) */
-    JTK_OPT_REUSE_CHUNK_PLAN = 4  /* 1: jtk_batch_encode_device keeps the chunk plan of the last batch while it is handed the same
+    JTK_OPT_REUSE_CHUNK_PLAN = 4, /* 1: jtk_batch_encode_device keeps the chunk plan of the last batch while it is handed the same
                                      offsets array again (same pointer and counts: a step loop) -- no plan kernel, no host
                                      synchronisation in the call.  The caller promises not to change those offsets in place
                                      (if it does: JTK_ERR_INVALID_ARGUMENT as the batch's worst status, never wrong tokens).
                                      Default 0 */
+    JTK_OPT_REPEAT_TABLE_BYTES = 5 /* jtk_batch_ngram_repeats: the budget in bytes for the table of one group of documents (20
+                                     bytes per slot, two slots per n-gram rounded up to a power of two); at least 1280 (64
+                                     slots).  A document that needs more is a group of its own with the table it needs.
+                                     Results never depend on it.  Default 256 MiB */
 };
 
 typedef struct jtk_encoding jtk_encoding;
@@ -299,6 +303,53 @@ int jtk_ngram_set_size(const jtk_ngram_set* s, int64_t* n_keys, int64_t* capacit
 int jtk_ngram_set_keys(const jtk_ngram_set* s, uint64_t* keys, int64_t cap);
 int jtk_batch_ngram_overlap(jtk_batch* b, const jtk_ngram_set* s, uint8_t* d_tok_flags_or_null, int32_t* d_n_hit_or_null,
                             int32_t* d_n_covered_or_null, int64_t* d_first_hit_or_null, void* stream_or_null);
+
+/* Repeated token n-grams inside a document: the repetition filters of Gopher (Rae et al. 2021, table A1; RedPajama-v2, Dolma,
+ * FineWeb / datatrove) on the ids of the last batch encode (jtk_repeat.hip; the rule, bit for bit, is csrc/jtk_repeat_rules.h --
+ * integer arithmetic only, so every result is exact).
+ *   With G and mix as for jtk_minhash_params, all modulo 2^64: key = mix(seed + G * (ngram + 97)) (MinHash has ngram + 1, the
+ *   n-gram set ngram + 33: no shared key family) and key_D = mix(key + G * (D + 1)), D = doc_index_base + d for document d of the
+ *   batch (doc_index_base as in jtk_fim_params: a shard gives what the whole corpus would).  A document of l tokens has the
+ *   n-grams t[i .. i + ngram), 0 <= i <= l - ngram -- none when l < ngram, none when its status < 0 whatever tokens the encode
+ *   left it --; H = H * G + id + 1 over an n-gram's ids (as uint32) and k = mix(H ^ key_D), G where that is 0.  Two n-grams of
+ *   one document are the same when their k are equal (a 64-bit collision inside a document is part of the rule); n-grams of
+ *   different documents are never compared.  first(i) = the smallest document-relative position with the k of the n-gram at i,
+ *   count(i) = the number of positions with it.
+ *   Per token p: JTK_RP_START when an n-gram starts at p and is a repeat, JTK_RP_COVERED when a start-flagged i of the same
+ *   document has p - ngram < i <= p.  A repeat: first(p) < p (a later occurrence); with JTK_REPEAT_MARK_FIRST: count(p) >= 2, so
+ *   the first occurrence is marked as well (as RedPajama-v2 counts it).  datatrove's variant, which skips ngram tokens ahead
+ *   behind every repeat it finds, is sequential in the document and not offered.
+ *   Per document: n_repeat = the start flags, n_covered = the covered tokens, top_count = the largest count over its n-grams (0
+ *   without any), top_first = the smallest first among the n-grams with that count (-1 without any).  Gopher's top-n-gram
+ *   fraction is top_count * ngram / l, its duplicate-n-gram fraction n_covered / l.
+ *   Deviation: the device keeps the n-grams of a group of documents in one table keyed by k alone, so two n-grams of different
+ *   documents with equal k (different key_D: probability 2^-64 per pair) would be conflated; for a table of m n-grams at most
+ *   m^2 / 2^65 such pairs are expected -- the order of the false-hit rate the n-gram set accepts.
+ * jtk_batch_ngram_repeats: works on the LAST batch encode on `b` (host or device input, any flags but JTK_ENCODE_COUNT_ONLY:
+ *   JTK_ERR_INVALID_ARGUMENT then, and with no result).  ngram 1..32, flags 0 or JTK_REPEAT_MARK_FIRST: anything else is
+ *   JTK_ERR_INVALID_ARGUMENT, as is a document of 2^31 tokens or more.  Caller-owned device buffers, each may be NULL and is then
+ *   not written: d_tok_flags[n_tokens] uint8 (any alignment; 8-byte aligned takes the fast path), d_n_repeat[n_docs],
+ *   d_n_covered[n_docs] and d_top_count[n_docs] int32 (4-byte aligned), d_top_first[n_docs] int64 (8-byte aligned); a misaligned
+ *   one is JTK_ERR_INVALID_ARGUMENT.  A refused call writes nothing.  The batch is walked in groups of whole consecutive
+ *   documents that share one table (20 bytes per slot; capacity the smallest power of two >= max(64, 2 * the group's n-grams)): a
+ *   group takes documents while its table stays within JTK_OPT_REPEAT_TABLE_BYTES, a document larger than that is a group of its
+ *   own.  The table belongs to the batch, is reused by later calls and freed with it; when it cannot be allocated the call
+ *   returns JTK_ERR_OUT_OF_MEMORY and nothing has been written.  Results never depend on the grouping.
+ *   Waits twice: for the token count (as jtk_batch_minhash), and for the documents' token offsets and statuses, from which the
+ *   groups are planned; the passes are then queued on stream_or_null (the batch's stream when NULL) behind the encode and
+ *   behind an earlier call's passes, and the call does not wait for them.  It reads the ids, tok_off and status only: chunk,
+ *   pack, truncate, FIM and fetch results are untouched. */
+#define JTK_RP_START 1
+#define JTK_RP_COVERED 2
+#define JTK_REPEAT_MARK_FIRST 1u
+typedef struct jtk_repeat_params {
+    uint64_t seed;
+    uint64_t doc_index_base;
+    int32_t ngram;          /* n: 1..32 */
+    uint32_t flags;         /* 0 or JTK_REPEAT_MARK_FIRST */
+} jtk_repeat_params;        /* 24 bytes */
+int jtk_batch_ngram_repeats(jtk_batch* b, const jtk_repeat_params* params, uint8_t* d_tok_flags_or_null, int32_t* d_n_repeat_or_null,
+                            int32_t* d_n_covered_or_null, int32_t* d_top_count_or_null, int64_t* d_top_first_or_null, void* stream_or_null);
 
 /* Device buffers already resident in HBM (what bench.py times).  `stream_or_null` = a hipStream_t
  * to order against, or NULL for the batch's own stream: the whole encode is ordered like one operation on that stream

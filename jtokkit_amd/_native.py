@@ -70,6 +70,11 @@ JTK_OPT_CHUNK_BYTES = 1
 JTK_OPT_CHUNKS_IN_FLIGHT = 2
 JTK_OPT_HOST_CHUNK_BYTES = 3
 JTK_OPT_REUSE_CHUNK_PLAN = 4
+JTK_OPT_REPEAT_TABLE_BYTES = 5
+JTK_RP_START = 1
+JTK_RP_COVERED = 2
+JTK_REPEAT_MARK_FIRST = 1
+JTK_RP_MIN_TABLE_BYTES = 1280
 
 
 
@@ -87,6 +92,11 @@ class MinhashParamsStruct(C.Structure):
 class NgramParamsStruct(C.Structure):
     """jtk_ngram_params"""
     _fields_ = [("seed", C.c_uint64), ("ngram", C.c_int32), ("flags", C.c_uint32)]
+
+
+class RepeatParamsStruct(C.Structure):
+    """jtk_repeat_params"""
+    _fields_ = [("seed", C.c_uint64), ("doc_index_base", C.c_uint64), ("ngram", C.c_int32), ("flags", C.c_uint32)]
 
 
 # every symbol include/jtokkit_amd.h declares: (restype, argtypes)
@@ -121,6 +131,7 @@ SIGNATURES = {
     "jtk_ngram_set_size": (C.c_int, [_p, C.POINTER(_i64), C.POINTER(_i64)]),
     "jtk_ngram_set_keys": (C.c_int, [_p, _p, _i64]),
     "jtk_batch_ngram_overlap": (C.c_int, [_p, _p, _p, _p, _p, _p, _p]),
+    "jtk_batch_ngram_repeats": (C.c_int, [_p, C.POINTER(RepeatParamsStruct), _p, _p, _p, _p, _p, _p]),
     "jtk_widen_ids": (C.c_int, [_p, _p, C.c_int, _i64, _i64, _p]),
     "jtk_batch_encode": (C.c_int, [_p, _p, _p, _i64, C.c_uint32, C.POINTER(_i64)]),
     "jtk_batch_encode_pieces": (C.c_int, [_p, _p, _p, _i64, _p, _p, _i64, C.c_uint32, C.POINTER(_i64)]),

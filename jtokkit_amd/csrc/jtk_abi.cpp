@@ -23,6 +23,7 @@
 #include "jtk_maxtok_rules.h"
 #include "jtk_ngram_rules.h"
 #include "jtk_owned.h"
+#include "jtk_repeat_rules.h"
 #include "jtk_tables.h"
 
 namespace {
@@ -189,6 +190,15 @@ struct jtk_batch {
     JtkStopWork stop{};
     bool have_stops = false;
     hipStream_t stop_stream = nullptr;   // stream of the last find_stops: the fetch waits for it
+    // jtk_batch_ngram_repeats (jtk_repeat.hip): the table of one group of documents (key | count | first, jtk_rp_table_at), reused
+    // from group to group and from call to call; the packed top word per document; the host copy of tok_off | status that the
+    // groups are planned from.  ev_rp is recorded behind every pass: the next one, maybe on another stream, reuses the table
+    // behind it, and the batch is not freed before it.
+    DevBuf rp_table, rp_top;
+    Pinned<uint8_t> h_rp;
+    Event ev_rp;
+    bool rp_queued = false;
+    int64_t rp_table_bytes = (int64_t)256 << 20;   // JTK_OPT_REPEAT_TABLE_BYTES
     JtkResult* host_result = nullptr;   // host_result_own, or the head of h_small after a small job
     Pinned<JtkResult> host_result_own;
     // the last job
@@ -487,6 +497,7 @@ void jtk_batch_destroy(jtk_batch* b) {
     for (ChunkSet& cs : b->set)
         if (cs.stream) (void)hipStreamSynchronize(cs.stream);
     if (b->copy_stream) (void)hipStreamSynchronize(b->copy_stream);
+    if (b->rp_queued) (void)hipEventSynchronize(b->ev_rp);      // (the last repeats pass may be on a caller's stream)
     delete b;                        // (every wait above comes before the first free: the members free themselves here)
 }
 
@@ -509,6 +520,10 @@ int jtk_batch_set_option(jtk_batch* b, int option, int64_t value) {
         case JTK_OPT_REUSE_CHUNK_PLAN:
             b->reuse_plan = value != 0;
             b->plan_doc_off = nullptr;
+            return JTK_OK;
+        case JTK_OPT_REPEAT_TABLE_BYTES:
+            if (value < JTK_RP_MIN_TABLE_BYTES) return fail(JTK_ERR_INVALID_ARGUMENT, "repeat table budget must be at least 1280 bytes (64 slots)");
+            b->rp_table_bytes = value;
             return JTK_OK;
         default: return fail(JTK_ERR_INVALID_ARGUMENT, "unknown option");
     }
@@ -2358,6 +2373,70 @@ int jtk_batch_ngram_overlap(jtk_batch* b, const jtk_ngram_set* s, uint8_t* d_tok
     jtk_launch_ngram_overlap(ng_view(b, nt, s->p.ngram), s->p.seed, s->slots(), s->capacity, d_tok_flags, d_n_hit, d_n_covered, d_first_hit, st);
     HIP_TRY(hipGetLastError());
     return ng_done(s, st);
+}
+
+// ---- repeated n-grams inside a document (jtk_repeat.hip) ------------------------------------------------------------------
+int jtk_batch_ngram_repeats(jtk_batch* b, const jtk_repeat_params* p, uint8_t* d_tok_flags, int32_t* d_n_repeat, int32_t* d_n_covered,
+                            int32_t* d_top_count, int64_t* d_top_first, void* stream_or_null) {
+    int rc;
+    if ((rc = need_encode(b, NEED_IDS))) return rc;
+    if (!p) return fail(JTK_ERR_INVALID_ARGUMENT, "params is NULL");
+    if (!jtk_rp_params_ok(p->ngram, p->flags)) return fail(JTK_ERR_INVALID_ARGUMENT, "n-gram repeats: ngram 1..32, flags 0 or JTK_REPEAT_MARK_FIRST");
+    if (((uintptr_t)d_n_repeat & 3u) || ((uintptr_t)d_n_covered & 3u) || ((uintptr_t)d_top_count & 3u) || ((uintptr_t)d_top_first & 7u))
+        return fail(JTK_ERR_INVALID_ARGUMENT, "unaligned array (4-byte n_repeat, n_covered and top_count, 8-byte top_first)");
+    HIP_TRY(hipSetDevice(b->enc->device));
+    int64_t nt = 0;
+    if ((rc = jtk_batch_result(b, &nt, nullptr, nullptr))) return rc;
+    const int64_t nd = b->job_docs;
+    const bool want_top = d_top_count || d_top_first;
+    if (nd <= 0 || !(d_tok_flags || d_n_repeat || d_n_covered || want_top)) return JTK_OK;
+    hipStream_t st = pick_stream(b, stream_or_null);
+    if ((rc = ck_order(b, b->last_stream, st))) return rc;
+    HIP_TRY(b->ev_rp.create());
+    if (b->rp_queued) HIP_TRY(hipStreamWaitEvent(st, b->ev_rp, 0));
+    // the plan: the groups come from the documents' token counts and statuses, read once
+    if ((rc = b->h_rp.ensure((size_t)(nd + 1) * 8 + (size_t)nd * 4))) return rc;
+    int64_t* const h_off = (int64_t*)b->h_rp.p;
+    int32_t* const h_status = (int32_t*)(h_off + nd + 1);
+    HIP_TRY(hipMemcpyAsync(h_off, b->tok_off.p, (size_t)(nd + 1) * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(h_status, b->status.p, (size_t)nd * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (h_off[0] != 0 || h_off[nd] > nt) return fail(JTK_ERR_HIP, "the token offsets of the last encode do not cover its tokens");
+    for (int64_t d = 0; d < nd; d++)
+        if (h_off[d + 1] - h_off[d] > JTK_RP_MAX_DOC_TOKENS) return fail(JTK_ERR_INVALID_ARGUMENT, "n-gram repeats: a document of 2^31 tokens or more");
+    struct Group { int64_t lo, hi, m; };
+    std::vector<Group> groups;
+    int64_t m_max = 0;
+    for (int64_t d0 = 0; d0 < nd;) {
+        int64_t m = 0;
+        const int64_t d1 = jtk_rp_group_end(h_off, h_status, nd, p->ngram, d0, b->rp_table_bytes, &m);
+        if (h_off[d1] > h_off[d0]) groups.push_back({h_off[d0], h_off[d1], m});
+        if (m > m_max) m_max = m;
+        d0 = d1;
+    }
+    // everything that can fail for lack of memory comes before the first write; a table that grows is not in use any more
+    const size_t table_bytes = m_max ? (size_t)jtk_rp_table_bytes(m_max) : 0, top_bytes = want_top ? (size_t)nd * 8 : 0;
+    if ((table_bytes > b->rp_table.cap || top_bytes > b->rp_top.cap) && b->rp_queued) HIP_TRY(hipEventSynchronize(b->ev_rp));
+    if ((rc = b->rp_table.ensure(table_bytes)) || (rc = b->rp_top.ensure(top_bytes))) return rc;
+    uint64_t* const top = want_top ? (uint64_t*)b->rp_top.p : nullptr;
+    const JtkMhView v = ng_view(b, nt, p->ngram);
+    jtk_launch_repeat_preset(nd, d_n_repeat, d_n_covered, top, st);
+    for (const Group& g : groups) {
+        if (g.m == 0) {                                          // (tokens without an n-gram: documents shorter than n, refused ones)
+            if (d_tok_flags) HIP_TRY(hipMemsetAsync(d_tok_flags + g.lo, 0, (size_t)(g.hi - g.lo), st));
+            continue;
+        }
+        const int64_t cap = jtk_rp_capacity(g.m);
+        const JtkRpTable t = jtk_rp_table_at(b->rp_table.p, cap);
+        HIP_TRY(hipMemsetAsync(t.key, 0, (size_t)cap * 12, st));                // key | count
+        HIP_TRY(hipMemsetAsync(t.first, 0xFF, (size_t)cap * 8, st));
+        jtk_launch_repeat_group(v, p->seed, p->doc_index_base, p->flags, t, g.lo, g.hi, d_tok_flags, d_n_repeat, d_n_covered, top, st);
+    }
+    if (want_top) jtk_launch_repeat_top(nd, top, d_top_count, d_top_first, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(b->ev_rp, st));
+    b->rp_queued = true;
+    return JTK_OK;
 }
 
 int jtk_batch_token_offsets(jtk_batch* b, int64_t* d_byte_pos, void* stream_or_null) {

@@ -148,6 +148,11 @@ public:
                       int64_t* dFirstHit = nullptr, void* stream = nullptr) {
         check(jtk_batch_ngram_overlap(batch_, s, dTokFlags, dNHit, dNCovered, dFirstHit, stream));
     }
+    // repeated n-grams inside the documents of the last encode (jtk_batch_ngram_repeats); every output may be nullptr
+    void ngramRepeats(const jtk_repeat_params& params, uint8_t* dTokFlags, int32_t* dNRepeat = nullptr, int32_t* dNCovered = nullptr,
+                      int32_t* dTopCount = nullptr, int64_t* dTopFirst = nullptr, void* stream = nullptr) {
+        check(jtk_batch_ngram_repeats(batch_, &params, dTokFlags, dNRepeat, dNCovered, dTopCount, dTopFirst, stream));
+    }
 
     // batch decodeBytes: token lists back to back in `ids`, n+1 offsets -> bytes back to back + n+1 byte offsets + status
     void decodeBatch(const int32_t* ids, const std::vector<int64_t>& seqOff, std::string& bytes,

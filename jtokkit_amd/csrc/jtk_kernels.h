@@ -434,6 +434,16 @@ void jtk_launch_ngram_insert(const JtkMhView& v, uint64_t seed, uint64_t* table,
 void jtk_launch_ngram_insert_keys(const uint64_t* keys, int64_t n, uint64_t* table, int64_t capacity, uint64_t* count_or_null, hipStream_t s);
 void jtk_launch_ngram_overlap(const JtkMhView& v, uint64_t seed, const uint64_t* table, int64_t capacity, uint8_t* flags, int32_t* n_hit,
                               int32_t* n_covered, int64_t* first_hit, hipStream_t s);
+// Repeated n-grams inside a document (jtk_repeat.hip; the rule is jtk_repeat_rules.h).  `top` is the batch's packed word per document.
+//   preset        n_repeat = n_covered = 0 and top = 0 for every document; each may be NULL
+//   group         the two passes over the token range [lo, hi) of a group of whole documents, with a table preset by the caller
+//                 (key and count 0, first all ones); tok_flags / n_repeat / n_covered / top may each be NULL
+//   top           top_count and top_first out of the packed words
+struct JtkRpTable;
+void jtk_launch_repeat_preset(int64_t n_docs, int32_t* n_repeat, int32_t* n_covered, uint64_t* top, hipStream_t s);
+void jtk_launch_repeat_group(const JtkMhView& v, uint64_t seed, uint64_t doc_index_base, uint32_t flags, const JtkRpTable& t, int64_t lo, int64_t hi,
+                             uint8_t* tok_flags, int32_t* n_repeat, int32_t* n_covered, uint64_t* top, hipStream_t s);
+void jtk_launch_repeat_top(int64_t n_docs, const uint64_t* top, int32_t* top_count, int64_t* top_first, hipStream_t s);
 // Device-side state of an allow-special encode (jtk_special.hip, JTK_ENCODE_ALLOW_SPECIAL; the rule is jtk_special_rules.h).
 // Candidates (per position, the longest allowed literal there) are found in position order, resolved to the kept matches, and
 // the batch is cut into sub-documents that partition the text: per document a segment, then per candidate i two slots

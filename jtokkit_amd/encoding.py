@@ -358,7 +358,7 @@ class Batch:
             pass
 
     def set_option(self, option, value):
-        """jtk_batch_set_option: N.JTK_OPT_CHUNK_BYTES, N.JTK_OPT_CHUNKS_IN_FLIGHT."""
+        """jtk_batch_set_option: N.JTK_OPT_CHUNK_BYTES, N.JTK_OPT_CHUNKS_IN_FLIGHT, ..., N.JTK_OPT_REPEAT_TABLE_BYTES."""
         _check(N.lib().jtk_batch_set_option(self._h, int(option), int(value)))
 
     def set_allowed_special(self, ids):
@@ -472,6 +472,17 @@ class Batch:
         d_n_hit_ptr and d_n_covered_ptr, int64 [n_docs] at d_first_hit_ptr, device pointers, each may be None and is then not
         written; waits for the token count, not for the pass."""
         _check(N.lib().jtk_batch_ngram_overlap(self._h, ngram_set._h, d_tok_flags_ptr, d_n_hit_ptr, d_n_covered_ptr, d_first_hit_ptr, stream))
+
+    def ngram_repeats(self, ngram, d_tok_flags_ptr=None, d_n_repeat_ptr=None, d_n_covered_ptr=None, d_top_count_ptr=None,
+                      d_top_first_ptr=None, seed=0, mark_first=False, doc_index_base=0, stream=None):
+        """jtk_batch_ngram_repeats of the last encode: uint8 [n_tokens] at d_tok_flags_ptr (JTK_RP_START | JTK_RP_COVERED per
+        token), int32 [n_docs] at d_n_repeat_ptr, d_n_covered_ptr and d_top_count_ptr, int64 [n_docs] at d_top_first_ptr, device
+        pointers, each may be None and is then not written; waits for the token count and for the documents' token counts (the
+        groups that share a table are planned from them), not for the pass."""
+        p = N.RepeatParamsStruct(seed & 0xFFFFFFFFFFFFFFFF, doc_index_base & 0xFFFFFFFFFFFFFFFF, ngram,
+                                 N.JTK_REPEAT_MARK_FIRST if mark_first else 0)
+        _check(N.lib().jtk_batch_ngram_repeats(self._h, C.byref(p), d_tok_flags_ptr, d_n_repeat_ptr, d_n_covered_ptr, d_top_count_ptr,
+                                               d_top_first_ptr, stream))
 
     def encode_device(self, d_text_ptr, d_doc_off_ptr, n_docs, n_bytes, ordinary=False, stream=None, sync=True,
                       allow_special=False, validate=False, count_only=False, fim=False):
@@ -1307,6 +1318,103 @@ class HipEncoding:
                             n_covered.data_ptr() if nd else None, first_hit.data_ptr() if nd else None, stream)
             tok_off, status = self._tok_off_and_status(b, nd, device, stream)
         return flags, n_hit, n_covered, first_hit, tok_off, status
+
+    def ngram_repeats_batch(self, texts, ngram, seed=0, mark_first=False, doc_index_base=0, ordinary=True, allowed_special=None):
+        """Repeated token n-grams inside each of a list of str/bytes (jtk_batch_ngram_repeats; the rule is in
+        include/jtokkit_amd.h): (flags uint8 [n_tokens] -- JTK_RP_START | JTK_RP_COVERED per token --, n_repeat int32 [n],
+        n_covered int32 [n], top_count int32 [n], top_first int64 [n] -- the document-relative first position of the most
+        frequent n-gram, or -1 --, tok_off int64 [n + 1]).  mark_first: the first occurrence of a repeated n-gram is marked as
+        well (RedPajama-v2's count); otherwise only the later ones."""
+        bs, text, doc_off = _join_texts(texts)
+        res = self.encode_batch_packed(text, doc_off, ordinary, False, allowed_special)
+        n = len(bs)
+        b = self._b()
+        with _device_arrays() as put:
+            outs = [put(np.zeros(len(res.tokens), dtype=np.uint8)), put(np.zeros(n, dtype=np.int32)), put(np.zeros(n, dtype=np.int32)),
+                    put(np.zeros(n, dtype=np.int32)), put(np.zeros(n, dtype=np.int64))]
+            b.ngram_repeats(ngram, *[x.ptr for x in outs], seed=seed, mark_first=mark_first, doc_index_base=doc_index_base)
+            _stream_sync(b.stream())
+            return tuple(x.fetch() for x in outs) + (res.tok_off.copy(),)
+
+    def ngram_repeats_batch_device(self, text, doc_off, ngram, seed=0, mark_first=False, doc_index_base=0, ordinary=True, allowed_special=None):
+        """Encodes a device-resident batch (text CUDA torch.uint8, doc_off CUDA torch.int64 [n_docs + 1]) and returns the repeated
+        n-grams inside its documents as CUDA tensors written on torch.cuda.current_stream(): (flags uint8 [n_tokens], n_repeat
+        int32 [n_docs], n_covered int32 [n_docs], top_count int32 [n_docs], top_first int64 [n_docs], tok_off int64 [n_docs + 1],
+        status int32 [n_docs]).  The ids stay in the batch (device_result).  Waits for the token count and for the documents'
+        token counts (and, with allowed_special, once more for the encode's count of literal candidates)."""
+        import torch
+        self._check_device_inputs("ngram_repeats_batch_device", ("text", text, torch.uint8), ("doc_off", doc_off, torch.int64))
+        allow = self._allow(self._b(), allowed_special)
+        with self._encode_device_batch(text, doc_off, ordinary, allow) as (b, nd, device, stream):
+            nt = b.result()[0]
+            flags = torch.empty(nt, dtype=torch.uint8, device=device)
+            rows = [torch.empty(nd, dtype=torch.int32, device=device) for _ in range(3)] + [torch.empty(nd, dtype=torch.int64, device=device)]
+            b.ngram_repeats(ngram, flags.data_ptr() if nt else None, *[t.data_ptr() if nd else None for t in rows], seed=seed,
+                            mark_first=mark_first, doc_index_base=doc_index_base, stream=stream)
+            tok_off, status = self._tok_off_and_status(b, nd, device, stream)
+        return (flags,) + tuple(rows) + (tok_off, status)
+
+    def repetition_signals(self, texts, top=(2, 3, 4), dup=(5, 6, 7, 8, 9, 10), mark_first=False, seed=0, ordinary=True, allowed_special=None):
+        """The fractions the repetition filters of Gopher (Rae et al. 2021, table A1) put a threshold on, for a list of str/bytes:
+        {"top": {n: (token_fraction, byte_fraction)}, "dup": {n: (token_fraction, byte_fraction)}, "n_tokens": int64 [n_docs],
+        "n_bytes": int64 [n_docs], "status": int32 [n_docs]}, the fractions numpy float64 [n_docs].
+          top[n]  the share of the document inside its most frequent n-gram: top_count * n / l in tokens, and top_count * the
+                  bytes of t[top_first .. top_first + n) / the document's bytes.
+          dup[n]  the share inside n-grams that occur more than once: n_covered / l in tokens, the bytes of the covered tokens /
+                  the document's bytes.  mark_first: as for ngram_repeats_batch.
+        0.0 for a document without n-grams.  One encode, one jtk_batch_ngram_repeats pass per n; token byte lengths come from
+        jtk_batch_token_offsets and the sums are done with torch on the device: no ids on the host."""
+        import torch
+        bs, text, doc_off = _join_texts(texts)
+        nd = len(bs)
+        top, dup = [int(n) for n in top], [int(n) for n in dup]
+        empty = lambda: (np.zeros(nd, dtype=np.float64), np.zeros(nd, dtype=np.float64))
+        if nd == 0 or not len(text):
+            return {"top": {n: empty() for n in top}, "dup": {n: empty() for n in dup}, "n_tokens": np.zeros(nd, dtype=np.int64),
+                    "n_bytes": np.zeros(nd, dtype=np.int64), "status": np.zeros(nd, dtype=np.int32)}
+        device = torch.device("cuda", N.lib().jtk_encoding_device(self._h))
+        d_off = torch.from_numpy(doc_off).to(device)
+        d_text = torch.from_numpy(text.copy()).to(device)                        # (a copy: frombuffer views are read-only)
+        self._check_device_inputs("repetition_signals", ("text", d_text, torch.uint8), ("doc_off", d_off, torch.int64))
+        allow = self._allow(self._b(), allowed_special)
+        tops, dups = {}, {}
+        with self._encode_device_batch(d_text, d_off, ordinary, allow) as (b, _, _, stream):
+            nt = b.result()[0]
+            pos = torch.empty(nt, dtype=torch.int64, device=device)
+            if nt:
+                b.token_offsets(pos.data_ptr(), stream)
+            for n in top:
+                tops[n] = (torch.empty(nd, dtype=torch.int32, device=device), torch.empty(nd, dtype=torch.int64, device=device))
+                b.ngram_repeats(n, None, None, None, tops[n][0].data_ptr(), tops[n][1].data_ptr(), seed=seed, stream=stream)
+            for n in dup:
+                dups[n] = (torch.empty(nt, dtype=torch.uint8, device=device), torch.empty(nd, dtype=torch.int32, device=device))
+                b.ngram_repeats(n, dups[n][0].data_ptr() if nt else None, None, dups[n][1].data_ptr(), None, None, seed=seed,
+                                mark_first=mark_first, stream=stream)
+            tok_off, status = self._tok_off_and_status(b, nd, device, stream)
+        # (joined into torch's current stream: the sums follow the passes)
+        l = tok_off[1:] - tok_off[:-1]
+        n_bytes = d_off[1:] - d_off[:-1]
+        has = l > 0
+        end = torch.cat([pos[1:], d_off[-1:]]) if nt else pos
+        if nt:
+            end[tok_off[1:][has] - 1] = d_off[1:][has]                           # a document's last token ends where the document does
+        cum = torch.zeros(nt + 1, dtype=torch.int64, device=device)              # cum[t] = the bytes of the tokens before t
+        cum[1:] = torch.cumsum(end - pos, 0)
+        lf, bf = l.clamp(min=1).double(), n_bytes.clamp(min=1).double()
+        out = {"top": {}, "dup": {}}
+        for n in top:
+            count, first = tops[n][0].long(), tops[n][1]
+            at = (tok_off[:-1] + first.clamp(min=0)).clamp(max=max(nt - n, 0))
+            gram = torch.where(count > 0, cum[(at + n).clamp(max=nt)] - cum[at], torch.zeros_like(at))
+            out["top"][n] = (((count * n).double() / lf).cpu().numpy(), ((count * gram).double() / bf).cpu().numpy())
+        for n in dup:
+            flags, covered = dups[n]
+            ccum = torch.zeros(nt + 1, dtype=torch.int64, device=device)
+            ccum[1:] = torch.cumsum((end - pos) * ((flags & N.JTK_RP_COVERED) != 0), 0)
+            cbytes = ccum[tok_off[1:]] - ccum[tok_off[:-1]]
+            out["dup"][n] = ((covered.double() / lf).cpu().numpy(), (cbytes.double() / bf).cpu().numpy())
+        out["n_tokens"], out["n_bytes"], out["status"] = l.cpu().numpy(), n_bytes.cpu().numpy(), status.cpu().numpy()
+        return out
 
     def near_duplicates(self, texts, threshold=0.8, ngram=5, num_hashes=128, bands=16, seed=0, ordinary=True, allowed_special=None):
         """Clusters of near-duplicate documents by MinHash and LSH: int64 [n] labels, the smallest document index of each
