@@ -351,6 +351,77 @@ typedef struct jtk_repeat_params {
 int jtk_batch_ngram_repeats(jtk_batch* b, const jtk_repeat_params* params, uint8_t* d_tok_flags_or_null, int32_t* d_n_repeat_or_null,
                             int32_t* d_n_covered_or_null, int32_t* d_top_count_or_null, int64_t* d_top_first_or_null, void* stream_or_null);
 
+/* Duplicate lines and paragraphs inside a document: the line-level half of Gopher's repetition filters (Rae et al. 2021, table
+ * A1; RedPajama-v2, Dolma, FineWeb / datatrove) on the TEXT of the last batch encode (jtk_lines.hip; the rule, bit for bit, is
+ * csrc/jtk_lines_rules.h -- integer arithmetic only, so every result is exact).
+ *   Text: document d of the batch is the bytes x[a, e), a = doc_off[d], e = doc_off[d + 1].  A document with status < 0 has no
+ *   units, whatever its text.  Parameters: seed, doc_index_base, unit = JTK_LINES_LINE (0) or JTK_LINES_PARAGRAPH (1), flags out
+ *   of JTK_LINES_MARK_FIRST (1u) and JTK_LINES_TRIM (2u); anything else is JTK_ERR_INVALID_ARGUMENT.
+ *   Bytes: the only line break is 0x0A.  W, the blank set, is empty without JTK_LINES_TRIM and {0x20, 0x09, 0x0D} with it.  A byte
+ *   is INK when it is neither 0x0A nor in W.
+ *   Units: a raw line is a maximal run of bytes of the document without 0x0A (the document's start and end bound raw lines:
+ *   nothing crosses a document edge); it is blank when it has no ink.  LINE: for each non-blank raw line, [its first ink byte, its
+ *   last ink byte + 1).  PARAGRAPH: for each maximal run of consecutive non-blank raw lines, [the first ink byte of the first
+ *   line, the last ink byte of the last line + 1); the bytes in between, line breaks and blanks included, are part of the unit
+ *   unchanged.  Per byte, equivalently: an ink byte p starts a unit when its document has no earlier ink byte, or when the number
+ *   of 0x0A between the previous ink byte and p is >= 1 (LINE) or >= 2 (PARAGRAPH); it ends a unit when the same holds towards
+ *   the next ink byte, or there is none.
+ *   What this matches: without TRIM, re.split("\n+") for LINE and re.split("\n{2,}") for PARAGRAPH on a document stripped of
+ *   leading and trailing newlines -- what datatrove's Gopher repetition filter does after strip().  With TRIM, CRLF text and lines
+ *   that differ only in indentation or trailing blanks behave as RedPajama-v2's normalised lines do.  No more is claimed.
+ *   Hash, all modulo 2^64, G and mix as for jtk_minhash_params: key = mix(seed + G * (unit + 161)) (MinHash has ngram + 1, the
+ *   n-gram set ngram + 33, n-gram repeats ngram + 97, ngram <= 32: no shared key family), key_D = mix(key + G * (D + 1)), D =
+ *   doc_index_base + d (as for jtk_repeat_params: a shard gives what the whole corpus would).  H = H * G + byte + 1 over the
+ *   unit's bytes, from 0; k = mix(H ^ key_D), G where that is 0.  Two units of ONE document are the same when their k are equal
+ *   (a 64-bit collision inside a document is part of the rule); units of different documents are never compared.
+ *   Per unit u, over a document's units in text order: first(u) = the smallest document-relative index with u's k, count(u) = the
+ *   number of units with it.  A repeat: first(u) < u (a later occurrence); with JTK_LINES_MARK_FIRST: count(u) >= 2.  chars of a
+ *   byte range = its bytes b with (b & 0xC0) != 0x80 (the weight of JTK_UNIT_CODEPOINT; defined for any bytes).
+ *   Results.  Per unit, in document order then text order: begin and end (batch byte positions), flag (1 for a repeat).  Per
+ *   document: unit_off [n_docs + 1]; n_dup, dup_bytes, dup_chars over the flagged units; unit_bytes, unit_chars over all units;
+ *   doc_chars over [a, e) (whatever the status); top_count = the largest count (0 without units); top_first = the
+ *   document-relative index of the first unit with that count (-1 without units).  Gopher's duplicate-line fraction is n_dup /
+ *   the document's units, its character fraction dup_chars / doc_chars.
+ *   Deviation: the device keeps the units of a group of documents in one table keyed by k alone, so two units of different
+ *   documents with equal k (different key_D: probability 2^-64 per pair) would be conflated; for a table of m units at most
+ *   m^2 / 2^65 such pairs are expected -- as for jtk_batch_ngram_repeats.
+ * Both calls work on the LAST batch encode on `b` under the conditions of jtk_batch_char_index: host or device input, any flags
+ *   (JTK_ENCODE_COUNT_ONLY included: the text is read, not the ids) but JTK_ENCODE_FIM; not after jtk_batch_encode_pieces or
+ *   jtk_batch_encode_device_max_tokens (JTK_ERR_INVALID_ARGUMENT); device-input text must still be valid and unchanged.
+ * jtk_batch_line_units: finds and hashes the units on stream_or_null (the batch's stream when NULL), waits once to read
+ *   *n_units, and keeps the list in the batch -- 48 bytes per unit, allocated at the counted size before anything is written to
+ *   it, and n_bytes / 4 + 52 bytes per 4096 of text of scratch -- until the next encode or until a call with another (unit, flags &
+ *   JTK_LINES_TRIM, seed, doc_index_base).  JTK_ERR_OUT_OF_MEMORY leaves no list.
+ * jtk_batch_line_repeats: needs the list of a jtk_batch_line_units call with the same (unit, flags & JTK_LINES_TRIM, seed,
+ *   doc_index_base) on the same encode: JTK_ERR_INVALID_ARGUMENT otherwise.  Every pointer of `out` is device memory, may be NULL
+ *   and is then not written; int32 arrays 4-byte aligned, int64 arrays 8-byte aligned (JTK_ERR_INVALID_ARGUMENT otherwise), the
+ *   flag bytes at any alignment.  A document of 2^31 units or more is JTK_ERR_INVALID_ARGUMENT.  A refused call writes nothing.
+ *   The batch is walked in groups of whole documents under JTK_OPT_REPEAT_TABLE_BYTES and shares the table of
+ *   jtk_batch_ngram_repeats (a pass of either waits for the one before it); results never depend on the grouping.  Waits once,
+ *   for the documents' unit counts, from which the groups are planned; the passes are then queued and the call does not wait for
+ *   them.  Chunk, pack, fetch, MinHash and n-gram results are untouched by both calls. */
+#define JTK_LINES_LINE 0
+#define JTK_LINES_PARAGRAPH 1
+#define JTK_LINES_MARK_FIRST 1u
+#define JTK_LINES_TRIM 2u
+typedef struct jtk_lines_params {
+    uint64_t seed;
+    uint64_t doc_index_base;
+    int32_t unit;           /* JTK_LINES_LINE or JTK_LINES_PARAGRAPH */
+    uint32_t flags;         /* JTK_LINES_MARK_FIRST | JTK_LINES_TRIM */
+} jtk_lines_params;         /* 24 bytes */
+typedef struct jtk_lines_out {      /* device pointers, each may be NULL and is then not written */
+    int64_t *unit_begin, *unit_end; /* [n_units] */
+    uint8_t* unit_flags;            /* [n_units] */
+    int64_t* unit_off;              /* [n_docs + 1] */
+    int32_t* n_dup;                 /* [n_docs], as are the following */
+    int64_t *dup_bytes, *dup_chars, *unit_bytes, *unit_chars, *doc_chars;
+    int32_t* top_count;
+    int64_t* top_first;
+} jtk_lines_out;
+int jtk_batch_line_units(jtk_batch* b, const jtk_lines_params* params, void* stream_or_null, int64_t* n_units);
+int jtk_batch_line_repeats(jtk_batch* b, const jtk_lines_params* params, const jtk_lines_out* out, void* stream_or_null);
+
 /* Device buffers already resident in HBM (what bench.py times).  `stream_or_null` = a hipStream_t
  * to order against, or NULL for the batch's own stream: the whole encode is ordered like one operation on that stream
  * (inside, the chunks of a large batch run on the batch's own streams, forked from and joined into it).  With

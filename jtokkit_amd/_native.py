@@ -75,6 +75,10 @@ JTK_RP_START = 1
 JTK_RP_COVERED = 2
 JTK_REPEAT_MARK_FIRST = 1
 JTK_RP_MIN_TABLE_BYTES = 1280
+JTK_LINES_LINE = 0
+JTK_LINES_PARAGRAPH = 1
+JTK_LINES_MARK_FIRST = 1
+JTK_LINES_TRIM = 2
 
 
 
@@ -97,6 +101,20 @@ class NgramParamsStruct(C.Structure):
 class RepeatParamsStruct(C.Structure):
     """jtk_repeat_params"""
     _fields_ = [("seed", C.c_uint64), ("doc_index_base", C.c_uint64), ("ngram", C.c_int32), ("flags", C.c_uint32)]
+
+
+class LinesParamsStruct(C.Structure):
+    """jtk_lines_params"""
+    _fields_ = [("seed", C.c_uint64), ("doc_index_base", C.c_uint64), ("unit", C.c_int32), ("flags", C.c_uint32)]
+
+
+LINES_OUT_FIELDS = ("unit_begin", "unit_end", "unit_flags", "unit_off", "n_dup", "dup_bytes", "dup_chars", "unit_bytes", "unit_chars",
+                    "doc_chars", "top_count", "top_first")
+
+
+class LinesOutStruct(C.Structure):
+    """jtk_lines_out"""
+    _fields_ = [(name, C.c_void_p) for name in LINES_OUT_FIELDS]
 
 
 # every symbol include/jtokkit_amd.h declares: (restype, argtypes)
@@ -132,6 +150,8 @@ SIGNATURES = {
     "jtk_ngram_set_keys": (C.c_int, [_p, _p, _i64]),
     "jtk_batch_ngram_overlap": (C.c_int, [_p, _p, _p, _p, _p, _p, _p]),
     "jtk_batch_ngram_repeats": (C.c_int, [_p, C.POINTER(RepeatParamsStruct), _p, _p, _p, _p, _p, _p]),
+    "jtk_batch_line_units": (C.c_int, [_p, C.POINTER(LinesParamsStruct), _p, C.POINTER(_i64)]),
+    "jtk_batch_line_repeats": (C.c_int, [_p, C.POINTER(LinesParamsStruct), C.POINTER(LinesOutStruct), _p]),
     "jtk_widen_ids": (C.c_int, [_p, _p, C.c_int, _i64, _i64, _p]),
     "jtk_batch_encode": (C.c_int, [_p, _p, _p, _i64, C.c_uint32, C.POINTER(_i64)]),
     "jtk_batch_encode_pieces": (C.c_int, [_p, _p, _p, _i64, _p, _p, _i64, C.c_uint32, C.POINTER(_i64)]),

@@ -20,6 +20,7 @@
 #include "jtk_compact_rules.h"
 #include "jtk_decode_rows_rules.h"
 #include "jtk_kernels.h"
+#include "jtk_lines_rules.h"
 #include "jtk_maxtok_rules.h"
 #include "jtk_ngram_rules.h"
 #include "jtk_owned.h"
@@ -199,6 +200,17 @@ struct jtk_batch {
     Event ev_rp;
     bool rp_queued = false;
     int64_t rp_table_bytes = (int64_t)256 << 20;   // JTK_OPT_REPEAT_TABLE_BYTES
+    // jtk_batch_line_units / jtk_batch_line_repeats (jtk_lines.hip): ln_scratch = the two bit planes | the tiles' summaries and
+    // carries | the per-document entries and offsets | hdr; ln_units = six 8-byte arrays per unit (begin, end, k, chars, and the two
+    // prefixes at the end byte), allocated at the counted size.  The list is the last encode's for ln_p (unit, JTK_LINES_TRIM,
+    // seed, doc_index_base): a new encode drops it, a call with other parameters replaces it.  The repeats share rp_table, rp_top
+    // and ev_rp with jtk_batch_ngram_repeats: whichever pass comes next waits for the one before it.
+    DevBuf ln_scratch, ln_units;
+    Pinned<int64_t> h_ln;
+    JtkLnWork ln{};
+    jtk_lines_params ln_p{};
+    bool have_lines = false;
+    hipStream_t ln_stream = nullptr;     // stream of the last call that built or read the list
     JtkResult* host_result = nullptr;   // host_result_own, or the head of h_small after a small job
     Pinned<JtkResult> host_result_own;
     // the last job
@@ -221,6 +233,7 @@ struct jtk_batch {
 static void drop_encode_result(jtk_batch* b) {
     b->have_result = b->have_host_result = b->have_trunc = b->have_chunk = b->have_tiles = b->have_pack = b->have_fim = false;
     b->cp_unit = -1;
+    b->have_lines = false;
     b->ck_end_level = nullptr;
     b->synced = false;
 }
@@ -2436,6 +2449,160 @@ int jtk_batch_ngram_repeats(jtk_batch* b, const jtk_repeat_params* p, uint8_t* d
     HIP_TRY(hipGetLastError());
     HIP_TRY(hipEventRecord(b->ev_rp, st));
     b->rp_queued = true;
+    return JTK_OK;
+}
+
+// ---- duplicate lines and paragraphs inside a document (jtk_lines.hip; the rule is jtk_lines_rules.h) -----------------------------
+static_assert(sizeof(jtk_lines_params) == 24 && sizeof(jtk_lines_out) == sizeof(JtkLnOut), "the ABI's structs are the kernels'");
+static int ln_check(const jtk_batch* b, const jtk_lines_params* p) {
+    int rc;
+    if ((rc = need_encode(b, NEED_TEXT_POS))) return rc;
+    if (!p) return fail(JTK_ERR_INVALID_ARGUMENT, "params is NULL");
+    if (!jtk_ln_params_ok(p->unit, p->flags))
+        return fail(JTK_ERR_INVALID_ARGUMENT, "line units: unit JTK_LINES_LINE or JTK_LINES_PARAGRAPH, flags out of JTK_LINES_MARK_FIRST | JTK_LINES_TRIM");
+    return JTK_OK;
+}
+static bool ln_same_list(const jtk_lines_params& a, const jtk_lines_params& b) {
+    return a.unit == b.unit && ((a.flags ^ b.flags) & JTK_LINES_TRIM) == 0 && a.seed == b.seed && a.doc_index_base == b.doc_index_base;
+}
+
+// Where the parts of ln_scratch lie for a text of n_tiles tiles and nd documents, every part 8-byte aligned:
+//   edge | ref        two bit planes, `plane` bytes each: one bit per byte of the tiles and the bit at n_bytes (k_ln_mark ORs whole
+//                     32-bit words), read 16 bits per granule plus the first bit of the next granule: (granules + 2) * 2 bytes
+//   8-byte per tile   sum_hash | tile_hash | tile_units | tile_chars
+//   per document      doc_units | doc_chars | unit_off | char_off, nd + 1 entries each
+//   hdr               2 entries (the unit count)
+//   4-byte per tile   sum_word | sum_units | sum_chars | tile_cf | tile_cb
+struct LnLayout {
+    size_t tiles, plane, per_tile8, per_doc, hdr, per_tile4, total;
+    int64_t nd;
+    LnLayout(int64_t n_tiles, int64_t n_docs) : tiles((size_t)n_tiles), nd(n_docs) {
+        plane = align_up((tiles * JTK_LN_TILE_GRANULES + 2) * 2, 16);
+        per_tile8 = tiles * 8;
+        per_doc = ((size_t)nd + 1) * 8;
+        hdr = 16;
+        per_tile4 = tiles * 4;
+        total = 2 * plane + 4 * per_tile8 + 4 * per_doc + hdr + 5 * per_tile4 + 16;
+    }
+    void place(uint8_t* z, JtkLnWork* w) const {
+        w->edge = (uint32_t*)z; w->ref = (uint32_t*)(z + plane);
+        uint64_t* const t8 = (uint64_t*)(z + 2 * plane);
+        w->sum_hash = t8; w->tile_hash = t8 + tiles; w->tile_units = (int64_t*)(t8 + 2 * tiles); w->tile_chars = (int64_t*)(t8 + 3 * tiles);
+        int64_t* const d8 = (int64_t*)(t8 + 4 * tiles);
+        w->doc_units = d8; w->doc_chars = d8 + (nd + 1); w->unit_off = d8 + 2 * (nd + 1); w->char_off = d8 + 3 * (nd + 1); w->hdr = d8 + 4 * (nd + 1);
+        uint32_t* const t4 = (uint32_t*)(w->hdr + 2);
+        w->sum_word = t4; w->sum_units = t4 + tiles; w->sum_chars = t4 + 2 * tiles; w->tile_cf = t4 + 3 * tiles; w->tile_cb = t4 + 4 * tiles;
+    }
+};
+
+int jtk_batch_line_units(jtk_batch* b, const jtk_lines_params* p, void* stream_or_null, int64_t* n_units) {
+    if (!n_units) return fail(JTK_ERR_INVALID_ARGUMENT, "n_units is NULL");
+    *n_units = 0;
+    int rc;
+    if ((rc = ln_check(b, p))) return rc;
+    HIP_TRY(hipSetDevice(b->enc->device));
+    hipStream_t st = pick_stream(b, stream_or_null);
+    const int64_t nd = b->job_docs, nb = b->job_bytes;
+    if (nd <= 0) {                                               // (no document: no unit, and no array to hold)
+        b->ln = JtkLnWork{};
+        b->ln_p = *p; b->ln_stream = st; b->have_lines = true;
+        return JTK_OK;
+    }
+    // behind the encode, behind the readers of the list that this one replaces, behind an earlier repeats pass
+    if ((rc = ck_order(b, b->last_stream, st))) return rc;
+    if (b->ln_stream && (rc = ck_order(b, b->ln_stream, st))) return rc;
+    if (b->rp_queued) HIP_TRY(hipStreamWaitEvent(st, b->ev_rp, 0));
+    b->have_lines = false;
+    const LnLayout lay(jtk_lines_tiles(nb), nd);
+    if (b->ln_scratch.cap < lay.total && b->rp_queued) HIP_TRY(hipEventSynchronize(b->ev_rp));      // (a buffer that grows is not in use any more)
+    if ((rc = b->ln_scratch.ensure(lay.total)) || (rc = b->h_ln.ensure(lay.per_doc + 16))) return rc;
+    uint8_t* const z = (uint8_t*)b->ln_scratch.p;
+    JtkLnWork w{};
+    w.text = b->job_text; w.doc_off = b->job_doc_off; w.status = (const int32_t*)b->status.p;
+    w.n_bytes = nb; w.n_docs = nd; w.unit = p->unit; w.flags = p->flags;
+    lay.place(z, &w);
+    // count, the one wait, the list at its exact size, write
+    HIP_TRY(hipMemsetAsync(z, 0, 2 * lay.plane, st));
+    jtk_launch_lines_count(w, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(b->h_ln.p, w.hdr, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int64_t n = b->h_ln.p[0];
+    if (n < 0 || n > nb) return fail(JTK_ERR_HIP, "the unit count of the text is outside [0, n_bytes]");
+    if (b->ln_units.cap < (size_t)n * JTK_LN_UNIT_BYTES + 16 && b->rp_queued) HIP_TRY(hipEventSynchronize(b->ev_rp));
+    if ((rc = b->ln_units.ensure((size_t)n * JTK_LN_UNIT_BYTES + 16))) return rc;
+    int64_t* const u8 = (int64_t*)b->ln_units.p;
+    w.n_units = n;
+    w.u_begin = u8; w.u_end = u8 + n; w.u_k = (uint64_t*)(u8 + 2 * n); w.u_chars = u8 + 3 * n; w.u_pe = (uint64_t*)(u8 + 4 * n); w.u_ce = u8 + 5 * n;
+    jtk_launch_lines_write(w, p->seed, p->doc_index_base, st);
+    HIP_TRY(hipGetLastError());
+    b->ln = w; b->ln_p = *p; b->ln_stream = st; b->have_lines = true;
+    *n_units = n;
+    return JTK_OK;
+}
+
+int jtk_batch_line_repeats(jtk_batch* b, const jtk_lines_params* p, const jtk_lines_out* out, void* stream_or_null) {
+    int rc;
+    if ((rc = ln_check(b, p))) return rc;
+    if (!out) return fail(JTK_ERR_INVALID_ARGUMENT, "out is NULL");
+    if (!b->have_lines || !ln_same_list(b->ln_p, *p))
+        return fail(JTK_ERR_INVALID_ARGUMENT, "no unit list of the last encode for these parameters: call jtk_batch_line_units first");
+    if (((uintptr_t)out->n_dup & 3u) || ((uintptr_t)out->top_count & 3u) || ((uintptr_t)out->unit_begin & 7u) || ((uintptr_t)out->unit_end & 7u) ||
+        ((uintptr_t)out->unit_off & 7u) || ((uintptr_t)out->dup_bytes & 7u) || ((uintptr_t)out->dup_chars & 7u) || ((uintptr_t)out->unit_bytes & 7u) ||
+        ((uintptr_t)out->unit_chars & 7u) || ((uintptr_t)out->doc_chars & 7u) || ((uintptr_t)out->top_first & 7u))
+        return fail(JTK_ERR_INVALID_ARGUMENT, "unaligned array (4-byte n_dup and top_count, 8-byte int64 arrays)");
+    const int64_t nd = b->job_docs;
+    if (nd <= 0) return JTK_OK;
+    HIP_TRY(hipSetDevice(b->enc->device));
+    hipStream_t st = pick_stream(b, stream_or_null);
+    if ((rc = ck_order(b, b->ln_stream, st))) return rc;
+    HIP_TRY(b->ev_rp.create());
+    if (b->rp_queued) HIP_TRY(hipStreamWaitEvent(st, b->ev_rp, 0));
+    // the plan: the groups come from the documents' unit counts, read once
+    const JtkLnWork& w = b->ln;
+    int64_t* const h_off = b->h_ln.p;
+    HIP_TRY(hipMemcpyAsync(h_off, w.unit_off, (size_t)(nd + 1) * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (h_off[0] != 0 || h_off[nd] != w.n_units) return fail(JTK_ERR_HIP, "the unit offsets of the list do not cover its units");
+    for (int64_t d = 0; d < nd; d++)
+        if (h_off[d + 1] - h_off[d] > JTK_LN_MAX_DOC_UNITS) return fail(JTK_ERR_INVALID_ARGUMENT, "line repeats: a document of 2^31 units or more");
+    struct Group { int64_t lo, hi; };
+    std::vector<Group> groups;
+    int64_t m_max = 0;
+    for (int64_t d0 = 0; d0 < nd;) {
+        int64_t m = 0;
+        const int64_t d1 = jtk_ln_group_end(h_off, nd, d0, b->rp_table_bytes, &m);
+        if (m > 0) groups.push_back({h_off[d0], h_off[d1]});
+        if (m > m_max) m_max = m;
+        d0 = d1;
+    }
+    // everything that can fail for lack of memory comes before the first write; a table that grows is not in use any more
+    const bool want_top = out->top_count || out->top_first;
+    const size_t table_bytes = m_max ? (size_t)jtk_rp_table_bytes(m_max) : 0, top_bytes = want_top ? (size_t)nd * 8 : 0;
+    if ((table_bytes > b->rp_table.cap || top_bytes > b->rp_top.cap) && b->rp_queued) HIP_TRY(hipEventSynchronize(b->ev_rp));
+    if ((rc = b->rp_table.ensure(table_bytes)) || (rc = b->rp_top.ensure(top_bytes))) return rc;
+    uint64_t* const top = want_top ? (uint64_t*)b->rp_top.p : nullptr;
+    JtkLnOut o;
+    memcpy(&o, out, sizeof o);
+    jtk_launch_lines_preset(w, o, top, st);
+    if (w.n_units > 0) {
+        if (o.unit_begin) HIP_TRY(hipMemcpyAsync(o.unit_begin, w.u_begin, (size_t)w.n_units * 8, hipMemcpyDeviceToDevice, st));
+        if (o.unit_end) HIP_TRY(hipMemcpyAsync(o.unit_end, w.u_end, (size_t)w.n_units * 8, hipMemcpyDeviceToDevice, st));
+    }
+    const bool passes = o.unit_flags || o.n_dup || o.dup_bytes || o.dup_chars || o.unit_bytes || o.unit_chars || want_top;
+    for (const Group& g : groups) {
+        if (!passes) break;
+        const int64_t cap = jtk_rp_capacity(g.hi - g.lo);
+        const JtkRpTable t = jtk_rp_table_at(b->rp_table.p, cap);
+        HIP_TRY(hipMemsetAsync(t.key, 0, (size_t)cap * 12, st));                // key | count
+        HIP_TRY(hipMemsetAsync(t.first, 0xFF, (size_t)cap * 8, st));
+        jtk_launch_lines_group(w, p->flags, t, g.lo, g.hi, o, top, st);
+    }
+    if (want_top) jtk_launch_repeat_top(nd, top, o.top_count, o.top_first, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(b->ev_rp, st));
+    b->rp_queued = true;
+    b->ln_stream = st;
     return JTK_OK;
 }
 

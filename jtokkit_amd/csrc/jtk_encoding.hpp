@@ -154,6 +154,17 @@ public:
         check(jtk_batch_ngram_repeats(batch_, &params, dTokFlags, dNRepeat, dNCovered, dTopCount, dTopFirst, stream));
     }
 
+    // duplicate lines / paragraphs inside the documents of the last encode's text: lineUnits finds and hashes the units and
+    // returns their number (jtk_batch_line_units), lineRepeats writes what `out` asks for (jtk_batch_line_repeats; same params)
+    int64_t lineUnits(const jtk_lines_params& params, void* stream = nullptr) {
+        int64_t n = 0;
+        check(jtk_batch_line_units(batch_, &params, stream, &n));
+        return n;
+    }
+    void lineRepeats(const jtk_lines_params& params, const jtk_lines_out& out, void* stream = nullptr) {
+        check(jtk_batch_line_repeats(batch_, &params, &out, stream));
+    }
+
     // batch decodeBytes: token lists back to back in `ids`, n+1 offsets -> bytes back to back + n+1 byte offsets + status
     void decodeBatch(const int32_t* ids, const std::vector<int64_t>& seqOff, std::string& bytes,
                      std::vector<int64_t>& byteOff, std::vector<int32_t>& status) {

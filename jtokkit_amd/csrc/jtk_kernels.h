@@ -444,6 +444,51 @@ void jtk_launch_repeat_preset(int64_t n_docs, int32_t* n_repeat, int32_t* n_cove
 void jtk_launch_repeat_group(const JtkMhView& v, uint64_t seed, uint64_t doc_index_base, uint32_t flags, const JtkRpTable& t, int64_t lo, int64_t hi,
                              uint8_t* tok_flags, int32_t* n_repeat, int32_t* n_covered, uint64_t* top, hipStream_t s);
 void jtk_launch_repeat_top(int64_t n_docs, const uint64_t* top, int32_t* top_count, int64_t* top_first, hipStream_t s);
+// Duplicate lines and paragraphs inside a document (jtk_lines.hip; the rule and the way the text is walked are jtk_lines_rules.h).
+// edge / ref: the two bit planes over the text, preset to 0, (tiles * 256 + 2) * 2 bytes each; sum_*: pass A's summary per tile;
+// tile_*: pass B's carries per tile; doc_units / doc_chars [n_docs + 1]: the units and chars before the document that starts at a
+// position (entries of empty documents are not used); unit_off / char_off [n_docs + 1]; per unit: begin, end, k (P at the start byte
+// until k_ln_keys), chars (the chars before the start byte until then), and P and the chars at the end byte.
+struct JtkLnWork {
+    const uint8_t* text;
+    const int64_t* doc_off;
+    const int32_t* status;
+    int64_t n_bytes, n_docs, n_units;
+    int32_t unit;
+    uint32_t flags;
+    uint32_t *edge, *ref;
+    uint32_t *sum_word, *sum_units, *sum_chars;
+    uint64_t* sum_hash;
+    uint32_t *tile_cf, *tile_cb;
+    int64_t *tile_units, *tile_chars;
+    uint64_t* tile_hash;
+    int64_t* hdr;
+    int64_t *doc_units, *doc_chars, *unit_off, *char_off;
+    int64_t *u_begin, *u_end;
+    uint64_t* u_k;
+    int64_t* u_chars;
+    uint64_t* u_pe;
+    int64_t* u_ce;
+};
+struct JtkLnOut {                  // jtk_lines_out of include/jtokkit_amd.h
+    int64_t *unit_begin, *unit_end;
+    uint8_t* unit_flags;
+    int64_t* unit_off;
+    int32_t* n_dup;
+    int64_t *dup_bytes, *dup_chars, *unit_bytes, *unit_chars, *doc_chars;
+    int32_t* top_count;
+    int64_t* top_first;
+};
+//   count         the planes, pass A and pass B: hdr[0] = the units of the batch
+//   write         pass C, unit_off / char_off and every unit's k and chars (n_units as counted)
+//   preset        the per-document sums and top = 0; unit_off and doc_chars out of the batch's arrays
+//   group         the two passes over the units [lo, hi) of a group of whole documents, with a table preset by the caller
+int64_t jtk_lines_tiles(int64_t n_bytes);
+void jtk_launch_lines_count(const JtkLnWork& w, hipStream_t s);
+void jtk_launch_lines_write(const JtkLnWork& w, uint64_t seed, uint64_t doc_index_base, hipStream_t s);
+void jtk_launch_lines_preset(const JtkLnWork& w, const JtkLnOut& o, uint64_t* top, hipStream_t s);
+void jtk_launch_lines_group(const JtkLnWork& w, uint32_t flags, const JtkRpTable& t, int64_t lo, int64_t hi, const JtkLnOut& o, uint64_t* top,
+                            hipStream_t s);
 // Device-side state of an allow-special encode (jtk_special.hip, JTK_ENCODE_ALLOW_SPECIAL; the rule is jtk_special_rules.h).
 // Candidates (per position, the longest allowed literal there) are found in position order, resolved to the kept matches, and
 // the batch is cut into sub-documents that partition the text: per document a segment, then per candidate i two slots

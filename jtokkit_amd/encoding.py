@@ -161,6 +161,21 @@ def _stream_sync(stream):
         raise EncodingError(N.JTK_ERR_HIP, "hipStreamSynchronize failed (%d)" % rc)
 
 
+def _lines_params(unit, trim, mark_first, seed, doc_index_base):
+    """jtk_lines_params; unit: "line", "paragraph" or a JTK_LINES_* value."""
+    u = {"line": N.JTK_LINES_LINE, "paragraph": N.JTK_LINES_PARAGRAPH}.get(unit, unit)
+    if not isinstance(u, int):
+        raise ValueError('unit must be "line" or "paragraph"')
+    return N.LinesParamsStruct(seed & 0xFFFFFFFFFFFFFFFF, doc_index_base & 0xFFFFFFFFFFFFFFFF, u,
+                               (N.JTK_LINES_MARK_FIRST if mark_first else 0) | (N.JTK_LINES_TRIM if trim else 0))
+
+
+# jtk_lines_out: the arrays per unit, per document + 1 and per document, with their element types
+_LINES_PER_UNIT = (("unit_begin", np.int64), ("unit_end", np.int64), ("unit_flags", np.uint8))
+_LINES_PER_DOC = (("n_dup", np.int32), ("dup_bytes", np.int64), ("dup_chars", np.int64), ("unit_bytes", np.int64), ("unit_chars", np.int64),
+                  ("doc_chars", np.int64), ("top_count", np.int32), ("top_first", np.int64))
+
+
 def _stop_blob(stop_strings):
     """Stop strings (bytes or str, a str as its UTF-8 bytes; one alone is a list of one) -> (blob uint8, str_off uint32
     [n + 1]).  The library checks counts and lengths."""
@@ -483,6 +498,24 @@ class Batch:
                                  N.JTK_REPEAT_MARK_FIRST if mark_first else 0)
         _check(N.lib().jtk_batch_ngram_repeats(self._h, C.byref(p), d_tok_flags_ptr, d_n_repeat_ptr, d_n_covered_ptr, d_top_count_ptr,
                                                d_top_first_ptr, stream))
+
+    def line_units(self, unit="line", trim=False, seed=0, doc_index_base=0, stream=None):
+        """jtk_batch_line_units of the last encode's text: finds and hashes the lines (unit="line") or paragraphs ("paragraph"),
+        keeps the list in the batch and returns the number of units; waits once, for that number."""
+        n = C.c_int64(0)
+        _check(N.lib().jtk_batch_line_units(self._h, C.byref(_lines_params(unit, trim, False, seed, doc_index_base)), stream, C.byref(n)))
+        return n.value
+
+    def line_repeats(self, unit="line", trim=False, mark_first=False, seed=0, doc_index_base=0, stream=None, **ptrs):
+        """jtk_batch_line_repeats over the list of a line_units call with the same unit, trim, seed and doc_index_base: device
+        pointers by the field names of jtk_lines_out (unit_begin=, unit_end=, unit_flags=, unit_off=, n_dup=, dup_bytes=,
+        dup_chars=, unit_bytes=, unit_chars=, doc_chars=, top_count=, top_first=), each may be left out or None and is then not
+        written; waits for the documents' unit counts, not for the pass."""
+        unknown = set(ptrs) - set(N.LINES_OUT_FIELDS)
+        if unknown:
+            raise TypeError("line_repeats: no output named %s" % ", ".join(sorted(unknown)))
+        out = N.LinesOutStruct(**{k: v for k, v in ptrs.items() if v})
+        _check(N.lib().jtk_batch_line_repeats(self._h, C.byref(_lines_params(unit, trim, mark_first, seed, doc_index_base)), C.byref(out), stream))
 
     def encode_device(self, d_text_ptr, d_doc_off_ptr, n_docs, n_bytes, ordinary=False, stream=None, sync=True,
                       allow_special=False, validate=False, count_only=False, fim=False):
@@ -1354,7 +1387,55 @@ class HipEncoding:
             tok_off, status = self._tok_off_and_status(b, nd, device, stream)
         return (flags,) + tuple(rows) + (tok_off, status)
 
-    def repetition_signals(self, texts, top=(2, 3, 4), dup=(5, 6, 7, 8, 9, 10), mark_first=False, seed=0, ordinary=True, allowed_special=None):
+    def line_repeats_batch(self, texts, unit="line", trim=False, mark_first=False, seed=0, doc_index_base=0):
+        """Duplicate lines (unit="line") or paragraphs ("paragraph") inside each of a list of str/bytes (jtk_batch_line_units and
+        jtk_batch_line_repeats; the rule is in include/jtokkit_amd.h): a dict of numpy arrays by the field names of jtk_lines_out
+        -- unit_begin, unit_end int64 [n_units] (byte positions in the documents back to back), unit_flags uint8 [n_units] (1: a
+        repeat), unit_off int64 [n + 1], n_dup and top_count int32 [n], dup_bytes, dup_chars, unit_bytes, unit_chars, doc_chars
+        and top_first int64 [n].  trim: blanks (space, tab, CR) at a line's ends do not count and a line of blanks is blank;
+        mark_first: the first occurrence of a repeated unit is flagged as well."""
+        bs, text, doc_off = _join_texts(texts)
+        n = len(bs)
+        self.encode_batch_packed(text, doc_off, True, False, None)
+        b = self._b()
+        nu = b.line_units(unit, trim, seed, doc_index_base)
+        with _device_arrays() as put:
+            outs = {name: put(np.zeros(nu, dtype=dt)) for name, dt in _LINES_PER_UNIT}
+            outs["unit_off"] = put(np.zeros(n + 1, dtype=np.int64))
+            outs.update({name: put(np.zeros(n, dtype=dt)) for name, dt in _LINES_PER_DOC})
+            b.line_repeats(unit, trim, mark_first, seed, doc_index_base, **{name: x.ptr for name, x in outs.items() if x._arr.size})
+            _stream_sync(b.stream())
+            res = {name: x.fetch() for name, x in outs.items()}
+        return res
+
+    def line_repeats_batch_device(self, text, doc_off, unit="line", trim=False, mark_first=False, seed=0, doc_index_base=0, ordinary=True,
+                                  allowed_special=None):
+        """Encodes a device-resident batch (text CUDA torch.uint8, doc_off CUDA torch.int64 [n_docs + 1]) and returns the duplicate
+        lines or paragraphs inside its documents as a dict of CUDA tensors written on torch.cuda.current_stream(), by the field
+        names of jtk_lines_out (as line_repeats_batch; unit_flags uint8), plus "status" int32 [n_docs].  Waits once for the number of
+        units and once for the documents' unit counts (and, with allowed_special, once more for the encode's count of literal
+        candidates), not for the encode's token count."""
+        import torch
+        self._check_device_inputs("line_repeats_batch_device", ("text", text, torch.uint8), ("doc_off", doc_off, torch.int64))
+        allow = self._allow(self._b(), allowed_special)
+        with self._encode_device_batch(text, doc_off, ordinary, allow) as (b, nd, device, stream):
+            res = self._line_repeats_on(b, nd, device, stream, unit, trim, mark_first, seed, doc_index_base)
+            res["status"] = self._tok_off_and_status(b, nd, device, stream)[1]
+        return res
+
+    @staticmethod
+    def _line_repeats_on(b, nd, device, stream, unit, trim, mark_first, seed, doc_index_base):
+        """line_units and line_repeats of the batch's last encode into new CUDA tensors, on `stream`."""
+        import torch
+        nu = b.line_units(unit, trim, seed, doc_index_base, stream)
+        res = {name: torch.empty(nu, dtype=getattr(torch, np.dtype(dt).name), device=device) for name, dt in _LINES_PER_UNIT}
+        res["unit_off"] = torch.zeros(nd + 1, dtype=torch.int64, device=device)
+        res.update({name: torch.empty(nd, dtype=getattr(torch, np.dtype(dt).name), device=device) for name, dt in _LINES_PER_DOC})
+        b.line_repeats(unit, trim, mark_first, seed, doc_index_base, stream, **{name: t.data_ptr() for name, t in res.items() if t.numel()})
+        return res
+
+    def repetition_signals(self, texts, top=(2, 3, 4), dup=(5, 6, 7, 8, 9, 10), mark_first=False, seed=0, ordinary=True, allowed_special=None,
+                           lines=False, trim=False):
         """The fractions the repetition filters of Gopher (Rae et al. 2021, table A1) put a threshold on, for a list of str/bytes:
         {"top": {n: (token_fraction, byte_fraction)}, "dup": {n: (token_fraction, byte_fraction)}, "n_tokens": int64 [n_docs],
         "n_bytes": int64 [n_docs], "status": int32 [n_docs]}, the fractions numpy float64 [n_docs].
@@ -1363,15 +1444,23 @@ class HipEncoding:
           dup[n]  the share inside n-grams that occur more than once: n_covered / l in tokens, the bytes of the covered tokens /
                   the document's bytes.  mark_first: as for ngram_repeats_batch.
         0.0 for a document without n-grams.  One encode, one jtk_batch_ngram_repeats pass per n; token byte lengths come from
-        jtk_batch_token_offsets and the sums are done with torch on the device: no ids on the host."""
+        jtk_batch_token_offsets and the sums are done with torch on the device: no ids on the host.
+          lines=True adds the four line-level signals of the same table, from the same encode (jtk_batch_line_repeats):
+                  "dup_line" and "dup_paragraph", each (unit_fraction, byte_fraction, char_fraction) = n_dup / the document's
+                  units, dup_bytes / the document's bytes, dup_chars / doc_chars -- 0.0 where the denominator is 0 --, and
+                  "n_lines", "n_paragraphs" int64 [n_docs].  trim as for line_repeats_batch; mark_first applies here too."""
         import torch
         bs, text, doc_off = _join_texts(texts)
         nd = len(bs)
         top, dup = [int(n) for n in top], [int(n) for n in dup]
         empty = lambda: (np.zeros(nd, dtype=np.float64), np.zeros(nd, dtype=np.float64))
         if nd == 0 or not len(text):
-            return {"top": {n: empty() for n in top}, "dup": {n: empty() for n in dup}, "n_tokens": np.zeros(nd, dtype=np.int64),
-                    "n_bytes": np.zeros(nd, dtype=np.int64), "status": np.zeros(nd, dtype=np.int32)}
+            out = {"top": {n: empty() for n in top}, "dup": {n: empty() for n in dup}, "n_tokens": np.zeros(nd, dtype=np.int64),
+                   "n_bytes": np.zeros(nd, dtype=np.int64), "status": np.zeros(nd, dtype=np.int32)}
+            if lines:
+                out.update({"dup_line": empty() + empty()[:1], "dup_paragraph": empty() + empty()[:1],
+                            "n_lines": np.zeros(nd, dtype=np.int64), "n_paragraphs": np.zeros(nd, dtype=np.int64)})
+            return out
         device = torch.device("cuda", N.lib().jtk_encoding_device(self._h))
         d_off = torch.from_numpy(doc_off).to(device)
         d_text = torch.from_numpy(text.copy()).to(device)                        # (a copy: frombuffer views are read-only)
@@ -1390,6 +1479,10 @@ class HipEncoding:
                 dups[n] = (torch.empty(nt, dtype=torch.uint8, device=device), torch.empty(nd, dtype=torch.int32, device=device))
                 b.ngram_repeats(n, dups[n][0].data_ptr() if nt else None, None, dups[n][1].data_ptr(), None, None, seed=seed,
                                 mark_first=mark_first, stream=stream)
+            units = {}
+            if lines:
+                for name in ("line", "paragraph"):
+                    units[name] = self._line_repeats_on(b, nd, device, stream, name, trim, mark_first, seed, 0)
             tok_off, status = self._tok_off_and_status(b, nd, device, stream)
         # (joined into torch's current stream: the sums follow the passes)
         l = tok_off[1:] - tok_off[:-1]
@@ -1413,6 +1506,11 @@ class HipEncoding:
             ccum[1:] = torch.cumsum((end - pos) * ((flags & N.JTK_RP_COVERED) != 0), 0)
             cbytes = ccum[tok_off[1:]] - ccum[tok_off[:-1]]
             out["dup"][n] = ((covered.double() / lf).cpu().numpy(), (cbytes.double() / bf).cpu().numpy())
+        frac = lambda num, den: torch.where(den > 0, num.double() / den.clamp(min=1).double(), torch.zeros_like(num, dtype=torch.float64)).cpu().numpy()
+        for name, r in units.items():
+            n_units = r["unit_off"][1:] - r["unit_off"][:-1]
+            out["dup_" + name] = (frac(r["n_dup"].long(), n_units), frac(r["dup_bytes"], n_bytes), frac(r["dup_chars"], r["doc_chars"]))
+            out["n_%ss" % name] = n_units.cpu().numpy()
         out["n_tokens"], out["n_bytes"], out["status"] = l.cpu().numpy(), n_bytes.cpu().numpy(), status.cpu().numpy()
         return out
 
