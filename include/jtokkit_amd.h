@@ -422,6 +422,62 @@ typedef struct jtk_lines_out {      /* device pointers, each may be NULL and is 
 int jtk_batch_line_units(jtk_batch* b, const jtk_lines_params* params, void* stream_or_null, int64_t* n_units);
 int jtk_batch_line_repeats(jtk_batch* b, const jtk_lines_params* params, const jtk_lines_out* out, void* stream_or_null);
 
+/* Word-level quality signals: the quality half of Gopher's filter (Rae et al. 2021, table A1; datatrove's GopherQualityFilter,
+ * RedPajama-v2's rps_doc_* signals, Dolma's Gopher tagger, FineWeb's line rules) on the TEXT of the last batch encode
+ * (jtk_words.hip; the rule, bit for bit, is csrc/jtk_words_rules.h -- integer arithmetic only, so every count is exact).
+ *   Text: document d is the bytes x[doc_off[d], doc_off[d + 1]); nothing crosses a document edge.  A document with status < 0 gets
+ *   0 in every output.  The rule is defined for well-formed UTF-8; on ill-formed bytes every count is some value and no access
+ *   leaves the text.
+ *   Characters: a character is a byte b with (b & 0xC0) != 0x80 (the weight of JTK_UNIT_CODEPOINT).  Its class is that of its code
+ *   point in the library's Unicode tables: L, N, W (White_Space) or other; a continuation byte belongs to the character before it.
+ *   Words: a word is a maximal run of characters that are not W -- Python's str.split() with White_Space as the separator set.  It
+ *   is ALPHA when it holds at least one L character, SYMBOL-ONLY when it holds neither L nor N.
+ *   Counts: n_words; word_chars, the characters of all words; n_alpha_words; n_symbol_words; symbol_word_chars, the characters of
+ *   the symbol-only words.  datatrove's mean word length is (word_chars - symbol_word_chars) / (n_words - n_symbol_words),
+ *   Gopher's alpha fraction n_alpha_words / n_words.
+ *   Symbols: n_hash, the bytes 0x23.  n_ellipsis, the sum over the maximal runs of 0x2E of floor(run length / 3) plus the
+ *   occurrences of U+2026: Python's text.count("...") + text.count("…").
+ *   Stop words: n_stop <= 32 words, word i the bytes stop_bytes[stop_off[i], stop_off[i + 1]) (HOST pointers, copied by the call):
+ *   1 to 8 bytes of well-formed UTF-8 without a White_Space character; anything else is JTK_ERR_INVALID_ARGUMENT.  A word of the
+ *   text IS stop word i when its bytes equal it exactly; with JTK_WORDS_FOLD_ASCII 'A'..'Z' of the TEXT are folded to 'a'..'z'
+ *   before the comparison (the list is taken as it is).  stop_mask has bit i set when stop word i occurs in the document;
+ *   n_stop_hits counts the words of the text that are some stop word, each once however often the list repeats it.  "the,", "bathe"
+ *   and "then" are not "the": word tokenizers that split punctuation off (datatrove's, NLTK) find "the" in "the," and this rule
+ *   does not.
+ *   Lines: over the units of jtk_batch_line_units(unit = JTK_LINES_LINE, flags with JTK_LINES_TRIM) on the same encode -- exactly
+ *   the trimmed non-blank lines.  n_lines; n_bullet_lines, the unit begins with U+2022 or '-'; n_ellipsis_lines, it ends with
+ *   "..." or U+2026; n_terminal_lines, its last byte is one of . ! ? " (C4's end marks); n_short_lines, it has fewer than
+ *   short_line_chars characters (FineWeb: 30; short_line_chars <= 0 writes 0).  When a line output is asked for and the batch
+ *   holds no such list, the call is JTK_ERR_INVALID_ARGUMENT.
+ * Works on the LAST batch encode on `b` under the conditions of jtk_batch_char_index: host or device input, any flags
+ *   (JTK_ENCODE_COUNT_ONLY included) but JTK_ENCODE_FIM; not after jtk_batch_encode_pieces or jtk_batch_encode_device_max_tokens
+ *   (JTK_ERR_INVALID_ARGUMENT); device-input text must still be valid and unchanged.  Every pointer of `out` is device memory
+ *   [n_docs], may be NULL and is then not written; int32 / uint32 arrays 4-byte aligned, int64 arrays 8-byte aligned
+ *   (JTK_ERR_INVALID_ARGUMENT otherwise).  The int32 counts are exact for documents of less than 2^31 bytes.  Scratch: n_bytes / 4 +
+ *   12 bytes per 4096 of text, allocated before anything is written; a refused call writes nothing.  The passes are queued on
+ *   stream_or_null (the batch's stream when NULL) and the call does not wait for them.  Chunk, pack, fetch, MinHash, n-gram,
+ *   repeat and line results are untouched. */
+#define JTK_WORDS_FOLD_ASCII 1u
+typedef struct jtk_words_params {
+    uint32_t flags;             /* JTK_WORDS_FOLD_ASCII */
+    int32_t short_line_chars;
+    int32_t n_stop;             /* 0 .. 32 */
+    int32_t reserved;           /* 0 */
+    const uint8_t* stop_bytes;  /* host */
+    const uint32_t* stop_off;   /* host, [n_stop + 1] */
+} jtk_words_params;
+typedef struct jtk_words_out {  /* device pointers [n_docs], each may be NULL and is then not written */
+    int32_t* n_words;
+    int64_t* word_chars;
+    int32_t *n_alpha_words, *n_symbol_words;
+    int64_t *symbol_word_chars, *n_hash;
+    int32_t* n_ellipsis;
+    uint32_t* stop_mask;
+    int32_t* n_stop_hits;
+    int32_t *n_lines, *n_bullet_lines, *n_ellipsis_lines, *n_terminal_lines, *n_short_lines;
+} jtk_words_out;
+int jtk_batch_word_stats(jtk_batch* b, const jtk_words_params* params, const jtk_words_out* out, void* stream_or_null);
+
 /* Device buffers already resident in HBM (what bench.py times).  `stream_or_null` = a hipStream_t
  * to order against, or NULL for the batch's own stream: the whole encode is ordered like one operation on that stream
  * (inside, the chunks of a large batch run on the batch's own streams, forked from and joined into it).  With

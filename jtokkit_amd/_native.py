@@ -79,6 +79,14 @@ JTK_LINES_LINE = 0
 JTK_LINES_PARAGRAPH = 1
 JTK_LINES_MARK_FIRST = 1
 JTK_LINES_TRIM = 2
+JTK_WORDS_FOLD_ASCII = 1
+JTK_WD_MAX_STOP = 32
+JTK_WD_MAX_STOP_LEN = 8
+# how jtk_words.hip cuts the text (csrc/jtk_words_rules.h): a lane's granule, a wave, a workgroup's tile, a step of the scan in tiles
+JTK_WD_GRANULE = 16
+JTK_WD_WAVE_BYTES = 1024
+JTK_WD_TILE = 4096
+JTK_WD_SCAN_STEP = 1024
 
 
 
@@ -117,6 +125,26 @@ class LinesOutStruct(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in LINES_OUT_FIELDS]
 
 
+class WordsParamsStruct(C.Structure):
+    """jtk_words_params"""
+    _fields_ = [("flags", C.c_uint32), ("short_line_chars", C.c_int32), ("n_stop", C.c_int32), ("reserved", C.c_int32),
+                ("stop_bytes", C.c_void_p), ("stop_off", C.c_void_p)]
+
+
+# jtk_words_out: the field names in order, with their element types
+WORDS_OUT_TYPES = (("n_words", "int32"), ("word_chars", "int64"), ("n_alpha_words", "int32"), ("n_symbol_words", "int32"),
+                   ("symbol_word_chars", "int64"), ("n_hash", "int64"), ("n_ellipsis", "int32"), ("stop_mask", "uint32"), ("n_stop_hits", "int32"),
+                   ("n_lines", "int32"), ("n_bullet_lines", "int32"), ("n_ellipsis_lines", "int32"), ("n_terminal_lines", "int32"),
+                   ("n_short_lines", "int32"))
+WORDS_OUT_FIELDS = tuple(name for name, _ in WORDS_OUT_TYPES)
+WORDS_LINE_FIELDS = WORDS_OUT_FIELDS[9:]
+
+
+class WordsOutStruct(C.Structure):
+    """jtk_words_out"""
+    _fields_ = [(name, C.c_void_p) for name in WORDS_OUT_FIELDS]
+
+
 # every symbol include/jtokkit_amd.h declares: (restype, argtypes)
 _p = C.c_void_p
 _i64 = C.c_int64
@@ -152,6 +180,7 @@ SIGNATURES = {
     "jtk_batch_ngram_repeats": (C.c_int, [_p, C.POINTER(RepeatParamsStruct), _p, _p, _p, _p, _p, _p]),
     "jtk_batch_line_units": (C.c_int, [_p, C.POINTER(LinesParamsStruct), _p, C.POINTER(_i64)]),
     "jtk_batch_line_repeats": (C.c_int, [_p, C.POINTER(LinesParamsStruct), C.POINTER(LinesOutStruct), _p]),
+    "jtk_batch_word_stats": (C.c_int, [_p, C.POINTER(WordsParamsStruct), C.POINTER(WordsOutStruct), _p]),
     "jtk_widen_ids": (C.c_int, [_p, _p, C.c_int, _i64, _i64, _p]),
     "jtk_batch_encode": (C.c_int, [_p, _p, _p, _i64, C.c_uint32, C.POINTER(_i64)]),
     "jtk_batch_encode_pieces": (C.c_int, [_p, _p, _p, _i64, _p, _p, _i64, C.c_uint32, C.POINTER(_i64)]),

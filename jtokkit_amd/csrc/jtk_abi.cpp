@@ -21,6 +21,7 @@
 #include "jtk_decode_rows_rules.h"
 #include "jtk_kernels.h"
 #include "jtk_lines_rules.h"
+#include "jtk_words_rules.h"
 #include "jtk_maxtok_rules.h"
 #include "jtk_ngram_rules.h"
 #include "jtk_owned.h"
@@ -211,6 +212,9 @@ struct jtk_batch {
     jtk_lines_params ln_p{};
     bool have_lines = false;
     hipStream_t ln_stream = nullptr;     // stream of the last call that built or read the list
+    // jtk_batch_word_stats (jtk_words.hip): the two bit planes | sum_word | tile_cf | tile_cb, reused from call to call
+    DevBuf wd_scratch;
+    hipStream_t wd_stream = nullptr;     // stream of the last word pass: the next one, on another stream, reuses the scratch behind it
     JtkResult* host_result = nullptr;   // host_result_own, or the head of h_small after a small job
     Pinned<JtkResult> host_result_own;
     // the last job
@@ -2603,6 +2607,103 @@ int jtk_batch_line_repeats(jtk_batch* b, const jtk_lines_params* p, const jtk_li
     HIP_TRY(hipEventRecord(b->ev_rp, st));
     b->rp_queued = true;
     b->ln_stream = st;
+    return JTK_OK;
+}
+
+// ---- word-level quality signals (jtk_words.hip; the rule is jtk_words_rules.h) --------------------------------------------------
+static_assert(sizeof(jtk_words_out) == sizeof(JtkWdOut) && sizeof(jtk_words_params) == 32, "the ABI's structs are the kernels'");
+// The caller's stop list into the kernels' form: sorted by length, each word's bytes little-endian in a 64-bit key.
+static int wd_stops(const jtk_words_params* p, JtkWdStops* s) {
+    memset(s, 0, sizeof *s);
+    s->fold = p->flags & JTK_WORDS_FOLD_ASCII;
+    if (p->n_stop < 0 || p->n_stop > JTK_WD_MAX_STOP) return fail(JTK_ERR_INVALID_ARGUMENT, "word stats: n_stop 0..32");
+    if (p->n_stop > 0 && (!p->stop_bytes || !p->stop_off)) return fail(JTK_ERR_INVALID_ARGUMENT, "stop_bytes or stop_off is NULL");
+    const JtkUcTables uc{jtk_uc_stage1_init, jtk_uc_stage2_init};
+    uint32_t len_of[JTK_WD_MAX_STOP];
+    for (int i = 0; i < p->n_stop; i++) {
+        const uint32_t a = p->stop_off[i], e = p->stop_off[i + 1];
+        if (e <= a || e - a > JTK_WD_MAX_STOP_LEN) return fail(JTK_ERR_INVALID_ARGUMENT, "word stats: a stop word has 1 to 8 bytes");
+        const uint8_t* x = p->stop_bytes + a;
+        const uint32_t n = e - a;
+        for (uint32_t k = 0; k < n;) {                           // well-formed, no White_Space character
+            const uint32_t b0 = x[k];
+            const uint32_t m = b0 < 0x80u ? 1u : (b0 >= 0xC2u && b0 < 0xE0u) ? 2u : (b0 >= 0xE0u && b0 < 0xF0u) ? 3u : (b0 >= 0xF0u && b0 < 0xF5u) ? 4u : 0u;
+            if (m == 0 || k + m > n) return fail(JTK_ERR_INVALID_ARGUMENT, "word stats: a stop word is not well-formed UTF-8");
+            uint32_t cp = m == 1 ? b0 : m == 2 ? b0 & 0x1Fu : m == 3 ? b0 & 0x0Fu : b0 & 0x07u;
+            for (uint32_t j = 1; j < m; j++) {
+                if ((x[k + j] & 0xC0u) != 0x80u) return fail(JTK_ERR_INVALID_ARGUMENT, "word stats: a stop word is not well-formed UTF-8");
+                cp = (cp << 6) | (x[k + j] & 0x3Fu);
+            }
+            if (jtk_wd_class_of(uc, cp) == JTK_CLS_W) return fail(JTK_ERR_INVALID_ARGUMENT, "word stats: a stop word holds a White_Space character");
+            k += m;
+        }
+        len_of[i] = n;
+    }
+    uint32_t at = 0;
+    for (uint32_t n = 1; n <= JTK_WD_MAX_STOP_LEN; n++) {
+        s->first[n] = (uint8_t)at;
+        for (int i = 0; i < p->n_stop; i++) {
+            if (len_of[i] != n) continue;
+            uint64_t key = 0;
+            for (uint32_t k = 0; k < n; k++) key |= (uint64_t)p->stop_bytes[p->stop_off[i] + k] << (8 * k);
+            s->key[at] = key;
+            s->idx[at++] = (uint8_t)i;
+        }
+    }
+    s->first[0] = 0;
+    s->first[JTK_WD_MAX_STOP_LEN + 1] = (uint8_t)at;
+    return JTK_OK;
+}
+
+int jtk_batch_word_stats(jtk_batch* b, const jtk_words_params* p, const jtk_words_out* out, void* stream_or_null) {
+    int rc;
+    if ((rc = need_encode(b, NEED_TEXT_POS))) return rc;
+    if (!p || !out) return fail(JTK_ERR_INVALID_ARGUMENT, "params or out is NULL");
+    if (p->flags & ~JTK_WORDS_FOLD_ASCII) return fail(JTK_ERR_INVALID_ARGUMENT, "word stats: flags 0 or JTK_WORDS_FOLD_ASCII");
+    JtkWdStops stops;
+    if ((rc = wd_stops(p, &stops))) return rc;
+    JtkWdWork w{};
+    memcpy(&w.out, out, sizeof w.out);
+    const JtkWdOut& o = w.out;
+    if (((uintptr_t)o.n_words & 3u) || ((uintptr_t)o.n_alpha_words & 3u) || ((uintptr_t)o.n_symbol_words & 3u) || ((uintptr_t)o.n_ellipsis & 3u) ||
+        ((uintptr_t)o.stop_mask & 3u) || ((uintptr_t)o.n_stop_hits & 3u) || ((uintptr_t)o.n_lines & 3u) || ((uintptr_t)o.n_bullet_lines & 3u) ||
+        ((uintptr_t)o.n_ellipsis_lines & 3u) || ((uintptr_t)o.n_terminal_lines & 3u) || ((uintptr_t)o.n_short_lines & 3u) ||
+        ((uintptr_t)o.word_chars & 7u) || ((uintptr_t)o.symbol_word_chars & 7u) || ((uintptr_t)o.n_hash & 7u))
+        return fail(JTK_ERR_INVALID_ARGUMENT, "unaligned array (4-byte int32 arrays, 8-byte word_chars, symbol_word_chars and n_hash)");
+    const bool want_text = o.n_words || o.word_chars || o.n_alpha_words || o.n_symbol_words || o.symbol_word_chars || o.n_hash || o.n_ellipsis ||
+                           o.stop_mask || o.n_stop_hits;
+    const bool want_lines = o.n_lines || o.n_bullet_lines || o.n_ellipsis_lines || o.n_terminal_lines || o.n_short_lines;
+    if (want_lines && !(b->have_lines && b->ln_p.unit == JTK_LINES_LINE && (b->ln_p.flags & JTK_LINES_TRIM)))
+        return fail(JTK_ERR_INVALID_ARGUMENT, "no line list of the last encode: call jtk_batch_line_units(JTK_LINES_LINE, JTK_LINES_TRIM) first");
+    const int64_t nd = b->job_docs, nb = b->job_bytes;
+    if (nd <= 0 || !(want_text || want_lines)) return JTK_OK;
+    HIP_TRY(hipSetDevice(b->enc->device));
+    hipStream_t st = pick_stream(b, stream_or_null);
+    // everything that can fail for lack of memory comes before the first write; a scratch that grows is not in use any more
+    const size_t tiles = (size_t)jtk_words_tiles(nb), plane = align_up((tiles * JTK_WD_TILE_GRANULES + 2) * 2, 16);
+    const size_t total = want_text ? 2 * plane + 3 * tiles * 4 + 16 : 0;
+    if (b->wd_scratch.cap < total && b->wd_stream) HIP_TRY(hipStreamSynchronize(b->wd_stream));
+    if ((rc = b->wd_scratch.ensure(total))) return rc;
+    // behind the encode, behind the last word pass (its scratch), behind the list's builder
+    if ((rc = ck_order(b, b->last_stream, st))) return rc;
+    if (b->wd_stream && (rc = ck_order(b, b->wd_stream, st))) return rc;
+    if (want_lines && b->ln_stream && (rc = ck_order(b, b->ln_stream, st))) return rc;
+    w.text = b->job_text; w.doc_off = b->job_doc_off; w.status = (const int32_t*)b->status.p;
+    w.n_bytes = nb; w.n_docs = nd; w.uc = b->enc->dt.uc;
+    jtk_launch_words_preset(w, want_lines ? b->ln.unit_off : nullptr, st);
+    if (want_text && tiles > 0) {
+        uint8_t* const z = (uint8_t*)b->wd_scratch.p;
+        w.edge = (uint32_t*)z; w.ref = (uint32_t*)(z + plane);
+        w.sum_word = (uint32_t*)(z + 2 * plane); w.tile_cf = w.sum_word + tiles; w.tile_cb = w.tile_cf + tiles;
+        HIP_TRY(hipMemsetAsync(z, 0, 2 * plane, st));
+        jtk_launch_words_text(w, stops, st);
+        b->wd_stream = st;
+    }
+    if (want_lines) {
+        jtk_launch_words_lines(w, b->ln, p->short_line_chars, st);
+        b->ln_stream = st;
+    }
+    HIP_TRY(hipGetLastError());
     return JTK_OK;
 }
 

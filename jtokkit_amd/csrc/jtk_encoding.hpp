@@ -164,6 +164,11 @@ public:
     void lineRepeats(const jtk_lines_params& params, const jtk_lines_out& out, void* stream = nullptr) {
         check(jtk_batch_line_repeats(batch_, &params, &out, stream));
     }
+    // word-level quality signals of the last encode's text (jtk_batch_word_stats): writes what `out` asks for; its line counts need
+    // the list of lineUnits(JTK_LINES_LINE, JTK_LINES_TRIM)
+    void wordStats(const jtk_words_params& params, const jtk_words_out& out, void* stream = nullptr) {
+        check(jtk_batch_word_stats(batch_, &params, &out, stream));
+    }
 
     // batch decodeBytes: token lists back to back in `ids`, n+1 offsets -> bytes back to back + n+1 byte offsets + status
     void decodeBatch(const int32_t* ids, const std::vector<int64_t>& seqOff, std::string& bytes,

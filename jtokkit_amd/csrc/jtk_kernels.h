@@ -489,6 +489,36 @@ void jtk_launch_lines_write(const JtkLnWork& w, uint64_t seed, uint64_t doc_inde
 void jtk_launch_lines_preset(const JtkLnWork& w, const JtkLnOut& o, uint64_t* top, hipStream_t s);
 void jtk_launch_lines_group(const JtkLnWork& w, uint32_t flags, const JtkRpTable& t, int64_t lo, int64_t hi, const JtkLnOut& o, uint64_t* top,
                             hipStream_t s);
+// Word-level quality signals (jtk_words.hip; the rule and the way the text is walked are jtk_words_rules.h).  edge / ref: the two
+// bit planes of jtk_lines_rules.h, preset to 0; sum_word: pass A's summary per tile; tile_cf / tile_cb: pass B's carries per tile,
+// forward (the L-or-N state, the dot carry << 3) and backward (L-or-N, L << 1).
+struct JtkWdStops;
+struct JtkWdOut {                  // jtk_words_out of include/jtokkit_amd.h
+    int32_t* n_words;
+    int64_t* word_chars;
+    int32_t *n_alpha_words, *n_symbol_words;
+    int64_t *symbol_word_chars, *n_hash;
+    int32_t* n_ellipsis;
+    uint32_t* stop_mask;
+    int32_t* n_stop_hits;
+    int32_t *n_lines, *n_bullet_lines, *n_ellipsis_lines, *n_terminal_lines, *n_short_lines;
+};
+struct JtkWdWork {
+    const uint8_t* text;
+    const int64_t* doc_off;
+    const int32_t* status;
+    int64_t n_bytes, n_docs;
+    JtkUcTables uc;
+    uint32_t *edge, *ref, *sum_word, *tile_cf, *tile_cb;
+    JtkWdOut out;
+};
+//   preset        every output that is asked for = 0 for every document; n_lines from unit_off (may be NULL without line outputs)
+//   text          the planes (preset to 0 by the caller), pass A, pass B, pass C: the nine word outputs
+//   lines         one lane per unit of the held list: the four line counts besides n_lines
+int64_t jtk_words_tiles(int64_t n_bytes);
+void jtk_launch_words_preset(const JtkWdWork& w, const int64_t* unit_off, hipStream_t s);
+void jtk_launch_words_text(const JtkWdWork& w, const JtkWdStops& stops, hipStream_t s);
+void jtk_launch_words_lines(const JtkWdWork& w, const JtkLnWork& ln, int32_t short_line_chars, hipStream_t s);
 // Device-side state of an allow-special encode (jtk_special.hip, JTK_ENCODE_ALLOW_SPECIAL; the rule is jtk_special_rules.h).
 // Candidates (per position, the longest allowed literal there) are found in position order, resolved to the kept matches, and
 // the batch is cut into sub-documents that partition the text: per document a segment, then per candidate i two slots

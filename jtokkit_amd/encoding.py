@@ -176,6 +176,19 @@ _LINES_PER_DOC = (("n_dup", np.int32), ("dup_bytes", np.int64), ("dup_chars", np
                   ("doc_chars", np.int64), ("top_count", np.int32), ("top_first", np.int64))
 
 
+# Gopher's stop-word test (Rae et al. 2021, table A1): a document keeps at least two of these
+GOPHER_STOP_WORDS = ("the", "be", "to", "of", "and", "that", "have", "with")
+
+
+def _words_params(stop_words, fold_ascii, short_line_chars):
+    """(jtk_words_params, the arrays it points into); stop_words: str or bytes, a str as its UTF-8 bytes."""
+    blob, off = _stop_blob(stop_words if isinstance(stop_words, (str, bytes, bytearray)) else tuple(stop_words))
+    blob, off = np.ascontiguousarray(blob), np.ascontiguousarray(off)
+    p = N.WordsParamsStruct(N.JTK_WORDS_FOLD_ASCII if fold_ascii else 0, int(short_line_chars), len(off) - 1, 0,
+                            blob.ctypes.data if blob.size else None, off.ctypes.data)
+    return p, (blob, off)
+
+
 def _stop_blob(stop_strings):
     """Stop strings (bytes or str, a str as its UTF-8 bytes; one alone is a list of one) -> (blob uint8, str_off uint32
     [n + 1]).  The library checks counts and lengths."""
@@ -516,6 +529,19 @@ class Batch:
             raise TypeError("line_repeats: no output named %s" % ", ".join(sorted(unknown)))
         out = N.LinesOutStruct(**{k: v for k, v in ptrs.items() if v})
         _check(N.lib().jtk_batch_line_repeats(self._h, C.byref(_lines_params(unit, trim, mark_first, seed, doc_index_base)), C.byref(out), stream))
+
+    def word_stats(self, stop_words=GOPHER_STOP_WORDS, fold_ascii=False, short_line_chars=0, stream=None, **ptrs):
+        """jtk_batch_word_stats of the last encode's text: device pointers by the field names of jtk_words_out (n_words=,
+        word_chars=, n_alpha_words=, n_symbol_words=, symbol_word_chars=, n_hash=, n_ellipsis=, stop_mask=, n_stop_hits=, n_lines=,
+        n_bullet_lines=, n_ellipsis_lines=, n_terminal_lines=, n_short_lines=), each may be left out or None and is then not
+        written.  The line counts need line_units("line", trim=True) on the same encode.  Does not wait."""
+        unknown = set(ptrs) - set(N.WORDS_OUT_FIELDS)
+        if unknown:
+            raise TypeError("word_stats: no output named %s" % ", ".join(sorted(unknown)))
+        p, keep = _words_params(stop_words, fold_ascii, short_line_chars)
+        out = N.WordsOutStruct(**{k: v for k, v in ptrs.items() if v})
+        _check(N.lib().jtk_batch_word_stats(self._h, C.byref(p), C.byref(out), stream))
+        del keep                                                 # (the call has copied the list)
 
     def encode_device(self, d_text_ptr, d_doc_off_ptr, n_docs, n_bytes, ordinary=False, stream=None, sync=True,
                       allow_special=False, validate=False, count_only=False, fim=False):
@@ -1433,6 +1459,75 @@ class HipEncoding:
         res.update({name: torch.empty(nd, dtype=getattr(torch, np.dtype(dt).name), device=device) for name, dt in _LINES_PER_DOC})
         b.line_repeats(unit, trim, mark_first, seed, doc_index_base, stream, **{name: t.data_ptr() for name, t in res.items() if t.numel()})
         return res
+
+    def word_stats_batch(self, texts, stop_words=GOPHER_STOP_WORDS, fold_ascii=False, short_line_chars=0):
+        """Word-level quality signals of each of a list of str/bytes (jtk_batch_word_stats; the rule is in include/jtokkit_amd.h):
+        a dict of numpy arrays [n] by the field names of jtk_words_out -- word_chars, symbol_word_chars and n_hash int64, stop_mask
+        uint32 (bit i: stop word i occurs), the others int32.  The line counts are over the trimmed non-blank lines."""
+        bs, text, doc_off = _join_texts(texts)
+        n = len(bs)
+        self.encode_batch_packed(text, doc_off, True, False, None)
+        b = self._b()
+        b.line_units("line", True)
+        with _device_arrays() as put:
+            outs = {name: put(np.zeros(n, dtype=dt)) for name, dt in N.WORDS_OUT_TYPES}
+            b.word_stats(stop_words, fold_ascii, short_line_chars, **{name: x.ptr for name, x in outs.items() if n})
+            _stream_sync(b.stream())
+            res = {name: x.fetch() for name, x in outs.items()}
+        return res
+
+    def word_stats_batch_device(self, text, doc_off, stop_words=GOPHER_STOP_WORDS, fold_ascii=False, short_line_chars=0, ordinary=True,
+                                allowed_special=None):
+        """Encodes a device-resident batch (text CUDA torch.uint8, doc_off CUDA torch.int64 [n_docs + 1]) and returns its word-level
+        quality signals as a dict of CUDA tensors [n_docs] written on torch.cuda.current_stream(), by the field names of
+        jtk_words_out (as word_stats_batch; stop_mask as int32 bits), plus "status" int32 [n_docs].  Waits once, for the number of
+        lines (and, with allowed_special, once more for the encode's count of literal candidates)."""
+        import torch
+        self._check_device_inputs("word_stats_batch_device", ("text", text, torch.uint8), ("doc_off", doc_off, torch.int64))
+        allow = self._allow(self._b(), allowed_special)
+        with self._encode_device_batch(text, doc_off, ordinary, allow) as (b, nd, device, stream):
+            res = self._word_stats_on(b, nd, device, stream, stop_words, fold_ascii, short_line_chars)
+            res["status"] = self._tok_off_and_status(b, nd, device, stream)[1]
+        return res
+
+    @staticmethod
+    def _word_stats_on(b, nd, device, stream, stop_words, fold_ascii, short_line_chars):
+        """line_units("line", trim=True) and word_stats of the batch's last encode into new CUDA tensors, on `stream`."""
+        import torch
+        b.line_units("line", True, stream=stream)
+        res = {name: torch.zeros(nd, dtype=torch.int64 if dt == "int64" else torch.int32, device=device) for name, dt in N.WORDS_OUT_TYPES}
+        b.word_stats(stop_words, fold_ascii, short_line_chars, stream, **{name: t.data_ptr() for name, t in res.items() if nd})
+        return res
+
+    def quality_signals(self, texts, stop_words=GOPHER_STOP_WORDS, fold_ascii=False, short_line_chars=0, ordinary=True, allowed_special=None):
+        """The quantities Gopher's quality filter (Rae et al. 2021, table A1; datatrove's GopherQualityFilter) puts a threshold on,
+        for a list of str/bytes: a dict of numpy arrays [n_docs] -- "n_words" int64; "mean_word_length" = (word_chars -
+        symbol_word_chars) / (n_words - n_symbol_words); "hash_to_word", "ellipsis_to_word" = n_hash, n_ellipsis / n_words;
+        "bullet_line_fraction", "ellipsis_line_fraction", "terminal_line_fraction" over the trimmed non-blank lines;
+        "alpha_word_fraction" = n_alpha_words / n_words; "n_stop_words" int64, the stop words of the list that occur (the bits of
+        stop_mask); "status" int32.  float64, 0.0 where the denominator is 0.  One encode, one line_units("line", trim=True), one
+        jtk_batch_word_stats pass; the fractions are formed with torch on the device: no text or ids on the host."""
+        import torch
+        bs, text, doc_off = _join_texts(texts)
+        nd = len(bs)
+        names = ("mean_word_length", "hash_to_word", "ellipsis_to_word", "bullet_line_fraction", "ellipsis_line_fraction",
+                 "terminal_line_fraction", "alpha_word_fraction")
+        if nd == 0 or not len(text):
+            out = {name: np.zeros(nd, dtype=np.float64) for name in names}
+            out.update(n_words=np.zeros(nd, dtype=np.int64), n_stop_words=np.zeros(nd, dtype=np.int64), status=np.zeros(nd, dtype=np.int32))
+            return out
+        device = torch.device("cuda", N.lib().jtk_encoding_device(self._h))
+        d_off = torch.from_numpy(doc_off).to(device)
+        d_text = torch.from_numpy(text.copy()).to(device)                        # (a copy: frombuffer views are read-only)
+        r = self.word_stats_batch_device(d_text, d_off, stop_words, fold_ascii, short_line_chars, ordinary, allowed_special)
+        frac = lambda num, den: torch.where(den > 0, num.double() / den.clamp(min=1).double(), torch.zeros_like(num, dtype=torch.float64)).cpu().numpy()
+        nw, nl = r["n_words"].long(), r["n_lines"].long()
+        bits = sum((r["stop_mask"].long() >> i) & 1 for i in range(N.JTK_WD_MAX_STOP))
+        return {"n_words": nw.cpu().numpy(), "mean_word_length": frac(r["word_chars"] - r["symbol_word_chars"], nw - r["n_symbol_words"].long()),
+                "hash_to_word": frac(r["n_hash"], nw), "ellipsis_to_word": frac(r["n_ellipsis"].long(), nw),
+                "bullet_line_fraction": frac(r["n_bullet_lines"].long(), nl), "ellipsis_line_fraction": frac(r["n_ellipsis_lines"].long(), nl),
+                "terminal_line_fraction": frac(r["n_terminal_lines"].long(), nl), "alpha_word_fraction": frac(r["n_alpha_words"].long(), nw),
+                "n_stop_words": bits.cpu().numpy(), "status": r["status"].cpu().numpy()}
 
     def repetition_signals(self, texts, top=(2, 3, 4), dup=(5, 6, 7, 8, 9, 10), mark_first=False, seed=0, ordinary=True, allowed_special=None,
                            lines=False, trim=False):
