@@ -252,6 +252,31 @@ int jtk_batch_minhash(jtk_batch* b, const jtk_minhash_params* params, uint32_t* 
 int jtk_batch_minhash_agree(jtk_batch* b, const uint32_t* d_sig, int64_t n_sig, int32_t num_hashes, const int64_t* d_pair_a,
                             const int64_t* d_pair_b, int64_t n_pairs, int32_t* d_agree, void* stream_or_null);
 
+/* Near-duplicate clusters out of MinHash signatures and LSH band keys, on the device with no sort and no host round trip
+ * (jtk_cluster.hip; the rule, bit for bit, is csrc/jtk_cluster_rules.h -- integer only, every result is exact).
+ *   d_sig[n * num_hashes] uint32 and d_band_keys[n * bands] uint64 are rows as jtk_batch_minhash writes them, gathered from any
+ *   number of batches; num_hashes 1..256, bands 1..256 (bands need not divide num_hashes here: any 64-bit keys will do).
+ *   d_n_shingles[n] int32 may be NULL: a document is LIVE when it is NULL or its entry is > 0.
+ *   rep(d, j) of a live d = the smallest live e with band_keys[e][j] == band_keys[d][j] -- all 64 bits, inside band j only;
+ *   every key value is legal, 0 and 2^64 - 1 too --, and -1 for a d that is not live.  (e, d) is a candidate when e = rep(d, j)
+ *   < d for some j, and verified when sig[e] and sig[d] agree on >= min_agree words (1 <= min_agree <= num_hashes).
+ *   d_labels[d] int64 = the smallest index of d's connected component in the graph of verified pairs; d itself where d is not
+ *   live or has no verified pair.  d_rep[n * bands] int64 (may be NULL, and is then not written) receives rep.
+ *   The results are a function of the inputs alone: not of the table budget, the streams or the order in which waves run.
+ *   Pairing with the bucket's smallest index -- one atomic minimum per (document, band) -- is not the predecessor pairing of a
+ *   sort per band: the two agree where all members of a bucket verify against each other, and can differ on a chain inside
+ *   one bucket that is not transitive (a ~ b, b ~ c, not a ~ c: c stays apart here unless another band joins b and c).
+ * `b` gives the device, the default stream and the scratch; no encode is needed.  The band tables are sized by n, which bounds
+ * the live count, so the call waits for nothing: it is queued on stream_or_null, or the batch's stream, and returns.  The tables
+ * share the allocation and the byte budget of jtk_batch_ngram_repeats (JTK_OPT_REPEAT_TABLE_BYTES): a band costs 16 bytes times
+ * the smallest power of two >= max(64, 2 n), plus 8; the bands are taken in groups that fit the budget, and a budget below one
+ * band is JTK_ERR_OUT_OF_MEMORY with nothing written.  Without d_rep the batch keeps n * bands * 8 bytes of its own for rep.
+ * n == 0 is a successful no-op.  JTK_ERR_INVALID_ARGUMENT, with nothing written: b, d_sig, d_band_keys or d_labels NULL (n > 0),
+ * num_hashes or bands outside 1..256, min_agree outside 1..num_hashes, n < 0, an array not aligned to its element. */
+int jtk_batch_minhash_cluster(jtk_batch* b, const uint32_t* d_sig, const uint64_t* d_band_keys, const int32_t* d_n_shingles_or_null,
+                              int64_t n, int32_t num_hashes, int32_t bands, int32_t min_agree, int64_t* d_labels,
+                              int64_t* d_rep_or_null, void* stream_or_null);
+
 /* Token n-gram sets and overlap, for benchmark decontamination: a corpus document is flagged, and the exact token ranges are
  * marked, where it shares a token n-gram with a set of held-out texts encoded by the same encoder (jtk_ngram.hip; the rule, bit
  * for bit, is csrc/jtk_ngram_rules.h -- integer arithmetic only, so every result is exact).

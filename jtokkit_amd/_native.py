@@ -170,6 +170,7 @@ SIGNATURES = {
     "jtk_batch_compact": (C.c_int, [_p, _p, _p, _p]),
     "jtk_batch_minhash": (C.c_int, [_p, C.POINTER(MinhashParamsStruct), _p, _p, _p, _p]),
     "jtk_batch_minhash_agree": (C.c_int, [_p, _p, _i64, C.c_int32, _p, _p, _i64, _p, _p]),
+    "jtk_batch_minhash_cluster": (C.c_int, [_p, _p, _p, _p, _i64, C.c_int32, C.c_int32, C.c_int32, _p, _p, _p]),
     "jtk_ngram_set_create": (C.c_int, [_p, C.POINTER(NgramParamsStruct), C.POINTER(_p)]),
     "jtk_ngram_set_destroy": (None, [_p]),
     "jtk_ngram_set_add_batch": (C.c_int, [_p, _p, _p]),

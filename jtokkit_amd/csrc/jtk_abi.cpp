@@ -17,6 +17,7 @@
 #include "../../include/jtokkit_amd.h"
 #include "jtk_chunk_rules.h"
 #include "jtk_chunk_prefer_rules.h"
+#include "jtk_cluster_rules.h"
 #include "jtk_compact_rules.h"
 #include "jtk_decode_rows_rules.h"
 #include "jtk_kernels.h"
@@ -201,6 +202,9 @@ struct jtk_batch {
     Event ev_rp;
     bool rp_queued = false;
     int64_t rp_table_bytes = (int64_t)256 << 20;   // JTK_OPT_REPEAT_TABLE_BYTES
+    // jtk_batch_minhash_cluster (jtk_cluster.hip): rep[n * bands] when the caller does not take it.  The band tables live in
+    // rp_table, under its budget, and the pass is ordered by ev_rp like the others that use it.
+    DevBuf cl_rep;
     // jtk_batch_line_units / jtk_batch_line_repeats (jtk_lines.hip): ln_scratch = the two bit planes | the tiles' summaries and
     // carries | the per-document entries and offsets | hdr; ln_units = six 8-byte arrays per unit (begin, end, k, chars, and the two
     // prefixes at the end byte), allocated at the counted size.  The list is the last encode's for ln_p (unit, JTK_LINES_TRIM,
@@ -2215,6 +2219,45 @@ int jtk_batch_minhash_agree(jtk_batch* b, const uint32_t* d_sig, int64_t n_sig, 
     HIP_TRY(hipSetDevice(b->enc->device));
     jtk_launch_minhash_agree(d_sig, n_sig, num_hashes, d_pair_a, d_pair_b, n_pairs, d_agree, pick_stream(b, stream_or_null));
     HIP_TRY(hipGetLastError());
+    return JTK_OK;
+}
+
+// ---- near-duplicate clusters out of signatures and band keys (jtk_cluster.hip; the rule is jtk_cluster_rules.h) -----------------
+int jtk_batch_minhash_cluster(jtk_batch* b, const uint32_t* d_sig, const uint64_t* d_band_keys, const int32_t* d_n_shingles, int64_t n,
+                              int32_t num_hashes, int32_t bands, int32_t min_agree, int64_t* d_labels, int64_t* d_rep, void* stream_or_null) {
+    int rc;
+    if (!b) return fail(JTK_ERR_INVALID_ARGUMENT, "batch is NULL");
+    if (!jtk_cl_params_ok(n, num_hashes, bands, min_agree))
+        return fail(JTK_ERR_INVALID_ARGUMENT, "minhash cluster: n >= 0, num_hashes 1..256, bands 1..256, min_agree 1..num_hashes");
+    if (n == 0) return JTK_OK;
+    if (!d_sig || !d_band_keys || !d_labels) return fail(JTK_ERR_INVALID_ARGUMENT, "d_sig, d_band_keys or d_labels is NULL");
+    if (((uintptr_t)d_sig & 3u) || ((uintptr_t)d_n_shingles & 3u) || ((uintptr_t)d_band_keys & 7u) || ((uintptr_t)d_labels & 7u) ||
+        ((uintptr_t)d_rep & 7u))
+        return fail(JTK_ERR_INVALID_ARGUMENT, "unaligned array (4-byte sig and n_shingles, 8-byte band keys, labels and rep)");
+    const int32_t g_max = jtk_cl_group_bands(n, bands, b->rp_table_bytes);
+    if (g_max < 1) return fail(JTK_ERR_OUT_OF_MEMORY, "minhash cluster: JTK_OPT_REPEAT_TABLE_BYTES does not hold the table of one band");
+    HIP_TRY(hipSetDevice(b->enc->device));
+    hipStream_t st = pick_stream(b, stream_or_null);
+    HIP_TRY(b->ev_rp.create());
+    // everything that can fail for lack of memory comes before the first write; scratch that grows is not in use any more
+    const int64_t cap = jtk_cl_capacity(n);
+    const size_t table_bytes = (size_t)g_max * (size_t)jtk_cl_band_bytes(n), rep_bytes = d_rep ? 0 : (size_t)n * (size_t)bands * 8;
+    if ((table_bytes > b->rp_table.cap || rep_bytes > b->cl_rep.cap) && b->rp_queued) HIP_TRY(hipEventSynchronize(b->ev_rp));
+    if ((rc = b->rp_table.ensure(table_bytes)) || (rc = b->cl_rep.ensure(rep_bytes))) return rc;
+    if (b->rp_queued) HIP_TRY(hipStreamWaitEvent(st, b->ev_rp, 0));
+    int64_t* const rep = d_rep ? d_rep : (int64_t*)b->cl_rep.p;
+    jtk_launch_cluster_preset(n, d_labels, st);
+    for (int32_t j0 = 0; j0 < bands; j0 += g_max) {
+        const int32_t g = bands - j0 < g_max ? bands - j0 : g_max;
+        const JtkClTable t = jtk_cl_table_at(b->rp_table.p, cap, g);
+        HIP_TRY(hipMemsetAsync(t.key, 0, (size_t)g * (size_t)cap * 8, st));
+        HIP_TRY(hipMemsetAsync(t.val, 0xFF, (size_t)g * (size_t)cap * 8 + (size_t)g * 8, st));      // values | side cells
+        jtk_launch_cluster_group(d_band_keys, d_n_shingles, n, bands, j0, g, t, rep, st);
+    }
+    jtk_launch_cluster_join(d_sig, d_n_shingles, rep, n, num_hashes, bands, min_agree, d_labels, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(b->ev_rp, st));
+    b->rp_queued = true;
     return JTK_OK;
 }
 

@@ -123,6 +123,18 @@ public:
         check(jtk_batch_token_char_offsets(batch_, unit, dBegin, dEnd, stream));
     }
 
+    // MinHash of the last encodeBatch into device arrays (jtk_batch_minhash), and near-duplicate clusters out of device rows of
+    // signatures and band keys gathered from any number of batches (jtk_batch_minhash_cluster: no encode needed, does not wait;
+    // dNShingles and dRep may be nullptr)
+    void minhash(const jtk_minhash_params& params, uint32_t* dSig, int32_t* dNShingles = nullptr, uint64_t* dBandKeys = nullptr,
+                 void* stream = nullptr) {
+        check(jtk_batch_minhash(batch_, &params, dSig, dNShingles, dBandKeys, stream));
+    }
+    void minhashCluster(const uint32_t* dSig, const uint64_t* dBandKeys, const int32_t* dNShingles, int64_t n, int32_t numHashes,
+                        int32_t bands, int32_t minAgree, int64_t* dLabels, int64_t* dRep = nullptr, void* stream = nullptr) {
+        check(jtk_batch_minhash_cluster(batch_, dSig, dBandKeys, dNShingles, n, numHashes, bands, minAgree, dLabels, dRep, stream));
+    }
+
     // token n-gram sets for decontamination (the rule is in jtokkit_amd.h): a set of this encoding, owned by the caller and freed
     // with ngramSetDestroy before the Encoding; the n-grams of the last encodeBatch or host keys into it; its size and keys; and
     // the overlap of the last encodeBatch with it into device arrays (each may be NULL)

@@ -423,6 +423,17 @@ void jtk_launch_minhash(const JtkMhView& v, uint64_t seed, int32_t num_hashes, i
 // agree[p] = the words on which rows pair_a[p] and pair_b[p] of sig[n_sig * num_hashes] agree; -1 for an index outside [0, n_sig)
 void jtk_launch_minhash_agree(const uint32_t* sig, int64_t n_sig, int32_t num_hashes, const int64_t* pair_a, const int64_t* pair_b,
                               int64_t n_pairs, int32_t* agree, hipStream_t s);
+// Near-duplicate clusters (jtk_cluster.hip; the rule is jtk_cluster_rules.h), n > 0.
+//   preset        labels[d] = d: the union-find's parents
+//   group         bands [j0, j0 + g) of band_keys[n * bands]: insert into the group's tables, preset by the caller (keys 0, values
+//                 and side cells all ones), then rep[d * bands + j] for those bands; two kernels
+//   join          verify the candidates of rep against sig[n * num_hashes], hook, then labels[d] = d's root; two kernels
+struct JtkClTable;
+void jtk_launch_cluster_preset(int64_t n, int64_t* labels, hipStream_t s);
+void jtk_launch_cluster_group(const uint64_t* band_keys, const int32_t* n_shingles, int64_t n, int32_t bands, int32_t j0, int32_t g,
+                              const JtkClTable& t, int64_t* rep, hipStream_t s);
+void jtk_launch_cluster_join(const uint32_t* sig, const int32_t* n_shingles, const int64_t* rep, int64_t n, int32_t num_hashes, int32_t bands,
+                             int32_t min_agree, int64_t* labels, hipStream_t s);
 // Token n-gram sets and overlap (jtk_ngram.hip; the rule is jtk_ngram_rules.h).  A set is a table of `capacity` (a power of two)
 // 64-bit slots, 0 = empty, and a device word that counts its keys.
 //   count         *sum += the n-grams of the documents of v (what an insert of them adds at most)

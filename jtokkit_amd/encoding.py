@@ -495,6 +495,14 @@ class Batch:
         _check(N.lib().jtk_batch_minhash_agree(self._h, d_sig_ptr, n_sig, num_hashes, d_pair_a_ptr, d_pair_b_ptr, n_pairs,
                                                d_agree_ptr, stream))
 
+    def minhash_cluster(self, d_sig_ptr, d_band_keys_ptr, n, num_hashes, bands, min_agree, d_labels_ptr, d_n_shingles_ptr=None,
+                        d_rep_ptr=None, stream=None):
+        """jtk_batch_minhash_cluster: int64 [n] cluster labels at d_labels_ptr (and int64 [n * bands] bucket representatives at
+        d_rep_ptr, or None) out of uint32 [n * num_hashes] at d_sig_ptr, uint64 [n * bands] at d_band_keys_ptr and int32 [n] at
+        d_n_shingles_ptr (or None: every document is live), device pointers.  Needs no encode on the batch; does not wait."""
+        _check(N.lib().jtk_batch_minhash_cluster(self._h, d_sig_ptr, d_band_keys_ptr, d_n_shingles_ptr, n, num_hashes, bands, min_agree,
+                                                 d_labels_ptr, d_rep_ptr, stream))
+
     def ngram_overlap(self, ngram_set, d_tok_flags_ptr=None, d_n_hit_ptr=None, d_n_covered_ptr=None, d_first_hit_ptr=None, stream=None):
         """jtk_batch_ngram_overlap of the last encode against an NgramSet: uint8 [n_tokens] at d_tok_flags_ptr, int32 [n_docs] at
         d_n_hit_ptr and d_n_covered_ptr, int64 [n_docs] at d_first_hit_ptr, device pointers, each may be None and is then not
@@ -1666,6 +1674,60 @@ class HipEncoding:
         for d in range(n):
             labels[d] = find(d)
         return labels
+
+    def minhash_cluster_device(self, sig, band_keys, threshold, n_shingles=None, return_rep=False):
+        """Near-duplicate clusters out of device-resident MinHash rows (jtk_batch_minhash_cluster; the rule is in
+        include/jtokkit_amd.h): sig CUDA int32 [n, K] and band_keys CUDA int64 [n, B] in the bit-pattern conventions of
+        minhash_batch_device -- rows of any number of batches, concatenated --, n_shingles CUDA int32 [n] or None (then every
+        document is live).  Returns labels, CUDA int64 [n]: the smallest index of each document's cluster; with return_rep
+        (labels, rep), rep CUDA int64 [n, B]: per band the smallest live index with the document's key, -1 for a document that
+        is not live.  Each document is paired with the smallest index of its bucket and the pair is kept when the rows agree on
+        min_agree = ceil(threshold * K) columns.  That is not near_duplicates' rule (predecessor in a sort per band): the two
+        agree where all members of a bucket verify against each other and can differ on a chain inside one bucket that is not
+        transitive.  Queued on torch.cuda.current_stream(); no sort and no wait."""
+        import math
+        import torch
+        if not (isinstance(sig, torch.Tensor) and isinstance(band_keys, torch.Tensor) and sig.dim() == 2 and band_keys.dim() == 2):
+            raise ValueError("sig and band_keys must be 2-d CUDA tensors")
+        n, K = sig.shape
+        B = band_keys.shape[1]
+        if band_keys.shape[0] != n:
+            raise ValueError("sig and band_keys must have one row per document")
+        flat = [("sig", sig.reshape(-1), torch.int32), ("band_keys", band_keys.reshape(-1), torch.int64)]
+        if n_shingles is not None:
+            if n_shingles.shape != (n,):
+                raise ValueError("n_shingles must have one entry per document")
+            flat.append(("n_shingles", n_shingles, torch.int32))
+        if not (sig.is_contiguous() and band_keys.is_contiguous()):
+            raise ValueError("sig and band_keys must be contiguous")
+        self._check_device_inputs("minhash_cluster_device", *flat)
+        device = sig.device
+        labels = torch.empty(n, dtype=torch.int64, device=device)
+        rep = torch.empty((n, B), dtype=torch.int64, device=device) if return_rep else None
+        b = self._b()
+        with self._on_current_stream(b, device) as stream:
+            b.minhash_cluster(sig.data_ptr() or None, band_keys.data_ptr() or None, n, K, B, int(math.ceil(threshold * K)),
+                              labels.data_ptr() or None, n_shingles.data_ptr() or None if n_shingles is not None else None,
+                              rep.data_ptr() or None if return_rep else None, stream)
+        return (labels, rep) if return_rep else labels
+
+    def near_duplicate_clusters(self, texts, threshold=0.8, ngram=5, num_hashes=128, bands=16, seed=0, ordinary=True, allowed_special=None):
+        """Clusters of near-duplicate documents by MinHash and LSH, computed on the device end to end: int64 [n] numpy labels,
+        the smallest document index of each document's cluster.  minhash_batch_device, then minhash_cluster_device on its rows
+        (see there for the rule, and for where it differs from near_duplicates); a document without shingles (empty or refused)
+        is its own cluster.  The only waits are the encode's (for its token count) and the copy of the labels to the host."""
+        import torch
+        if bands < 1:
+            raise ValueError("near_duplicate_clusters needs bands >= 1")
+        bs, text, doc_off = _join_texts(texts)
+        n = len(bs)
+        if n < 2 or not len(text):
+            return np.arange(n, dtype=np.int64)
+        device = torch.device("cuda", N.lib().jtk_encoding_device(self._h))
+        doc_off = torch.from_numpy(doc_off).to(device)
+        text = torch.from_numpy(text.copy()).to(device)                          # (a copy: frombuffer views are read-only)
+        sig, n_shingles, band_keys, _, _ = self.minhash_batch_device(text, doc_off, ngram, num_hashes, bands, seed, ordinary, allowed_special)
+        return self.minhash_cluster_device(sig, band_keys, threshold, n_shingles).cpu().numpy()
 
     def special_ids(self, allowed_special):
         """"all" or an iterable of special-token literals -> their ids (ValueError for a literal that is no special token)."""
