@@ -79,7 +79,7 @@ struct __attribute__((visibility("hidden"))) ChunkSet {      // (internal: no we
     bool used = false;               // by the current job
 };
 
-constexpr int MAX_SETS = 4;
+constexpr int MAX_SETS = JTK_SETS_MAX;
 constexpr int64_t SMALL_JOB_BYTES = 1 << 20;
 constexpr int64_t TINY_JOB_BYTES = 128 << 10;     // host jobs this small are staged so that offsets and text go down in one copy
 
@@ -91,8 +91,8 @@ struct jtk_batch {
     Event ev_fork, ev_copy;
     Pinned<int64_t> h_info;              // device-visible: per chunk, its first token and the end of its last
     ChunkSet set[MAX_SETS];
-    int n_sets = 2;                      // chunks in flight (JTK_OPT_CHUNKS_IN_FLIGHT)
-    bool n_sets_chosen = false;          // by the caller or the environment (else a job that streams ids to the host takes 3)
+    int n_sets = JTK_SETS_DEFAULT;       // chunks in flight (JTK_OPT_CHUNKS_IN_FLIGHT)
+    bool n_sets_chosen = false;          // by the caller or the environment (else run_job takes JTK_SETS_DEFAULT_DEVICE where that pays)
     int64_t chunk_bytes = (int64_t)1 << 30;    // JTK_OPT_CHUNK_BYTES: device-resident input (large chunks: fewer launches and kernel tails)
     int64_t host_chunk_bytes = (int64_t)32 << 20;   // JTK_OPT_HOST_CHUNK_BYTES: host input (small chunks: copies overlap kernels)
     // the whole batch
@@ -629,25 +629,23 @@ int prepare_set(ChunkSet& cs, int64_t n_bytes, int64_t n_docs, size_t* bytes_to_
     JtkWork& w = cs.work;
     w.n_bytes = n_bytes;
     w.n_docs = n_docs;
-    w.n_words = (n_bytes + 1 + 63) / 64 + 2;
-    w.n_tiles = (n_bytes + 1 + JTK_TILE - 1) / JTK_TILE;
-    const size_t mask_bytes = (size_t)w.n_words * 8;
+    // every array at the largest size an input can require of it (jtk_scratch_rules.h)
+    const JtkSetSizes z_ = jtk_set_sizes(n_bytes);
+    w.n_words = z_.n_words;
+    w.n_tiles = z_.n_tiles;
+    const size_t mask_bytes = (size_t)z_.mask;
     const size_t nt = (size_t)w.n_tiles;
-    const size_t qcnt_bytes = (size_t)(JTK_NBINS + 1) * JTK_Q_SHARDS * JTK_QC_STRIDE * 4;
-    const size_t zero_bytes = mask_bytes + 32 + qcnt_bytes;
-    const size_t n_long_max = (size_t)n_bytes / (JTK_BIN_MAXLEN + 1) + 2;
-    const size_t n_giant_max = (size_t)n_bytes / JTK_LONG_CAP + 2;
-    const size_t tps = (nt + JTK_Q_SHARDS - 1) / JTK_Q_SHARDS;      // tiles per queue shard
+    const size_t zero_bytes = (size_t)z_.zeroed;
     int rc;
     if ((rc = cs.zeroed.ensure(zero_bytes)) || (rc = cs.piecemask.ensure(mask_bytes)) ||
-        (rc = cs.plist.ensure(nt * JTK_TILE * 4)) || (rc = cs.htok.ensure(nt * JTK_TILE * 4 + 64)) ||
-        (rc = cs.docpre.ensure(nt * JTK_TILE * 4)) ||
-        (rc = cs.tile_np.ensure(align_up(nt * 4, 16) * 2)) || (rc = cs.tile_off.ensure((nt + 1) * 8)) ||
-        (rc = cs.q_meta.ensure(nt * 4 * 16)) ||
-        (rc = cs.queues.ensure(tps * JTK_Q_SHARDS * ((size_t)(JTK_BIN_CAP0 + JTK_BIN_CAP1 + JTK_BIN_CAP2 + JTK_BIN_CAP3 + JTK_BIN_CAP4 + JTK_BIN_CAP5 + JTK_BIN_CAP6) * 24 + (size_t)JTK_TINY_CAP * 8))) ||
-        (rc = cs.mid_list.ensure(n_long_max * sizeof(JtkLongPiece))) ||
-        (rc = cs.long_list.ensure(n_long_max * sizeof(JtkLongPiece))) ||
-        (rc = cs.giant_list.ensure(n_giant_max * sizeof(JtkLongPiece))))
+        (rc = cs.plist.ensure((size_t)z_.plist)) || (rc = cs.htok.ensure((size_t)z_.htok)) ||
+        (rc = cs.docpre.ensure((size_t)z_.docpre)) ||
+        (rc = cs.tile_np.ensure((size_t)z_.tile_np)) || (rc = cs.tile_off.ensure((size_t)z_.tile_off)) ||
+        (rc = cs.q_meta.ensure((size_t)z_.q_meta)) ||
+        (rc = cs.queues.ensure((size_t)z_.queues)) ||
+        (rc = cs.mid_list.ensure((size_t)z_.mid_list)) ||
+        (rc = cs.long_list.ensure((size_t)z_.long_list)) ||
+        (rc = cs.giant_list.ensure((size_t)z_.giant_list)))
         return rc;
     uint8_t* z = (uint8_t*)cs.zeroed.p;
     w.docmask = (uint64_t*)z;
@@ -663,20 +661,19 @@ int prepare_set(ChunkSet& cs, int64_t n_bytes, int64_t n_docs, size_t* bytes_to_
     w.tile_tot = (uint32_t*)((uint8_t*)cs.tile_np.p + align_up(nt * 4, 16));
     w.tile_off = (int64_t*)cs.tile_off.p;
     {
-        const size_t caps[JTK_NBINS] = {JTK_BIN_CAP0, JTK_BIN_CAP1, JTK_BIN_CAP2, JTK_BIN_CAP3, JTK_BIN_CAP4, JTK_BIN_CAP5, JTK_BIN_CAP6};
         uint8_t* qp = (uint8_t*)cs.queues.p;                      // all the 16-byte arrays first, then the 8-byte ones
         w.q_meta = (uint32_t*)cs.q_meta.p;
         for (int k = 0; k < JTK_NBINS; k++) {
             w.qd[k] = (uint4*)qp;
-            w.q_cap[k] = (int64_t)(tps * caps[k]);
-            qp += tps * caps[k] * JTK_Q_SHARDS * 16;
+            w.q_cap[k] = jtk_bin_shard_cap(k, w.n_tiles);
+            qp += (size_t)w.q_cap[k] * JTK_Q_SHARDS * 16;
         }
         for (int k = 0; k < JTK_NBINS; k++) {
             w.qm[k] = (uint64_t*)qp;
-            qp += tps * caps[k] * JTK_Q_SHARDS * 8;
+            qp += (size_t)w.q_cap[k] * JTK_Q_SHARDS * 8;
         }
         w.qt = (uint64_t*)qp;
-        w.qt_cap = (int64_t)(tps * JTK_TINY_CAP);
+        w.qt_cap = jtk_bin_shard_cap(JTK_BIN_TINY, w.n_tiles);
     }
     w.mid_list = (JtkLongPiece*)cs.mid_list.p;
     w.long_list = (JtkLongPiece*)cs.long_list.p;
@@ -713,7 +710,11 @@ int run_job(jtk_batch* b, const uint8_t* d_text, const uint8_t* h_text, const in
     // (ids streamed to the host chunk by chunk: the host waits for a chunk's scan before it can issue that chunk's copy, one
     // chunk behind the enqueueing -- with two sets that wait stalls the pipeline: 404 ms per step on the headline corpus against
     // 163 with three, profiles/r03_experiments/r03bc_e2e_memcpy.txt -- so such a job takes three unless the caller chose)
-    const int want_sets = (!b->n_sets_chosen && to_host && h_text && b->n_sets < 3) ? 3 : b->n_sets;   // (host input: small chunks, small sets)
+    // Device-resident input: three as well.  Every kernel of a chunk fills the GPU, but not to its end -- k_bpe_merge's workgroups
+    // hold a CU each and finish at different times, every kernel has a tail -- and only a kernel of another chunk that is
+    // already queued can take the CUs that come free.  25.89 -> 24.95 ms per step on the headline corpus
+    // (profiles/chunks_in_flight.txt).  Host input whose result stays on the device keeps two.
+    const int want_sets = (!b->n_sets_chosen && (!h_text || to_host)) ? JTK_SETS_DEFAULT_DEVICE : b->n_sets;
     const int n_sets = n_chunks < want_sets ? (n_chunks < 1 ? 1 : n_chunks) : want_sets;
     int rc;
     // batch-wide buffers
@@ -780,8 +781,14 @@ int run_job(jtk_batch* b, const uint8_t* d_text, const uint8_t* h_text, const in
     const bool fork = n_chunks > 1 || (h_text != nullptr && !(n_chunks == 1 && n_bytes <= SMALL_JOB_BYTES));
     if (fork) {
         HIP_TRY(b->ev_fork.create());                              // (each made by the first job that needs it)
-        HIP_TRY(b->ev_copy.create());
-        HIP_TRY(b->copy_stream.create());
+        // (the copy stream only for a job that uses it.  The runtime spreads a process's streams over a few hardware queues, and
+        // streams that share one run one after the other: with an idle copy stream made first, two of the sets' streams landed
+        // on one queue -- with two sets both of them, which is why two chunks in flight used to measure like one --;
+        // profiles/chunks_in_flight.txt, 25.27 -> 24.95 ms per step)
+        if (to_host) {
+            HIP_TRY(b->ev_copy.create());
+            HIP_TRY(b->copy_stream.create());
+        }
         for (int k = 0; k < n_sets; k++) {
             ChunkSet& cs = b->set[k];
             HIP_TRY(cs.stream.create());

@@ -63,6 +63,7 @@
 #define JTK_LONG_CAP 8192        // wave-per-piece kernel, large bin
 #define JTK_GIANT_CAP (1 << 20)  // workgroup-per-piece kernel with parts in global scratch (= JTK_MAX_PIECE_BYTES)
 #define JTK_GIANT_CHUNK 256      // positions per cached chunk minimum
+#include "jtk_scratch_rules.h"    // how large the queues and the other arrays of a scratch set are, from the constants above
 #define JTK_MAX_SPECIALS 65536           // special-token literals live in a device blob: the bounds are sanity checks only
 #define JTK_SPECIAL_MAXLEN 65535
 
@@ -111,6 +112,7 @@ struct JtkLongPiece {
     int64_t start;
     int64_t len;
 };
+static_assert(sizeof(JtkLongPiece) == JTK_LONG_PIECE_BYTES, "jtk_set_sizes sizes the piece lists");
 
 struct JtkResult {          // of a whole batch (all its chunks)
     int64_t n_tokens;

@@ -393,6 +393,17 @@ __host__ __device__ __forceinline__ constexpr int q_off(int bin) {
 }
 constexpr int Q_TOTAL = q_off(JTK_BIN_TINY) + JTK_TINY_CAP;
 
+// k_piece_resolve spells its binning out where it bins; the queues are sized from jtk_piece_bin (jtk_scratch_rules.h): the same
+// bin for every length that is queued, checked when the kernel is compiled
+template <uint64_t BIN16>
+constexpr bool bins_are_the_rule() {
+    for (uint32_t len = 2; len <= (uint32_t)JTK_BIN_MAXLEN; len++) {
+        const uint32_t bin = len <= 16u ? (uint32_t)(BIN16 >> (3u * len)) & 7u : 30u - (uint32_t)__builtin_clz(len - 1u);
+        if (bin != jtk_piece_bin(len)) return false;
+    }
+    return true;
+}
+
 #ifndef JTK_RES_WAVES
 #define JTK_RES_WAVES 4
 #endif
@@ -617,6 +628,7 @@ __global__ void __launch_bounds__(RES_THREADS) __attribute__((amdgpu_waves_per_e
             constexpr uint64_t BIN16 = (7ull << 6) | (7ull << 9) | (1ull << 27) | (1ull << 30) | (1ull << 33) | (1ull << 36) |
                                        (2ull << 39) | (2ull << 42) | (2ull << 45) | (2ull << 48);
             const uint32_t bin = len <= 16u ? (uint32_t)(BIN16 >> (3u * len)) & 7u : 30u - (uint32_t)__builtin_clz(len - 1u);
+            static_assert(bins_are_the_rule<BIN16>(), "jtk_piece_bin, by which the queues are sized, is this rule");
             const uint32_t bc = s_binc[bin];                           // q_off | staging cap << 12 | staging offset << 21
             const uint32_t i = atomicAdd(&s_qn[bin], 1u);
             s_q[(bc & 0xFFFu) + i] = s | ((len - 1u) << 11) | (i << 19);
