@@ -505,6 +505,98 @@ typedef struct jtk_words_out {  /* device pointers [n_docs], each may be NULL an
 } jtk_words_out;
 int jtk_batch_word_stats(jtk_batch* b, const jtk_words_params* params, const jtk_words_out* out, void* stream_or_null);
 
+/* Exact duplicates across documents and batches: CCNet's and Dolma's paragraph dedup, Dolma's document dedup, the "drop lines
+ * that occur N times in the crawl" step of RefinedWeb and FineWeb, on the TEXT of batch encodes (jtk_seen.hip; the rule, bit for
+ * bit, is csrc/jtk_seen_rules.h -- integer arithmetic only, so every result is exact).  A set lives on its encoding's device,
+ * outlives batches, and maps the 64-bit key of a text unit to the smallest global position at which the unit was ever added
+ * (first) and to how often it was added (count).
+ *   Parameters of a set, fixed at creation: seed, unit = JTK_SEEN_LINE (0), JTK_SEEN_PARAGRAPH (1) or JTK_SEEN_DOCUMENT (2), flags =
+ *   JTK_SEEN_TRIM (2u) or 0; anything else is JTK_ERR_INVALID_ARGUMENT.
+ *   Units: LINE and PARAGRAPH are the units of jtk_batch_line_units, under the same ink, blank and newline definitions (TRIM as
+ *   JTK_LINES_TRIM); a document with status < 0 has none.  DOCUMENT is that rule with a threshold no newline count reaches: one
+ *   unit from the document's first ink byte to its last ink byte + 1 -- bytes.strip(b"\n"), with TRIM strip(b"\n \t\r") --, none
+ *   for a document that is empty, all blank or refused.
+ *   Key, all modulo 2^64, G and mix as for jtk_minhash_params: key = mix(seed + G * (unit + 193)) (a family of its own: MinHash
+ *   has ngram + 1, the n-gram set ngram + 33, n-gram repeats ngram + 97, line repeats unit + 161).  H = H * G + byte + 1 over the
+ *   unit's bytes, from 0; k = mix(H ^ key), G where that is 0.  There is no per-document salt: equal units of different documents
+ *   have equal k.  A 64-bit collision is part of the rule, as for the n-gram set.
+ *   Position of a unit: pos = (D << 24) | u, D = doc_index_base + d for document d of the batch, u the unit's document-relative
+ *   index.  D must be below 2^40 and u below 2^24: a call whose batch would break either bound is JTK_ERR_INVALID_ARGUMENT and
+ *   leaves the set as it was.
+ *   The set holds, for every k ever added, first = the smallest pos added with it and count = the number of units added with it
+ *   (both uint64).  Adding the same batch twice leaves first alone and doubles its share of count.  Entries merge by (min, +),
+ *   which is associative and commutative: what the set holds does not depend on the order in which batches or shards arrive.
+ *   The table is three planes of `capacity` uint64 (key, 0 = empty; first; count), 24 bytes per slot, 48 bytes per key at a load
+ *   of at most 1/2: home slot k & (capacity - 1), linear probing with wrap-around.  Before m units are added to a set of c keys
+ *   the capacity grows to the smallest power of two >= max(64, 2 (c + m)) when that is larger (rehashed on the device; it never
+ *   shrinks).  A new set has 64 slots.
+ *   Marking a batch: mode out of JTK_SEEN_ADD (1) and JTK_SEEN_QUERY (2), at least one.  With ADD all units of the batch are added
+ *   first.  With QUERY every unit then reads its key's entry: first and count, all ones and 0 when the key is absent; its flag
+ *   has JTK_SEEN_DUP (1) when first < pos and JTK_SEEN_FREQUENT (2) when min_count > 0 and count >= min_count.  Outputs are
+ *   written only with QUERY.  Streaming a corpus in order with ADD | QUERY keeps the first occurrence; ADD over everything and
+ *   then QUERY over everything gives the same answer in any batch order, and is how every copy of a frequent line is dropped.
+ *   JTK_SEEN_NO_COMBINE (4) in the mode changes no result: the add then sends every unit to memory on its own instead of merging
+ *   equal keys inside a workgroup first (for measuring what the merge saves).
+ *   Results.  Per unit, in document order then text order: begin, end (batch byte positions), first, count, flag.  Per document:
+ *   unit_off [n_docs + 1]; n_dup, dup_bytes, dup_chars over the DUP-flagged units; unit_bytes, unit_chars over all units.  chars
+ *   as for jtk_batch_line_repeats.
+ * jtk_seen_set_create: an empty set on enc's device.  A set belongs to `enc` (which must outlive it), takes batches of that
+ *   encoding object only and holds no reference to any batch.  Calls on one set are not thread-safe; calls that queue work are
+ *   ordered behind the set's earlier ones, whatever their streams.
+ * jtk_seen_set_destroy: waits for the set's queued work; NULL is allowed.
+ * jtk_seen_set_size: the number of distinct keys and the capacity (either may be NULL); waits for the set's queued work.
+ * jtk_seen_set_entries: the n_keys entries into HOST arrays keys / first / count [cap], in no particular order; cap < n_keys is
+ *   JTK_ERR_INVALID_ARGUMENT.  Waits.
+ * jtk_seen_set_add_entries: merges n entries from HOST arrays -- the jtk_seen_set_entries of a saved set or of another shard's --
+ *   by (min, +).  n < 0, a NULL array with n > 0 and a key of 0 are JTK_ERR_INVALID_ARGUMENT (the set is then unchanged).  Waits.
+ * jtk_batch_seen_mark: works on the LAST batch encode on `b` under the conditions of jtk_batch_line_units.  Every pointer of
+ *   `out` (which may itself be NULL) is device memory, may be NULL and is then not written; int32 arrays 4-byte aligned, 64-bit
+ *   arrays 8-byte aligned (JTK_ERR_INVALID_ARGUMENT otherwise).  *n_units (may be NULL) = the units of the batch.  The per-unit
+ *   arrays need n_units elements: a caller that does not know the number marks with JTK_SEEN_ADD alone first, or with every
+ *   per-unit pointer NULL, and reads it; a second call on the same encode with the same set parameters and doc_index_base reuses
+ *   the units the first one found (56 bytes per unit and the scratch of jtk_batch_line_units, kept in the batch apart from the
+ *   list of jtk_batch_line_units, which is untouched).  Waits for the unit count, then for the largest unit count of a document and
+ *   the set's key count; the add and the query are queued on stream_or_null (the batch's stream when NULL) behind the encode and
+ *   the set's earlier work, and the call does not wait for them.  A NULL set, a set of another encoding object than the batch's,
+ *   mode 0 or unknown mode bits, and a batch without an encode are JTK_ERR_INVALID_ARGUMENT; a refused call and one that returns
+ *   JTK_ERR_OUT_OF_MEMORY (the growth included) leave the set as it was. */
+#define JTK_SEEN_LINE 0
+#define JTK_SEEN_PARAGRAPH 1
+#define JTK_SEEN_DOCUMENT 2
+#define JTK_SEEN_TRIM 2u
+#define JTK_SEEN_ADD 1u
+#define JTK_SEEN_QUERY 2u
+#define JTK_SEEN_NO_COMBINE 4u
+#define JTK_SEEN_DUP 1
+#define JTK_SEEN_FREQUENT 2
+typedef struct jtk_seen_params {
+    uint64_t seed;
+    int32_t unit;           /* JTK_SEEN_LINE, JTK_SEEN_PARAGRAPH or JTK_SEEN_DOCUMENT */
+    uint32_t flags;         /* 0 or JTK_SEEN_TRIM */
+} jtk_seen_params;          /* 16 bytes */
+typedef struct jtk_seen_mark_params {
+    uint64_t doc_index_base;
+    uint64_t min_count;     /* 0: no unit is JTK_SEEN_FREQUENT */
+    uint32_t mode;          /* JTK_SEEN_ADD | JTK_SEEN_QUERY (| JTK_SEEN_NO_COMBINE) */
+    uint32_t reserved;      /* 0 */
+} jtk_seen_mark_params;     /* 24 bytes */
+typedef struct jtk_seen_out {       /* device pointers, each may be NULL and is then not written */
+    int64_t *unit_begin, *unit_end; /* [n_units] */
+    uint64_t *unit_first, *unit_count;  /* [n_units] */
+    uint8_t* unit_flags;            /* [n_units] JTK_SEEN_DUP | JTK_SEEN_FREQUENT */
+    int64_t* unit_off;              /* [n_docs + 1] */
+    int32_t* n_dup;                 /* [n_docs], as are the following */
+    int64_t *dup_bytes, *dup_chars, *unit_bytes, *unit_chars;
+} jtk_seen_out;
+typedef struct jtk_seen_set jtk_seen_set;
+int jtk_seen_set_create(const jtk_encoding* enc, const jtk_seen_params* params, jtk_seen_set** out);
+void jtk_seen_set_destroy(jtk_seen_set* s);
+int jtk_seen_set_size(const jtk_seen_set* s, int64_t* n_keys, int64_t* capacity);
+int jtk_seen_set_entries(const jtk_seen_set* s, uint64_t* keys, uint64_t* first, uint64_t* count, int64_t cap);
+int jtk_seen_set_add_entries(jtk_seen_set* s, const uint64_t* keys, const uint64_t* first, const uint64_t* count, int64_t n);
+int jtk_batch_seen_mark(jtk_batch* b, jtk_seen_set* s, const jtk_seen_mark_params* params, const jtk_seen_out* out, void* stream_or_null,
+                        int64_t* n_units);
+
 /* Device buffers already resident in HBM (what bench.py times).  `stream_or_null` = a hipStream_t
  * to order against, or NULL for the batch's own stream: the whole encode is ordered like one operation on that stream
  * (inside, the chunks of a large batch run on the batch's own streams, forked from and joined into it).  With

@@ -80,6 +80,15 @@ JTK_LINES_PARAGRAPH = 1
 JTK_LINES_MARK_FIRST = 1
 JTK_LINES_TRIM = 2
 JTK_WORDS_FOLD_ASCII = 1
+JTK_SEEN_LINE = 0
+JTK_SEEN_PARAGRAPH = 1
+JTK_SEEN_DOCUMENT = 2
+JTK_SEEN_TRIM = 2
+JTK_SEEN_ADD = 1
+JTK_SEEN_QUERY = 2
+JTK_SEEN_NO_COMBINE = 4
+JTK_SEEN_DUP = 1
+JTK_SEEN_FREQUENT = 2
 JTK_WD_MAX_STOP = 32
 JTK_WD_MAX_STOP_LEN = 8
 # how jtk_words.hip cuts the text (csrc/jtk_words_rules.h): a lane's granule, a wave, a workgroup's tile, a step of the scan in tiles
@@ -123,6 +132,25 @@ LINES_OUT_FIELDS = ("unit_begin", "unit_end", "unit_flags", "unit_off", "n_dup",
 class LinesOutStruct(C.Structure):
     """jtk_lines_out"""
     _fields_ = [(name, C.c_void_p) for name in LINES_OUT_FIELDS]
+
+
+class SeenParamsStruct(C.Structure):
+    """jtk_seen_params"""
+    _fields_ = [("seed", C.c_uint64), ("unit", C.c_int32), ("flags", C.c_uint32)]
+
+
+class SeenMarkParamsStruct(C.Structure):
+    """jtk_seen_mark_params"""
+    _fields_ = [("doc_index_base", C.c_uint64), ("min_count", C.c_uint64), ("mode", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+SEEN_OUT_FIELDS = ("unit_begin", "unit_end", "unit_first", "unit_count", "unit_flags", "unit_off", "n_dup", "dup_bytes", "dup_chars",
+                   "unit_bytes", "unit_chars")
+
+
+class SeenOutStruct(C.Structure):
+    """jtk_seen_out"""
+    _fields_ = [(name, C.c_void_p) for name in SEEN_OUT_FIELDS]
 
 
 class WordsParamsStruct(C.Structure):
@@ -182,6 +210,12 @@ SIGNATURES = {
     "jtk_batch_line_units": (C.c_int, [_p, C.POINTER(LinesParamsStruct), _p, C.POINTER(_i64)]),
     "jtk_batch_line_repeats": (C.c_int, [_p, C.POINTER(LinesParamsStruct), C.POINTER(LinesOutStruct), _p]),
     "jtk_batch_word_stats": (C.c_int, [_p, C.POINTER(WordsParamsStruct), C.POINTER(WordsOutStruct), _p]),
+    "jtk_seen_set_create": (C.c_int, [_p, C.POINTER(SeenParamsStruct), C.POINTER(_p)]),
+    "jtk_seen_set_destroy": (None, [_p]),
+    "jtk_seen_set_size": (C.c_int, [_p, C.POINTER(_i64), C.POINTER(_i64)]),
+    "jtk_seen_set_entries": (C.c_int, [_p, _p, _p, _p, _i64]),
+    "jtk_seen_set_add_entries": (C.c_int, [_p, _p, _p, _p, _i64]),
+    "jtk_batch_seen_mark": (C.c_int, [_p, _p, C.POINTER(SeenMarkParamsStruct), C.POINTER(SeenOutStruct), _p, C.POINTER(_i64)]),
     "jtk_widen_ids": (C.c_int, [_p, _p, C.c_int, _i64, _i64, _p]),
     "jtk_batch_encode": (C.c_int, [_p, _p, _p, _i64, C.c_uint32, C.POINTER(_i64)]),
     "jtk_batch_encode_pieces": (C.c_int, [_p, _p, _p, _i64, _p, _p, _i64, C.c_uint32, C.POINTER(_i64)]),

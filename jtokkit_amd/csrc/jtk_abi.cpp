@@ -22,6 +22,7 @@
 #include "jtk_decode_rows_rules.h"
 #include "jtk_kernels.h"
 #include "jtk_lines_rules.h"
+#include "jtk_seen_rules.h"
 #include "jtk_words_rules.h"
 #include "jtk_maxtok_rules.h"
 #include "jtk_ngram_rules.h"
@@ -216,6 +217,17 @@ struct jtk_batch {
     jtk_lines_params ln_p{};
     bool have_lines = false;
     hipStream_t ln_stream = nullptr;     // stream of the last call that built or read the list
+    // jtk_batch_seen_mark (jtk_seen.hip): the walk of jtk_lines.hip on buffers of this pass's own -- sn_scratch laid out as
+    // ln_scratch (hdr[1] = the largest unit count of a document), sn_units = ln_units' six arrays and pos per unit.  The units are
+    // the last encode's for sn_p (unit, flags, seed) and sn_base: a new encode drops them, a call with others replaces them.
+    DevBuf sn_scratch, sn_units;
+    Pinned<int64_t> h_sn;
+    JtkLnWork sn{};
+    uint64_t* sn_pos = nullptr;
+    jtk_seen_params sn_p{};
+    uint64_t sn_base = 0;
+    bool have_seen = false;
+    hipStream_t sn_stream = nullptr;     // stream of the last call that built or read the units
     // jtk_batch_word_stats (jtk_words.hip): the two bit planes | sum_word | tile_cf | tile_cb, reused from call to call
     DevBuf wd_scratch;
     hipStream_t wd_stream = nullptr;     // stream of the last word pass: the next one, on another stream, reuses the scratch behind it
@@ -241,7 +253,7 @@ struct jtk_batch {
 static void drop_encode_result(jtk_batch* b) {
     b->have_result = b->have_host_result = b->have_trunc = b->have_chunk = b->have_tiles = b->have_pack = b->have_fim = false;
     b->cp_unit = -1;
-    b->have_lines = false;
+    b->have_lines = b->have_seen = false;
     b->ck_end_level = nullptr;
     b->synced = false;
 }
@@ -2573,7 +2585,7 @@ int jtk_batch_line_units(jtk_batch* b, const jtk_lines_params* p, void* stream_o
     uint8_t* const z = (uint8_t*)b->ln_scratch.p;
     JtkLnWork w{};
     w.text = b->job_text; w.doc_off = b->job_doc_off; w.status = (const int32_t*)b->status.p;
-    w.n_bytes = nb; w.n_docs = nd; w.unit = p->unit; w.flags = p->flags;
+    w.n_bytes = nb; w.n_docs = nd; w.unit = p->unit; w.flags = p->flags; w.thr = jtk_ln_threshold(p->unit);
     lay.place(z, &w);
     // count, the one wait, the list at its exact size, write
     HIP_TRY(hipMemsetAsync(z, 0, 2 * lay.plane, st));
@@ -2658,6 +2670,228 @@ int jtk_batch_line_repeats(jtk_batch* b, const jtk_lines_params* p, const jtk_li
     b->rp_queued = true;
     b->ln_stream = st;
     return JTK_OK;
+}
+
+// ---- exact duplicates across documents and batches (jtk_seen.hip; the rule is jtk_seen_rules.h) ---------------------------------
+// A set lives on its encoding's device and outlives batches; its calls are ordered by `ev` as the n-gram set's are.
+static_assert(sizeof(jtk_seen_params) == 16 && sizeof(jtk_seen_mark_params) == 24 && sizeof(jtk_seen_out) == sizeof(JtkSnOut),
+              "the ABI's structs are the kernels'");
+struct jtk_seen_set {
+    const jtk_encoding* enc = nullptr;
+    jtk_seen_params p{};
+    DevBuf planes;                   // key | count | first, uint64 [capacity] each (jtk_sn_table_at)
+    int64_t capacity = 0;
+    DevBuf d_hdr;                    // uint64: [0] the key count, [1] the cursor of jtk_seen_set_entries
+    Stream own;                      // add_entries and the reads
+    Event ev;
+    JtkSnTable table() const { return jtk_sn_table_at(planes.p, capacity); }
+    uint64_t* hdr() const { return (uint64_t*)d_hdr.p; }
+};
+
+static int sn_wait(const jtk_seen_set* s, hipStream_t st) { HIP_TRY(hipStreamWaitEvent(st, s->ev, 0)); return JTK_OK; }
+static int sn_done(const jtk_seen_set* s, hipStream_t st) { HIP_TRY(hipEventRecord(s->ev, st)); return JTK_OK; }
+
+static void sn_free(jtk_seen_set* s) {
+    if (s->ev) (void)hipEventSynchronize(s->ev);                // (the last call that queued work on the table)
+    delete s;
+}
+
+static hipError_t sn_preset(void* planes, int64_t cap, hipStream_t st) {
+    const hipError_t e = hipMemsetAsync(planes, 0, (size_t)cap * 16, st);                              // key | count
+    return e != hipSuccess ? e : hipMemsetAsync((uint8_t*)planes + (size_t)cap * 16, 0xFF, (size_t)cap * 8, st);   // first
+}
+
+// room for m more keys beside c, by the capacity rule; larger planes are filled from the old ones -- every live slot re-added as
+// an entry, the code path of add_entries -- on `st`, which is waited for.  A failure leaves the set as it was.
+static int sn_reserve(jtk_seen_set* s, int64_t c, int64_t m, hipStream_t st) {
+    const int64_t cap = jtk_sn_capacity(c, m);
+    if (cap <= s->capacity) return JTK_OK;
+    DevBuf grown;
+    hipError_t e = grown.alloc((size_t)cap * JTK_SN_SLOT_BYTES);
+    if (e != hipSuccess) return fail(JTK_ERR_OUT_OF_MEMORY, std::string("hipMalloc (seen table): ") + hipGetErrorString(e));
+    e = sn_preset(grown.p, cap, st);
+    if (e == hipSuccess) {
+        const JtkSnTable old = s->table();
+        jtk_launch_seen_add(old.key, old.first, old.count, s->capacity, jtk_sn_table_at(grown.p, cap), nullptr, true, st);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) return fail(JTK_ERR_HIP, std::string("seen table growth: ") + hipGetErrorString(e));
+    s->planes = std::move(grown);    // (frees the old planes: the add that read them is done)
+    s->capacity = cap;
+    return JTK_OK;
+}
+
+int jtk_seen_set_create(const jtk_encoding* enc, const jtk_seen_params* p, jtk_seen_set** out) {
+    if (!enc || !p || !out) return fail(JTK_ERR_INVALID_ARGUMENT, "enc, params or out is NULL");
+    if (!jtk_sn_params_ok(p->unit, p->flags))
+        return fail(JTK_ERR_INVALID_ARGUMENT, "seen set: unit JTK_SEEN_LINE, JTK_SEEN_PARAGRAPH or JTK_SEEN_DOCUMENT, flags 0 or JTK_SEEN_TRIM");
+    HIP_TRY(hipSetDevice(enc->device));
+    jtk_seen_set* s = new (std::nothrow) jtk_seen_set();
+    if (!s) return fail(JTK_ERR_OUT_OF_MEMORY, "out of host memory");
+    s->enc = enc;
+    s->p = *p;
+    s->capacity = jtk_sn_capacity(0, 0);
+    hipError_t e = s->own.create();
+    if (e == hipSuccess) e = s->ev.create();
+    if (e == hipSuccess) e = s->planes.alloc((size_t)s->capacity * JTK_SN_SLOT_BYTES);
+    if (e == hipSuccess) e = s->d_hdr.alloc(16);
+    if (e == hipSuccess) e = sn_preset(s->planes.p, s->capacity, s->own);
+    if (e == hipSuccess) e = hipMemsetAsync(s->d_hdr.p, 0, 16, s->own);
+    if (e == hipSuccess) e = hipEventRecord(s->ev, s->own);
+    if (e != hipSuccess) {
+        sn_free(s);
+        return fail(e == hipErrorOutOfMemory ? JTK_ERR_OUT_OF_MEMORY : JTK_ERR_HIP, std::string("jtk_seen_set_create: ") + hipGetErrorString(e));
+    }
+    *out = s;
+    return JTK_OK;
+}
+
+void jtk_seen_set_destroy(jtk_seen_set* s) {
+    if (!s) return;
+    (void)hipSetDevice(s->enc->device);
+    sn_free(s);
+}
+
+int jtk_seen_set_size(const jtk_seen_set* s, int64_t* n_keys, int64_t* capacity) {
+    if (!s) return fail(JTK_ERR_INVALID_ARGUMENT, "the seen set is NULL");
+    HIP_TRY(hipSetDevice(s->enc->device));
+    if (n_keys) {
+        int rc;
+        if ((rc = sn_wait(s, s->own))) return rc;
+        HIP_TRY(hipMemcpyAsync(n_keys, s->hdr(), 8, hipMemcpyDeviceToHost, s->own));
+        HIP_TRY(hipStreamSynchronize(s->own));
+    }
+    if (capacity) *capacity = s->capacity;
+    return JTK_OK;
+}
+
+int jtk_seen_set_entries(const jtk_seen_set* s, uint64_t* keys, uint64_t* first, uint64_t* count, int64_t cap) {
+    int64_t c = 0;
+    int rc;
+    if ((rc = jtk_seen_set_size(s, &c, nullptr))) return rc;
+    if (cap < c) return fail(JTK_ERR_INVALID_ARGUMENT, "the arrays have room for fewer than n_keys entries");
+    if (c == 0) return JTK_OK;
+    if (!keys || !first || !count) return fail(JTK_ERR_INVALID_ARGUMENT, "keys, first or count is NULL");
+    DevBuf tmp;                                                  // (the compacted entries, for this call)
+    if ((rc = tmp.ensure((size_t)c * 24))) return rc;
+    uint64_t* const d = (uint64_t*)tmp.p;
+    HIP_TRY(hipMemsetAsync(s->hdr() + 1, 0, 8, s->own));
+    jtk_launch_seen_entries(s->table(), d, d + c, d + 2 * c, c, s->hdr() + 1, s->own);
+    HIP_TRY(hipGetLastError());
+    int64_t n = 0;
+    HIP_TRY(hipMemcpyAsync(&n, s->hdr() + 1, 8, hipMemcpyDeviceToHost, s->own));
+    HIP_TRY(hipMemcpyAsync(keys, d, (size_t)c * 8, hipMemcpyDeviceToHost, s->own));
+    HIP_TRY(hipMemcpyAsync(first, d + c, (size_t)c * 8, hipMemcpyDeviceToHost, s->own));
+    HIP_TRY(hipMemcpyAsync(count, d + 2 * c, (size_t)c * 8, hipMemcpyDeviceToHost, s->own));
+    HIP_TRY(hipStreamSynchronize(s->own));
+    if (n != c) return fail(JTK_ERR_HIP, "the seen table does not hold the number of keys it counts");
+    return sn_done(s, s->own);
+}
+
+int jtk_seen_set_add_entries(jtk_seen_set* s, const uint64_t* keys, const uint64_t* first, const uint64_t* count, int64_t n) {
+    if (!s) return fail(JTK_ERR_INVALID_ARGUMENT, "the seen set is NULL");
+    if (n < 0) return fail(JTK_ERR_INVALID_ARGUMENT, "n must not be negative");
+    if (n > 0 && (!keys || !first || !count)) return fail(JTK_ERR_INVALID_ARGUMENT, "keys, first or count is NULL");
+    for (int64_t i = 0; i < n; i++)
+        if (keys[i] == 0) return fail(JTK_ERR_INVALID_ARGUMENT, "a key of 0 cannot be in a seen set (0 is the empty slot)");
+    if (n == 0) return JTK_OK;
+    HIP_TRY(hipSetDevice(s->enc->device));
+    int rc;
+    if ((rc = sn_wait(s, s->own))) return rc;
+    DevBuf tmp;                                                  // (staging that lives for this call)
+    if ((rc = tmp.ensure((size_t)n * 24))) return rc;
+    uint64_t* const d = (uint64_t*)tmp.p;
+    HIP_TRY(hipMemcpyAsync(d, keys, (size_t)n * 8, hipMemcpyHostToDevice, s->own));
+    HIP_TRY(hipMemcpyAsync(d + n, first, (size_t)n * 8, hipMemcpyHostToDevice, s->own));
+    HIP_TRY(hipMemcpyAsync(d + 2 * n, count, (size_t)n * 8, hipMemcpyHostToDevice, s->own));
+    int64_t c = 0;
+    HIP_TRY(hipMemcpyAsync(&c, s->hdr(), 8, hipMemcpyDeviceToHost, s->own));
+    HIP_TRY(hipStreamSynchronize(s->own));
+    if ((rc = sn_reserve(s, c, n, s->own))) return rc;
+    jtk_launch_seen_add(d, d + n, d + 2 * n, n, s->table(), s->hdr(), true, s->own);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s->own));
+    return sn_done(s, s->own);
+}
+
+// the units of the last encode for the set's parameters and `base` into the batch's sn_* buffers, on st; *n = their number
+static int sn_units(jtk_batch* b, const jtk_seen_set* s, uint64_t base, hipStream_t st, int64_t* n_out) {
+    const int64_t nd = b->job_docs, nb = b->job_bytes;
+    int rc;
+    if ((rc = ck_order(b, b->last_stream, st))) return rc;
+    if (b->sn_stream && (rc = ck_order(b, b->sn_stream, st))) return rc;
+    if (b->have_seen && b->sn_p.unit == s->p.unit && b->sn_p.flags == s->p.flags && b->sn_p.seed == s->p.seed && b->sn_base == base) {
+        *n_out = b->sn.n_units;
+        return JTK_OK;
+    }
+    b->have_seen = false;
+    const LnLayout lay(jtk_lines_tiles(nb), nd);
+    if ((rc = b->sn_scratch.ensure(lay.total)) || (rc = b->h_sn.ensure(16))) return rc;
+    uint8_t* const z = (uint8_t*)b->sn_scratch.p;
+    JtkLnWork w{};
+    w.text = b->job_text; w.doc_off = b->job_doc_off; w.status = (const int32_t*)b->status.p;
+    w.n_bytes = nb; w.n_docs = nd; w.unit = s->p.unit; w.flags = s->p.flags; w.thr = jtk_sn_threshold(s->p.unit);
+    lay.place(z, &w);
+    HIP_TRY(hipMemsetAsync(z, 0, 2 * lay.plane, st));
+    HIP_TRY(hipMemsetAsync(w.hdr, 0, 16, st));
+    jtk_launch_lines_count(w, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(b->h_sn.p, w.hdr, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    const int64_t n = b->h_sn.p[0];
+    if (n < 0 || n > nb) return fail(JTK_ERR_HIP, "the unit count of the text is outside [0, n_bytes]");
+    if ((rc = b->sn_units.ensure((size_t)n * (JTK_LN_UNIT_BYTES + 8) + 16))) return rc;
+    int64_t* const u8 = (int64_t*)b->sn_units.p;
+    w.n_units = n;
+    w.u_begin = u8; w.u_end = u8 + n; w.u_k = (uint64_t*)(u8 + 2 * n); w.u_chars = u8 + 3 * n; w.u_pe = (uint64_t*)(u8 + 4 * n); w.u_ce = u8 + 5 * n;
+    b->sn_pos = (uint64_t*)(u8 + 6 * n);
+    jtk_launch_lines_walk(w, st);
+    jtk_launch_seen_keys(w, jtk_sn_key(s->p.seed, s->p.unit), base, b->sn_pos, w.hdr + 1, st);
+    HIP_TRY(hipGetLastError());
+    b->sn = w; b->sn_p = s->p; b->sn_base = base; b->sn_stream = st;
+    *n_out = n;
+    return JTK_OK;
+}
+
+int jtk_batch_seen_mark(jtk_batch* b, jtk_seen_set* s, const jtk_seen_mark_params* p, const jtk_seen_out* out, void* stream_or_null,
+                        int64_t* n_units) {
+    if (n_units) *n_units = 0;
+    if (!s) return fail(JTK_ERR_INVALID_ARGUMENT, "the seen set is NULL");
+    int rc;
+    if ((rc = need_encode(b, NEED_TEXT_POS))) return rc;
+    if (b->enc != s->enc) return fail(JTK_ERR_INVALID_ARGUMENT, "the batch belongs to another encoding object than the seen set");
+    if (!p) return fail(JTK_ERR_INVALID_ARGUMENT, "params is NULL");
+    if (!jtk_sn_mode_ok(p->mode)) return fail(JTK_ERR_INVALID_ARGUMENT, "seen mark: mode out of JTK_SEEN_ADD | JTK_SEEN_QUERY, at least one of them");
+    const int64_t nd = b->job_docs;
+    if (!jtk_sn_docs_ok(p->doc_index_base, nd)) return fail(JTK_ERR_INVALID_ARGUMENT, "seen mark: doc_index_base + n_docs must not exceed 2^40");
+    JtkSnOut o{};
+    if (out) memcpy(&o, out, sizeof o);
+    if (((uintptr_t)o.n_dup & 3u) || ((uintptr_t)o.unit_begin & 7u) || ((uintptr_t)o.unit_end & 7u) || ((uintptr_t)o.unit_first & 7u) ||
+        ((uintptr_t)o.unit_count & 7u) || ((uintptr_t)o.unit_off & 7u) || ((uintptr_t)o.dup_bytes & 7u) || ((uintptr_t)o.dup_chars & 7u) ||
+        ((uintptr_t)o.unit_bytes & 7u) || ((uintptr_t)o.unit_chars & 7u))
+        return fail(JTK_ERR_INVALID_ARGUMENT, "unaligned array (4-byte n_dup, 8-byte 64-bit arrays)");
+    if (nd <= 0) return JTK_OK;                                  // (no document: no unit, nothing to add and nothing to write)
+    HIP_TRY(hipSetDevice(b->enc->device));
+    hipStream_t st = pick_stream(b, stream_or_null);
+    int64_t n = 0;
+    if ((rc = sn_units(b, s, p->doc_index_base, st, &n)) || (rc = sn_wait(s, st))) return rc;
+    // the second wait: the largest unit count of a document and the set's key count, before anything touches the set
+    const JtkLnWork& w = b->sn;
+    HIP_TRY(hipMemcpyAsync(b->h_sn.p, w.hdr + 1, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(b->h_sn.p + 1, s->hdr(), 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (b->h_sn.p[0] > JTK_SN_MAX_DOC_UNITS) return fail(JTK_ERR_INVALID_ARGUMENT, "seen mark: a document of more than 2^24 units");
+    b->have_seen = true;
+    if (n_units) *n_units = n;
+    if ((p->mode & JTK_SEEN_ADD) && n > 0) {
+        if ((rc = sn_reserve(s, b->h_sn.p[1], n, st))) return rc;
+        jtk_launch_seen_add(w.u_k, b->sn_pos, nullptr, n, s->table(), s->hdr(), !(p->mode & JTK_SEEN_NO_COMBINE), st);
+    }
+    if ((p->mode & JTK_SEEN_QUERY) && out) jtk_launch_seen_query(w, b->sn_pos, p->doc_index_base, s->table(), p->min_count, o, st);
+    HIP_TRY(hipGetLastError());
+    b->sn_stream = st;
+    return sn_done(s, st);
 }
 
 // ---- word-level quality signals (jtk_words.hip; the rule is jtk_words_rules.h) --------------------------------------------------

@@ -182,6 +182,42 @@ public:
         check(jtk_batch_word_stats(batch_, &params, &out, stream));
     }
 
+    // exact duplicates across documents and batches (the rule is in jtokkit_amd.h): a set of this encoding -- units seen so far,
+    // with the first position and the count of each --, freed before the Encoding; seenMark adds the units of the last
+    // encodeBatch's text to it and / or writes what `out` asks for into device arrays, and returns the number of units
+    class SeenSet {
+    public:
+        SeenSet(Encoding& enc, int32_t unit, uint32_t flags = 0, uint64_t seed = 0) {
+            const jtk_seen_params p{seed, unit, flags};
+            check(jtk_seen_set_create(enc.enc_, &p, &set_));
+        }
+        ~SeenSet() { jtk_seen_set_destroy(set_); }
+        SeenSet(const SeenSet&) = delete;
+        SeenSet& operator=(const SeenSet&) = delete;
+        int64_t size(int64_t* capacity = nullptr) const {
+            int64_t n = 0;
+            check(jtk_seen_set_size(set_, &n, capacity));
+            return n;
+        }
+        void entries(std::vector<uint64_t>& keys, std::vector<uint64_t>& first, std::vector<uint64_t>& count) const {
+            const size_t n = (size_t)size();
+            keys.resize(n); first.resize(n); count.resize(n);
+            check(jtk_seen_set_entries(set_, keys.data(), first.data(), count.data(), (int64_t)n));
+        }
+        void addEntries(const std::vector<uint64_t>& keys, const std::vector<uint64_t>& first, const std::vector<uint64_t>& count) {
+            if (first.size() != keys.size() || count.size() != keys.size()) throw IllegalArgumentException("keys, first and count must have one length");
+            check(jtk_seen_set_add_entries(set_, keys.data(), first.data(), count.data(), (int64_t)keys.size()));
+        }
+        jtk_seen_set* handle() const { return set_; }
+    private:
+        jtk_seen_set* set_ = nullptr;
+    };
+    int64_t seenMark(SeenSet& set, const jtk_seen_mark_params& params, const jtk_seen_out* out = nullptr, void* stream = nullptr) {
+        int64_t n = 0;
+        check(jtk_batch_seen_mark(batch_, set.handle(), &params, out, stream, &n));
+        return n;
+    }
+
     // batch decodeBytes: token lists back to back in `ids`, n+1 offsets -> bytes back to back + n+1 byte offsets + status
     void decodeBatch(const int32_t* ids, const std::vector<int64_t>& seqOff, std::string& bytes,
                      std::vector<int64_t>& byteOff, std::vector<int32_t>& status) {

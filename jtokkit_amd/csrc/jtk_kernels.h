@@ -469,6 +469,7 @@ struct JtkLnWork {
     int64_t n_bytes, n_docs, n_units;
     int32_t unit;
     uint32_t flags;
+    uint32_t thr;                  // newlines between two ink bytes from which on the second starts a unit (jtk_ln_threshold(unit))
     uint32_t *edge, *ref;
     uint32_t *sum_word, *sum_units, *sum_chars;
     uint64_t* sum_hash;
@@ -493,15 +494,41 @@ struct JtkLnOut {                  // jtk_lines_out of include/jtokkit_amd.h
     int64_t* top_first;
 };
 //   count         the planes, pass A and pass B: hdr[0] = the units of the batch
-//   write         pass C, unit_off / char_off and every unit's k and chars (n_units as counted)
+//   walk          pass C and unit_off / char_off (n_units as counted): per unit begin, end and, at both ends, P and the chars before
+//   write         walk, then every unit's k and chars
 //   preset        the per-document sums and top = 0; unit_off and doc_chars out of the batch's arrays
 //   group         the two passes over the units [lo, hi) of a group of whole documents, with a table preset by the caller
 int64_t jtk_lines_tiles(int64_t n_bytes);
 void jtk_launch_lines_count(const JtkLnWork& w, hipStream_t s);
+void jtk_launch_lines_walk(const JtkLnWork& w, hipStream_t s);
 void jtk_launch_lines_write(const JtkLnWork& w, uint64_t seed, uint64_t doc_index_base, hipStream_t s);
 void jtk_launch_lines_preset(const JtkLnWork& w, const JtkLnOut& o, uint64_t* top, hipStream_t s);
 void jtk_launch_lines_group(const JtkLnWork& w, uint32_t flags, const JtkRpTable& t, int64_t lo, int64_t hi, const JtkLnOut& o, uint64_t* top,
                             hipStream_t s);
+// Exact duplicates across documents and batches (jtk_seen.hip; the rule and the table are jtk_seen_rules.h).  The units come from
+// jtk_launch_lines_count and jtk_launch_lines_walk on a JtkLnWork of the pass's own, with thr = jtk_sn_threshold(unit).
+//   keys          every unit's unsalted k and chars (as jtk_launch_lines_write leaves them), u_pos [n_units], and *max_doc_units
+//                 (preset to 0 by the caller) = the largest number of units of one document
+//   add           n entries (keys, first, count; count NULL: 1 each; key 0 skipped, so old planes can be given: the rehash) merged
+//                 into the table by (min, +); *n_keys (may be NULL) += the keys that were new.  combine: merge inside the workgroup
+//                 in LDS first
+//   query         every unit against the table: what `o` asks for; two kernels
+//   entries       the live slots into keys / first / count [cap] behind *cursor (preset to 0 by the caller), in no particular order
+struct JtkSnTable;
+struct JtkSnOut {                  // jtk_seen_out of include/jtokkit_amd.h
+    int64_t *unit_begin, *unit_end;
+    uint64_t *unit_first, *unit_count;
+    uint8_t* unit_flags;
+    int64_t* unit_off;
+    int32_t* n_dup;
+    int64_t *dup_bytes, *dup_chars, *unit_bytes, *unit_chars;
+};
+void jtk_launch_seen_keys(const JtkLnWork& w, uint64_t key, uint64_t doc_index_base, uint64_t* u_pos, int64_t* max_doc_units, hipStream_t s);
+void jtk_launch_seen_add(const uint64_t* keys, const uint64_t* first, const uint64_t* count_or_null, int64_t n, const JtkSnTable& t,
+                         uint64_t* n_keys_or_null, bool combine, hipStream_t s);
+void jtk_launch_seen_query(const JtkLnWork& w, const uint64_t* u_pos, uint64_t doc_index_base, const JtkSnTable& t, uint64_t min_count,
+                           const JtkSnOut& o, hipStream_t s);
+void jtk_launch_seen_entries(const JtkSnTable& t, uint64_t* keys, uint64_t* first, uint64_t* count, int64_t cap, uint64_t* cursor, hipStream_t s);
 // Word-level quality signals (jtk_words.hip; the rule and the way the text is walked are jtk_words_rules.h).  edge / ref: the two
 // bit planes of jtk_lines_rules.h, preset to 0; sum_word: pass A's summary per tile; tile_cf / tile_cb: pass B's carries per tile,
 // forward (the L-or-N state, the dot carry << 3) and backward (L-or-N, L << 1).

@@ -94,7 +94,7 @@ __global__ void __launch_bounds__(LN_THREADS) k_ln_tile(JtkLnWork w) {
     const int64_t g = tile * JTK_LN_TILE_GRANULES + tid, g0 = g * JTK_LN_GRANULE;
     const int64_t left = w.n_bytes - g0;
     const int valid = left >= JTK_LN_GRANULE ? JTK_LN_GRANULE : left > 0 ? (int)left : 0;
-    const uint32_t thr = jtk_ln_threshold(w.unit);
+    const uint32_t thr = w.thr;
 
     uint32_t x[4] = {0, 0, 0, 0};
     if (valid > 0) {                                             // (the text is readable up to the next multiple of 16)
@@ -191,7 +191,7 @@ __global__ void __launch_bounds__(SCAN_THREADS) k_ln_scan(JtkLnWork w, int64_t n
     __shared__ uint32_t s_t[SCAN_THREADS / 64], s_state;
     __shared__ uint64_t s_u[SCAN_THREADS / 64], s_c[SCAN_THREADS / 64], s_h[SCAN_THREADS / 64], s_base[3];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const uint32_t thr = jtk_ln_threshold(w.unit);
+    const uint32_t thr = w.thr;
     const int64_t n_steps = (n_tiles + JTK_LN_SCAN_STEP - 1) / JTK_LN_SCAN_STEP;
     if (tid == 0) { s_state = JTK_LN_NOINK; s_base[0] = s_base[1] = s_base[2] = 0; }
     __syncthreads();
@@ -371,10 +371,14 @@ void jtk_launch_lines_count(const JtkLnWork& w, hipStream_t s) {
     hipLaunchKernelGGL(k_ln_scan, dim3(1), dim3(SCAN_THREADS), 0, s, w, n_tiles);
 }
 
-void jtk_launch_lines_write(const JtkLnWork& w, uint64_t seed, uint64_t doc_index_base, hipStream_t s) {
+void jtk_launch_lines_walk(const JtkLnWork& w, hipStream_t s) {
     const int64_t n_tiles = jtk_lines_tiles(w.n_bytes);
     if (n_tiles > 0) hipLaunchKernelGGL(k_ln_tile<true>, dim3((unsigned)n_tiles), dim3(LN_THREADS), 0, s, w);
     hipLaunchKernelGGL(k_ln_docs, dim3(strided_blocks(w.n_docs + 1)), dim3(256), 0, s, w);
+}
+
+void jtk_launch_lines_write(const JtkLnWork& w, uint64_t seed, uint64_t doc_index_base, hipStream_t s) {
+    jtk_launch_lines_walk(w, s);
     if (w.n_units > 0)
         hipLaunchKernelGGL(k_ln_keys, dim3(jtk_blocks_for(w.n_units, 256)), dim3(256), 0, s, w, jtk_ln_key(seed, w.unit), doc_index_base);
 }

@@ -176,6 +176,11 @@ _LINES_PER_DOC = (("n_dup", np.int32), ("dup_bytes", np.int64), ("dup_chars", np
                   ("doc_chars", np.int64), ("top_count", np.int32), ("top_first", np.int64))
 
 
+# jtk_seen_out: the arrays per unit and per document, with their element types
+_SEEN_PER_UNIT = (("unit_begin", np.int64), ("unit_end", np.int64), ("unit_first", np.uint64), ("unit_count", np.uint64), ("unit_flags", np.uint8))
+_SEEN_PER_DOC = (("n_dup", np.int32), ("dup_bytes", np.int64), ("dup_chars", np.int64), ("unit_bytes", np.int64), ("unit_chars", np.int64))
+
+
 # Gopher's stop-word test (Rae et al. 2021, table A1): a document keeps at least two of these
 GOPHER_STOP_WORDS = ("the", "be", "to", "of", "and", "that", "have", "with")
 
@@ -537,6 +542,23 @@ class Batch:
             raise TypeError("line_repeats: no output named %s" % ", ".join(sorted(unknown)))
         out = N.LinesOutStruct(**{k: v for k, v in ptrs.items() if v})
         _check(N.lib().jtk_batch_line_repeats(self._h, C.byref(_lines_params(unit, trim, mark_first, seed, doc_index_base)), C.byref(out), stream))
+
+    def seen_mark(self, seen_set, add=True, query=True, doc_index_base=0, min_count=0, stream=None, combine=True, **ptrs):
+        """jtk_batch_seen_mark of the last encode's text against a SeenSet: adds the batch's units (add), then reads every unit's
+        entry (query) into device pointers by the field names of jtk_seen_out (unit_begin=, unit_end=, unit_first=, unit_count=,
+        unit_flags=, unit_off=, n_dup=, dup_bytes=, dup_chars=, unit_bytes=, unit_chars=), each may be left out or None and is then
+        not written.  Returns the number of units; a second call on the same encode with the same set parameters and
+        doc_index_base reuses the units of the first.  combine=False: the add merges nothing inside a workgroup (for measuring).
+        Waits for the unit counts, not for the passes."""
+        unknown = set(ptrs) - set(N.SEEN_OUT_FIELDS)
+        if unknown:
+            raise TypeError("seen_mark: no output named %s" % ", ".join(sorted(unknown)))
+        mode = (N.JTK_SEEN_ADD if add else 0) | (N.JTK_SEEN_QUERY if query else 0) | (0 if combine else N.JTK_SEEN_NO_COMBINE)
+        p = N.SeenMarkParamsStruct(doc_index_base & 0xFFFFFFFFFFFFFFFF, min_count & 0xFFFFFFFFFFFFFFFF, mode, 0)
+        out = N.SeenOutStruct(**{k: v for k, v in ptrs.items() if v})
+        n = C.c_int64(0)
+        _check(N.lib().jtk_batch_seen_mark(self._h, seen_set._h if seen_set is not None else None, C.byref(p), C.byref(out), stream, C.byref(n)))
+        return n.value
 
     def word_stats(self, stop_words=GOPHER_STOP_WORDS, fold_ascii=False, short_line_chars=0, stream=None, **ptrs):
         """jtk_batch_word_stats of the last encode's text: device pointers by the field names of jtk_words_out (n_words=,
@@ -998,6 +1020,64 @@ class NgramSet:
         out = np.zeros(len(self), dtype=np.uint64)
         _check(N.lib().jtk_ngram_set_keys(self._h, out.ctypes.data if out.size else None, out.size))
         return out
+
+
+class SeenSet:
+    """A device-resident map from the key of a text unit -- a line, a paragraph or a whole document -- to the smallest global
+    position at which it was ever added and to how often (jtk_seen_set; the rule is in include/jtokkit_amd.h), for exact
+    deduplication across documents and batches: HipEncoding.exact_duplicates_batch adds a batch and marks what was seen before.
+    It belongs to its encoding, which must stay open while the set is used, and keeps no reference to any batch."""
+
+    UNITS = {"line": N.JTK_SEEN_LINE, "paragraph": N.JTK_SEEN_PARAGRAPH, "document": N.JTK_SEEN_DOCUMENT}
+
+    def __init__(self, encoding, unit="line", trim=False, seed=0):
+        self.encoding = encoding
+        self.unit = self.UNITS.get(unit, unit)
+        if not isinstance(self.unit, int):
+            raise ValueError('unit must be "line", "paragraph" or "document"')
+        self.trim = bool(trim)
+        self.seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+        p = N.SeenParamsStruct(self.seed, self.unit, N.JTK_SEEN_TRIM if trim else 0)
+        h = C.c_void_p()
+        _check(N.lib().jtk_seen_set_create(encoding._h, C.byref(p), C.byref(h)))
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            N.lib().jtk_seen_set_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:          # (interpreter shutdown: the module's globals may be gone)
+            pass
+
+    def _size(self):
+        n, cap = C.c_int64(0), C.c_int64(0)
+        _check(N.lib().jtk_seen_set_size(self._h, C.byref(n), C.byref(cap)))
+        return n.value, cap.value
+
+    def __len__(self):
+        return self._size()[0]
+
+    @property
+    def capacity(self):
+        """Slots of the device table: the smallest power of two >= max(64, 2 (keys + the units of the largest batch added))."""
+        return self._size()[1]
+
+    def entries(self):
+        """(keys, first, count), uint64 [len(self)] each, in no particular order."""
+        out = [np.zeros(len(self), dtype=np.uint64) for _ in range(3)]
+        _check(N.lib().jtk_seen_set_entries(self._h, *[x.ctypes.data if x.size else None for x in out], out[0].size))
+        return tuple(out)
+
+    def add_entries(self, keys, first, count):
+        """jtk_seen_set_add_entries: the entries() of a saved set, or of another shard's, merged by (min, +); a key of 0 is refused."""
+        arrs = [np.ascontiguousarray(x, dtype=np.uint64) for x in (keys, first, count)]
+        if not arrs[0].size == arrs[1].size == arrs[2].size:
+            raise ValueError("keys, first and count must have one length")
+        _check(N.lib().jtk_seen_set_add_entries(self._h, *[x.ctypes.data if x.size else None for x in arrs], arrs[0].size))
 
 
 class HipEncoding:
@@ -1466,6 +1546,61 @@ class HipEncoding:
         res["unit_off"] = torch.zeros(nd + 1, dtype=torch.int64, device=device)
         res.update({name: torch.empty(nd, dtype=getattr(torch, np.dtype(dt).name), device=device) for name, dt in _LINES_PER_DOC})
         b.line_repeats(unit, trim, mark_first, seed, doc_index_base, stream, **{name: t.data_ptr() for name, t in res.items() if t.numel()})
+        return res
+
+    def seen_set(self, unit="line", trim=False, seed=0):
+        """An empty SeenSet of this encoding: lines, paragraphs or documents seen so far, for exact_duplicates_batch."""
+        return SeenSet(self, unit, trim, seed)
+
+    def exact_duplicates_batch(self, texts, seen_set, add=True, query=True, doc_index_base=0, min_count=0, validate=False):
+        """Units of a list of str/bytes that `seen_set` has seen before (jtk_batch_seen_mark; the rule is in
+        include/jtokkit_amd.h): with add the batch's units go into the set first, with query a dict of numpy arrays by the field
+        names of jtk_seen_out comes back -- unit_begin, unit_end int64 [n_units] (byte positions in the documents back to back),
+        unit_first, unit_count uint64 [n_units] (the entry of the unit's key: all ones and 0 when absent), unit_flags uint8
+        [n_units] (JTK_SEEN_DUP: first < the unit's own position (doc_index_base + d) << 24 | u; JTK_SEEN_FREQUENT: min_count > 0
+        and count >= min_count), unit_off int64 [n + 1], n_dup int32 [n], dup_bytes, dup_chars, unit_bytes, unit_chars int64 [n].
+        Without query: None.  validate: a document that is not well-formed UTF-8 is refused and has no units."""
+        bs, text, doc_off = _join_texts(texts)
+        n = len(bs)
+        self.encode_batch_packed(text, doc_off, True, validate, None)
+        b = self._b()
+        nu = b.seen_mark(seen_set, add, False, doc_index_base) if add or not query else 0
+        if not query:
+            _stream_sync(b.stream())
+            return None
+        with _device_arrays() as put:
+            if not add:
+                nu = b.seen_mark(seen_set, False, True, doc_index_base)          # (nothing asked for: the number of units)
+            outs = {name: put(np.zeros(nu, dtype=dt)) for name, dt in _SEEN_PER_UNIT}
+            outs["unit_off"] = put(np.zeros(n + 1, dtype=np.int64))
+            outs.update({name: put(np.zeros(n, dtype=dt)) for name, dt in _SEEN_PER_DOC})
+            b.seen_mark(seen_set, False, True, doc_index_base, min_count, **{name: x.ptr for name, x in outs.items() if x._arr.size})
+            _stream_sync(b.stream())
+            res = {name: x.fetch() for name, x in outs.items()}
+        return res
+
+    def exact_duplicates_batch_device(self, text, doc_off, seen_set, add=True, query=True, doc_index_base=0, min_count=0, ordinary=True,
+                                      allowed_special=None):
+        """Encodes a device-resident batch (text CUDA torch.uint8, doc_off CUDA torch.int64 [n_docs + 1]), adds its units to
+        `seen_set` (add) and returns what exact_duplicates_batch returns as a dict of CUDA tensors written on
+        torch.cuda.current_stream() (unit_first and unit_count as int64 bit patterns), plus "status" int32 [n_docs]; None without
+        query.  Waits for the unit counts (and, with allowed_special, once more for the encode's count of literal candidates),
+        not for the encode's token count."""
+        import torch
+        if not (add or query):
+            raise ValueError("exact_duplicates_batch_device: add or query")
+        self._check_device_inputs("exact_duplicates_batch_device", ("text", text, torch.uint8), ("doc_off", doc_off, torch.int64))
+        allow = self._allow(self._b(), allowed_special)
+        with self._encode_device_batch(text, doc_off, ordinary, allow) as (b, nd, device, stream):
+            nu = b.seen_mark(seen_set, add, not add, doc_index_base, stream=stream)
+            if not query:
+                return None
+            res = {name: torch.empty(nu, dtype=getattr(torch, np.dtype(dt).name.replace("uint64", "int64")), device=device)
+                   for name, dt in _SEEN_PER_UNIT}
+            res["unit_off"] = torch.zeros(nd + 1, dtype=torch.int64, device=device)
+            res.update({name: torch.zeros(nd, dtype=getattr(torch, np.dtype(dt).name), device=device) for name, dt in _SEEN_PER_DOC})
+            b.seen_mark(seen_set, False, True, doc_index_base, min_count, stream, **{name: t.data_ptr() for name, t in res.items() if t.numel()})
+            res["status"] = self._tok_off_and_status(b, nd, device, stream)[1]
         return res
 
     def word_stats_batch(self, texts, stop_words=GOPHER_STOP_WORDS, fold_ascii=False, short_line_chars=0):
