@@ -903,6 +903,26 @@ enum {
 };
 int jtk_batch_pack(jtk_batch* b, int64_t seq_len, int32_t sep_id, uint32_t flags, void* stream_or_null,
                    int64_t* n_rows, int64_t* n_segments, int32_t* max_seqlen);
+/* Best-fit-decreasing packing of whole documents: fewer rows and less pad than the next-fit of JTK_PACK_WHOLE_DOCS, and no
+ * truncated document (what fine-tuning loaders call "bfd").  The rule (jtokkit_amd/csrc/jtk_pack_fit_rules.h), over the same
+ * units as jtk_batch_pack:
+ *   Pieces       a unit of length l gives floor(l / L) full pieces of L cells and, if l mod L > 0, one rest of l mod L cells.
+ *   Full pieces  in document order, then piece order, each is a row of its own: rows 0 .. F - 1.
+ *   Rests        taken in order of (length descending, document index ascending).  Each goes into the open row with free >=
+ *                its length and the smallest free; among equal free, into the row whose content changed longest ago (the
+ *                smallest sequence number of its last placed rest).  If no row fits it opens the next row: F, F + 1, ... in
+ *                order of opening.  Inside a row the pieces stand in order of placement, then pad.  A document has at most
+ *                one rest, so two pieces of one document never share a row.
+ *   Outputs      segments, positions, cu_seqlens, seg_doc and max_seqlen as for jtk_batch_pack; n_rows = F + opened rows.
+ *   Input:   as jtk_batch_pack; flags: JTK_PACK_SEP_FIRST only; seq_len <= JTK_PACK_FIT_MAX_LEN (the driver keeps one bit per
+ *            free-space class in on-chip memory).  Any violation: JTK_ERR_INVALID_ARGUMENT.
+ *   Order:   as jtk_batch_pack (one wait, for the counts).  The plan REPLACES the batch's pack plan, and a later jtk_batch_pack
+ *            replaces this one: jtk_batch_pack_write, _fetch, _labels and _labels_fetch serve whichever plan is the last.
+ *   Cost:    the placement is serial in the number of (length, row class) groups, not of documents: a few thousand steps per
+ *            million documents of a typical corpus; one step per document when all rests are distinct and longer than L / 2. */
+#define JTK_PACK_FIT_MAX_LEN 262144
+int jtk_batch_pack_best_fit(jtk_batch* b, int64_t seq_len, int32_t sep_id, uint32_t flags, void* stream_or_null,
+                            int64_t* n_rows, int64_t* n_segments, int32_t* max_seqlen);
 /* The packed rows of the last jtk_batch_pack to device memory: d_rows[n_rows * seq_len] int32 (ids, then pad_id),
  * d_positions[n_rows * seq_len] int32, d_cu_seqlens[n_segments + 1] int32, d_seg_doc[n_segments] int64; all but d_rows may
  * be NULL.  Ordered after the plan on stream_or_null (or the batch's stream); does not wait. */

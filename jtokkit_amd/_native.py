@@ -38,6 +38,7 @@ JTK_FIM_SPM = 2
 JTK_PACK_WHOLE_DOCS = 1
 JTK_PACK_SEP_FIRST = 2
 JTK_PACK_DROP_LAST = 4
+JTK_PACK_FIT_MAX_LEN = 262144
 JTK_CUT_WORD = 1
 JTK_CUT_SENTENCE = 2
 JTK_CUT_LINE = 4
@@ -248,6 +249,7 @@ SIGNATURES = {
     "jtk_batch_byte_positions": (C.c_int, [_p, C.c_int, _p, _p, _i64, _p, _p]),
     "jtk_batch_token_char_offsets": (C.c_int, [_p, C.c_int, _p, _p, _p]),
     "jtk_batch_pack": (C.c_int, [_p, _i64, C.c_int32, C.c_uint32, _p, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(C.c_int32)]),
+    "jtk_batch_pack_best_fit": (C.c_int, [_p, _i64, C.c_int32, C.c_uint32, _p, C.POINTER(_i64), C.POINTER(_i64), C.POINTER(C.c_int32)]),
     "jtk_batch_pack_write": (C.c_int, [_p, C.c_int32, _p, _p, _p, _p, _p]),
     "jtk_batch_pack_fetch": (C.c_int, [_p, C.c_int32, _p, _p, _p, _p]),
     "jtk_batch_token_spans": (C.c_int, [_p, _p, _p, _i64, C.c_int, _p, _p]),

@@ -153,6 +153,10 @@ struct jtk_batch {
     JtkPackWork pk{};
     bool have_pack = false;
     hipStream_t pk_stream = nullptr;     // stream of the last pack plan
+    // jtk_batch_pack_best_fit: its plan lives in pk_scratch too and replaces jtk_batch_pack's (pk keeps n_rows, n_seg, L and
+    // the separator for the fetch calls); pk_fit: the plan is this kind, and write and labels go to jtk_pack_fit.hip
+    JtkPackFitWork pf{};
+    bool pk_fit = false;
     // jtk_batch_char_*: the rank / select index over the last encode's text for cp_unit (-1: none; a new encode drops it, a call
     // with another unit rebuilds it): sup [n_sup + 1] | dunit [n_docs + 1] (i64) | superblock totals [n_sup] (u32) | sub (u16)
     DevBuf cp_buf;
@@ -3106,6 +3110,7 @@ int jtk_batch_pack(jtk_batch* b, int64_t seq_len, int32_t sep_id, uint32_t flags
     HIP_TRY(hipSetDevice(b->enc->device));
     hipStream_t s = pick_stream(b, stream_or_null);
     b->have_pack = false;                                              // (this call replaces its own result)
+    b->pk_fit = false;
     int K = 1;
     while (K < 62 && ((int64_t)1 << K) <= n) K++;                      // 2^K > n >= the number of groups
     // scratch: hdr[4] | P | SEG | RS [n + 1] | flag [n] | up [K][n + 1]
@@ -3158,6 +3163,78 @@ int jtk_batch_pack(jtk_batch* b, int64_t seq_len, int32_t sep_id, uint32_t flags
     return JTK_OK;
 }
 
+// Best-fit-decreasing rows (jtk_pack_fit.hip; the rule is jtk_pack_fit_rules.h).  The plan replaces jtk_batch_pack's.
+static_assert(JTK_PACK_FIT_MAX_LEN == JTK_FIT_MAX_LEN, "the rule header's cap is the ABI's");
+int jtk_batch_pack_best_fit(jtk_batch* b, int64_t seq_len, int32_t sep_id, uint32_t flags, void* stream_or_null,
+                            int64_t* n_rows, int64_t* n_segments, int32_t* max_seqlen) {
+    if (!b || !n_rows || !n_segments || !max_seqlen) return fail(JTK_ERR_INVALID_ARGUMENT, "bad arguments");
+    *n_rows = 0; *n_segments = 0; *max_seqlen = 0;
+    int rc;
+    if ((rc = need_encode(b, NEED_IDS))) return rc;
+    if (seq_len < 1) return fail(JTK_ERR_INVALID_ARGUMENT, "seq_len must be at least 1");
+    if (seq_len > JTK_PACK_FIT_MAX_LEN)
+        return fail(JTK_ERR_INVALID_ARGUMENT, "seq_len must not exceed JTK_PACK_FIT_MAX_LEN (" + std::to_string(JTK_PACK_FIT_MAX_LEN) +
+                                                  "): the driver keeps a bit per free-space class on chip");
+    if (sep_id < -1) return fail(JTK_ERR_INVALID_ARGUMENT, "sep_id must be -1 (no separator) or a token id");
+    if (sep_id >= 0 && !pk_known_id(b->enc, sep_id))
+        return fail(JTK_ERR_INVALID_ARGUMENT, "sep_id " + std::to_string(sep_id) + " is neither a rank id nor a special id of the encoding");
+    if (flags & ~(uint32_t)JTK_PACK_SEP_FIRST) return fail(JTK_ERR_INVALID_ARGUMENT, "flags: JTK_PACK_SEP_FIRST");
+    const int64_t n = b->job_docs;
+    if (n >= INT32_MAX / 2) return fail(JTK_ERR_INVALID_ARGUMENT, "too many documents to pack in one call (2^30 - 1 at most)");
+    HIP_TRY(hipSetDevice(b->enc->device));
+    hipStream_t s = pick_stream(b, stream_or_null);
+    b->have_pack = false;                                              // (this call replaces the batch's pack plan)
+    b->pk_fit = false;
+    JtkPackFitWork& w = b->pf;
+    w = JtkPackFitWork{};
+    w.tiles = (n + JTK_FIT_SORT_TILE - 1) / JTK_FIT_SORT_TILE;
+    int bits = 1;
+    while (((int64_t)1 << bits) <= seq_len) bits++;                    // the keys are 1 .. L
+    w.passes = (bits + 7) / 8;
+    // scratch: hdr[8] | FR | DF | ITEM | SEGR [n + 1] | hist [256 tiles + 1] | runs [2 n] | recs [n] | 4-byte arrays [n]: key x 2,
+    // val x 2, dl_len, dl_slot, row_fill, item_doc, item_col | head, tail [L]
+    const size_t m = (size_t)n + 1, nh = 256 * (size_t)w.tiles + 1;
+    const size_t o_hist = 64 + 4 * m * 8, o_runs = o_hist + nh * 8, o_recs = o_runs + 2 * m * sizeof(JtkFitRun);
+    const size_t o_i32 = o_recs + m * sizeof(JtkFitRec), o_cls = o_i32 + 9 * m * 4, bytes = o_cls + 2 * (size_t)seq_len * 4;
+    if ((rc = b->pk_scratch.ensure(bytes)) || (rc = b->h_pk.ensure(64)) || (rc = ck_order(b, b->last_stream, s))) return rc;
+    uint8_t* base = (uint8_t*)b->pk_scratch.p;
+    w.hdr = (int64_t*)base;
+    w.FR = (int64_t*)(base + 64); w.DF = w.FR + m; w.ITEM = w.DF + m; w.SEGR = w.ITEM + m;
+    w.hist = (int64_t*)(base + o_hist);
+    w.runs = (JtkFitRun*)(base + o_runs);
+    w.recs = (JtkFitRec*)(base + o_recs);
+    int32_t* i32 = (int32_t*)(base + o_i32);
+    w.key[0] = (uint32_t*)i32; w.key[1] = (uint32_t*)(i32 + m); w.val[0] = i32 + 2 * m; w.val[1] = i32 + 3 * m;
+    w.dl_len = i32 + 4 * m; w.dl_slot = i32 + 5 * m; w.row_fill = i32 + 6 * m; w.item_doc = i32 + 7 * m; w.item_col = i32 + 8 * m;
+    w.head = (int32_t*)(base + o_cls); w.tail = w.head + seq_len;
+    w.status = (const int32_t*)b->status.p;
+    JtkFitView& v = w.v;
+    v.tokens = (const int32_t*)b->tokens.p; v.tok_off = (const int64_t*)b->tok_off.p;
+    v.FR = w.FR; v.ITEM = w.ITEM; v.SEGR = w.SEGR; v.row_fill = w.row_fill; v.item_doc = w.item_doc; v.item_col = w.item_col;
+    v.n = n; v.L = seq_len; v.F = 0; v.sep_id = sep_id; v.sep_first = (flags & JTK_PACK_SEP_FIRST) != 0 && sep_id >= 0;
+    // plan; the one wait: hdr
+    HIP_TRY(hipMemsetAsync(w.hdr, 0, 64, s));
+    jtk_launch_pack_fit_plan(w, s);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(b->h_pk.p, w.hdr, 64, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    const int64_t* h = b->h_pk.p;
+    const int64_t rows = h[0] + h[4], segs = h[0] + h[7];
+    if (rows > INT32_MAX / seq_len)
+        return fail(JTK_ERR_INVALID_ARGUMENT, "the rows would hold " + std::to_string(rows) + " x " + std::to_string(seq_len) +
+                                                  " cells, more than cu_seqlens (int32) can index (2^31 - 1): split the batch");
+    v.F = h[0];
+    b->pk = JtkPackWork{};
+    b->pk.v.n = n; b->pk.v.L = seq_len; b->pk.v.sep_id = sep_id; b->pk.v.sep_first = v.sep_first; b->pk.v.whole = true;
+    b->pk.n_rows = rows;
+    b->pk.n_seg = segs;
+    b->have_pack = true;
+    b->pk_fit = true;
+    b->pk_stream = s;
+    *n_rows = rows; *n_segments = segs; *max_seqlen = (int32_t)h[3];
+    return JTK_OK;
+}
+
 int jtk_batch_pack_write(jtk_batch* b, int32_t pad_id, int32_t* d_rows, int32_t* d_positions, int32_t* d_cu_seqlens,
                          int64_t* d_seg_doc, void* stream_or_null) {
     if (!b || !b->have_pack) return fail(JTK_ERR_INVALID_ARGUMENT, "jtk_batch_pack has not run on the last encode of this batch");
@@ -3168,7 +3245,8 @@ int jtk_batch_pack_write(jtk_batch* b, int32_t pad_id, int32_t* d_rows, int32_t*
     hipStream_t s = pick_stream(b, stream_or_null);
     int rc;
     if ((rc = ck_order(b, b->pk_stream, s))) return rc;
-    jtk_launch_pack_write(b->pk, pad_id, d_rows, d_positions, d_cu_seqlens, d_seg_doc, s);
+    if (b->pk_fit) jtk_launch_pack_fit_write(b->pf, b->pk.n_rows, b->pk.n_seg, pad_id, d_rows, d_positions, d_cu_seqlens, d_seg_doc, s);
+    else jtk_launch_pack_write(b->pk, pad_id, d_rows, d_positions, d_cu_seqlens, d_seg_doc, s);
     HIP_TRY(hipGetLastError());
     return JTK_OK;
 }
@@ -3227,7 +3305,8 @@ int jtk_batch_pack_labels(jtk_batch* b, const int32_t* d_tok_span_or_null, int32
     if ((rc = ck_order(b, b->pk_stream, s))) return rc;
     JtkLabelView lv;
     lv.tok_span = d_tok_span_or_null; lv.ignore_index = ignore_index; lv.label_sep = (flags & JTK_LABEL_SEP) != 0;
-    jtk_launch_label_pack(b->pk, lv, (flags & JTK_LABEL_SHIFT) != 0, d_labels, s);
+    if (b->pk_fit) jtk_launch_pack_fit_labels(b->pf, b->pk.n_rows, lv, (flags & JTK_LABEL_SHIFT) != 0, d_labels, s);
+    else jtk_launch_label_pack(b->pk, lv, (flags & JTK_LABEL_SHIFT) != 0, d_labels, s);
     HIP_TRY(hipGetLastError());
     return JTK_OK;
 }

@@ -7,6 +7,7 @@
 
 #include "jtk_common.h"
 #include "jtk_pack_rules.h"
+#include "jtk_pack_fit_rules.h"
 #include "jtk_label_rules.h"
 #include "jtk_stage_rules.h"
 #include "jtk_decode_rows_rules.h"
@@ -342,6 +343,38 @@ struct JtkPackWork {
 void jtk_launch_pack_plan(const JtkPackWork& w, hipStream_t s);        // units, scans, groups -> hdr
 void jtk_launch_pack_write(const JtkPackWork& w, int32_t pad_id, int32_t* rows, int32_t* positions, int32_t* cu_seqlens,
                            int64_t* seg_doc, hipStream_t s);           // (needs n_rows, n_seg)
+// Device-side state of jtk_batch_pack_best_fit (jtk_pack_fit.hip): best-fit-decreasing rows by the rule of
+// jtk_pack_fit_rules.h.  Everything points into the batch's pack scratch; the view's arrays are the ones below.
+struct JtkPackFitWork {
+    JtkFitView v;               // (v.F is set after the plan's one wait)
+    const int32_t* status;      // [n] of the last encode
+    int64_t* hdr;               // [0] F, [1] R (rests), [2] distinct rest lengths, [3] the longest segment, [4] rows opened,
+                                // [5] records (the driver's steps), [6] runs, [7] SEGR[n]
+    int64_t* FR;                // [n + 1]
+    int64_t* DF;                // [n + 1] 1 where a sorted slot opens a new rest length; scanned: that length's number
+    int64_t* ITEM;              // [n + 1]
+    int64_t* SEGR;              // [n + 1]
+    int64_t* hist;              // [256][tiles] digit counts of a radix pass, digit-major, scanned in place
+    uint32_t* key[2];           // [n] L - rest (L without one), ping-pong
+    int32_t* val[2];            // [n] the document
+    int32_t* dl_len;            // [distinct] the distinct rest lengths, longest first, and the first sorted slot of each
+    int32_t* dl_slot;
+    int32_t* head;              // [L] the driver's class queues
+    int32_t* tail;
+    JtkFitRun* runs;            // [2 n]
+    JtkFitRec* recs;            // [n]
+    int32_t* row_fill;          // [n]
+    int32_t* item_doc;          // [n]
+    int32_t* item_col;          // [n]
+    int64_t tiles;              // sort tiles of JTK_FIT_SORT_TILE keys
+    int passes;                 // radix passes of 8 bits: the sorted order ends in key[passes & 1]
+};
+#define JTK_FIT_SORT_TILE 1024
+void jtk_launch_pack_fit_plan(const JtkPackFitWork& w, hipStream_t s);  // lengths, sort, driver, rows, expand -> hdr
+void jtk_launch_pack_fit_write(const JtkPackFitWork& w, int64_t n_rows, int64_t n_seg, int32_t pad_id, int32_t* rows,
+                               int32_t* positions, int32_t* cu_seqlens, int64_t* seg_doc, hipStream_t s);
+void jtk_launch_pack_fit_labels(const JtkPackFitWork& w, int64_t n_rows, const JtkLabelView& lv, bool shift, int32_t* labels,
+                                hipStream_t s);
 // Labels (jtk_label.hip; the rule is jtk_label_rules.h).  tok_span[n_tok] of the chunk work's tokens from the spans
 // [begin[i], end[i]), i < n_spans (needs the tiles of jtk_launch_chunk_tiles); labels[n_rows * L] of the pack work's rows.
 void jtk_launch_label_spans(const JtkChunkWork& w, const int64_t* begin, const int64_t* end, int64_t n_spans, int rule,

@@ -110,6 +110,16 @@ def _span_rule(rule):
     return int(rule)
 
 
+def _fit_best(fit, drop_last):
+    """fit= of the pack calls: "next" -> False, "best" -> True (whole documents by best-fit-decreasing: every row is padded,
+    so drop_last does not apply)."""
+    if fit not in ("next", "best"):
+        raise ValueError("fit must be 'next' or 'best', not %r" % (fit,))
+    if fit == "best" and drop_last:
+        raise ValueError("drop_last applies to the concatenated stream only, not to fit='best'")
+    return fit == "best"
+
+
 _UNITS = {"byte": N.JTK_UNIT_BYTE, "utf16": N.JTK_UNIT_UTF16, "char": N.JTK_UNIT_CODEPOINT}
 _ROUNDS = {"floor": N.JTK_CHAR_FLOOR, "ceil": N.JTK_CHAR_CEIL}
 
@@ -709,12 +719,17 @@ class Batch:
         _check(N.lib().jtk_batch_token_cut_levels(self._h, prefer_mask(prefer), d_level_ptr, stream))
 
     # ---- packed training rows (device) -------------------------------------------------------------------
-    def pack(self, seq_len, sep_id=-1, whole_docs=False, sep_first=False, drop_last=False, stream=None):
-        """jtk_batch_pack on the last encode (the rule is in jtk_pack_rules.h).  Returns (n_rows, n_segments, max_seqlen)."""
-        flags = ((N.JTK_PACK_WHOLE_DOCS if whole_docs else 0) | (N.JTK_PACK_SEP_FIRST if sep_first else 0)
-                 | (N.JTK_PACK_DROP_LAST if drop_last else 0))
+    def pack(self, seq_len, sep_id=-1, whole_docs=False, sep_first=False, drop_last=False, stream=None, fit="next"):
+        """jtk_batch_pack on the last encode (the rule is in jtk_pack_rules.h), or with fit="best" jtk_batch_pack_best_fit
+        (best-fit-decreasing of whole documents, jtk_pack_fit_rules.h).  Returns (n_rows, n_segments, max_seqlen)."""
         nr, ns, mx = C.c_int64(0), C.c_int64(0), C.c_int32(0)
-        _check(N.lib().jtk_batch_pack(self._h, int(seq_len), int(sep_id), flags, stream, C.byref(nr), C.byref(ns), C.byref(mx)))
+        if _fit_best(fit, drop_last):
+            pack, flags = N.lib().jtk_batch_pack_best_fit, N.JTK_PACK_SEP_FIRST if sep_first else 0
+        else:
+            pack = N.lib().jtk_batch_pack
+            flags = ((N.JTK_PACK_WHOLE_DOCS if whole_docs else 0) | (N.JTK_PACK_SEP_FIRST if sep_first else 0)
+                     | (N.JTK_PACK_DROP_LAST if drop_last else 0))
+        _check(pack(self._h, int(seq_len), int(sep_id), flags, stream, C.byref(nr), C.byref(ns), C.byref(mx)))
         self._pack = (nr.value, int(seq_len), ns.value)
         return nr.value, ns.value, mx.value
 
@@ -2093,13 +2108,15 @@ class HipEncoding:
 
     def pack_batch(self, texts, seq_len, sep=None, sep_first=False, whole_docs=False, drop_last=False, pad_id=-1, ordinary=False,
                    allowed_special=None, train_spans=None, span_rule="whole", label_shift=False, label_sep=False,
-                   ignore_index=-100, span_unit="byte", fim=None):
+                   ignore_index=-100, span_unit="byte", fim=None, fit="next"):
         """Every text encoded, then packed into rows of seq_len tokens (jtk_batch_pack; the rule is in jtk_pack_rules.h): a dict
         of numpy arrays rows, positions int32 [n_rows, seq_len], cu_seqlens int32 [n_segments + 1], seg_doc int64
         [n_segments], status int32 [n_docs] and max_seqlen (int).  sep: None, a token id or a special-token literal such as
         "<|endoftext|>", after each document (or before it with sep_first).  whole_docs: next-fit of whole documents instead of
         one concatenated stream; drop_last (concat only): omit a partial last row.  Documents with a negative status are left
-        out (they do not raise).
+        out (they do not raise).  fit="best": whole documents by best-fit-decreasing instead of next-fit
+        (jtk_batch_pack_best_fit; the rule is in jtk_pack_fit_rules.h) -- fewer rows, less pad; it implies whole_docs, and with
+        drop_last it raises ValueError.
         train_spans: per text a list of (start, end) byte ranges inside that text, sorted and not overlapping (ValueError
         otherwise; an empty list: nothing of the text is trained on).  The result then also holds labels int32
         [n_rows, seq_len] -- a cell's id where its token lies in a range by span_rule ("whole": entirely inside, "start": its
@@ -2112,6 +2129,7 @@ class HipEncoding:
         fim_part_tok.  Together with train_spans it raises ValueError: a rearranged document has no positions in the text."""
         if fim is not None and train_spans is not None:
             raise ValueError("fim= and train_spans= do not combine: after the transformation tokens have no positions in the text")
+        _fit_best(fit, drop_last)
         su = self._char_unit(span_unit, "pack_batch") if train_spans is not None else None
         bs, text, doc_off = _join_texts(texts)
         sep_id = self._sep_id(sep)
@@ -2123,7 +2141,7 @@ class HipEncoding:
                 self._batch_spans(train_spans, doc_off)                     # (raises: one list per text)
         res = self.encode_batch_packed(text, doc_off, ordinary, False, allowed_special, fim=fim)
         b = self._b()
-        _, _, mx = b.pack(seq_len, sep_id, whole_docs, sep_first, drop_last)
+        _, _, mx = b.pack(seq_len, sep_id, whole_docs, sep_first, drop_last, fit=fit)
         f = b.pack_fetch(pad_id)
         f["status"] = res.status.copy()
         if fim is not None:
@@ -2162,7 +2180,7 @@ class HipEncoding:
 
     def pack_batch_device(self, text, doc_off, seq_len, sep=None, sep_first=False, whole_docs=False, drop_last=False, pad_id=-1,
                           ordinary=False, allowed_special=None, span_begin=None, span_end=None, span_rule="whole",
-                          label_shift=False, label_sep=False, ignore_index=-100, fim=None):
+                          label_shift=False, label_sep=False, ignore_index=-100, fim=None, fit="next"):
         """pack_batch for a device-resident batch.  text: CUDA torch.uint8 tensor, doc_off: CUDA torch.int64 tensor [n_docs + 1],
         on this encoding's device.  Returns a dict of CUDA tensors written on torch.cuda.current_stream(): rows int32
         [n_rows, seq_len], positions int32 [n_rows, seq_len], cu_seqlens int32 [n_segments + 1], seg_doc int64 [n_segments],
@@ -2188,11 +2206,12 @@ class HipEncoding:
             raise ValueError("seq_len must be >= 1")
         if whole_docs and drop_last:
             raise ValueError("drop_last applies to the concatenated stream only")
+        _fit_best(fit, drop_last)
         sep_id = self._sep_id(sep)
         use_fim = self._fim(self._b(), fim, ordinary, allowed_special)
         allow = self._allow(self._b(), allowed_special)
         with self._encode_device_batch(text, doc_off, ordinary, allow, fim=use_fim) as (b, nd, device, stream):
-            nr, ns, mx = b.pack(L, sep_id, whole_docs, sep_first, drop_last, stream)
+            nr, ns, mx = b.pack(L, sep_id, whole_docs, sep_first, drop_last, stream, fit)
             out = dict(rows=torch.empty((nr, L), dtype=torch.int32, device=device),
                        positions=torch.empty((nr, L), dtype=torch.int32, device=device),
                        cu_seqlens=torch.empty(ns + 1, dtype=torch.int32, device=device),
