@@ -505,6 +505,65 @@ typedef struct jtk_words_out {  /* device pointers [n_docs], each may be NULL an
 } jtk_words_out;
 int jtk_batch_word_stats(jtk_batch* b, const jtk_words_params* params, const jtk_words_out* out, void* stream_or_null);
 
+/* Phrase sets: "does this document, or this line, contain one of these strings" -- C4's bad-words list, `lorem ipsum`, `{` and its
+ * line rules (`javascript`, the policy phrases), the blocklists of RefinedWeb, FineWeb and Dolma, a user's own boilerplate, licence
+ * headers and canary strings -- on the TEXT of the last batch encode (jtk_phrase.hip; the rule, bit for bit, is
+ * csrc/jtk_phrase_rules.h; every result is exact).  A set is device-resident and immutable, lives on its encoding's device and
+ * outlives batches.
+ *   Set: n phrases, 0 <= n <= 65,536.  Phrase i is bytes[off[i], off[i + 1]), 1 to 64 bytes long; group[i] is in 0..31 (a NULL
+ *   group array: all 0); the bytes of all phrases are at most 1 MiB.  bytes, off and group are HOST pointers, copied by the call.
+ *   flags out of JTK_PHRASE_FOLD_ASCII (1u) and JTK_PHRASE_WORD_BOUNDS (2u).  Anything else is JTK_ERR_INVALID_ARGUMENT, and no set
+ *   is made.  With FOLD_ASCII 'A'..'Z' of the phrases are folded to 'a'..'z' at create and 'A'..'Z' of the text at match time; no
+ *   other byte changes.  Equal phrases (after folding) are one phrase: its group mask is the OR of 1 << group over them, its index
+ *   the smallest of their indices.  n == 0 is a valid set: every output is 0 and first_* is -1.
+ *   Hit: a pair (p, phrase) in document d = x[a, e) is a hit when a <= p and p + len <= e (nothing crosses a document edge), the
+ *   folded text bytes equal the phrase and, with WORD_BOUNDS, both edges are boundaries: the character that ends at p - 1 is not a
+ *   word character, or p == a; the character that starts at p + len is not a word character, or p + len == e.  A word character is
+ *   '_' or a code point whose class in the library's Unicode tables is L or N.  The previous character is found by stepping back
+ *   over at most three continuation bytes without leaving the document.  The rule is defined for well-formed UTF-8; on ill-formed
+ *   bytes the result is some value and no access leaves the text.  This is Python's (?:\W|^)phrase(?:\W|$) with re.UNICODE, up to
+ *   the tables' Unicode version and the categories Python's \w adds beyond L, N and '_'; no more is claimed.  A document with
+ *   status < 0 has no hits.
+ *   Per document [n_docs]: group_mask, the OR of the hits' group masks; n_hits, the number of hits, one per pair of p and distinct
+ *   phrase, saturated at 2^31 - 1; first_hit, the smallest p - a, or -1; first_which, the smallest phrase index among the hits at
+ *   that p, or -1; n_hit_units, the number of units with a mask that is not 0.
+ *   Per unit [n_units] of the list that jtk_batch_line_units holds on the same encode (any unit, any flags): unit_mask, the OR over
+ *   the hits with begin <= p and p + len <= end.  A hit that straddles a unit's edge belongs to no unit.
+ * jtk_phrase_set_create: builds the tables on the host (two first-byte bitmaps, the trie's edges as an open-addressed table at a
+ *   load of at most 1/2, 16 bytes per state) and uploads them once.  A set belongs to `enc` (which must outlive it), takes batches
+ *   of that encoding object only and holds no reference to any batch.
+ * jtk_phrase_set_destroy: waits for the device's queued work (the passes that read the set, whatever their streams); NULL is allowed.
+ * jtk_phrase_set_size: the distinct phrases and the trie's states, the root included (either may be NULL).
+ * jtk_batch_phrase_hits: works on the LAST batch encode on `b` under the conditions of jtk_batch_char_index: host or device input,
+ *   any flags (JTK_ENCODE_COUNT_ONLY included) but JTK_ENCODE_FIM; not after jtk_batch_encode_pieces or
+ *   jtk_batch_encode_device_max_tokens.  Every pointer of `out` is device memory, may be NULL and is then not written; 32-bit arrays
+ *   4-byte aligned, first_hit 8-byte aligned.  unit_mask or n_hit_units without a held list, a NULL set, a set of another encoding
+ *   object, a misaligned output and the conditions above are JTK_ERR_INVALID_ARGUMENT; a refused call writes nothing.  Scratch: 16
+ *   bytes per document (the packed first hit and a 64-bit hit count) and, for n_hit_units without unit_mask, 4 bytes per unit,
+ *   allocated before anything is written: JTK_ERR_OUT_OF_MEMORY leaves nothing written.  The pass is queued on stream_or_null (the
+ *   batch's stream when NULL) and the call does not wait for it.  It touches no other result of the batch. */
+#define JTK_PHRASE_FOLD_ASCII 1u
+#define JTK_PHRASE_WORD_BOUNDS 2u
+typedef struct jtk_phrase_params {
+    uint32_t flags;             /* JTK_PHRASE_FOLD_ASCII | JTK_PHRASE_WORD_BOUNDS */
+    int32_t n;                  /* 0 .. 65536 */
+    const uint8_t* bytes;       /* host */
+    const uint32_t* off;        /* host, [n + 1] */
+    const uint8_t* group;       /* host, [n], each 0 .. 31; NULL: all 0 */
+} jtk_phrase_params;            /* 32 bytes */
+typedef struct jtk_phrase_out { /* device pointers, each may be NULL and is then not written */
+    uint32_t* group_mask;       /* [n_docs], as are the following four */
+    int32_t* n_hits;
+    int64_t* first_hit;
+    int32_t *first_which, *n_hit_units;
+    uint32_t* unit_mask;        /* [n_units] */
+} jtk_phrase_out;
+typedef struct jtk_phrase_set jtk_phrase_set;
+int jtk_phrase_set_create(const jtk_encoding* enc, const jtk_phrase_params* params, jtk_phrase_set** out);
+void jtk_phrase_set_destroy(jtk_phrase_set* s);
+int jtk_phrase_set_size(const jtk_phrase_set* s, int64_t* n_phrases, int64_t* n_states);
+int jtk_batch_phrase_hits(jtk_batch* b, const jtk_phrase_set* s, const jtk_phrase_out* out, void* stream_or_null);
+
 /* Exact duplicates across documents and batches: CCNet's and Dolma's paragraph dedup, Dolma's document dedup, the "drop lines
  * that occur N times in the crawl" step of RefinedWeb and FineWeb, on the TEXT of batch encodes (jtk_seen.hip; the rule, bit for
  * bit, is csrc/jtk_seen_rules.h -- integer arithmetic only, so every result is exact).  A set lives on its encoding's device,

@@ -97,6 +97,16 @@ JTK_WD_GRANULE = 16
 JTK_WD_WAVE_BYTES = 1024
 JTK_WD_TILE = 4096
 JTK_WD_SCAN_STEP = 1024
+JTK_PHRASE_FOLD_ASCII = 1
+JTK_PHRASE_WORD_BOUNDS = 2
+JTK_PH_MAX_PHRASES = 65536
+JTK_PH_MAX_LEN = 64
+JTK_PH_MAX_BYTES = 1 << 20
+# how jtk_phrase.hip cuts the text (csrc/jtk_phrase_rules.h): a lane's granule of start positions, a workgroup's tile, and the
+# largest edge table (in slots, two per edge) that is staged in LDS
+JTK_PH_GRANULE = 16
+JTK_PH_TILE = 4096
+JTK_PH_LDS_SLOTS = 5120
 
 
 
@@ -174,6 +184,23 @@ class WordsOutStruct(C.Structure):
     _fields_ = [(name, C.c_void_p) for name in WORDS_OUT_FIELDS]
 
 
+class PhraseParamsStruct(C.Structure):
+    """jtk_phrase_params"""
+    _fields_ = [("flags", C.c_uint32), ("n", C.c_int32), ("bytes", C.c_void_p), ("off", C.c_void_p), ("group", C.c_void_p)]
+
+
+# jtk_phrase_out: the field names in order, with their element types; all but the last are per document, the last per unit
+PHRASE_OUT_TYPES = (("group_mask", "uint32"), ("n_hits", "int32"), ("first_hit", "int64"), ("first_which", "int32"), ("n_hit_units", "int32"),
+                    ("unit_mask", "uint32"))
+PHRASE_OUT_FIELDS = tuple(name for name, _ in PHRASE_OUT_TYPES)
+PHRASE_UNIT_FIELDS = ("n_hit_units", "unit_mask")
+
+
+class PhraseOutStruct(C.Structure):
+    """jtk_phrase_out"""
+    _fields_ = [(name, C.c_void_p) for name in PHRASE_OUT_FIELDS]
+
+
 # every symbol include/jtokkit_amd.h declares: (restype, argtypes)
 _p = C.c_void_p
 _i64 = C.c_int64
@@ -211,6 +238,10 @@ SIGNATURES = {
     "jtk_batch_line_units": (C.c_int, [_p, C.POINTER(LinesParamsStruct), _p, C.POINTER(_i64)]),
     "jtk_batch_line_repeats": (C.c_int, [_p, C.POINTER(LinesParamsStruct), C.POINTER(LinesOutStruct), _p]),
     "jtk_batch_word_stats": (C.c_int, [_p, C.POINTER(WordsParamsStruct), C.POINTER(WordsOutStruct), _p]),
+    "jtk_phrase_set_create": (C.c_int, [_p, C.POINTER(PhraseParamsStruct), C.POINTER(_p)]),
+    "jtk_phrase_set_destroy": (None, [_p]),
+    "jtk_phrase_set_size": (C.c_int, [_p, C.POINTER(_i64), C.POINTER(_i64)]),
+    "jtk_batch_phrase_hits": (C.c_int, [_p, _p, C.POINTER(PhraseOutStruct), _p]),
     "jtk_seen_set_create": (C.c_int, [_p, C.POINTER(SeenParamsStruct), C.POINTER(_p)]),
     "jtk_seen_set_destroy": (None, [_p]),
     "jtk_seen_set_size": (C.c_int, [_p, C.POINTER(_i64), C.POINTER(_i64)]),

@@ -27,6 +27,8 @@
 #include "jtk_maxtok_rules.h"
 #include "jtk_ngram_rules.h"
 #include "jtk_owned.h"
+#define JTK_PHRASE_HOST_BUILD
+#include "jtk_phrase_rules.h"
 #include "jtk_repeat_rules.h"
 #include "jtk_tables.h"
 
@@ -235,6 +237,10 @@ struct jtk_batch {
     // jtk_batch_word_stats (jtk_words.hip): the two bit planes | sum_word | tile_cf | tile_cb, reused from call to call
     DevBuf wd_scratch;
     hipStream_t wd_stream = nullptr;     // stream of the last word pass: the next one, on another stream, reuses the scratch behind it
+    // jtk_batch_phrase_hits (jtk_phrase.hip): first | count [n_docs] (uint64 each), then the unit masks [n_units] when the caller
+    // asks for n_hit_units without unit_mask; reused from call to call
+    DevBuf ph_scratch;
+    hipStream_t ph_stream = nullptr;     // stream of the last phrase pass, as wd_stream
     JtkResult* host_result = nullptr;   // host_result_own, or the head of h_small after a small job
     Pinned<JtkResult> host_result_own;
     // the last job
@@ -2992,6 +2998,102 @@ int jtk_batch_word_stats(jtk_batch* b, const jtk_words_params* p, const jtk_word
         b->ln_stream = st;
     }
     HIP_TRY(hipGetLastError());
+    return JTK_OK;
+}
+
+// ---- phrase sets and phrase hits (jtk_phrase.hip; the rule and the host build are jtk_phrase_rules.h) -----------------------------
+// A set lives on its encoding's device, outlives batches and never changes: a pass only reads it, so passes on any number of
+// batches and streams need no order among themselves and the set keeps no event and no stream handle.  Destroy waits for the
+// DEVICE: whatever pass still reads the tables, on whichever stream, is done before they are freed.
+static_assert(sizeof(jtk_phrase_out) == sizeof(JtkPhOut) && sizeof(jtk_phrase_params) == 32, "the ABI's structs are the kernels'");
+struct jtk_phrase_set {
+    const jtk_encoding* enc = nullptr;
+    DevBuf tables;                   // first2 | first1 | edges | info
+    JtkPhSet view{};
+    int64_t n_distinct = 0, n_states = 0;
+};
+
+int jtk_phrase_set_create(const jtk_encoding* enc, const jtk_phrase_params* p, jtk_phrase_set** out) {
+    if (!enc || !p || !out) return fail(JTK_ERR_INVALID_ARGUMENT, "enc, params or out is NULL");
+    JtkPhHostSet h;
+    if (const char* what = jtk_ph_build(p->bytes, p->off, p->group, p->n, p->flags, &h)) return fail(JTK_ERR_INVALID_ARGUMENT, what);
+    HIP_TRY(hipSetDevice(enc->device));
+    jtk_phrase_set* s = new (std::nothrow) jtk_phrase_set();
+    if (!s) return fail(JTK_ERR_OUT_OF_MEMORY, "out of host memory");
+    s->enc = enc;
+    s->n_distinct = h.n_distinct;
+    s->n_states = (int64_t)h.info.size();
+    const size_t b2 = h.first2.size() * 4, b1 = h.first1.size() * 4, be = h.edges.size() * sizeof(JtkPhEdge), bi = h.info.size() * sizeof(JtkPhInfo);
+    hipError_t e = s->tables.alloc(b2 + b1 + be + bi);
+    uint8_t* const z = (uint8_t*)s->tables.p;
+    if (e == hipSuccess) e = hipMemcpy(z, h.first2.data(), b2, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(z + b2, h.first1.data(), b1, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(z + b2 + b1, h.edges.data(), be, hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemcpy(z + b2 + b1 + be, h.info.data(), bi, hipMemcpyHostToDevice);
+    if (e != hipSuccess) {
+        delete s;
+        return fail(e == hipErrorOutOfMemory ? JTK_ERR_OUT_OF_MEMORY : JTK_ERR_HIP, std::string("jtk_phrase_set_create: ") + hipGetErrorString(e));
+    }
+    s->view = JtkPhSet{(const uint32_t*)z, (const uint32_t*)(z + b2), (const JtkPhEdge*)(z + b2 + b1), (const JtkPhInfo*)(z + b2 + b1 + be),
+                       h.n_slots, h.flags, h.has1};
+    *out = s;
+    return JTK_OK;
+}
+
+void jtk_phrase_set_destroy(jtk_phrase_set* s) {
+    if (!s) return;
+    (void)hipSetDevice(s->enc->device);
+    (void)hipDeviceSynchronize();                                // (every pass that reads the tables, whatever its stream)
+    delete s;
+}
+
+int jtk_phrase_set_size(const jtk_phrase_set* s, int64_t* n_phrases, int64_t* n_states) {
+    if (!s) return fail(JTK_ERR_INVALID_ARGUMENT, "the phrase set is NULL");
+    if (n_phrases) *n_phrases = s->n_distinct;
+    if (n_states) *n_states = s->n_states;
+    return JTK_OK;
+}
+
+int jtk_batch_phrase_hits(jtk_batch* b, const jtk_phrase_set* s, const jtk_phrase_out* out, void* stream_or_null) {
+    int rc;
+    if ((rc = need_encode(b, NEED_TEXT_POS))) return rc;
+    if (!s) return fail(JTK_ERR_INVALID_ARGUMENT, "the phrase set is NULL");
+    if (b->enc != s->enc) return fail(JTK_ERR_INVALID_ARGUMENT, "the batch belongs to another encoding object than the phrase set");
+    if (!out) return fail(JTK_ERR_INVALID_ARGUMENT, "out is NULL");
+    JtkPhWork w{};
+    memcpy(&w.out, out, sizeof w.out);
+    const JtkPhOut& o = w.out;
+    if (((uintptr_t)o.group_mask & 3u) || ((uintptr_t)o.n_hits & 3u) || ((uintptr_t)o.first_which & 3u) || ((uintptr_t)o.n_hit_units & 3u) ||
+        ((uintptr_t)o.unit_mask & 3u) || ((uintptr_t)o.first_hit & 7u))
+        return fail(JTK_ERR_INVALID_ARGUMENT, "unaligned array (4-byte 32-bit arrays, 8-byte first_hit)");
+    const bool want_units = o.unit_mask || o.n_hit_units;
+    if (want_units && !b->have_lines)
+        return fail(JTK_ERR_INVALID_ARGUMENT, "no line list of the last encode: call jtk_batch_line_units first");
+    const int64_t nd = b->job_docs, nb = b->job_bytes, nu = want_units ? b->ln.n_units : 0;
+    if (nd <= 0 || !(o.group_mask || o.n_hits || o.first_hit || o.first_which || want_units)) return JTK_OK;
+    HIP_TRY(hipSetDevice(b->enc->device));
+    hipStream_t st = pick_stream(b, stream_or_null);
+    // everything that can fail for lack of memory comes before the first write; a scratch that grows is not in use any more
+    const size_t total = (size_t)nd * 16 + (o.n_hit_units && !o.unit_mask ? (size_t)nu * 4 : 0);
+    if (b->ph_scratch.cap < total && b->ph_stream) HIP_TRY(hipStreamSynchronize(b->ph_stream));
+    if ((rc = b->ph_scratch.ensure(total))) return rc;
+    // behind the encode, behind the last phrase pass (its scratch), behind the list's builder
+    if ((rc = ck_order(b, b->last_stream, st))) return rc;
+    if (b->ph_stream && (rc = ck_order(b, b->ph_stream, st))) return rc;
+    if (want_units && b->ln_stream && (rc = ck_order(b, b->ln_stream, st))) return rc;
+    w.text = b->job_text; w.doc_off = b->job_doc_off; w.status = (const int32_t*)b->status.p;
+    w.n_bytes = nb; w.n_docs = nd; w.n_units = nu; w.uc = b->enc->dt.uc;
+    w.first = (uint64_t*)b->ph_scratch.p; w.count = w.first + nd;
+    if (want_units) {
+        w.unit_off = b->ln.unit_off; w.u_begin = b->ln.u_begin; w.u_end = b->ln.u_end;
+        w.umask = o.unit_mask ? o.unit_mask : (uint32_t*)(w.count + nd);
+    }
+    jtk_launch_phrase_clear(w, st);
+    if (s->n_distinct > 0) jtk_launch_phrase_scan(w, s->view, st);
+    jtk_launch_phrase_close(w, st);
+    HIP_TRY(hipGetLastError());
+    b->ph_stream = st;
+    if (want_units) b->ln_stream = st;
     return JTK_OK;
 }
 

@@ -182,6 +182,35 @@ public:
         check(jtk_batch_word_stats(batch_, &params, &out, stream));
     }
 
+    // phrase hits (the rule is in jtokkit_amd.h): an immutable set of byte strings with a group (0..31) each, of this encoding and
+    // freed before it; phraseHits writes what `out` asks for about the last encodeBatch's text into device arrays (its unit outputs
+    // need a lineUnits call on the same encode)
+    class PhraseSet {
+    public:
+        PhraseSet(Encoding& enc, const std::vector<std::string>& phrases, const std::vector<uint8_t>& groups = {}, uint32_t flags = 0) {
+            if (!groups.empty() && groups.size() != phrases.size()) throw IllegalArgumentException("phrases and groups must have one length");
+            std::string blob;
+            std::vector<uint32_t> off(1, 0);
+            for (const std::string& p : phrases) { blob += p; off.push_back((uint32_t)blob.size()); }
+            const jtk_phrase_params p{flags, (int32_t)phrases.size(), (const uint8_t*)blob.data(), off.data(), groups.empty() ? nullptr : groups.data()};
+            check(jtk_phrase_set_create(enc.enc_, &p, &set_));
+        }
+        ~PhraseSet() { jtk_phrase_set_destroy(set_); }
+        PhraseSet(const PhraseSet&) = delete;
+        PhraseSet& operator=(const PhraseSet&) = delete;
+        int64_t size(int64_t* states = nullptr) const {
+            int64_t n = 0;
+            check(jtk_phrase_set_size(set_, &n, states));
+            return n;
+        }
+        const jtk_phrase_set* handle() const { return set_; }
+    private:
+        jtk_phrase_set* set_ = nullptr;
+    };
+    void phraseHits(const PhraseSet& set, const jtk_phrase_out& out, void* stream = nullptr) {
+        check(jtk_batch_phrase_hits(batch_, set.handle(), &out, stream));
+    }
+
     // exact duplicates across documents and batches (the rule is in jtokkit_amd.h): a set of this encoding -- units seen so far,
     // with the first position and the count of each --, freed before the Encoding; seenMark adds the units of the last
     // encodeBatch's text to it and / or writes what `out` asks for into device arrays, and returns the number of units

@@ -592,6 +592,41 @@ int64_t jtk_words_tiles(int64_t n_bytes);
 void jtk_launch_words_preset(const JtkWdWork& w, const int64_t* unit_off, hipStream_t s);
 void jtk_launch_words_text(const JtkWdWork& w, const JtkWdStops& stops, hipStream_t s);
 void jtk_launch_words_lines(const JtkWdWork& w, const JtkLnWork& ln, int32_t short_line_chars, hipStream_t s);
+// Phrase hits (jtk_phrase.hip; the rule and the tables are jtk_phrase_rules.h).  The set's tables are immutable device memory.
+// first / count: scratch [n_docs], the packed first hit and the hits of a document; umask: unit_mask of the caller, or scratch
+// [n_units] when only n_hit_units is asked for, or NULL when neither is (then unit_off, u_begin and u_end are not read).
+struct JtkPhEdge;
+struct JtkPhInfo;
+struct JtkPhSet {
+    const uint32_t *first2, *first1;
+    const JtkPhEdge* edges;
+    const JtkPhInfo* info;
+    uint32_t n_slots, flags, has1;
+};
+struct JtkPhOut {                  // jtk_phrase_out of include/jtokkit_amd.h
+    uint32_t* group_mask;
+    int32_t* n_hits;
+    int64_t* first_hit;
+    int32_t *first_which, *n_hit_units;
+    uint32_t* unit_mask;
+};
+struct JtkPhWork {
+    const uint8_t* text;
+    const int64_t* doc_off;
+    const int32_t* status;
+    int64_t n_bytes, n_docs, n_units;
+    JtkUcTables uc;
+    const int64_t *unit_off, *u_begin, *u_end;
+    uint64_t *first, *count;
+    uint32_t* umask;
+    JtkPhOut out;
+};
+//   clear         0 into group_mask, n_hit_units, umask and count, "no hit" into first
+//   scan          the hits of every tile of the text, by atomics into group_mask, umask, first and count (not for an empty set)
+//   close         n_hits, first_hit and first_which out of the scratch; n_hit_units out of umask
+void jtk_launch_phrase_clear(const JtkPhWork& w, hipStream_t s);
+void jtk_launch_phrase_scan(const JtkPhWork& w, const JtkPhSet& set, hipStream_t s);
+void jtk_launch_phrase_close(const JtkPhWork& w, hipStream_t s);
 // Device-side state of an allow-special encode (jtk_special.hip, JTK_ENCODE_ALLOW_SPECIAL; the rule is jtk_special_rules.h).
 // Candidates (per position, the longest allowed literal there) are found in position order, resolved to the kept matches, and
 // the batch is cut into sub-documents that partition the text: per document a segment, then per candidate i two slots

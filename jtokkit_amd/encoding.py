@@ -194,6 +194,12 @@ _SEEN_PER_DOC = (("n_dup", np.int32), ("dup_bytes", np.int64), ("dup_chars", np.
 # Gopher's stop-word test (Rae et al. 2021, table A1): a document keeps at least two of these
 GOPHER_STOP_WORDS = ("the", "be", "to", "of", "and", "that", "have", "with")
 
+# C4's phrase rules (Raffel et al. 2020, section 2.2) as (phrase, group) pairs for a PhraseSet with fold_ascii: a LINE is dropped
+# when it holds a policy phrase (group 0) or "javascript" (group 1), a PAGE when it holds "lorem ipsum" (group 2) or a curly
+# bracket (group 3).  The bad-words list is third-party data and is not part of this package.
+C4_PHRASES = (("terms of use", 0), ("privacy policy", 0), ("cookie policy", 0), ("uses cookies", 0), ("use of cookies", 0), ("use cookies", 0),
+              ("javascript", 1), ("lorem ipsum", 2), ("{", 3))
+
 
 def _words_params(stop_words, fold_ascii, short_line_chars):
     """(jtk_words_params, the arrays it points into); stop_words: str or bytes, a str as its UTF-8 bytes."""
@@ -582,6 +588,17 @@ class Batch:
         out = N.WordsOutStruct(**{k: v for k, v in ptrs.items() if v})
         _check(N.lib().jtk_batch_word_stats(self._h, C.byref(p), C.byref(out), stream))
         del keep                                                 # (the call has copied the list)
+
+    def phrase_hits(self, phrase_set, stream=None, **ptrs):
+        """jtk_batch_phrase_hits of the last encode's text against a PhraseSet: device pointers by the field names of
+        jtk_phrase_out (group_mask=, n_hits=, first_hit=, first_which=, n_hit_units= [n_docs], unit_mask= [n_units]), each may be
+        left out or None and is then not written.  n_hit_units and unit_mask need a line_units call on the same encode (any unit,
+        any trim).  Does not wait."""
+        unknown = set(ptrs) - set(N.PHRASE_OUT_FIELDS)
+        if unknown:
+            raise TypeError("phrase_hits: no output named %s" % ", ".join(sorted(unknown)))
+        out = N.PhraseOutStruct(**{k: v for k, v in ptrs.items() if v})
+        _check(N.lib().jtk_batch_phrase_hits(self._h, phrase_set._h if phrase_set is not None else None, C.byref(out), stream))
 
     def encode_device(self, d_text_ptr, d_doc_off_ptr, n_docs, n_bytes, ordinary=False, stream=None, sync=True,
                       allow_special=False, validate=False, count_only=False, fim=False):
@@ -1093,6 +1110,63 @@ class SeenSet:
         if not arrs[0].size == arrs[1].size == arrs[2].size:
             raise ValueError("keys, first and count must have one length")
         _check(N.lib().jtk_seen_set_add_entries(self._h, *[x.ctypes.data if x.size else None for x in arrs], arrs[0].size))
+
+
+class PhraseSet:
+    """A device-resident, immutable set of byte strings with a group (0..31) each (jtk_phrase_set; the rule is in
+    include/jtokkit_amd.h), for Batch.phrase_hits and HipEncoding.phrase_hits_batch: which groups hit in a document or a line, how
+    often and where first.  phrases: str or bytes (a str as its UTF-8 bytes), or (phrase, group) pairs such as C4_PHRASES; groups:
+    one group per phrase when the phrases are not pairs (None: all 0).  fold_ascii: 'A'..'Z' of phrases and text match 'a'..'z';
+    word_bounds: a hit has no word character (L, N or '_') next to it on either side.  It belongs to its encoding, which must stay
+    open while the set is used, and keeps no reference to any batch."""
+
+    def __init__(self, encoding, phrases, groups=None, fold_ascii=False, word_bounds=False):
+        phrases = list(phrases)
+        if groups is None and phrases and isinstance(phrases[0], tuple):
+            phrases, groups = [p for p, _ in phrases], [g for _, g in phrases]
+        bs = [p.encode("utf-8") if isinstance(p, str) else bytes(p) for p in phrases]
+        groups = [0] * len(bs) if groups is None else [int(g) for g in groups]
+        if len(groups) != len(bs):
+            raise ValueError("phrases and groups must have one length")
+        if any(not 0 <= g <= 31 for g in groups):
+            raise ValueError("a group is in 0..31")
+        off = np.zeros(len(bs) + 1, dtype=np.uint32)
+        if bs:
+            np.cumsum([len(x) for x in bs], out=off[1:])
+        blob = np.frombuffer(b"".join(bs) + b"\0", dtype=np.uint8)
+        grp = np.array(groups + [0], dtype=np.uint8)
+        self.encoding = encoding
+        self.fold_ascii, self.word_bounds = bool(fold_ascii), bool(word_bounds)
+        p = N.PhraseParamsStruct((N.JTK_PHRASE_FOLD_ASCII if fold_ascii else 0) | (N.JTK_PHRASE_WORD_BOUNDS if word_bounds else 0), len(bs),
+                                 blob.ctypes.data, off.ctypes.data, grp.ctypes.data)
+        h = C.c_void_p()
+        _check(N.lib().jtk_phrase_set_create(encoding._h, C.byref(p), C.byref(h)))      # (the call has copied the arrays)
+        self._h = h
+
+    def close(self):
+        if getattr(self, "_h", None):
+            N.lib().jtk_phrase_set_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:          # (interpreter shutdown: the module's globals may be gone)
+            pass
+
+    def _size(self):
+        n, states = C.c_int64(0), C.c_int64(0)
+        _check(N.lib().jtk_phrase_set_size(self._h, C.byref(n), C.byref(states)))
+        return n.value, states.value
+
+    def __len__(self):
+        """The distinct phrases (after folding)."""
+        return self._size()[0]
+
+    @property
+    def n_states(self):
+        """States of the trie, the root included."""
+        return self._size()[1]
 
 
 class HipEncoding:
@@ -1655,6 +1729,55 @@ class HipEncoding:
         b.line_units("line", True, stream=stream)
         res = {name: torch.zeros(nd, dtype=torch.int64 if dt == "int64" else torch.int32, device=device) for name, dt in N.WORDS_OUT_TYPES}
         b.word_stats(stop_words, fold_ascii, short_line_chars, stream, **{name: t.data_ptr() for name, t in res.items() if nd})
+        return res
+
+    def phrase_set(self, phrases, groups=None, fold_ascii=False, word_bounds=False):
+        """A PhraseSet of this encoding, for phrase_hits_batch: PhraseSet(self, phrases, groups, fold_ascii, word_bounds)."""
+        return PhraseSet(self, phrases, groups, fold_ascii, word_bounds)
+
+    def phrase_hits_batch(self, texts, phrase_set, units=None, trim=False):
+        """Phrase hits of each of a list of str/bytes against `phrase_set` (jtk_batch_phrase_hits; the rule is in
+        include/jtokkit_amd.h): a dict of numpy arrays [n] -- group_mask uint32 (bit g: a phrase of group g occurs), n_hits int32,
+        first_hit int64 (byte position in the document, -1 without a hit), first_which int32 (the phrase's index, -1).  With
+        units="line" or "paragraph" (trim as for line_units) also n_hit_units int32 [n], unit_off int64 [n + 1], and unit_begin,
+        unit_end int64 and unit_mask uint32 [n_units] (byte positions in the documents back to back)."""
+        bs, text, doc_off = _join_texts(texts)
+        n = len(bs)
+        self.encode_batch_packed(text, doc_off, True, False, None)
+        b = self._b()
+        nu = b.line_units(units, trim) if units is not None else 0
+        with _device_arrays() as put:
+            outs = {name: put(np.zeros(nu if name == "unit_mask" else n, dtype=dt)) for name, dt in N.PHRASE_OUT_TYPES
+                    if units is not None or name not in N.PHRASE_UNIT_FIELDS}
+            b.phrase_hits(phrase_set, **{name: x.ptr for name, x in outs.items() if x._arr.size})
+            if units is not None:
+                where = {"unit_off": put(np.zeros(n + 1, dtype=np.int64)), "unit_begin": put(np.zeros(nu, dtype=np.int64)),
+                         "unit_end": put(np.zeros(nu, dtype=np.int64))}
+                b.line_repeats(units, trim, **{name: x.ptr for name, x in where.items() if x._arr.size})
+                outs.update(where)
+            _stream_sync(b.stream())
+            res = {name: x.fetch() for name, x in outs.items()}
+        return res
+
+    def phrase_hits_batch_device(self, text, doc_off, phrase_set, units=None, trim=False, ordinary=True, allowed_special=None):
+        """Encodes a device-resident batch (text CUDA torch.uint8, doc_off CUDA torch.int64 [n_docs + 1]) and returns what
+        phrase_hits_batch returns as a dict of CUDA tensors written on torch.cuda.current_stream() (the masks as int32 bits), plus
+        "status" int32 [n_docs].  With units it waits once, for the number of units (and, with allowed_special, once more for the
+        encode's count of literal candidates); without, not at all."""
+        import torch
+        self._check_device_inputs("phrase_hits_batch_device", ("text", text, torch.uint8), ("doc_off", doc_off, torch.int64))
+        allow = self._allow(self._b(), allowed_special)
+        with self._encode_device_batch(text, doc_off, ordinary, allow) as (b, nd, device, stream):
+            nu = b.line_units(units, trim, stream=stream) if units is not None else 0
+            res = {name: torch.zeros(nu if name == "unit_mask" else nd, dtype=torch.int64 if dt == "int64" else torch.int32, device=device)
+                   for name, dt in N.PHRASE_OUT_TYPES if units is not None or name not in N.PHRASE_UNIT_FIELDS}
+            b.phrase_hits(phrase_set, stream, **{name: t.data_ptr() for name, t in res.items() if t.numel()})
+            if units is not None:
+                where = {"unit_off": torch.zeros(nd + 1, dtype=torch.int64, device=device), "unit_begin": torch.zeros(nu, dtype=torch.int64, device=device),
+                         "unit_end": torch.zeros(nu, dtype=torch.int64, device=device)}
+                b.line_repeats(units, trim, stream=stream, **{name: t.data_ptr() for name, t in where.items() if t.numel()})
+                res.update(where)
+            res["status"] = self._tok_off_and_status(b, nd, device, stream)[1]
         return res
 
     def quality_signals(self, texts, stop_words=GOPHER_STOP_WORDS, fold_ascii=False, short_line_chars=0, ordinary=True, allowed_special=None):
