@@ -22,10 +22,12 @@
 #define JTK_TILE 2048            // bytes per piece_resolve / pack workgroup; token counts are kept per tile
 // Pieces that need bytePairMerge are queued by length bin; bin k holds pieces of up to JTK_BIN_SLOTS(k) bytes.
 // Queues are dense and sharded: tile t appends its entries to shard t % JTK_Q_SHARDS with one returning
-// atomic per tile and bin.  A queue entry is two words in two parallel arrays:
+// atomic per tile and bin.  A queue entry of bins 1..6 is two words in two parallel arrays:
 //   qm  (8 bytes)   pos (37 bits) | (len - 1) << 37
-//   qd  (16 bytes)  bins 0..2: IN the piece's bytes (<= 16, what piece_resolve hashed), OUT the merge result;
+//   qd  (16 bytes)  bins 1..2: IN 16 bytes of the text from the piece's first byte on, OUT the merge result;
 //                   bins 3..6: OUT the merge result (their bytes are read from the text)
+// An entry of bin 0 (4..8 bytes) is its qd word alone: IN words x, y the 8 bytes of the text from the piece's first byte on, words
+// z, w the low and the high half of what would be its qm word; OUT the merge result.  qm[0] is allocated and not used.
 // Merge result: (token count - 1) in the top byte | up to seven token ids, 17 bits each from bit 0; a piece that
 // became more than seven tokens leaves its tokens in htok (packed from its first byte position).  The merge kernels
 // add every piece's token count to tile_tot[tile] (piece_resolve stored the resolved pieces' count there).
@@ -152,8 +154,8 @@ struct JtkWork {
     uint32_t* tile_tot;     // [n_tiles] tokens of the tile's pieces: piece_resolve stores the resolved pieces (one token
                             // each), the merge kernels add theirs
     int64_t* tile_off;      // [n_tiles + 1] exclusive scan of tile_tot
-    uint64_t* qm[JTK_NBINS];        // [JTK_Q_SHARDS][q_cap[k]] queue entries of bin k: position and length
-    uint4* qd[JTK_NBINS];           // [JTK_Q_SHARDS][q_cap[k]] ... : bytes in (bin 0), merge result out
+    uint64_t* qm[JTK_NBINS];        // [JTK_Q_SHARDS][q_cap[k]] queue entries of bin k: position and length (bin 0: not used)
+    uint4* qd[JTK_NBINS];           // [JTK_Q_SHARDS][q_cap[k]] ... : bytes in (bins 0..2; bin 0: and position and length), merge result out
     int64_t q_cap[JTK_NBINS];       // entries per shard
     uint64_t* qt;                   // [JTK_Q_SHARDS][qt_cap] the queue of JTK_BIN_TINY: bytes in, result out
     int64_t qt_cap;

@@ -677,8 +677,9 @@ __global__ void __launch_bounds__(RES_THREADS) __attribute__((amdgpu_waves_per_e
     }
     __syncthreads();
     // The tile's slices of its queue shards are claimed with one returning atomic per bin (a device-wide atomic:
-    // about 2 us), then the queue entries are written: position and length for every bin, and for bin 0 also the
-    // piece's bytes (so that the merge kernel reads 16 dense bytes per piece instead of a 64-byte slab of the text).
+    // about 2 us), then the queue entries are written: position and length for every bin, and for the bins of <= 16
+    // bytes also the piece's bytes (so that the merge kernel reads 16 dense bytes per piece instead of a 64-byte slab of
+    // the text); a piece of 4..8 bytes has all of it in one 16-byte word.
     // A tile with few merge pieces (ordinary text) leaves that to wave 0; the other waves are done and leave, so
     // their slots go to the next tile's workgroup while the atomic is in flight.
     const uint32_t n_queued = s_qn[0] + s_qn[1] + s_qn[2] + s_qn[3] + s_qn[4] + s_qn[5] + s_qn[6] + s_qn[JTK_BIN_TINY];
@@ -711,10 +712,18 @@ __global__ void __launch_bounds__(RES_THREADS) __attribute__((amdgpu_waves_per_e
             const uint32_t off = e & 2047u;
             const int a = (int)(off >> 2);
             const uint32_t sh = off & 3u;
-            const uint32_t w0 = tw[a], w1 = tw[a + 1], w2 = tw[a + 2], w3 = tw[a + 3], w4 = tw[a + 4];
-            w.qd[q][qbase + i] = make_uint4(__builtin_amdgcn_alignbyte(w1, w0, sh), __builtin_amdgcn_alignbyte(w2, w1, sh),
-                                            __builtin_amdgcn_alignbyte(w3, w2, sh), __builtin_amdgcn_alignbyte(w4, w3, sh));
-            w.qm[q][qbase + i] = (uint64_t)(B + off) | ((uint64_t)((e >> 11) & 255u) << JTK_QE_LEN_SHIFT);
+            const uint64_t meta = (uint64_t)(B + off) | ((uint64_t)((e >> 11) & 255u) << JTK_QE_LEN_SHIFT);
+            if (q == 0) {
+                // 4..8 bytes: the meta word rides in the idle half of the entry -- one store per piece, and no qm[0] word
+                const uint32_t w0 = tw[a], w1 = tw[a + 1], w2 = tw[a + 2];
+                w.qd[0][qbase + i] = make_uint4(__builtin_amdgcn_alignbyte(w1, w0, sh), __builtin_amdgcn_alignbyte(w2, w1, sh),
+                                                (uint32_t)meta, (uint32_t)(meta >> 32));
+            } else {
+                const uint32_t w0 = tw[a], w1 = tw[a + 1], w2 = tw[a + 2], w3 = tw[a + 3], w4 = tw[a + 4];
+                w.qd[q][qbase + i] = make_uint4(__builtin_amdgcn_alignbyte(w1, w0, sh), __builtin_amdgcn_alignbyte(w2, w1, sh),
+                                                __builtin_amdgcn_alignbyte(w3, w2, sh), __builtin_amdgcn_alignbyte(w4, w3, sh));
+                w.qm[q][qbase + i] = meta;
+            }
         }
     }
     {   // tiny pieces: position, length and the 2..3 bytes in one word
@@ -963,16 +972,16 @@ __device__ __forceinline__ uint4 lean_emit(const JtkWork& w, const uint32_t* id,
 }
 
 // token counts per tile: entries of a tile are consecutive, so a wave sees a few runs of equal tiles; the first
-// lane of each run adds the run's sum.  Evaluated by all lanes of the wave.
-__device__ __forceinline__ void lean_tile_counts(const JtkWork& w, bool have, int64_t pos, uint32_t c, int lane) {
-    const int64_t tile = have ? pos / T : -1;
+// lane of each run adds the run's sum.  Evaluated by all lanes of the wave.  tile: of the lane's piece (a chunk has fewer
+// than 2^26 tiles: positions have 37 bits), anything for a lane that has none.
+__device__ __forceinline__ void lean_tile_counts_of(const JtkWork& w, bool have, uint32_t tile, uint32_t c, int lane) {
+    const uint32_t tl = have ? tile : 0xFFFFFFFFu;
     const uint32_t cc = have ? c : 0u;
     const uint32_t inc = jtk_wave_incl_scan(cc);
-    const uint32_t tlo = (uint32_t)tile, thi = (uint32_t)((uint64_t)tile >> 32);
-    // (the shuffles are evaluated by ALL lanes, outside the condition: a lane that short-circuits an `||` leaves the
+    // (the shuffle is evaluated by ALL lanes, outside the condition: a lane that short-circuits an `||` leaves the
     // wave for the rest of the expression, and its neighbour would read a dead lane)
-    const uint32_t plo = (uint32_t)__shfl_up((int)tlo, 1), phi = (uint32_t)__shfl_up((int)thi, 1);
-    const bool head = lane == 0 || plo != tlo || phi != thi;
+    const uint32_t pl = (uint32_t)__shfl_up((int)tl, 1);
+    const bool head = lane == 0 || pl != tl;
     const uint64_t heads = __ballot(head);
     const uint64_t later = heads & ~((2ull << lane) - 1ull);                  // run heads after this lane
     const int last = later ? jtk_ctz64(later) - 1 : 63;                        // last lane of this lane's run
@@ -982,34 +991,46 @@ __device__ __forceinline__ void lean_tile_counts(const JtkWork& w, bool have, in
         if (sum) atomicAdd(&w.tile_tot[tile], sum);
     }
 }
+__device__ __forceinline__ void lean_tile_counts(const JtkWork& w, bool have, int64_t pos, uint32_t c, int lane) {
+    lean_tile_counts_of(w, have, (uint32_t)((uint64_t)pos / (uint32_t)T), c, lane);
+}
+
+// Position and length of an entry of the queue of 4..8-byte pieces: the meta word in the upper half of the 16 bytes
+__device__ __forceinline__ int64_t lean_e16_pos(uint32_t z, uint32_t w) {
+    return (int64_t)((((uint64_t)w << 32) | z) & JTK_QE_POS_MASK);
+}
+__device__ __forceinline__ uint32_t lean_e16_len(uint32_t w) { return ((w >> (JTK_QE_LEN_SHIFT - 32)) & 255u) + 1u; }
 
 // A window of 64 * R (R = 2 or 4, wave-uniform) consecutive entries of the queue of 4..8-byte pieces, all present, taken by
 // one wave in stable order of length (jtk_merge_order_rules.h): a round's 64 pieces are of nearly one length, so few of
 // its steps serve finished lanes.  The window comes in and its results go out in entry order, with the coalesced loads and
 // stores of a pass of R = 1; in between the 16-byte entries stay in the wave's columns of slots 8..15 of both part arrays
 // (idle while 8 slots are merged: 2 x 8 x 64 words = 256 entries), entry e in the four words from (e & 15) * 4 of slot
-// 8 + (e >> 4 & 7) of id (e < 128) or rk, where each result replaces its entry as it does in memory.  The queue words stay
-// with the lanes that loaded them; the lane that merges an entry is told its index and length through slots 0..3.
+// 8 + (e >> 4 & 7) of id (e < 128) or rk, where each result replaces its entry as it does in memory.  An entry carries its
+// position and length in its upper half (lean_e16_*), so the window reads nothing else; of that the lane that loaded an entry
+// keeps only the tile, for the token counts at the end, and the lane that merges an entry is told its index and length through
+// slots 0..3.  (A round scans 8 slots whatever its longest piece: 5 or 6 slots for rounds of shorter pieces were built and
+// measured no faster)
 template <int THREADS>
-__device__ __forceinline__ void lean_window(const JtkWork& w, const JtkDeviceTables& t, const LeanLds& L, const uint64_t* qm, uint4* qd,
-                                            uint32_t wbase, uint32_t R) {
+__device__ __forceinline__ void lean_window(const JtkWork& w, const JtkDeviceTables& t, const LeanLds& L, uint4* qd, uint32_t wbase, uint32_t R) {
     constexpr uint32_t LO = 4, NC = 5;                                          // 4..8 bytes
+    static_assert(jtk_piece_bin(LO - 1) != 0 && jtk_piece_bin(LO) == 0 && jtk_piece_bin(LO + NC - 1) == 0 && jtk_piece_bin(LO + NC) != 0,
+                  "a class is a length: LO + key");
     const int tid = threadIdx.x, lane = tid & 63, col0 = tid & ~63;
     uint32_t* const id = L.id + tid;
     uint32_t* const rk = L.rk + tid;
     uint32_t* const park_lo = L.id + 8 * THREADS + col0;
     uint32_t* const park_hi = L.rk + 8 * THREADS + col0;
-    uint64_t meta[JTK_MO_RMAX];
-    uint32_t key[JTK_MO_RMAX], place[JTK_MO_RMAX];
+    uint32_t tile[JTK_MO_RMAX], key[JTK_MO_RMAX], place[JTK_MO_RMAX];
 #pragma unroll
     for (uint32_t s = 0; s < JTK_MO_RMAX; s++) {
-        meta[s] = 0; key[s] = NC; place[s] = 0;
+        tile[s] = 0; key[s] = NC; place[s] = 0;
         if (s < R) {
             const uint32_t e = s * 64u + (uint32_t)lane;
-            meta[s] = qm[wbase + e];
             const uint4 by = qd[wbase + e];
             *reinterpret_cast<uint4*>((s < 2 ? park_lo : park_hi) + ((e >> 4) & 7u) * THREADS + (e & 15u) * 4u) = by;
-            key[s] = jtk_mo_class((uint32_t)((meta[s] >> JTK_QE_LEN_SHIFT) & 255u) + 1u, LO, NC);
+            key[s] = jtk_mo_class(lean_e16_len(by.w), LO, NC);
+            tile[s] = (uint32_t)((uint64_t)lean_e16_pos(by.z, by.w) / (uint32_t)T);
         }
     }
     uint32_t before = 0;
@@ -1024,10 +1045,7 @@ __device__ __forceinline__ void lean_window(const JtkWork& w, const JtkDeviceTab
     }
 #pragma unroll
     for (uint32_t s = 0; s < JTK_MO_RMAX; s++) {
-        if (s < R) {
-            const uint32_t len = (uint32_t)((meta[s] >> JTK_QE_LEN_SHIFT) & 255u) + 1u;
-            L.id[(place[s] >> 6) * THREADS + col0 + (place[s] & 63u)] = (s * 64u + (uint32_t)lane) | (len << 8);
-        }
+        if (s < R) L.id[(place[s] >> 6) * THREADS + col0 + (place[s] & 63u)] = (s * 64u + (uint32_t)lane) | ((key[s] + LO) << 8);
     }
     wave_lds_fence();
     // 16 bits per round: index in the window, length
@@ -1037,15 +1055,18 @@ __device__ __forceinline__ void lean_window(const JtkWork& w, const JtkDeviceTab
         const uint32_t el = (uint32_t)(mine >> (16u * r)) & 0xFFFFu, e = el & 255u;
         const int len = (int)(el >> 8);
         uint4* const slot = reinterpret_cast<uint4*>(((e & 128u) ? park_hi : park_lo) + ((e >> 4) & 7u) * THREADS + (e & 15u) * 4u);
-        const uint4 by = *slot;
-        const uint32_t d4[3] = {by.x, by.y, by.z};
+        const uint2 by = *reinterpret_cast<const uint2*>(slot);
         uint32_t b[9];
 #pragma unroll
-        for (int j = 0; j < 9; j++) b[j] = (d4[j >> 2] >> (8 * (j & 3))) & 255u;
+        for (int j = 0; j < 8; j++) b[j] = ((j < 4 ? by.x : by.y) >> (8 * (j & 3))) & 255u;
+        b[8] = 0;
         const uint32_t alive = lean_piece16<8, THREADS>(L, id, rk, b, len, t);
         const uint32_t c = (uint32_t)__popc(alive);
         int64_t pos = 0;
-        if (c > 7u) pos = (int64_t)(qm[wbase + e] & JTK_QE_POS_MASK);          // (eight bytes, no merge at all)
+        if (c > 7u) {                                                           // (eight bytes, no merge at all)
+            const uint2 m = reinterpret_cast<const uint2*>(slot)[1];
+            pos = lean_e16_pos(m.x, m.y);
+        }
         *slot = lean_emit<THREADS, uint32_t>(w, id, alive, c, pos);
     }
     wave_lds_fence();
@@ -1055,7 +1076,7 @@ __device__ __forceinline__ void lean_window(const JtkWork& w, const JtkDeviceTab
             const uint32_t e = s * 64u + (uint32_t)lane;
             const uint4 res = *reinterpret_cast<const uint4*>((s < 2 ? park_lo : park_hi) + ((e >> 4) & 7u) * THREADS + (e & 15u) * 4u);
             qd[wbase + e] = res;
-            lean_tile_counts(w, true, (int64_t)(meta[s] & JTK_QE_POS_MASK), (res.w >> 24) + 1u, lane);
+            lean_tile_counts_of(w, true, tile[s], (res.w >> 24) + 1u, lane);
         }
     }
     wave_lds_fence();               // (the words read here are other lanes' slots 8..15, which the next phase may write)
@@ -1079,14 +1100,18 @@ __device__ __forceinline__ void lean_bin(const JtkWork& w, const JtkDeviceTables
         const uint32_t n = (uint32_t)__builtin_amdgcn_readfirstlane((int)count);
         const uint32_t span = (uint32_t)__builtin_amdgcn_readfirstlane((int)(K * THREADS));
         for (uint32_t R; (R = jtk_mo_rounds(n - taken, span)) > 1u; taken += R * span)
-            lean_window<THREADS>(w, t, L, qm, qd, taken + R * (kq * THREADS + (uint32_t)(tid & ~63)), R);
+            lean_window<THREADS>(w, t, L, qd, taken + R * (kq * THREADS + (uint32_t)(tid & ~63)), R);
     }
     for (uint32_t base = taken + kq * THREADS; base < count; base += K * THREADS) {
         const uint32_t qi = base + (uint32_t)tid;
         bool have = qi < count;
         uint64_t meta = 0;
         uint4 by = make_uint4(0, 0, 0, 0);
-        if (have) { meta = qm[qi]; if (BIN < JTK_NBINS_BYTES) by = qd[qi]; }
+        if (have) {
+            if (BIN < JTK_NBINS_BYTES) by = qd[qi];
+            if (BIN == 0) meta = ((uint64_t)by.w << 32) | by.z;               // 4..8 bytes: the entry carries its meta word
+            else meta = qm[qi];
+        }
         if (BIN >= JTK_NBINS_BYTES && (meta & JTK_QE_DONE)) have = false;     // a table entry of > 16 bytes: result and count are in place
         const int64_t pos = (int64_t)(meta & JTK_QE_POS_MASK);
         const int len = have ? (int)((meta >> JTK_QE_LEN_SHIFT) & 255u) + 1 : 0;

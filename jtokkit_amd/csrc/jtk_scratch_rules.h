@@ -75,7 +75,8 @@ static_assert(JTK_BIN_CAP0 >= jtk_bin_tile_cap(0) && JTK_BIN_CAP1 >= jtk_bin_til
               JTK_BIN_CAP3 >= jtk_bin_tile_cap(3) && JTK_BIN_CAP4 >= jtk_bin_tile_cap(4) && JTK_BIN_CAP5 >= jtk_bin_tile_cap(5) &&
               JTK_BIN_CAP6 >= jtk_bin_tile_cap(6) && JTK_TINY_CAP >= jtk_bin_tile_cap(JTK_BIN_TINY), "a tile's LDS slice holds its bound");
 
-// Bytes of one queue entry of `bin`: qm (8) + qd (16); the tiny queue's entries are one 8-byte word.
+// Bytes of one queue entry of `bin`: qm (8) + qd (16); the tiny queue's entries are one 8-byte word.  (Bin 0's entries
+// live in qd alone since they carry position and length themselves; its qm array is still carved and counted here.)
 JTK_SC_HD int64_t jtk_bin_entry_bytes(int bin) { return bin == JTK_BIN_TINY ? 8 : 24; }
 
 // bytes of all queues of a chunk of n_tiles tiles
